@@ -389,6 +389,39 @@ def parity_check(cm, args, dev):
     return out
 
 
+DUMP_BUDGET = 64 * 10 ** 6      # bytes --dump-outputs may write in all
+DUMP_SEED = 20261015
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET):
+    """``--dump-outputs DIR``: writes what the timed path left in the caller's arrays after its
+    last step as float64 ``DIR/<name>.npy``.  ``arrays`` maps a name to a tensor whose first axis
+    is the rank's real elements.  When the arrays together would exceed ``budget`` bytes, each
+    keeps the same fraction of its elements, drawn with a fixed seed and sorted (the sample depends
+    on the array's shape alone), and ``DIR/<name>_elements.npy`` holds their indices.  Returns
+    {file name: shape}."""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    header = 128 * 2 * len(arrays)                       # .npy headers, an index file per array
+    row = {k: int(np.prod(a.shape[1:])) * 8 for k, a in arrays.items()}
+    full = sum(a.shape[0] * row[k] for k, a in arrays.items())
+    frac = 1.0
+    if full + header > budget:
+        frac = (budget - header) / sum(a.shape[0] * (row[k] + 8) for k, a in arrays.items())
+    written = {}
+    for name, a in arrays.items():
+        n = a.shape[0]
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, int(frac * n), replace=False))
+            a = a[torch.from_numpy(idx).to(a.device)]
+            written[name + "_elements.npy"] = idx.shape
+            np.save(os.path.join(outdir, name + "_elements.npy"), idx.astype(np.float64))
+        out = a.detach().cpu().numpy().astype(np.float64)
+        written[name + ".npy"] = out.shape
+        np.save(os.path.join(outdir, name + ".npy"), out)
+    return written
+
+
 def timed_run(cm, dg, law, grid, dt, steps, warmup, sync_all, distributed, dev):
     """W warm-up steps, then K timed steps bracketed by barrier + synchronize."""
     import torch
@@ -450,9 +483,10 @@ def committed_traffic(workload, nreal, dom):
     return 1024.0 * (2.0 * pm["FETCH_SIZE"] + pm["WRITE_SIZE"]), "profiles/" + name
 
 
-def measure(cm, args, workload_args, rank, world, distributed, dev, with_halo):
+def measure(cm, args, workload_args, rank, world, distributed, dev, with_halo, dump=None):
     """Builds one workload on this rank, runs the timed region and the event pass, and (rank 0)
-    returns the fields of the JSON line for it."""
+    returns the fields of the JSON line for it.  ``dump``: directory for rank 0's state after the
+    timed steps (``--dump-outputs``)."""
     import torch
     import torch.distributed as dist
     t0 = time.time()
@@ -506,6 +540,8 @@ def measure(cm, args, workload_args, rank, world, distributed, dev, with_halo):
         total_elems = int(nn.item())
     else:
         total_elems = grid.nreal
+    if dump and rank == 0:
+        log("[dump] %s" % json.dumps(dump_outputs(dump, {"state": Q[:grid.nreal]})))
     # ---- same K steps again with a HIP event pair around every kernel launch (recorded on
     # the launch stream): per-kernel durations for the roofline.  The events themselves cost
     # ~10 % of a step at this size, hence the separate pass.
@@ -716,6 +752,9 @@ def parse_args(argv):
     ap.add_argument("--dry-launch", action="store_true",
                     help="start the ranks as usual, but each only prints its launch environment "
                          "(no torch, no GPU): checks the launcher itself")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's state as DIR/<name>.npy (float64, "
+                         "at most 64 MB in all; a seeded sample of the elements when larger)")
     return ap.parse_args(argv)
 
 
@@ -786,7 +825,7 @@ def main(argv=None):
         args.scaling if hs else "weak")
     main_args = with_scaling(args, "strong" if head_scaling == "strong" else args.scaling)
     res = measure(cm, args, main_args, rank, world, distributed, dev,
-                  with_halo=multi or bool(os.environ.get("BENCH_HALO_BLOCK")))
+                  with_halo=multi or bool(os.environ.get("BENCH_HALO_BLOCK")), dump=args.dump_outputs)
     sec = None
     if both and not args.no_secondary:
         sec = measure(cm, args, with_scaling(args, "weak"), rank, world, distributed, dev, with_halo=True)
@@ -917,6 +956,9 @@ def main_ocean(args, rank, world, local):
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     total3 = g3.nreal
+    if args.dump_outputs and rank == 0:
+        log("[dump] %s" % json.dumps(dump_outputs(args.dump_outputs, {
+            "state_3d": Q3[:g3.nreal], "state_2d": Q2[:g2.nreal]})))
     if distributed:
         dist.barrier()
         tt = torch.tensor([el, float(g3.nreal)], device=dev, dtype=torch.float64)

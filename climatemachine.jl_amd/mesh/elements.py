@@ -3,7 +3,7 @@
 Reference: ``src/Numerics/Mesh/Elements.jl`` -- lglpoints :11-14, baryweights
 :34-46, spectralderivative :60-82.  The reference obtains the Legendre-Gauss-Lobatto
 rule from the third-party GaussQuadrature.jl 0.5.5 (``legendre(T, N+1, both)``,
-absent from /root/reference); here the published definition is used directly:
+absent from the reference); here the published definition is used directly:
 the interior nodes are the roots of P'_N, found by Newton iteration, and
 ``w_i = 2 / (N (N+1) P_N(x_i)^2)``.
 """

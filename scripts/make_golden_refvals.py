@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Transcribes a StateCheck reference-value file of the reference (test/Ocean/refvals/*.jl: the
 `varr` rows [array, field, max?, ...] and the precision rows `parr`) into a JSON fixture: data only,
-by a regex over the file's text.  Usage (in the build container, where /root/reference exists):
+by a regex over the file's text.  Usage, with a checkout of the reference at REF:
 
-    python scripts/make_golden_refvals.py /root/reference/test/Ocean/refvals/simple_box_2dt_refvals.jl \
+    python scripts/make_golden_refvals.py REF/test/Ocean/refvals/simple_box_2dt_refvals.jl \
         tests/golden/ocean_simple_box_2dt_refvals.json
 """
 import json
@@ -25,7 +25,7 @@ def rows(block):
 
 varr = text[text.index("varr = ["):text.index("parr = [")]
 parr = text[text.index("parr = ["):text.index("# END SCPRINT")]
-json.dump({"source": src.replace("/root/reference/", ""),
+json.dump({"source": src[src.rindex("test/"):],
            "columns": ["array", "field", "min", "max", "mean", "std"],
            "varr": rows(varr), "parr": rows(parr)}, open(dst, "w"), ensure_ascii=False, indent=1)
 print(len(rows(varr)), "rows")

@@ -2,6 +2,10 @@ import os
 import sys
 
 import pytest
+# torch carries its own HIP and HSA runtimes under the sonames libcmdg.so links against; loaded
+# first, they serve libcmdg.so as well.  A test that loads libcmdg.so before anything imports torch
+# maps a second pair into the session, and every device test after it finds no device.
+import torch as _torch  # noqa: F401,E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

@@ -88,19 +88,25 @@ def test_engine_plugin_builds_and_loads():
     """climatemachine.jl_amd/plugins.py writes a plug-in translation unit, hipcc cross-compiles it
     for gfx950 against libcmdg.so, it exports cmdg_plugin_make_engine and cmdg_load_plugin takes
     it; something that is not a plug-in is refused with the reason.  (Its engine runs on the GPU:
-    tests/test_gpu_plugins.py.)"""
-    import ctypes as C
+    tests/test_gpu_plugins.py.)  The loads happen in a child process: a plug-in stays loaded for the
+    life of the process, and tests/test_gpu_plugins.py first checks that the session's library
+    refuses the combination."""
     import subprocess
+    import sys
     from cmdg_loader import cm
     so = cm.plugins.build_dry_atmos(orient=True, ref_state=False, hyperdiffusion=True, N=4)
     names = subprocess.check_output(["nm", "-D", so]).decode()
     assert " T cmdg_plugin_make_engine" in names
-    L = cm._lib.lib()
-    assert L.cmdg_load_plugin(so.encode()) == 0
-    assert L.cmdg_load_plugin(so.encode()) == 0          # idempotent
-    L.cmdg_last_error.restype = C.c_char_p
-    assert L.cmdg_load_plugin(b"/nonexistent/plugin.so") != 0
-    assert b"cannot load plug-in" in L.cmdg_last_error(None)
+    code = ("import ctypes as C, sys; sys.path.insert(0, %r)\n"
+            "from cmdg_loader import cm\n"
+            "L = cm._lib.lib(); so = sys.argv[1].encode()\n"
+            "assert L.cmdg_load_plugin(so) == 0\n"
+            "assert L.cmdg_load_plugin(so) == 0          # idempotent\n"
+            "L.cmdg_last_error.restype = C.c_char_p\n"
+            "assert L.cmdg_load_plugin(b'/nonexistent/plugin.so') != 0\n"
+            "assert b'cannot load plug-in' in L.cmdg_last_error(None)\n" % ROOT)
+    r = subprocess.run([sys.executable, "-c", code, so], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
 
 
 def test_plugin_built_against_other_headers_is_refused(tmp_path):

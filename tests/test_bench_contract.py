@@ -144,3 +144,29 @@ def test_cpu_baseline_reports_its_threads_and_memory_ceiling(monkeypatch):
     assert out["omp"] == {"OMP_PROC_BIND": os.environ.get("OMP_PROC_BIND"), "OMP_PLACES": os.environ.get("OMP_PLACES")}
     assert out["omp"]["OMP_PROC_BIND"] is not None      # bench.py sets them before libgomp loads
     assert out["stream_triad_GBs"] > 0 and "first_touch" in out and out["host"] == info
+
+
+def test_dump_outputs_stays_within_budget_and_is_reproducible(tmp_path):
+    """``--dump-outputs``: the whole state when it fits, otherwise the same seeded sample of
+    elements every time, with the indices beside it; never more bytes than the budget."""
+    import numpy as np
+    import torch
+    big = torch.arange(1000 * 5 * 27, dtype=torch.float64).reshape(1000, 5, 27)
+    small = torch.linspace(0.0, 1.0, 40 * 3, dtype=torch.float64).reshape(40, 3)
+    budget = 256 * 1024
+    one, two = tmp_path / "one", tmp_path / "two"
+    for d in (one, two):
+        bench.dump_outputs(str(d), {"state": big, "aux": small}, budget=budget)
+    assert sum(f.stat().st_size for f in one.iterdir()) <= budget
+    for f in one.iterdir():
+        assert np.array_equal(np.load(f), np.load(two / f.name))
+        assert np.load(f).dtype == np.float64
+    idx = np.load(one / "state_elements.npy").astype(np.int64)
+    assert len(idx) > 100 and np.all(np.diff(idx) > 0) and idx[-1] < 1000
+    assert np.array_equal(np.load(one / "state.npy"), big.numpy()[idx])
+    aidx = np.load(one / "aux_elements.npy").astype(np.int64)
+    assert np.array_equal(np.load(one / "aux.npy"), small.numpy()[aidx])
+    whole = tmp_path / "whole"
+    bench.dump_outputs(str(whole), {"state": big})
+    assert sorted(f.name for f in whole.iterdir()) == ["state.npy"]
+    assert np.array_equal(np.load(whole / "state.npy"), big.numpy())

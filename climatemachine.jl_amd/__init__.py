@@ -7,11 +7,18 @@ need torch (device memory) and ``libcmdg.so`` (the hand-written HIP kernels); th
 are imported lazily so that the host-side pieces work without a GPU."""
 from . import atmos, balancelaws, mesh, moist, ocean, ocean01  # noqa: F401
 
-__all__ = ["mesh", "balancelaws", "atmos", "moist", "ocean", "ocean01", "dgmodel", "odesolvers", "plugins"]
+__all__ = ["mesh", "balancelaws", "atmos", "moist", "ocean", "ocean01", "dgmodel", "odesolvers", "plugins",
+           "reductions", "weightedsum", "norm", "dot", "euclidean_distance", "mapreduce", "ConsCallback"]
+
+# MPIStateArrays reductions (reductions.py), exported by name; loaded on first use like dgmodel
+_REDUCTIONS = ("weightedsum", "norm", "dot", "euclidean_distance", "mapreduce", "group_weightedsum",
+               "group_norm", "group_dot", "group_euclidean_distance", "group_mapreduce", "ConsCallback")
 
 
 def __getattr__(name):
-    if name in ("dgmodel", "odesolvers", "_lib", "plugins"):
-        import importlib
+    import importlib
+    if name in ("dgmodel", "odesolvers", "_lib", "plugins", "reductions"):
         return importlib.import_module("." + name, __name__)
+    if name in _REDUCTIONS:
+        return getattr(importlib.import_module(".reductions", __name__), name)
     raise AttributeError(name)

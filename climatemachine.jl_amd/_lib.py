@@ -99,6 +99,16 @@ class CmdgOceanCouplingDesc(C.Structure):
     ]
 
 
+RED_WEIGHTEDSUM, RED_SUM, RED_DOT, RED_DISTANCE, RED_NORM, RED_MAX, RED_MIN = range(7)
+
+
+class CmdgReduceDesc(C.Structure):
+    """``cmdg_reduce_desc`` of include/cmdg.h."""
+    _fields_ = [("op", C.c_int32), ("p", C.c_double), ("weighted", C.c_int32),
+                ("per_state", C.c_int32), ("nstate", C.c_int32), ("states", C.c_void_p),
+                ("nstates", C.c_int32)]
+
+
 # every symbol include/cmdg.h declares: (name, restype, argtypes)
 _vp, _i32, _i64, _d = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = [
@@ -130,6 +140,10 @@ SYMBOLS = [
     ("cmdg_group_lsrk_run", C.c_int, [_vp, _i32, _vp, _vp, _d, _d, _i64, _i32, _vp, _vp, _vp]),
     ("cmdg_norm2_local", C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     ("cmdg_distance2_local", C.c_int, [_vp, _vp, _vp, _i32, _vp]),
+    ("cmdg_reduce_local", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    ("cmdg_reduce_combine", C.c_int, [_vp, _vp, _i32, _vp]),
+    ("cmdg_reduce", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    ("cmdg_group_reduce", C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
     ("cmdg_courant", C.c_int, [_vp, _i32, _vp, _d, _d, _i32, _vp]),
     ("cmdg_min_node_distance", C.c_int, [_vp, _i32, _vp]),
     ("cmdg_indefinite_stack_integral", C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),

@@ -180,13 +180,20 @@ def _ls3n(name):
 LS3NRK44Classic, LS3NRK33Heuns = _ls3n("LS3NRK44Classic"), _ls3n("LS3NRK33Heuns")
 
 
-def solve(Q, solver, timeend=None, numberofsteps=0, adjustfinalstep=True):
-    """``solve!(Q, solver; timeend, adjustfinalstep, numberofsteps)`` without callbacks:
-    whole steps are batched into one library call, the last (shortened) step is
-    issued separately like ``general_dostep!`` does."""
+def solve(Q, solver, timeend=None, numberofsteps=0, adjustfinalstep=True, callbacks=()):
+    """``solve!(Q, solver; timeend, adjustfinalstep, numberofsteps, callbacks)``: steps are issued
+    one library call each, the last (shortened) step like ``general_dostep!`` does.
+    ``callbacks``: ``(every_n_steps, callback)`` pairs, as ``EveryXSimulationSteps`` wraps them
+    (GenericCallbacks.jl:205-229): ``callback.init(solver, Q, t)`` (if it has one) before the
+    first step, then ``callback(solver, Q, t)`` after every ``every_n_steps``-th step; a return
+    value > 0 stops the run (ODESolvers.jl:126-150)."""
     assert timeend is not None or numberofsteps > 0
     dt = solver.dt
     assert dt > 0
+    cbs = [[int(n), cb, 0] for n, cb in callbacks]
+    for c in cbs:
+        if hasattr(c[1], "init"):
+            c[1].init(solver, Q, solver.t)
     step = 0
     while (timeend is None or solver.t < timeend):
         if timeend is not None and adjustfinalstep and solver.t + dt > timeend:
@@ -195,7 +202,14 @@ def solve(Q, solver, timeend=None, numberofsteps=0, adjustfinalstep=True):
         else:
             solver.dostep(Q, 1)
         step += 1
-        if step == numberofsteps:
+        stop = False
+        for c in cbs:
+            c[2] += 1
+            if c[2] >= c[0]:
+                c[2] = 0
+                val = c[1](solver, Q, solver.t)
+                stop = stop or (val is not None and val > 0)
+        if stop or step == numberofsteps:
             break
     solver.dg.synchronize()
     return solver.t

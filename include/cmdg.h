@@ -349,6 +349,54 @@ int cmdg_norm2_local(cmdg_handle h, const double *A, int32_t nstate, int32_t wei
 int cmdg_distance2_local(cmdg_handle h, const double *A, const double *B, int32_t nstate,
                          double *out_host);
 
+/* ---- reductions of state arrays, all-reduced (MPIStateArrays.jl:583-807) ------------------
+ * weightedsum (:655-674), dot (:608-626), norm for p = 1, 2, any finite p > 0 and INFINITY with
+ * or without dims = (1, 3) (:583-604, :676-768), euclidean_distance (:628-644) and sum / maximum /
+ * minimum (mapreduce, :775-807) over the real elements of an (Np, nstate, nelem) array; ghost
+ * elements are never read.  Sums accumulate in double-double (an unevaluated pair hi + lo, as the
+ * reference's DoubleFloat): error-free products (fma) and sums form every term, per thread, wave
+ * and block; M (vgeo column VM, the reference's `weights`) times A is exact for _WEIGHTEDSUM.  Per-
+ * block partials are folded in a fixed order on the device, with no atomics: the same input gives
+ * the same bits on every call.  A NaN in a real element propagates (max / min / inf-norm too).
+ * The kernels run on the handle's compute stream after any deferred CMDG_OPT_ASYNC_RUN run. */
+enum {
+    CMDG_RED_WEIGHTEDSUM = 0, /* sum of M .* A[:, states, :]  (always weighted) */
+    CMDG_RED_SUM = 1,         /* sum of A                     (never weighted) */
+    CMDG_RED_DOT = 2,         /* sum of (M .*) A .* B */
+    CMDG_RED_DISTANCE = 3,    /* sqrt(sum of M .* (A - B).^2) (always weighted) */
+    CMDG_RED_NORM = 4,        /* (sum of (M .*) |A|.^p)^(1/p); p = INFINITY: maximum |A|, unweighted */
+    CMDG_RED_MAX = 5,         /* maximum of A */
+    CMDG_RED_MIN = 6          /* minimum of A */
+};
+typedef struct cmdg_reduce_desc {
+    int32_t op;            /* CMDG_RED_* */
+    double p;              /* _NORM only: 1, 2, any finite p > 0, or INFINITY */
+    int32_t weighted;      /* _DOT, _NORM (ignored for p = INFINITY); _WEIGHTEDSUM, _DISTANCE always weighted */
+    int32_t per_state;     /* 0: one value; 1: one value per chosen state (dims = (1,3)) */
+    int32_t nstate;        /* columns of A (and B) */
+    const int32_t *states; /* 0-based subset, NULL = all */
+    int32_t nstates;
+} cmdg_reduce_desc;
+
+/* this rank's unrounded partials: nout (hi, lo) pairs, nout = per_state ? number of chosen states
+ * : 1; max / min / inf-norm in hi, lo = 0 */
+int cmdg_reduce_local(cmdg_handle h, const cmdg_reduce_desc *d, const double *A, const double *B,
+                      double *partials_host);
+/* host only, needs no GPU: combines nranks x nout partials in rank order (the exact sum of every
+ * hi and lo, correctly rounded to double), applies the finishing power (sqrt / ^(1/p)); what every
+ * rank runs after an all-gather of the partials.  Errors: cmdg_last_error(NULL). */
+int cmdg_reduce_combine(const cmdg_reduce_desc *d, const double *partials, int32_t nranks,
+                        double *out);
+/* global value on every rank: single rank = local; RCCL handle = ncclAllGather of the partials
+ * on the handle's communicator, then cmdg_reduce_combine; a local-transport handle of a group
+ * with n > 1 is refused (CMDG_ERR_INVALID: use cmdg_group_reduce) */
+int cmdg_reduce(cmdg_handle h, const cmdg_reduce_desc *d, const double *A, const double *B,
+                double *out_host);
+/* handles connected with cmdg_comm_connect_local: one host thread plays every rank; A[i], B[i]
+ * are rank i's arrays (B may be NULL where the op takes none) */
+int cmdg_group_reduce(cmdg_handle *handles, int32_t n, const cmdg_reduce_desc *d,
+                      const double **A, const double **B, double *out_host);
+
 /* ---- Courant numbers and time-step selection ------------------------------------------ */
 /* local_courant functions of src/Atmos/Model/courant.jl:29-83 and, for the ocean model,
  * src/Ocean/HydrostaticBoussinesq/Courant.jl:13-111 (which adds viscous_courant) */

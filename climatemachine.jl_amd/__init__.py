@@ -7,7 +7,7 @@ need torch (device memory) and ``libcmdg.so`` (the hand-written HIP kernels); th
 are imported lazily so that the host-side pieces work without a GPU."""
 from . import atmos, balancelaws, mesh, moist, ocean, ocean01  # noqa: F401
 
-__all__ = ["mesh", "balancelaws", "atmos", "moist", "ocean", "ocean01", "dgmodel", "odesolvers", "plugins",
+__all__ = ["mesh", "balancelaws", "atmos", "moist", "ocean", "ocean01", "dgmodel", "odesolvers", "systemsolvers", "plugins",
            "reductions", "weightedsum", "norm", "dot", "euclidean_distance", "mapreduce", "ConsCallback"]
 
 # MPIStateArrays reductions (reductions.py), exported by name; loaded on first use like dgmodel
@@ -17,7 +17,7 @@ _REDUCTIONS = ("weightedsum", "norm", "dot", "euclidean_distance", "mapreduce", 
 
 def __getattr__(name):
     import importlib
-    if name in ("dgmodel", "odesolvers", "_lib", "plugins", "reductions"):
+    if name in ("dgmodel", "odesolvers", "_lib", "plugins", "reductions", "systemsolvers"):
         return importlib.import_module("." + name, __name__)
     if name in _REDUCTIONS:
         return getattr(importlib.import_module(".reductions", __name__), name)

@@ -171,6 +171,15 @@ SYMBOLS = [
     ("cmdg_profile_enable", C.c_int, [_vp, _i32]),
     ("cmdg_profile_get", C.c_int, [_vp, _i32, _vp, _vp]),
     ("cmdg_profile_reset", C.c_int, [_vp]),
+    ("cmdg_columnlu_create", C.c_int, [_vp, _i32, _d, C.POINTER(_vp)]),
+    ("cmdg_columnlu_update", C.c_int, [_vp, _d]),
+    ("cmdg_columnlu_assemble", C.c_int, [_vp, _d]),
+    ("cmdg_columnlu_solve", C.c_int, [_vp, _vp, _vp]),
+    ("cmdg_columnlu_info", C.c_int, [_vp, _vp]),
+    ("cmdg_columnlu_alpha", C.c_int, [_vp, _vp]),
+    ("cmdg_columnlu_export_band", C.c_int, [_vp, _i64, _vp]),
+    ("cmdg_columnlu_destroy", C.c_int, [_vp]),
+    ("cmdg_ark_step", C.c_int, [_vp, _vp, _vp, _vp, _d, _d, _i32, _vp, _vp, _vp, _vp, _i32]),
 ]
 
 _LIB = None

@@ -25,12 +25,12 @@ grad^3 h_tot (3)``.
 """
 import numpy as np
 
-from .balancelaws import PHYSICS_DRY_ATMOS
+from .balancelaws import PHYSICS_ATMOS_LINEAR_AG, PHYSICS_DRY_ATMOS
 from .mesh import grids as G
 
 __all__ = ["PlanetParameters", "DryAtmosModel", "IsentropicVortexSetup", "HeldSuarezSetup",
            "DecayingTemperatureProfile", "DryAdiabaticProfile", "RisingBubbleSetup",
-           "CourantTestSetup", "MMSSetup"]
+           "CourantTestSetup", "MMSSetup", "IsothermalProfile", "AtmosAcousticGravityLinearModel"]
 
 
 class PlanetParameters:
@@ -78,6 +78,20 @@ class DecayingTemperatureProfile:
         p = -self.Ht * (zp + dTvp * (np.log(1 - dTvp * th) - np.log(1 + th) + zp))
         p = p / (H_sfc * (1 - dTvp ** 2))
         p = ps.MSLP * np.exp(p)
+        return Tv, p
+
+
+class IsothermalProfile:
+    """``IsothermalProfile(param_set, T)`` of Thermodynamics.TemperatureProfiles (not vendored):
+    ``T_virt = T`` and ``p = MSLP exp(-g z / (R_d T))`` at altitude ``z``."""
+
+    def __init__(self, ps, T=300.0):
+        self.ps, self.T = ps, float(T)
+
+    def __call__(self, z):
+        ps = self.ps
+        Tv = self.T + 0.0 * z
+        p = ps.MSLP * np.exp(-z * ps.grav / (ps.R_d * self.T))
         return Tv, p
 
 
@@ -400,3 +414,39 @@ class DryAtmosModel:
             Q[:, 1 + d, :] = rhou[d]
         Q[:, 4, :] = rhoe
         return Q
+
+
+class AtmosAcousticGravityLinearModel:
+    """``AtmosAcousticGravityLinearModel(atmos)`` (src/Atmos/Model/linear.jl:249-345,
+    linear_tendencies.jl) of a dry ``DryAtmosModel``: prognostic ``rho, rho u, rho e`` (the first
+    five states of the full model), first-order fluxes ``rho u``, ``p_lin I`` and
+    ``((rho e_ref + p_ref) / rho_ref) rho u`` with ``p_lin = rho R_d T_0 + R_d / cv_d (rho e -
+    rho Phi)``, source ``-rho grad Phi`` (vertical and every direction), Rusanov wavespeed
+    ``soundspeed(ref.T)``, ``AtmosBC()`` on every boundary.  It reads the full model's auxiliary
+    state: build it as ``DGModel(linear, grid, direction=VerticalDirection,
+    state_auxiliary=dg.state_auxiliary)``.  Device functor: csrc/physics_atmos_linear.h."""
+    physics_id = PHYSICS_ATMOS_LINEAR_AG
+
+    def __init__(self, atmos):
+        if atmos.ref_state is None:
+            raise ValueError("AtmosAcousticGravityLinearModel needs a model with a reference state")
+        if atmos.orientation == ORIENT_NONE:
+            raise ValueError("AtmosAcousticGravityLinearModel needs a model with an orientation")
+        self.atmos = atmos
+        self.ps = atmos.ps
+        self.off_phi, self.off_ref = atmos.off_phi, atmos.off_ref
+        self.ns, self.naux = 5, atmos.naux
+        self.ngrad = self.ngradflux = self.ngradlap = self.nhyper = 0
+
+    def descriptor(self):
+        return self.atmos.descriptor()
+
+    def state_names(self):
+        return self.atmos.state_names()
+
+    def init_state_auxiliary(self, grid):
+        raise ValueError("AtmosAcousticGravityLinearModel shares the full model's auxiliary state: "
+                         "pass state_auxiliary=dg.state_auxiliary")
+
+    def init_state_prognostic(self, grid, aux, t):
+        return np.zeros((grid.nelem, self.ns, grid.Np))

@@ -1,0 +1,480 @@
+// ManyColumnLU (src/Numerics/SystemSolvers/columnwise_lu_solver.jl) and the low-storage additive
+// Runge-Kutta step that uses it (AdditiveRungeKuttaMethod.jl, LowStorageVariant).
+//
+// The operator is I - alpha L of a vertical-direction DG model on a stacked grid: a banded matrix
+// per column, one column = one horizontal node (i, j) of one stack of elements, n = Nq_v nstate
+// nvert unknowns ordered (state, vertical node, element) fastest first, bandwidths
+// p = q = Nq_v nstate - 1 (eband = 1, an inviscid law: columnwise_lu_solver.jl:56-74, :339-349).
+//
+// Band layout: band[(col * P + d) * ncol + c], P = p + q + 1, d = row - col + q (the reference's
+// A[i, j, d, col, h] with the column index c innermost).  Every kernel runs one matrix column c
+// per lane, so the 64 lanes of a wave read 512 contiguous bytes per (matrix column, diagonal).
+//
+// Assembly by probing (update_banded_matrix!, :404-480): one unit per (state, vertical node,
+// element mod 3) in every column, one evaluation of the vertical DG at t = NaN, the result
+// scattered into the band as Q + (-alpha) dQ (EulerOperator, BackwardEulerSolvers.jl:21-40).
+// Factorisation (band_lu_kernel!, :555-600) and substitution (band_forward_kernel! /
+// band_back_kernel!, :615-780) keep the reference's operations and order, without pivoting;
+// the substitutions keep the p + 1 wide window of the solution in registers.
+#include <math.h>
+
+#include <cstring>
+#include <string>
+
+#include "engine.h"
+
+namespace cmdg {
+namespace {
+
+constexpr int NS = 5;  // the dry law's prognostic states
+
+unsigned blocks(int64_t n, int nt = 256) { return (unsigned)((n + nt - 1) / nt); }
+
+__global__ void k_probe_set(double *Q, int64_t nreal, int Np, int nqh2, int nvert, int kin,
+                            int sin_, int ev0)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= nreal * NS * Np) return;
+    const int n = (int)(i % Np);
+    const int s = (int)((i / Np) % NS);
+    const int64_t e = i / ((int64_t)Np * NS);
+    const int v = (int)(e % nvert), k = n / nqh2;
+    Q[i] = (k == kin && s == sin_ && (v - ev0) % 3 == 0 && v >= ev0) ? 1.0 : 0.0;
+}
+
+// every real node of dQ belongs to the band of the probed column in its own or an adjacent element
+__global__ void k_probe_scatter(double *band, const double *Q, const double *dQ, int64_t nreal,
+                                int Np, int nqh2, int nqv, int nvert, int kin, int sin_, int ev0,
+                                int p, int q, int64_t ncol, double eps)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= nreal * NS * Np) return;
+    const int n = (int)(i % Np);
+    const int s = (int)((i / Np) % NS);
+    const int64_t e = i / ((int64_t)Np * NS);
+    const int v = (int)(e % nvert), k = n / nqh2, ij = n % nqh2;
+    const int64_t c = (e / nvert) * nqh2 + ij;
+    int evin = -1;
+    for (int dv = -1; dv <= 1; ++dv) {
+        const int ev = v + dv;
+        if (ev >= ev0 && ev < nvert && (ev - ev0) % 3 == 0) evin = ev;
+    }
+    if (evin < 0) return;
+    const int64_t jj = sin_ + (int64_t)NS * kin + (int64_t)NS * nqv * evin;
+    const int64_t ii = s + (int64_t)NS * k + (int64_t)NS * nqv * v;
+    const int64_t bb = ii - jj;
+    if (bb < -q || bb > p) return;
+    const int P = p + q + 1;
+    band[(jj * P + (bb + q)) * ncol + c] = Q[i] + eps * dQ[i];
+}
+
+// band_lu_kernel!: no pivoting, one matrix column per lane
+__global__ void k_band_lu(double *A, int64_t ncol, int64_t n, int p, int q)
+{
+    const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (c >= ncol) return;
+    const int P = p + q + 1;
+    auto at = [&](int64_t col, int d) -> double & { return A[(col * P + d) * ncol + c]; };
+    for (int64_t kk = 0; kk < n; ++kk) {
+        const double Aq = at(kk, q);
+        for (int ii = 1; ii <= p; ++ii) at(kk, q + ii) /= Aq;
+        for (int jj = 1; jj <= q; ++jj) {
+            if (jj + kk < n) {
+                const double Ajj = at(kk + jj, q - jj);
+                for (int ii = 1; ii <= p; ++ii) at(kk + jj, q + ii - jj) -= at(kk, q + ii) * Ajj;
+            }
+        }
+    }
+}
+
+// band_forward_kernel! then band_back_kernel! on one matrix column per lane.  W = p + 1 = q + 1 =
+// NQV * NS: the row loaded ahead (behind) is the same (node, state) of the next (previous)
+// element, so the window indices are static once the rows of an element are unrolled.
+template <int NQV>
+__global__ void __launch_bounds__(64) k_band_solve(double *X, const double *B, const double *A, int64_t ncol,
+                                                   int nvert, int nqh2)
+{
+    constexpr int W = NQV * NS, p = W - 1, q = W - 1, P = p + q + 1;
+    const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (c >= ncol) return;
+    const int Np = nqh2 * NQV;
+    const int64_t h = c / nqh2;
+    const int ij = (int)(c % nqh2);
+    const int64_t n = (int64_t)W * nvert;
+    // node (k, s) of vertical element v of this column in the (Np, nstate, nelem) layout
+    auto idx = [&](int v, int r) -> int64_t {
+        const int k = r / NS, s = r % NS;
+        return ((h * nvert + v) * NS + s) * (int64_t)Np + ij + (int64_t)nqh2 * k;
+    };
+    auto L = [&](int64_t col, int d) -> double { return A[(col * P + d) * ncol + c]; };
+    double lb[W];
+#pragma unroll
+    for (int r = 0; r < W; ++r) lb[r] = B[idx(0, r)];
+    for (int v = 0; v < nvert; ++v) {
+#pragma unroll
+        for (int r = 0; r < W; ++r) {
+            const int64_t jj = (int64_t)v * W + r;
+#pragma unroll
+            for (int ii = 1; ii <= p; ++ii) lb[ii] -= L(jj, ii + q) * lb[0];
+            X[idx(v, r)] = lb[0];
+#pragma unroll
+            for (int ii = 0; ii < p; ++ii) lb[ii] = lb[ii + 1];
+            lb[p] = 0.0;
+            if (jj + p + 1 < n) lb[p] = B[idx(v + 1, r)];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < W; ++r) lb[r] = X[idx(nvert - 1, r)];
+    for (int v = nvert - 1; v >= 0; --v) {
+#pragma unroll
+        for (int r = W - 1; r >= 0; --r) {
+            const int64_t jj = (int64_t)v * W + r;
+            lb[q] /= L(jj, q);
+#pragma unroll
+            for (int ii = 0; ii < q; ++ii) lb[ii] -= L(jj, ii) * lb[q];
+            X[idx(v, r)] = lb[q];
+#pragma unroll
+            for (int ii = q - 1; ii >= 0; --ii) lb[ii + 1] = lb[ii];
+            lb[0] = 0.0;
+            if (jj - q > 0) lb[0] = X[idx(v - 1, r)];
+        }
+    }
+}
+
+// stage_update! (LowStorageVariant, AdditiveRungeKuttaMethod.jl:565-605) over the real elements
+__global__ void k_ark_stage(const double *Q, double *const *Qs, const double *const *R,
+                            double *Qhat, int is, const double *__restrict__ rkcoeff,
+                            const double *__restrict__ dtA, int64_t len)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    double Qhat_i = Q[i];
+    double Qst = -0.0;
+    for (int js = 0; js < is; ++js) {
+        const double common = rkcoeff[js] * (js == 0 ? Q[i] : Qs[js][i]);
+        Qhat_i += common + dtA[js] * R[js][i];
+        Qst -= common;
+    }
+    Qs[is][i] = Qst;
+    Qhat[i] = Qhat_i;
+}
+
+__global__ void k_add(double *a, const double *b, int64_t len)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i < len) a[i] += b[i];
+}
+
+// solution_update! (LowStorageVariant, :670-690)
+__global__ void k_ark_solution(double *Q, const double *const *R, int nstages,
+                               const double *__restrict__ bdt, int64_t len)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    double q = Q[i];
+    for (int is = 0; is < nstages; ++is) q += bdt[is] * R[is][i];
+    Q[i] = q;
+}
+
+}  // namespace
+}  // namespace cmdg
+
+using namespace cmdg;
+
+struct cmdg_columnlu {
+    cmdg_handle lin = nullptr;
+    int dev = 0;  // the linear handle's device (destroy does not need the handle any more)
+    int nvert = 0, nqh2 = 0, nqv = 0, p = 0, q = 0, P = 0;
+    int64_t ncol = 0, n = 0;
+    double alpha = 0;
+    int state = 0;  // 0 empty, 1 assembled (I - alpha L), 2 factored
+    double *band = nullptr, *probe = nullptr, *dprobe = nullptr;
+    double *args = nullptr;  // device copies of the step's pointer tables and coefficients
+    hipEvent_t ev = nullptr;
+};
+
+namespace {
+
+int lu_fail(cmdg_columnlu *lu, int code, const std::string &msg)
+{
+    if (lu && lu->lin) lu->lin->err = "columnlu: " + msg;
+    return code;
+}
+
+int hip_ok(cmdg_columnlu *lu, hipError_t r, const char *what)
+{
+    if (r == hipSuccess) return CMDG_OK;
+    return lu_fail(lu, CMDG_ERR_HIP, std::string(what) + ": " + hipGetErrorString(r));
+}
+
+// make stream `later` wait for what has been enqueued on `earlier`
+int order(cmdg_columnlu *lu, hipStream_t earlier, hipStream_t later)
+{
+    if (earlier == later) return CMDG_OK;
+    if (int r = hip_ok(lu, hipEventRecord(lu->ev, earlier), "hipEventRecord")) return r;
+    return hip_ok(lu, hipStreamWaitEvent(later, lu->ev, 0), "hipStreamWaitEvent");
+}
+
+int assemble(cmdg_columnlu *lu, double alpha)
+{
+    EngineBase *e = lu->lin->eng;
+    hipStream_t st = e->s_comp;
+    const int64_t len = e->nreal * NS * e->Np;
+    const size_t bytes = (size_t)lu->n * lu->P * lu->ncol * sizeof(double);
+    if (int r = hip_ok(lu, hipMemsetAsync(lu->band, 0, bytes, st), "hipMemsetAsync")) return r;
+    const int nev = lu->nvert < 3 ? lu->nvert : 3;
+    for (int ev0 = 0; ev0 < nev; ++ev0)
+        for (int s = 0; s < NS; ++s)
+            for (int k = 0; k < lu->nqv; ++k) {
+                hipLaunchKernelGGL(k_probe_set, dim3(blocks(len)), dim3(256), 0, st, lu->probe, e->nreal,
+                                   e->Np, lu->nqh2, lu->nvert, k, s, ev0);
+                if (int r = cmdg_rhs_async(lu->lin, lu->dprobe, lu->probe, NAN, 1.0, 0.0)) return r;
+                hipLaunchKernelGGL(k_probe_scatter, dim3(blocks(len)), dim3(256), 0, st, lu->band,
+                                   lu->probe, lu->dprobe, e->nreal, e->Np, lu->nqh2, lu->nqv, lu->nvert,
+                                   k, s, ev0, lu->p, lu->q, lu->ncol, -alpha);
+            }
+    lu->alpha = alpha;
+    lu->state = 1;
+    return hip_ok(lu, hipGetLastError(), "assembly kernels");
+}
+
+int factor(cmdg_columnlu *lu)
+{
+    hipLaunchKernelGGL(k_band_lu, dim3(blocks(lu->ncol, 64)), dim3(64), 0, lu->lin->eng->s_comp, lu->band,
+                       lu->ncol, lu->n, lu->p, lu->q);
+    lu->state = 2;
+    return hip_ok(lu, hipGetLastError(), "band_lu");
+}
+
+int update(cmdg_columnlu *lu, double alpha)
+{
+    if (int r = assemble(lu, alpha)) return r;
+    return factor(lu);
+}
+
+// solve on the linear handle's stream
+int solve(cmdg_columnlu *lu, double *X, const double *B)
+{
+    if (lu->state != 2) return lu_fail(lu, CMDG_ERR_INVALID, "the band is not factored");
+    hipStream_t st = lu->lin->eng->s_comp;
+    const dim3 g(blocks(lu->ncol, 64)), b(64);
+    switch (lu->nqv) {
+    case 5: hipLaunchKernelGGL(k_band_solve<5>, g, b, 0, st, X, B, lu->band, lu->ncol, lu->nvert, lu->nqh2); break;
+    case 6: hipLaunchKernelGGL(k_band_solve<6>, g, b, 0, st, X, B, lu->band, lu->ncol, lu->nvert, lu->nqh2); break;
+    default: return lu_fail(lu, CMDG_ERR_UNSUPPORTED, "vertical order not compiled in (have N = 4, 5)");
+    }
+    return hip_ok(lu, hipGetLastError(), "band solve");
+}
+
+}  // namespace
+
+extern "C" {
+
+int cmdg_columnlu_create(cmdg_handle linear, int32_t nvertelem, double alpha, cmdg_columnlu_handle *out)
+{
+    if (!linear || !out || nvertelem < 1) return CMDG_ERR_INVALID;
+    *out = nullptr;
+    EngineBase *e = linear->eng;
+    DevGuard guard_(e);
+    cmdg_columnlu tmp;
+    tmp.lin = linear;
+    if (e->direction != DIR_VERTICAL || !e->stacked)
+        return lu_fail(&tmp, CMDG_ERR_INVALID, "the operator must be a VerticalDirection DG model on a stacked grid");
+    if (e->ns != NS || e->ngf != 0)
+        return lu_fail(&tmp, CMDG_ERR_UNSUPPORTED, "five prognostic states and no second-order terms (eband = 1) only");
+    if (e->NQV != 5 && e->NQV != 6)
+        return lu_fail(&tmp, CMDG_ERR_UNSUPPORTED, "vertical order not compiled in (have N = 4, 5)");
+    if (e->nreal % nvertelem != 0)
+        return lu_fail(&tmp, CMDG_ERR_INVALID, "the real elements are not whole stacks");
+    auto *lu = new cmdg_columnlu(tmp);
+    lu->dev = e->dev;
+    lu->nvert = nvertelem;
+    lu->nqh2 = e->NQ * e->NQ;
+    lu->nqv = e->NQV;
+    lu->p = lu->q = lu->nqv * NS - 1;  // lower_bandwidth(N, nstate, eband = 1)
+    lu->P = lu->p + lu->q + 1;
+    lu->ncol = (e->nreal / nvertelem) * lu->nqh2;
+    lu->n = (int64_t)lu->nqv * NS * nvertelem;
+    const size_t band = (size_t)lu->n * lu->P * lu->ncol * sizeof(double);
+    const size_t states = 2 * (size_t)e->nelem * NS * e->Np * sizeof(double);
+    size_t freeb = 0, total = 0;
+    int r = hip_ok(lu, hipMemGetInfo(&freeb, &total), "hipMemGetInfo");
+    if (!r && band + states + (64u << 20) > freeb) {
+        char msg[256];
+        snprintf(msg, sizeof msg,
+                 "the band needs %.3f GB (%lld columns x %lld rows x %d diagonals x 8 B) plus %.3f GB of "
+                 "probe states; %.3f GB of device memory are free",
+                 band / 1e9, (long long)lu->ncol, (long long)lu->n, lu->P, states / 1e9, freeb / 1e9);
+        r = lu_fail(lu, CMDG_ERR_INVALID, msg);
+    }
+    if (!r) r = hip_ok(lu, hipMalloc(&lu->band, band), "hipMalloc(band)");
+    if (!r) r = hip_ok(lu, hipMalloc(&lu->probe, states / 2), "hipMalloc(probe)");
+    if (!r) r = hip_ok(lu, hipMalloc(&lu->dprobe, states / 2), "hipMalloc(probe)");
+    if (!r) r = hip_ok(lu, hipMalloc(&lu->args, 64 * sizeof(double)), "hipMalloc(args)");
+    if (!r) r = hip_ok(lu, hipMemset(lu->probe, 0, states / 2), "hipMemset");
+    if (!r) r = hip_ok(lu, hipMemset(lu->dprobe, 0, states / 2), "hipMemset");
+    if (!r) r = hip_ok(lu, hipEventCreateWithFlags(&lu->ev, hipEventDisableTiming), "hipEventCreate");
+    if (!r) r = update(lu, alpha);
+    if (!r) r = hip_ok(lu, hipStreamSynchronize(e->s_comp), "hipStreamSynchronize");
+    if (r) {
+        cmdg_columnlu_destroy(lu);
+        return r;
+    }
+    *out = lu;
+    return CMDG_OK;
+}
+
+int cmdg_columnlu_assemble(cmdg_columnlu_handle lu, double alpha)
+{
+    if (!lu) return CMDG_ERR_INVALID;
+    DevGuard guard_(lu->lin->eng);
+    if (int r = assemble(lu, alpha)) return r;
+    return hip_ok(lu, hipStreamSynchronize(lu->lin->eng->s_comp), "hipStreamSynchronize");
+}
+
+int cmdg_columnlu_update(cmdg_columnlu_handle lu, double alpha)
+{
+    if (!lu) return CMDG_ERR_INVALID;
+    DevGuard guard_(lu->lin->eng);
+    if (int r = update(lu, alpha)) return r;
+    return hip_ok(lu, hipStreamSynchronize(lu->lin->eng->s_comp), "hipStreamSynchronize");
+}
+
+int cmdg_columnlu_solve(cmdg_columnlu_handle lu, double *Q, const double *Qrhs)
+{
+    if (!lu || !Q || !Qrhs) return CMDG_ERR_INVALID;
+    DevGuard guard_(lu->lin->eng);
+    if (int r = solve(lu, Q, Qrhs)) return r;
+    return hip_ok(lu, hipStreamSynchronize(lu->lin->eng->s_comp), "hipStreamSynchronize");
+}
+
+int cmdg_columnlu_info(cmdg_columnlu_handle lu, int64_t out[8])
+{
+    if (!lu || !out) return CMDG_ERR_INVALID;
+    out[0] = lu->n;
+    out[1] = lu->p;
+    out[2] = lu->q;
+    out[3] = lu->ncol;
+    out[4] = lu->n * lu->P * lu->ncol * (int64_t)sizeof(double);
+    out[5] = lu->state;
+    out[6] = lu->nvert;
+    out[7] = lu->nqv;
+    return CMDG_OK;
+}
+
+int cmdg_columnlu_alpha(cmdg_columnlu_handle lu, double *alpha)
+{
+    if (!lu || !alpha) return CMDG_ERR_INVALID;
+    *alpha = lu->alpha;
+    return CMDG_OK;
+}
+
+int cmdg_columnlu_export_band(cmdg_columnlu_handle lu, int64_t column, double *out)
+{
+    if (!lu || !out || column < 0 || column >= lu->ncol) return CMDG_ERR_INVALID;
+    DevGuard guard_(lu->lin->eng);
+    if (int r = hip_ok(lu, hipStreamSynchronize(lu->lin->eng->s_comp), "hipStreamSynchronize")) return r;
+    // element (d, col) of the reference's A[:, :] at out[col * P + d]
+    return hip_ok(lu, hipMemcpy2D(out, sizeof(double), lu->band + column, lu->ncol * sizeof(double),
+                                  sizeof(double), (size_t)lu->n * lu->P, hipMemcpyDeviceToHost),
+                  "hipMemcpy2D");
+}
+
+int cmdg_columnlu_destroy(cmdg_columnlu_handle lu)
+{
+    if (!lu) return CMDG_ERR_INVALID;
+    {
+        // the linear handle may already be destroyed: bind the device by hand, wait for it
+        int prev = -1;
+        (void)hipGetDevice(&prev);
+        (void)hipSetDevice(lu->dev);
+        (void)hipDeviceSynchronize();
+        if (lu->band) (void)hipFree(lu->band);
+        if (lu->probe) (void)hipFree(lu->probe);
+        if (lu->dprobe) (void)hipFree(lu->dprobe);
+        if (lu->args) (void)hipFree(lu->args);
+        if (lu->ev) (void)hipEventDestroy(lu->ev);
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+    delete lu;
+    return CMDG_OK;
+}
+
+int cmdg_ark_step(cmdg_handle full, cmdg_columnlu_handle lu, double *Q, double *const *work, double t,
+                  double dt, int32_t nstages, const double *rka_explicit, const double *rka_implicit,
+                  const double *rkb, const double *rkc, int32_t split_explicit_implicit)
+{
+    if (!full || !lu || !Q || !work || !rka_explicit || !rka_implicit || !rkb || !rkc) return CMDG_ERR_INVALID;
+    if (nstages < 2 || nstages > 4) return lu_fail(lu, CMDG_ERR_INVALID, "ark: 2 to 4 stages");
+    EngineBase *ef = full->eng, *el = lu->lin->eng;
+    if (ef->nreal != el->nreal || ef->Np != el->Np || ef->ns != NS)
+        return lu_fail(lu, CMDG_ERR_INVALID, "ark: the full and the linear model live on different grids");
+    DevGuard guard_(ef);
+    const int ns = nstages;
+    auto A = [&](const double *m, int i, int j) { return m[i * ns + j]; };  // row-major (stage, stage)
+    // work: Qstages[1..ns-1], Rstages[0..ns-1], Qhat, Qtt
+    double *Qs[4] = {Q, nullptr, nullptr, nullptr}, *R[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int i = 1; i < ns; ++i) Qs[i] = work[i - 1];
+    for (int i = 0; i < ns; ++i) R[i] = work[ns - 1 + i];
+    double *Qhat = work[2 * ns - 1], *Qtt = work[2 * ns];
+    const int64_t len = ef->nreal * NS * ef->Np;
+    hipStream_t sf = ef->s_comp, sl = el->s_comp;
+    // device tables: Qs (4), R (4), then per stage rkcoeff (4) and dt A (4), then b dt (4)
+    double host[64] = {0};
+    std::memcpy(host, Qs, sizeof Qs);
+    std::memcpy(host + 4, R, sizeof R);
+    for (int is = 1; is < ns; ++is)
+        for (int js = 0; js < is; ++js) {
+            host[8 + 8 * is + js] = split_explicit_implicit
+                                        ? A(rka_implicit, is, js) / A(rka_implicit, is, is)
+                                        : (A(rka_implicit, is, js) - A(rka_explicit, is, js)) / A(rka_implicit, is, is);
+            host[12 + 8 * is + js] = dt * A(rka_explicit, is, js);
+        }
+    for (int is = 0; is < ns; ++is) host[48 + is] = rkb[is] * dt;
+    int r = hip_ok(lu, hipMemcpyAsync(lu->args, host, sizeof host, hipMemcpyHostToDevice, sf), "hipMemcpyAsync");
+    if (!r) r = hip_ok(lu, hipStreamSynchronize(sf), "hipStreamSynchronize");  // (host is a stack buffer)
+    if (r) return r;
+    double *const *dQs = (double *const *)lu->args;
+    const double *const *dR = (const double *const *)(lu->args + 4);
+    const unsigned g = blocks(len);
+    // the first stage's explicit tendency
+    if ((r = cmdg_rhs_async(full, R[0], Qs[0], t + rkc[0] * dt, 1.0, 0.0))) return r;
+    if (split_explicit_implicit) {
+        if ((r = order(lu, sf, sl))) return r;
+        if ((r = cmdg_rhs_async(lu->lin, R[0], Qs[0], t + rkc[0] * dt, -1.0, 1.0))) return r;
+        if ((r = order(lu, sl, sf))) return r;
+    }
+    for (int is = 1; is < ns; ++is) {
+        const double stagetime = t + rkc[is] * dt;
+        hipLaunchKernelGGL(k_ark_stage, dim3(g), dim3(256), 0, sf, Q, dQs, dR, Qhat, is,
+                           lu->args + 8 + 8 * is, lu->args + 12 + 8 * is, len);
+        if ((r = order(lu, sf, sl))) return r;
+        // Q_tt = Qhat + alpha L(Q_tt), alpha = dt a_ii; refactored when alpha changes
+        const double alpha = dt * A(rka_implicit, is, is);
+        if (alpha != lu->alpha || lu->state != 2) {
+            if ((r = update(lu, alpha))) return r;
+        }
+        if ((r = solve(lu, Qtt, Qhat))) return r;
+        hipLaunchKernelGGL(k_add, dim3(g), dim3(256), 0, sl, Qs[is], Qtt, len);
+        if ((r = order(lu, sl, sf))) return r;
+        if ((r = cmdg_rhs_async(full, R[is], Qs[is], stagetime, 1.0, 0.0))) return r;
+        if (split_explicit_implicit) {
+            // "full minus linear" as two evaluations (not the reference's fused RemBL kernel)
+            if ((r = order(lu, sf, sl))) return r;
+            if ((r = cmdg_rhs_async(lu->lin, R[is], Qs[is], stagetime, -1.0, 1.0))) return r;
+            if ((r = order(lu, sl, sf))) return r;
+        }
+    }
+    if (split_explicit_implicit) {
+        // rhs_implicit!(Rstages[is], Qstages[is], p, stagetime, increment = true)
+        if ((r = order(lu, sf, sl))) return r;
+        for (int is = 0; is < ns; ++is)
+            if ((r = cmdg_rhs_async(lu->lin, R[is], Qs[is], t + rkc[is] * dt, 1.0, 1.0))) return r;
+        if ((r = order(lu, sl, sf))) return r;
+    }
+    hipLaunchKernelGGL(k_ark_solution, dim3(g), dim3(256), 0, sf, Q, dR, ns, lu->args + 48, len);
+    if ((r = hip_ok(lu, hipGetLastError(), "ark kernels"))) return r;
+    return hip_ok(lu, hipStreamSynchronize(sf), "hipStreamSynchronize");
+}
+
+}  // extern "C"

@@ -1,0 +1,57 @@
+// Engine instantiations for AtmosAcousticGravityLinearModel (physics_atmos_linear.h).  The law
+// shares the full DryAtmosModel's auxiliary array, so the count comes from the full model's
+// parameter block: orientation and reference state are required, hyperdiffusion or
+// SmagorinskyLilly add one column each.
+#include "engine.h"
+#include "physics_atmos_linear.h"
+
+namespace cmdg {
+
+static int naux_of_full(const int32_t *ip)
+{
+    int32_t c[6];
+    counts_atmos(ip, c);
+    return c[1];
+}
+
+int counts_atmos_linear(const int32_t *ip, int32_t out[6])
+{
+    out[0] = 5;
+    out[1] = naux_of_full(ip);
+    out[2] = out[3] = out[4] = out[5] = 0;
+    return CMDG_OK;
+}
+
+template <int NQ>
+static EngineBase *pick(const cmdg_desc *d, std::string &err)
+{
+    switch (naux_of_full(d->iparam)) {
+    case 16: return make_engine<AtmosLinearAG<16>, NQ>(d);  // no hyperdiffusion, no Smagorinsky
+    case 17: return make_engine<AtmosLinearAG<17>, NQ>(d);  // DryBiharmonic (Held-Suarez)
+    default:
+        err = "AtmosAcousticGravityLinearModel: the full model's auxiliary layout is not compiled in "
+              "(have orientation + reference state, with or without hyperdiffusion)";
+        return nullptr;
+    }
+}
+
+EngineBase *make_engine_atmos_linear(const cmdg_desc *d, std::string &err)
+{
+    if (d->iparam[0] == 0 || d->iparam[1] == 0) {
+        err = "AtmosAcousticGravityLinearModel needs a model with an orientation and a reference state";
+        return nullptr;
+    }
+    if (d->nf_first != CMDG_RUSANOV && d->nf_first != CMDG_CENTRAL_FIRST_ORDER) {
+        err = "AtmosAcousticGravityLinearModel: Rusanov or central first-order flux only";
+        return nullptr;
+    }
+    switch (d->N[0]) {
+    case 4: return pick<5>(d, err);
+    case 5: return pick<6>(d, err);
+    default:
+        err = "AtmosAcousticGravityLinearModel: polynomial order not compiled in (have N = 4, 5)";
+        return nullptr;
+    }
+}
+
+}  // namespace cmdg

@@ -1,0 +1,147 @@
+// Device functor for AtmosAcousticGravityLinearModel (dry), the linear balance law the reference's
+// IMEX configurations solve implicitly in the vertical.  Restates, term by term and in the
+// reference's summation order:
+//   src/Atmos/Model/linear.jl:17-55 (linearized_air_pressure, DryModel), :95-345 (state
+//       layout shared with the full model, no second-order terms, wavespeed soundspeed(ref.T),
+//       AtmosBC boundary), linear_atmos_tendencies.jl (which terms),
+//   linear_tendencies.jl (Advect, LinearPressureGradient, LinearEnergyFlux, Gravity source).
+// The auxiliary array is the full DryAtmosModel's (Phi, grad Phi, reference state ...), shared
+// with it (DGModel(...; state_auxiliary = dg.state_auxiliary)): NAUX is the full model's count.
+//
+// Parameter block: the full model's (climatemachine.jl_amd/atmos.py); this law reads
+// dparam[2..6] R_d cp_d cv_d T_0 grav.  Boundaries: every tag is AtmosBC() (Impenetrable
+// FreeSlip, Insulating), boundary_conditions(::AtmosLinearModel) at linear.jl:215-216.
+#pragma once
+#include "cmdg_common.h"
+
+namespace cmdg {
+
+struct AtmosLinearParams {
+    double R_d, cp_d, cv_d, T_0;
+};
+
+template <int NAUX_FULL>
+struct AtmosLinearAG {
+    using Params = AtmosLinearParams;
+    // auxiliary layout of DryAtmos with orientation and reference state (physics_atmos.h)
+    static constexpr int OPHI = 3, OREF = 7;
+    static constexpr int NS = 5, NAUX = NAUX_FULL, NGRAD = 0, NGF = 0, NGL = 0, NHYP = 0;
+    static constexpr bool HAS_UPDATE_AUX = false, FUSE_UPDATE_AUX = false, HAS_SOURCE = true;
+    static constexpr bool HAS_COURANT = false, HAS_PENALTY = false;
+    static constexpr int NUPD = 0, NDER = 0;
+    // faces read Phi and the reference rho, p, T, rho e
+    static constexpr int NFAUX = 5;
+    __host__ __device__ static constexpr int face_aux(int i) { return i == 0 ? OPHI : OREF + (i - 1); }
+    __host__ __device__ static constexpr int upd_aux(int) { return 0; }
+    __host__ __device__ static constexpr int hv_indexmap(int) { return 0; }
+    __host__ __device__ static bool needs_gradflux(const Params &) { return false; }
+    static void make_params(Params &p, const int32_t *, const double *dp)
+    {
+        p.R_d = dp[2];
+        p.cp_d = dp[3];
+        p.cv_d = dp[4];
+        p.T_0 = dp[5];
+    }
+    // linearized_air_pressure (linear.jl:17-36) for DryModel: the moisture terms are zeros
+    __device__ static double p_lin(const Params &m, const double *Q, const double *aux)
+    {
+        const double rhoe_pot = Q[0] * aux[OPHI];
+        return Q[0] * m.R_d * m.T_0 + m.R_d / m.cv_d * (Q[4] - rhoe_pot);
+    }
+    __device__ static double soundspeed(const Params &m, double T)
+    {
+        const double gamma = m.cp_d / m.cv_d;
+        return sqrt(gamma * m.R_d * T);
+    }
+
+    __device__ static void flux_first_order(const Params &m, double *F, const double *Q,
+                                            const double *aux, double, int)
+    {
+        const double pL = p_lin(m, Q, aux);
+        const double h_ref = (aux[OREF + 3] + aux[OREF + 1]) / aux[OREF];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) F[d] = Q[1 + d];  // Advect
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) F[d + 3 * (1 + c)] = d == c ? pL : 0.0;  // pL I
+#pragma unroll
+        for (int d = 0; d < 3; ++d) F[d + 12] = h_ref * Q[1 + d];  // LinearEnergyFlux
+    }
+    __device__ static void flux_second_order(const Params &, double *, const double *,
+                                             const double *, const double *, const double *, double)
+    {
+    }
+    // Gravity (linear_tendencies.jl: -rho grad Phi in VerticalDirection / EveryDirection only)
+    __device__ static void source(const Params &, double *S, const double *Q, const double *,
+                                  const double *aux, const double *, double, int direction)
+    {
+        S[0] = 0;
+        S[4] = 0;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) S[1 + d] = direction == DIR_HORIZONTAL ? 0.0 : -Q[0] * aux[OPHI + 1 + d];
+    }
+    __device__ static void init_derived(const Params &, double *, const double *) {}
+    __device__ static void gradient_argument(const Params &, double *, const double *,
+                                             const double *, double)
+    {
+    }
+    __device__ static void gradient_flux(const Params &, double *, const double *, const double *,
+                                         const double *, double)
+    {
+    }
+    __device__ static void post_gradient_laplacian(const Params &, double *, const double *,
+                                                   const double *, const double *, double)
+    {
+    }
+    // wavespeed(::AtmosLinearModel) = soundspeed_air(ref.T) (linear.jl:200-212)
+    __device__ static void wavespeed(const Params &m, double *ws, const double *, const double *,
+                                     const double *aux, double, int)
+    {
+        const double c = soundspeed(m, aux[OREF + 2]);
+#pragma unroll
+        for (int s = 0; s < 5; ++s) ws[s] = c;
+    }
+    __device__ static void update_penalty(const Params &, double *, const double *, const double *,
+                                          const double *)
+    {
+    }
+    // atmos_boundary_state! of AtmosBC(): Impenetrable(FreeSlip) reflects the normal momentum,
+    // Insulating leaves the energy; the plus-side auxiliary state is the minus side's
+    __device__ static void boundary_state(const Params &, int, int, double *QP, double *,
+                                          const double *n, const double *QM, const double *,
+                                          double, const double *, const double *)
+    {
+        const double dn = QM[1] * n[0] + QM[2] * n[1] + QM[3] * n[2];
+        const double f = 2 * dn;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) QP[1 + d] -= f * n[d];
+    }
+    __device__ static void boundary_flux_second_order(const Params &, int, double *, double *,
+                                                      double *, double *, double *, const double *,
+                                                      const double *, const double *,
+                                                      const double *, const double *, double,
+                                                      const double *, const double *,
+                                                      const double *)
+    {
+    }
+    __device__ static void boundary_state_divergence(const Params &, int, double *, double *,
+                                                     const double *, const double *,
+                                                     const double *, double)
+    {
+    }
+    __device__ static void boundary_state_higher_order(const Params &, int, double *, double *,
+                                                       double *, const double *, const double *,
+                                                       const double *, const double *, double)
+    {
+    }
+    __device__ static void update_aux(const Params &, const double *, double *, double) {}
+    __host__ __device__ static bool update_aux_active(const Params &) { return false; }
+    __device__ static double courant(const Params &, int, const double *, const double *,
+                                     const double *, double, double, double, int)
+    {
+        return 0.0;
+    }
+};
+
+}  // namespace cmdg

@@ -11,13 +11,18 @@ Reference: ``LowStorageRungeKutta2N`` / ``dostep!`` / ``update!``
 The stage loop itself runs inside libcmdg (``cmdg_lsrk_run``): five fused
 RHS+update passes per step, enqueued without host synchronisation.
 """
+import ctypes as C
+import math
 from fractions import Fraction
+
+from .systemsolvers import ManyColumnLU
 
 __all__ = ["LSRK54CarpenterKennedy", "LSRK144NiegemannDiehlBusch", "solve",
            "LowStorageRungeKutta2N", "LSRK144_COEFFICIENTS", "StrongStabilityPreservingRungeKutta",
            "SSPRK22Heuns", "SSPRK22Ralstons", "SSPRK33ShuOsher", "SSPRK34SpiteriRuuth",
            "SSPRK_COEFFICIENTS", "LowStorageRungeKutta3N", "LS3NRK44Classic", "LS3NRK33Heuns",
-           "LS3N_COEFFICIENTS"]
+           "LS3N_COEFFICIENTS", "AdditiveRungeKutta", "ARK2GiraldoKellyConstantinescu",
+           "ark2gkc_tableau", "LinearBackwardEulerSolver", "ManyColumnLU"]
 
 
 def _f(num, den):
@@ -180,6 +185,98 @@ def _ls3n(name):
 LS3NRK44Classic, LS3NRK33Heuns = _ls3n("LS3NRK44Classic"), _ls3n("LS3NRK33Heuns")
 
 
+# -- IMEX: additive Runge-Kutta, LowStorageVariant (AdditiveRungeKuttaMethod.jl) ----------------
+
+class LinearBackwardEulerSolver:
+    """``LinearBackwardEulerSolver(solver; isadjustable = true)`` (BackwardEulerSolvers.jl:108-190):
+    solves ``Q = Qhat + alpha L(Q)`` with a direct column solver, refactored whenever alpha
+    changes."""
+
+    def __init__(self, solver, isadjustable=True):
+        if not isinstance(solver, ManyColumnLU):
+            raise TypeError("LinearBackwardEulerSolver: only ManyColumnLU() is implemented")
+        if not isadjustable:
+            raise ValueError("LinearBackwardEulerSolver: isadjustable = false is not implemented")
+        self.solver, self.isadjustable = solver, True
+
+
+def ark2gkc_tableau(paperversion=False):
+    """``(RKA_explicit, RKA_implicit, RKB, RKC)`` of ``ARK2GiraldoKellyConstantinescu``
+    (AdditiveRungeKuttaMethod.jl:839-895), the same Float64 expressions; B and C are shared by
+    the explicit and implicit tables."""
+    s2 = math.sqrt(2)
+    a32 = (3 + 2 * s2) / 6 if paperversion else float(Fraction(1, 2))
+    RKA_explicit = ((0.0, 0.0, 0.0), (2 - s2, 0.0, 0.0), (1 - a32, a32, 0.0))
+    RKA_implicit = ((0.0, 0.0, 0.0), (1 - 1 / s2, 1 - 1 / s2, 0.0),
+                    (1 / (2 * s2), 1 / (2 * s2), 1 - 1 / s2))
+    RKB = (1 / (2 * s2), 1 / (2 * s2), 1 - 1 / s2)
+    RKC = (0.0, 2 - s2, 1.0)
+    return RKA_explicit, RKA_implicit, RKB, RKC
+
+
+class AdditiveRungeKutta:
+    """``AdditiveRungeKutta(F, L, backward_euler_solver, RKA_explicit, RKA_implicit, RKB, RKC,
+    split_explicit_implicit, LowStorageVariant(), Q; dt, t0)`` (AdditiveRungeKuttaMethod.jl:95-200)
+    with ``LinearBackwardEulerSolver(ManyColumnLU())``.  ``dg`` is the full model (every
+    direction), ``linear_dg`` the vertical linear model on the same auxiliary state.  One step is
+    one ``cmdg_ark_step``; the column solver is built once for ``dt a_ii`` and refactored when
+    ``dt`` changes (``updatedt``)."""
+
+    def __init__(self, dg, linear_dg, backward_euler_solver, RKA_explicit, RKA_implicit, RKB, RKC,
+                 Q, dt=None, t0=0.0, split_explicit_implicit=False):
+        import numpy as np
+        from .systemsolvers import ColumnLU
+        assert dt is not None
+        if not isinstance(backward_euler_solver, LinearBackwardEulerSolver):
+            raise TypeError("AdditiveRungeKutta: a LinearBackwardEulerSolver(ManyColumnLU()) is needed")
+        A_e = np.ascontiguousarray(RKA_explicit, dtype=np.float64)
+        A_i = np.ascontiguousarray(RKA_implicit, dtype=np.float64)
+        ns = A_e.shape[0]
+        diag = [A_i[i, i] for i in range(ns)]
+        # LowStorageVariant preconditions (:157-168): diagonal (0, c, ..., c)
+        if diag[0] != 0 or len(set(diag[1:])) != 1 or diag[1] == 0:
+            raise ValueError("LowStorageVariant needs an implicit diagonal (0, c, ..., c)")
+        self.dg, self.linear_dg = dg, linear_dg
+        self.RKA_explicit, self.RKA_implicit = A_e, A_i
+        self.RKB = np.ascontiguousarray(RKB, dtype=np.float64)
+        self.RKC = np.ascontiguousarray(RKC, dtype=np.float64)
+        self.split_explicit_implicit = bool(split_explicit_implicit)
+        self.dt, self.t, self.steps = float(dt), t0, 0
+        self.work = [dg.create_state(Q.shape[1]) for _ in range(2 * ns + 1)]
+        self._ptrs = (C.c_void_p * len(self.work))(*[w.data_ptr() for w in self.work])
+        self.lu = ColumnLU(linear_dg, self.dt * diag[1])
+
+    def updatedt(self, dt):
+        """``updatedt!``: the next stage refactors the column matrices for ``dt a_ii``."""
+        self.dt = float(dt)
+
+    def dostep(self, Q, nsteps=1, dt=None):
+        from . import _lib
+        dt = self.dt if dt is None else dt
+        p = lambda a: C.c_void_p(a.ctypes.data)
+        self.dg._torch_ready()
+        for _ in range(int(nsteps)):
+            _lib.check(self.dg.L.cmdg_ark_step(
+                self.dg.handle, self.lu.handle, Q.data_ptr(), C.cast(self._ptrs, C.c_void_p),
+                float(self.t), float(dt), len(self.RKB), p(self.RKA_explicit),
+                p(self.RKA_implicit), p(self.RKB), p(self.RKC),
+                int(self.split_explicit_implicit)), self.linear_dg.handle)
+            _advance(self, 1, dt)
+
+    def close(self):
+        self.lu.close()
+
+
+def ARK2GiraldoKellyConstantinescu(dg, linear_dg, backward_euler_solver, Q, dt=None, t0=0.0,
+                                   split_explicit_implicit=False, paperversion=False):
+    """``ARK2GiraldoKellyConstantinescu(F, L, backward_euler_solver, Q; dt, t0,
+    split_explicit_implicit, variant = LowStorageVariant(), paperversion)``
+    (AdditiveRungeKuttaMethod.jl:839-895)."""
+    A_e, A_i, B, Cc = ark2gkc_tableau(paperversion)
+    return AdditiveRungeKutta(dg, linear_dg, backward_euler_solver, A_e, A_i, B, Cc, Q, dt=dt,
+                              t0=t0, split_explicit_implicit=split_explicit_implicit)
+
+
 def solve(Q, solver, timeend=None, numberofsteps=0, adjustfinalstep=True, callbacks=()):
     """``solve!(Q, solver; timeend, adjustfinalstep, numberofsteps, callbacks)``: steps are issued
     one library call each, the last (shortened) step like ``general_dostep!`` does.
@@ -203,6 +300,9 @@ def solve(Q, solver, timeend=None, numberofsteps=0, adjustfinalstep=True, callba
             solver.dostep(Q, 1)
         step += 1
         stop = False
+        if cbs:
+            # a callback reads or writes Q: the step (enqueued without a host wait) finishes first
+            solver.dg.synchronize()
         for c in cbs:
             c[2] += 1
             if c[2] >= c[0]:

@@ -1,0 +1,116 @@
+"""Host side of ``ManyColumnLU`` (src/Numerics/SystemSolvers/columnwise_lu_solver.jl): the
+banded column matrices of ``I - alpha L`` for a vertical-direction DG model, factored and solved
+on the device (csrc/columnlu.hip, ``cmdg_columnlu_*`` in include/cmdg.h).
+
+Band layout on the device: ``band[(col * P + d) * ncol + c]``, ``P = p + q + 1``,
+``d = row - col + q``, ``c`` the column (horizontal node ``i + Nq j`` of stack ``h`` is column
+``h Nq^2 + i + Nq j``); the reference's ``A[i, j, d + 1, col + 1, h + 1]``."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+__all__ = ["ManyColumnLU", "ColumnLU", "lower_bandwidth", "upper_bandwidth", "band_offset",
+           "band_bytes"]
+
+
+def lower_bandwidth(N, nstate, eband):
+    """``lower_bandwidth(N, nstate, eband) = (N + 1) nstate eband - 1`` (columnwise_lu_solver.jl:69)."""
+    return (N + 1) * nstate * eband - 1
+
+
+upper_bandwidth = lower_bandwidth
+
+
+def band_offset(column, row, diag, n, p, q, ncol):
+    """Offset (in doubles) of band entry ``diag`` (``d = matrix row - matrix column + q``) of
+    matrix column ``row`` of column ``column`` in the device band."""
+    assert 0 <= column < ncol and 0 <= row < n and 0 <= diag <= p + q
+    return (row * (p + q + 1) + diag) * ncol + column
+
+
+def band_bytes(ncol, n, p, q):
+    """Bytes of the device band: ``ncol n (p + q + 1) 8``."""
+    return ncol * n * (p + q + 1) * 8
+
+
+class ManyColumnLU:
+    """``ManyColumnLU()``: one banded LU per column of the vertical operator."""
+
+
+class ColumnLU:
+    """``prefactorize(EulerOperator(linear_dg, -alpha), ManyColumnLU(), Q, nothing, NaN)``:
+    assembles and factors ``I - alpha L`` for every column of ``linear_dg`` (a
+    ``VerticalDirection`` ``DGModel`` on a stacked grid)."""
+
+    def __init__(self, linear_dg, alpha):
+        g = linear_dg.grid
+        if not (g.topology.isstacked and g.topology.stacksize):
+            raise _lib.CmdgError("ManyColumnLU needs a stacked grid")
+        self.dg = linear_dg
+        self.nvert = int(g.topology.stacksize)
+        _check_stack_order(g, self.nvert)
+        h = C.c_void_p()
+        linear_dg._torch_ready()
+        _lib.check(linear_dg.L.cmdg_columnlu_create(linear_dg.handle, self.nvert, float(alpha),
+                                                    C.byref(h)), linear_dg.handle)
+        self.handle = h
+        info = (C.c_int64 * 8)()
+        _lib.check(linear_dg.L.cmdg_columnlu_info(h, C.cast(info, C.c_void_p)), linear_dg.handle)
+        self.n, self.p, self.q, self.ncol, self.band_bytes = [int(v) for v in info[:5]]
+
+    @property
+    def alpha(self):
+        a = C.c_double()
+        _lib.check(self.dg.L.cmdg_columnlu_alpha(self.handle, C.cast(C.byref(a), C.c_void_p)))
+        return a.value
+
+    def update(self, alpha):
+        """``update_backward_Euler_solver!``: reassemble and refactor for ``alpha``."""
+        _lib.check(self.dg.L.cmdg_columnlu_update(self.handle, float(alpha)), self.dg.handle)
+
+    def assemble(self, alpha):
+        """``I - alpha L`` into the band, unfactored (for ``export_band``)."""
+        _lib.check(self.dg.L.cmdg_columnlu_assemble(self.handle, float(alpha)), self.dg.handle)
+
+    def solve(self, Q, Qrhs):
+        """``linearsolve!``: ``Q = (I - alpha L)^-1 Qrhs`` on the real elements."""
+        self.dg._torch_ready()
+        _lib.check(self.dg.L.cmdg_columnlu_solve(self.handle, Q.data_ptr(), Qrhs.data_ptr()),
+                   self.dg.handle)
+
+    def export_band(self, column):
+        """The band of one column in the reference's layout, ``(p + q + 1, n)`` (``A[d, col]``)."""
+        P = self.p + self.q + 1
+        out = np.empty(self.n * P)
+        _lib.check(self.dg.L.cmdg_columnlu_export_band(self.handle, int(column), out.ctypes.data),
+                   self.dg.handle)
+        return out.reshape(self.n, P).T.copy()
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.dg.L.cmdg_columnlu_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _check_stack_order(grid, nvert):
+    """The solver's columns assume the reference's element order: stack after stack, bottom to
+    top (e = v + nvert h, radius increasing with v)."""
+    from .mesh import grids as G
+    nr = grid.nreal
+    if nr % nvert:
+        raise _lib.CmdgError("ManyColumnLU: the real elements are not whole stacks")
+    x = np.stack([grid.vgeo[:nr, c, 0] for c in (G._x1, G._x2, G._x3)])
+    r = np.sqrt((x * x).sum(axis=0)).reshape(-1, nvert)
+    z = grid.vgeo[:nr, G._x3, 0].reshape(-1, nvert)
+    ok = np.all(np.diff(r, axis=1) > 0) or np.all(np.diff(z, axis=1) > 0)
+    if not ok:
+        raise _lib.CmdgError("ManyColumnLU: the real elements are not ordered bottom to top "
+                             "within each stack")

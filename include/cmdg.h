@@ -70,7 +70,10 @@ enum {
      * Continuity3dModel its update_auxiliary_state! evaluates, and the BarotropicModel (on the
      * one-layer extrusion of the 2-D grid) */
     CMDG_PHYSICS_OCEAN_SE01 = 7, CMDG_PHYSICS_CONTINUITY3D_SE01 = 8,
-    CMDG_PHYSICS_BAROTROPIC_SE01 = 9
+    CMDG_PHYSICS_BAROTROPIC_SE01 = 9,
+    /* AtmosAcousticGravityLinearModel of the dry AtmosModel (src/Atmos/Model/linear.jl), on the
+     * full model's parameter block and auxiliary array (orientation + reference state) */
+    CMDG_PHYSICS_ATMOS_LINEAR_AG = 10
 };
 
 /* Construction record: the fields of `DGModel(balance_law, grid, nf1, nf2, nfgrad;
@@ -663,6 +666,44 @@ enum {
 int cmdg_profile_enable(cmdg_handle h, int32_t on);
 int cmdg_profile_get(cmdg_handle h, int32_t kernel, double *total_ms, int64_t *launches);
 int cmdg_profile_reset(cmdg_handle h);
+
+/* ---- ManyColumnLU and the IMEX step (columnwise_lu_solver.jl, AdditiveRungeKuttaMethod.jl) ----
+ * A column solver owns the banded matrix I - alpha L of every column of a VerticalDirection DG
+ * model `linear` on a stacked grid (CMDG_PHYSICS_ATMOS_LINEAR_AG; eband = 1, bandwidths
+ * p = q = Nq_v nstate - 1).  A column is one horizontal node of one stack of `nvertelem` elements;
+ * the real elements must be whole stacks, bottom first.  Assembly probes `linear` (3 Nq_v nstate
+ * evaluations at t = NaN, update_banded_matrix!); factorisation is band_lu! without pivoting.
+ * The band lives on the device, ncol n (p + q + 1) doubles: cmdg_columnlu_create refuses
+ * (CMDG_ERR_INVALID, message naming the size) when that does not fit in free device memory.
+ * Errors are reported through cmdg_last_error(linear).  The solver is driven on linear's stream. */
+typedef struct cmdg_columnlu *cmdg_columnlu_handle;
+/* assemble I - alpha L and factor it (prefactorize(EulerOperator(f, -alpha), ManyColumnLU(), ...)) */
+int cmdg_columnlu_create(cmdg_handle linear, int32_t nvertelem, double alpha, cmdg_columnlu_handle *out);
+/* reassemble and refactor for a new alpha (update_backward_Euler_solver!, isadjustable = true) */
+int cmdg_columnlu_update(cmdg_columnlu_handle lu, double alpha);
+/* assemble I - alpha L only, unfactored (for cmdg_columnlu_export_band; a solve then refuses) */
+int cmdg_columnlu_assemble(cmdg_columnlu_handle lu, double alpha);
+/* Q = (I - alpha L)^-1 Qrhs, both (Np, 5, nelem) device arrays, real elements; Q may be Qrhs */
+int cmdg_columnlu_solve(cmdg_columnlu_handle lu, double *Q, const double *Qrhs);
+/* out[8] = n, p, q, ncol, band bytes, state (1 assembled, 2 factored), nvertelem, Nq_v */
+int cmdg_columnlu_info(cmdg_columnlu_handle lu, int64_t *out);
+/* the alpha the band was last assembled for */
+int cmdg_columnlu_alpha(cmdg_columnlu_handle lu, double *alpha);
+/* HOST out[n (p + q + 1)]: the band of column `column` (horizontal node i + Nq j of stack h is
+ * column h Nq^2 + i + Nq j, all 0-based) in the reference's layout, A[d, col] at out[col (p + q + 1)
+ * + d] with d = row - col + q: the assembled operator or its LU factors, whichever it holds now */
+int cmdg_columnlu_export_band(cmdg_columnlu_handle lu, int64_t column, double *out);
+int cmdg_columnlu_destroy(cmdg_columnlu_handle lu);
+/* One step of a low-storage additive Runge-Kutta method (dostep!(..., ::LowStorageVariant),
+ * AdditiveRungeKuttaMethod.jl:415-523) with the explicit operator `full` and the implicit one the
+ * solver's `linear`: tableaus row-major (nstages, nstages), 2 <= nstages <= 4, the implicit diagonal
+ * (0, c, ..., c).  work: 2 nstages + 1 device state arrays shaped like Q (Qstages[2..], Rstages,
+ * Qhat, Qtt).  split_explicit_implicit != 0: the explicit operator is full minus linear,
+ * evaluated as `full` followed by `linear` with alpha = -1 and increment.  The solver is refactored
+ * when dt a_ii differs from its alpha.  Returns after the step has finished. */
+int cmdg_ark_step(cmdg_handle full, cmdg_columnlu_handle lu, double *Q, double *const *work, double t,
+                  double dt, int32_t nstages, const double *rka_explicit, const double *rka_implicit,
+                  const double *rkb, const double *rkc, int32_t split_explicit_implicit);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,150 @@
+"""IMEX stepping on the bench-size Held-Suarez state: ARK2GiraldoKellyConstantinescu with
+LinearBackwardEulerSolver(ManyColumnLU()) (csrc/columnlu.hip) against explicit LSRK54.
+6 x 30 x 30 x 8 = 43 200 elements, N = 4; the full physics as bench.py builds it (hyperdiffusion,
+Gravity, Coriolis, Held-Suarez forcing) and AtmosAcousticGravityLinearModel on the same auxiliary
+state.  Prints one JSON line.
+
+  dt:          vertical and horizontal acoustic Courant dts, dg.courant(NONDIFFUSIVE, Q, 1, 0,
+               direction) -> dt = 1 / courant (Courant number 1); the IMEX steps run at a tenth of
+               the horizontal dt, LSRK54 is quoted at the every-direction dt
+  step time:   host clock around --reps steps ending in a device synchronise, for both
+               split_explicit_implicit values and for LSRK54
+  solve time:  host clock around --reps cmdg_columnlu_solve calls (each ends in a synchronise);
+               with --kernel-stats also the k_band_solve kernel mean from a rocprofv3
+               --kernel-trace --stats run of this script
+  bytes:       band bytes ncol n (p + q + 1) 8, read once per solve, plus the state read twice
+               and written twice (forward then back substitution)
+
+Usage: python scripts/measure_imex.py [--n-horz 30] [--reps 10] [--kernel-stats CSV]
+       python scripts/measure_imex.py --combine RESULT.json --kernel-stats CSV   (no GPU: adds the
+       kernel times of a rocprofv3 run of the first form to the JSON line it printed)"""
+import argparse
+import csv
+import json
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, ".")
+sys.path.insert(0, "tests")
+from cmdg_loader import cm            # noqa: E402
+from helpers import held_suarez_setup  # noqa: E402
+
+COPY_TBS = 6.29   # measured float4 copy rate of the MI355X (MI355X_MICROARCH: HBM)
+VERTICAL, HORIZONTAL = 2, 1
+
+
+def kernel_stats(path):
+    """{kernel name: (calls, mean ns)} of the column-solver and ARK kernels in a rocprofv3 stats file"""
+    out = {}
+    with open(path) as f:
+        for row in csv.DictReader(f):
+            name = row.get("Name") or row.get("KernelName") or ""
+            if any(k in name for k in ("k_band_", "k_probe_", "k_ark_", "k_add")):
+                out[name] = (int(row["Calls"]), float(row["AverageNs"]))
+    return out
+
+
+def add_kernel_stats(res, path):
+    ks = kernel_stats(path)
+    res["kernel_stats"] = {k: {"calls": c, "mean_us": v / 1e3} for k, (c, v) in ks.items()}
+    sol = [v for k, v in ks.items() if "k_band_solve" in k]
+    if sol:
+        us = sol[0][1] / 1e3
+        nb = res["solve"]["bytes"]
+        res["solve"]["kernel_us"] = us
+        res["solve"]["kernel_TBs"] = nb / us / 1e6
+        res["solve"]["kernel_fraction_of_copy_rate"] = nb / us / 1e6 / COPY_TBS
+
+
+def timed(fn, reps, sync):
+    fn()
+    sync()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    sync()
+    return (time.perf_counter() - t0) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n-horz", type=int, default=30)
+    ap.add_argument("--n-vert", type=int, default=8)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--kernel-stats", default=None)
+    ap.add_argument("--combine", default=None)
+    args = ap.parse_args()
+    if args.combine:
+        with open(args.combine) as f:
+            res = json.loads(f.read().strip().splitlines()[-1])
+        add_kernel_stats(res, args.kernel_stats)
+        print(json.dumps(res))
+        return
+    assert torch.cuda.is_available(), "the measurement needs the GPU"
+    ode = cm.odesolvers
+    law, grid, d, dd = held_suarez_setup(n_horz=args.n_horz, n_vert=args.n_vert)
+    dg = cm.dgmodel.DGModel(law, grid, direction=d, diffusion_direction=dd)
+    lin = cm.dgmodel.DGModel(cm.atmos.AtmosAcousticGravityLinearModel(law), grid, direction=VERTICAL,
+                             state_auxiliary=dg.state_auxiliary)
+    Q0 = dg.init_ode_state(0.0)
+    c_v = dg.courant(cm.dgmodel.NONDIFFUSIVE_COURANT, Q0, 1.0, 0.0, VERTICAL)
+    c_h = dg.courant(cm.dgmodel.NONDIFFUSIVE_COURANT, Q0, 1.0, 0.0, HORIZONTAL)
+    c_e = dg.courant(cm.dgmodel.NONDIFFUSIVE_COURANT, Q0, 1.0, 0.0, 0)
+    dt_v, dt_h, dt_e = 1 / c_v, 1 / c_h, 1 / c_e
+    res = {"workload": "Held-Suarez 6x%dx%dx%d, N=4, %d elements, fp64, full physics as bench.py"
+           % (args.n_horz, args.n_horz, args.n_vert, grid.nreal),
+           "copy_rate_TBs": COPY_TBS,
+           "acoustic_courant_dt_s": {"vertical": dt_v, "horizontal": dt_h, "every": dt_e,
+                                     "ratio_horizontal_over_vertical": dt_h / dt_v}}
+    sync = dg.synchronize
+    # explicit LSRK54 at the bench's dt (its cost per step does not depend on dt)
+    Q = Q0.clone()
+    s = ode.LSRK54CarpenterKennedy(dg, Q, dt=0.15)
+    lsrk = timed(lambda: s.dostep(Q, 1), args.reps, sync)
+    res["lsrk54_ms_per_step"] = 1e3 * lsrk
+    # IMEX at a tenth of the horizontal acoustic dt (the explicit part's limit; the reference's
+    # heldsuarez.jl picks its dt from the horizontal Courant number)
+    dt_imex = 0.1 * dt_h
+    res["imex_dt_s"] = dt_imex
+    for split in (False, True):
+        Q = Q0.clone()
+        t0 = time.perf_counter()
+        solver = ode.ARK2GiraldoKellyConstantinescu(
+            dg, lin, ode.LinearBackwardEulerSolver(ode.ManyColumnLU()), Q, dt=dt_imex,
+            split_explicit_implicit=split)
+        sync()
+        setup = time.perf_counter() - t0
+        step = timed(lambda: solver.dostep(Q, 1), args.reps, sync)
+        ok = bool(torch.isfinite(Q[:grid.nreal]).all())
+        key = "split" if split else "nosplit"
+        res["imex_" + key] = {"ms_per_step": 1e3 * step, "finite": ok,
+                              "create_assemble_factor_s": setup}
+        lu = solver.lu
+        if not split:
+            res["band"] = {"ncol": lu.ncol, "n": lu.n, "p": lu.p, "q": lu.q, "bytes": lu.band_bytes}
+            # one solve: band once, the state read twice and written twice
+            X, B = dg.create_state(), Q0.clone()
+            solve = timed(lambda: lu.solve(X, B), args.reps, lambda: None)
+            nb = lu.band_bytes + 4 * grid.nreal * 5 * grid.Np * 8
+            res["solve"] = {"call_ms": 1e3 * solve, "bytes": nb, "call_TBs": nb / solve / 1e12,
+                            "call_fraction_of_copy_rate": nb / solve / 1e12 / COPY_TBS}
+            t0 = time.perf_counter()
+            lu.update(dt_imex * 0.29289321881345254)
+            res["assemble_factor_s"] = time.perf_counter() - t0
+        solver.close()
+    # simulated seconds per wall second
+    res["simulated_s_per_wall_s"] = {
+        "lsrk54_at_every_direction_courant_1": dt_e / lsrk,
+        "imex_nosplit": dt_imex / (res["imex_nosplit"]["ms_per_step"] / 1e3),
+        "imex_split": dt_imex / (res["imex_split"]["ms_per_step"] / 1e3)}
+    if args.kernel_stats:
+        add_kernel_stats(res, args.kernel_stats)
+    lin.close()
+    dg.close()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

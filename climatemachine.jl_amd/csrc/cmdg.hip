@@ -133,13 +133,11 @@ EngineBase::~EngineBase()
     }
     if (own_gf && gf) hipFree(gf);
     if (gf_scratch) hipFree(gf_scratch);
-    if (own_hg && hypgrad) hipFree(hypgrad);
+    if (hypgrad) hipFree(hypgrad);
     if (own_hd && hypdiv) hipFree(hypdiv);
     if (W[0]) hipFree(W[0]);
     if (W[1]) hipFree(W[1]);
     if (d_D) hipFree(d_D);
-    if (d_pairs[0]) hipFree(d_pairs[0]);
-    if (d_pairs[1]) hipFree(d_pairs[1]);
     if (d_interior_tiled) hipFree(d_interior_tiled);
     if (d_exterior_tiled) hipFree(d_exterior_tiled);
     if (d_faceP) hipFree(d_faceP);
@@ -226,10 +224,10 @@ int EngineBase::init(const cmdg_desc *d)
         // CMDG_HALO_PRIORITY=1: the halo stream (the latency chain of a partitioned run: exchange ->
         // exterior launch -> exchange ...) as a high-priority stream, so that its small kernels go
         // ahead of the interior launches' blocks.  Off by default: it gains nothing measurable at
-        // 5 400 elements per rank (profiles/r03_halo_exposure_*), and with the slow and the fast
-        // model of the split-explicit ocean both on priority streams the two-rank local-transport
-        // test fails reproducibly (passes with either one alone, with three ranks, and with
-        // AMD_SERIALIZE_KERNEL=3): an ordering the events express is not kept -- unexplained.
+        // 5 400 elements per rank (profiles/r03_halo_exposure_*).  The two-rank local-transport
+        // failure once seen with both models of the split-explicit ocean on priority streams was a
+        // hipMemset of the work states not ordered before the first stage, not the priorities
+        // (scripts/probe/memset_null_stream_order.py); every fill now goes on s_comp.
         int lo = 0, hi = 0;
         const char *pv = getenv("CMDG_HALO_PRIORITY");
         if (communicate() && pv && *pv == '1' && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi < lo)
@@ -299,13 +297,9 @@ int EngineBase::init(const cmdg_desc *d)
         if (int r = alloc0(&gf, nd * ngf)) return r;
     }
     // Qhypervisc_grad is node-major inside the library (cmdg_common.h); a caller's array receives
-    // the reference layout after every evaluation (export_hypgrad)
-    hypgrad = CMDG_HG_NODE_MAJOR ? nullptr : d->Qhypervisc_grad;
-    hypgrad_user = CMDG_HG_NODE_MAJOR && ngl > 0 ? d->Qhypervisc_grad : nullptr;
-    if (!hypgrad) {
-        own_hg = true;
-        if (int r = alloc0(&hypgrad, nd * 3 * ngl)) return r;
-    }
+    // the reference layout only from cmdg_export_hypervisc_grad (export_hypgrad)
+    hypgrad_user = ngl > 0 ? d->Qhypervisc_grad : nullptr;
+    if (int r = alloc0(&hypgrad, nd * 3 * ngl)) return r;
     hypdiv = d->Qhypervisc_div;
     if (!hypdiv) {
         own_hd = true;
@@ -328,9 +322,6 @@ int EngineBase::init(const cmdg_desc *d)
     if (const char *v = getenv("CMDG_REFERENCE_HALO")) reference_halo = *v && *v != '0';
     if (const char *v = getenv("CMDG_HALO_PIPELINE")) no_pipeline = *v == '0';
     if (const char *v = getenv("CMDG_FUSED_COLUMNS")) fused_columns = atoi(v);
-    if (const char *v = getenv("CMDG_TENDENCY_PAIRS")) tendency_pairs = *v && *v != '0';
-    if (const char *v = getenv("CMDG_TENDENCY_FOUR_WAVES")) tendency_four_waves = *v && *v != '0';
-    if (int r = build_pairs()) return r;
     if (int r = init_derived()) return r;
     HIPCHK(hipStreamSynchronize(s_comp));  // the fills of alloc0 have run
     return CMDG_OK;
@@ -453,12 +444,8 @@ int EngineBase::export_hypgrad(double *dst)
     if (ngl == 0) return CMDG_OK;
     if (!dst) return fail(CMDG_ERR_INVALID, "cmdg_export_hypervisc_grad: no destination (cmdg_desc.Qhypervisc_grad was NULL)");
     const int64_t n = (int64_t)Np * 3 * ngl * nelem;
-    if (CMDG_HG_NODE_MAJOR) {
-        hipLaunchKernelGGL(k_export_node_major, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s_comp, dst, hypgrad,
-                           Np, 3 * ngl, nelem);
-    } else if (dst != hypgrad) {
-        HIPCHK(hipMemcpyAsync(dst, hypgrad, sizeof(double) * n, hipMemcpyDeviceToDevice, s_comp));
-    }
+    hipLaunchKernelGGL(k_export_node_major, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s_comp, dst, hypgrad, Np,
+                       3 * ngl, nelem);
     HIPCHK(hipStreamSynchronize(s_comp));
     return CMDG_OK;
 }
@@ -604,7 +591,7 @@ int EngineBase::set_stack_height(int nv)
     HIPCHK(hipStreamSynchronize(s_comp));
     d_interior = d_interior_user;
     d_exterior = d_exterior_user;
-    if (nv < MIN_HEIGHT) return build_pairs();
+    if (nv < MIN_HEIGHT) return CMDG_OK;
     for (int which = 0; which < 2; ++which) {
         const int64_t n = which ? nexterior : ninterior;
         if (n == 0) continue;
@@ -621,7 +608,7 @@ int EngineBase::set_stack_height(int nv)
         HIPCHK(hipMemcpy(own, h.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
         (which ? d_exterior : d_interior) = own;
     }
-    return build_pairs();
+    return CMDG_OK;
 }
 
 // CMDG_OPT_STREAM_PRIORITY: both streams of the handle at the highest (1), the default (0) or the
@@ -645,76 +632,6 @@ int EngineBase::set_stream_priority(int level)
     s_comp = nc;
     s_comm = nm;
     stream_priority = level;
-    return CMDG_OK;
-}
-
-// Pair lists of the tendency pass (TendencyShape<..., PAIR>): walk each element list in its launch
-// order and give every element its xi1+ neighbour (else its xi1- neighbour) as a partner when the
-// two faces match node for node, both are real elements of the same list and neither is taken;
-// what is left over shares work-groups two by two without a shared face.
-int EngineBase::build_pairs()
-{
-    for (int w = 0; w < 2; ++w) {
-        if (d_pairs[w]) hipFree(d_pairs[w]);
-        d_pairs[w] = nullptr;
-        npairs[w] = nshared[w] = 0;
-    }
-    if (!tendency_pairs || !law_pairable() || nreal == 0) return CMDG_OK;
-    const int Nfph = NQ * NQV, NFT = 4 * Nfph + 2 * NQ * NQ;
-    std::vector<int32_t> fP((size_t)nreal * NFT);
-    HIPCHK(hipMemcpy(fP.data(), d_faceP, sizeof(int32_t) * fP.size(), hipMemcpyDeviceToHost));
-    auto vid = [&](int f, int n) {  // face_vid of kernels.h, faces 1 and 2 only
-        const int a = n % NQ, b = n / NQ;
-        return f == 0 ? NQ * (a + NQ * b) : (NQ - 1) + NQ * (a + NQ * b);
-    };
-    // the element across face f of e whose face f^1 meets it node for node, -1: none
-    auto across = [&](int64_t e, int f) -> int64_t {
-        int64_t cand = -1;
-        for (int n = 0; n < Nfph; ++n) {
-            const int64_t id = fP[(size_t)e * NFT + f * Nfph + n], eP = id / Np;
-            if (n == 0) cand = eP;
-            if (eP != cand || id - eP * Np != vid(f ^ 1, n)) return -1;
-        }
-        if (cand == e || cand >= nreal) return -1;
-        for (int n = 0; n < Nfph; ++n)  // (and back)
-            if (fP[(size_t)cand * NFT + (f ^ 1) * Nfph + n] != e * Np + vid(f, n)) return -1;
-        return cand;
-    };
-    std::vector<int32_t> where((size_t)nreal);
-    for (int w = 0; w < 2; ++w) {
-        const int64_t n = w ? nexterior : ninterior;
-        if (n == 0) continue;
-        std::vector<int64_t> h((size_t)n), out, single;
-        HIPCHK(hipMemcpy(h.data(), w ? d_exterior : d_interior, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
-        std::fill(where.begin(), where.end(), -1);
-        for (int64_t i = 0; i < n; ++i) where[h[i] - 1] = (int32_t)i;
-        std::vector<uint8_t> used((size_t)n, 0);
-        out.reserve((size_t)n + 2);
-        for (int64_t i = 0; i < n; ++i) {
-            if (used[i]) continue;
-            const int64_t e = h[i] - 1;
-            used[i] = 1;
-            const int64_t ep = across(e, 1), em = across(e, 0);
-            if (ep >= 0 && where[ep] >= 0 && !used[where[ep]]) {
-                used[where[ep]] = 1;
-                out.push_back(e + 1), out.push_back(ep + 1);
-                nshared[w] += 1;
-            } else if (em >= 0 && where[em] >= 0 && !used[where[em]]) {
-                used[where[em]] = 1;
-                out.push_back(em + 1), out.push_back(e + 1);
-                nshared[w] += 1;
-            } else {
-                single.push_back(e + 1);
-            }
-        }
-        for (size_t q = 0; q < single.size(); q += 2) {
-            out.push_back(single[q]);
-            out.push_back(q + 1 < single.size() ? -single[q + 1] : 0);
-        }
-        npairs[w] = (int64_t)out.size() / 2;
-        HIPCHK(hipMalloc(&d_pairs[w], sizeof(int64_t) * out.size()));
-        HIPCHK(hipMemcpy(d_pairs[w], out.data(), sizeof(int64_t) * out.size(), hipMemcpyHostToDevice));
-    }
     return CMDG_OK;
 }
 
@@ -2182,11 +2099,6 @@ int cmdg_set_option(cmdg_handle h, int32_t option, int32_t value)
         e->graph_failed = false;
         return CMDG_OK;
     case CMDG_OPT_STREAM_PRIORITY: return set_err(h, e->set_stream_priority(value));
-    case CMDG_OPT_TENDENCY_FOUR_WAVES:
-        if (int r = e->synchronize()) return set_err(h, r);
-        e->drop_graph();
-        e->tendency_four_waves = value != 0;
-        return CMDG_OK;
     case CMDG_OPT_ASYNC_RUN:
         if (value && !e->worker) {
             e->worker = new (std::nothrow) RunWorker();
@@ -2198,10 +2110,7 @@ int cmdg_set_option(cmdg_handle h, int32_t option, int32_t value)
         }
         return CMDG_OK;
     case CMDG_OPT_TENDENCY_PAIRS:
-        if (int r = e->synchronize()) return set_err(h, r);
-        e->drop_graph();
-        e->tendency_pairs = value != 0;
-        return set_err(h, e->build_pairs());
+    case CMDG_OPT_TENDENCY_FOUR_WAVES: return CMDG_OK;  // retired: no effect
     case CMDG_OPT_HALO_PIPELINE:
         if (int r = e->synchronize()) return set_err(h, r);
         e->drop_graph();
@@ -2226,7 +2135,7 @@ int cmdg_query(cmdg_handle h, int32_t what, int64_t *out)
     case CMDG_Q_DIRECT_RECV: *out = e->communicate() && e->direct_recv(); return CMDG_OK;
     case CMDG_Q_TENDENCY_ELEMS_PER_GROUP: *out = e->tendency_epb(); return CMDG_OK;
     case CMDG_Q_GRAPH_STEPS: *out = e->graph_steps; return CMDG_OK;
-    case CMDG_Q_TENDENCY_PAIRS: *out = e->d_pairs[0] || e->d_pairs[1] ? e->nshared[0] + e->nshared[1] : -1; return CMDG_OK;
+    case CMDG_Q_TENDENCY_PAIRS: *out = -1; return CMDG_OK;  // retired option: always off
     case CMDG_Q_HOST_POST_NS: *out = e->host_post_ns; return CMDG_OK;
     case CMDG_Q_HOST_POST_COUNT: *out = e->host_post_n; return CMDG_OK;
     case CMDG_Q_HALO_PIPELINE:

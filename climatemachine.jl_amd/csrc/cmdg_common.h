@@ -152,12 +152,9 @@ __device__ __forceinline__ void load_plus(Vec<NLOAD> &dst, const double *__restr
 // contiguous bytes instead of NHG values at a stride of Np * 8: on a xi1 / xi2 face of an N = 4
 // element the column-major form touches every 128-byte line of all NHG columns of the neighbour
 // (5 x the bytes used), the node-major form 1.3-2.3 x.  The volume reads are one contiguous
-// record per thread, the stores go out of LDS in memory order.  A caller that hands
-// Qhypervisc_grad to cmdg_create gets the reference layout copied out after every evaluation
-// (k_export_hg); CMDG_HG_NODE_MAJOR=0 builds the reference layout in place (the A/B).
-#ifndef CMDG_HG_NODE_MAJOR
-#define CMDG_HG_NODE_MAJOR 1
-#endif
+// record per thread, the stores go out of LDS in memory order.  The library owns this array: a
+// Qhypervisc_grad handed to cmdg_create is not written by an evaluation, only by
+// cmdg_export_hypervisc_grad, which copies the reference layout out.
 template <bool NODE_MAJOR, int NCOL, int Np>
 __device__ __forceinline__ int64_t col_at(int n, int s, int64_t e)
 {
@@ -166,7 +163,7 @@ __device__ __forceinline__ int64_t col_at(int n, int s, int64_t e)
 template <int NHG, int Np>
 __device__ __forceinline__ int64_t hg_at(int n, int s, int64_t e)
 {
-    return col_at<CMDG_HG_NODE_MAJOR != 0, NHG, Np>(n, s, e);
+    return col_at<true, NHG, Np>(n, s, e);
 }
 template <int NHG, int Np, int NLOAD>
 __device__ __forceinline__ void load_plus_hg(Vec<NLOAD> &dst, const double *__restrict__ arr,

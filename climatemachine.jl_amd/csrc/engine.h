@@ -162,16 +162,6 @@ struct EngineBase {
     int set_stack_height(int nv);
     int set_stream_priority(int level);  // CMDG_OPT_STREAM_PRIORITY
     int stream_priority = 0;
-    // CMDG_OPT_TENDENCY_PAIRS: the tendency pass takes horizontally adjacent elements two to a
-    // work-group and keeps the xi1 face they share on chip (TendencyShape<..., PAIR>, kernels.h);
-    // the lists: (e0, e1) 1-based per work-group, e1 < 0 unrelated, 0 none
-    bool tendency_four_waves = false;  // CMDG_OPT_TENDENCY_FOUR_WAVES
-    bool tendency_pairs = false;
-    int64_t *d_pairs[2] = {nullptr, nullptr};  // interior, exterior
-    int64_t npairs[2] = {0, 0};                // work-groups
-    int64_t nshared[2] = {0, 0};               // ... of which share a face
-    int build_pairs();
-    virtual bool law_pairable() const = 0;
     int64_t ninterior = 0, nexterior = 0;
     const uint8_t *d_activedofs = nullptr;
     double *d_D = nullptr;
@@ -183,13 +173,13 @@ struct EngineBase {
     std::vector<int64_t> nabrsend, nabrrecv;  // 2*nnabr (first,last) 1-based
     double *aux = nullptr, *gf = nullptr, *hypgrad = nullptr, *hypdiv = nullptr;
     double *derived = nullptr;  // (Np, NDER, nelem), library-owned
-    bool own_gf = false, own_hg = false, own_hd = false;
+    bool own_gf = false, own_hd = false;  // (hypgrad is always the library's own)
     // the caller's Qhypervisc_grad / state_gradient_flux (reference layout) when the working copy is
     // node-major: written by cmdg_export_* only; gf_scratch: reference-layout copy for a gradient filter
     double *hypgrad_user = nullptr, *gf_user = nullptr, *gf_scratch = nullptr;
     bool node_major(const double *array) const
     {
-        return (CMDG_HG_NODE_MAJOR && array == hypgrad) || (array == gf && gf_node_major());
+        return array == hypgrad || (array == gf && gf_node_major());
     }
     // ---- runtime -----------------------------------------------------------------------
     int dev = 0;  // the device this engine was created on (every ABI entry binds to it)
@@ -556,82 +546,13 @@ struct EngineT : EngineBase {
         args.h = halo_dev(exterior, c.lsrk ? slot[SLOT_Q].sendbuf : nullptr, nullptr);
         const bool recv = args.h.ghostslot != nullptr && exterior;  // (interior elements have no ghost neighbour)
         if (!recv) args.h.ghostslot = nullptr;
-        if constexpr (SH::PAIRABLE) {
-            const int w = elems == d_exterior ? 1 : 0;
-            if (tendency_pairs && d_pairs[w] && (elems == d_interior || elems == d_exterior)) {
-                using SP = TendencyShape<P, NQ_, NQV_, true>;
-                args.elems = d_pairs[w];
-                args.nelems = 2 * npairs[w];
-                const dim3 pgrid((unsigned)npairs[w]), pblock(SP::NT);
-#define CMDG_TENDP(L, G)                                                                              \
-    do {                                                                                              \
-        if constexpr (KDims<NQ_, NQV_>::Np <= 125) {                                                  \
-            constexpr size_t lds = sizeof(double) * TendencyLds<P, NQ_, NQV_, G, true>::doubles;      \
-            if (recv)                                                                                 \
-                hipLaunchKernelGGL((k_tendency_pair_small<P, NQ_, NQV_, L, G, true>), pgrid, pblock,  \
-                                   lds, st, args);                                                    \
-            else                                                                                      \
-                hipLaunchKernelGGL((k_tendency_pair_small<P, NQ_, NQV_, L, G, false>), pgrid, pblock, \
-                                   lds, st, args);                                                    \
-        } else if (recv)                                                                              \
-            hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, L, G, true, TEND_FUSED, true>), pgrid,       \
-                               pblock, 0, st, args);                                                  \
-        else                                                                                          \
-            hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, L, G, false, TEND_FUSED, true>), pgrid,      \
-                               pblock, 0, st, args);                                                  \
-    } while (0)
-                if (c.lsrk) {
-                    if (gfl) CMDG_TENDP(true, true);
-                    else CMDG_TENDP(true, false);
-                } else {
-                    if (gfl) CMDG_TENDP(false, true);
-                    else CMDG_TENDP(false, false);
-                }
-#undef CMDG_TENDP
-                prof_end(st);
-                return;
-            }
-        }
-        if constexpr (CMDG_TEND_FOUR_WAVES != 0 && KDims<NQ_, NQV_>::Np > 125 && node_cache_size<P>::value == 0 &&
-                      NQ_ == NQV_) {
-            if (tendency_four_waves) {  // CMDG_OPT_TENDENCY_FOUR_WAVES (k_tendency_big)
-                const dim3 bgrid((unsigned)n), bblock(256);
-#define CMDG_TENDB(L, G)                                                                                 \
-    do {                                                                                                 \
-        if (recv)                                                                                        \
-            hipLaunchKernelGGL((k_tendency_big<P, NQ_, NQV_, L, G, true>), bgrid, bblock, 0, st, args);  \
-        else                                                                                             \
-            hipLaunchKernelGGL((k_tendency_big<P, NQ_, NQV_, L, G, false>), bgrid, bblock, 0, st, args); \
-    } while (0)
-                if (c.lsrk) {
-                    if (gfl) CMDG_TENDB(true, true);
-                    else CMDG_TENDB(true, false);
-                } else {
-                    if (gfl) CMDG_TENDB(false, true);
-                    else CMDG_TENDB(false, false);
-                }
-#undef CMDG_TENDB
-                prof_end(st);
-                return;
-            }
-        }
         const dim3 grid((unsigned)SH::blocks(n)), block(SH::NT);
-        // large elements: volume half, then interface half + update (TendencyShape::SPLIT)
-#define CMDG_TEND(L, G)                                                                             \
-    do {                                                                                            \
-        if constexpr (SH::SPLIT) {                                                                  \
-            hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, false, G, false, TEND_VOLUME>), grid,      \
-                               dim3(SH::NTV), 0, st, args);                                         \
-            if (recv)                                                                               \
-                hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, L, G, true, TEND_FACES>), grid, block, \
-                                   0, st, args);                                                    \
-            else                                                                                    \
-                hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, L, G, false, TEND_FACES>), grid,       \
-                                   block, 0, st, args);                                             \
-        } else if (recv)                                                                            \
-            hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, L, G, true>), grid, block, 0, st, args);   \
-        else                                                                                        \
-            hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, L, G, false>), grid, block, 0, st, args);  \
+#define CMDG_TEND(L, G)                                                                            \
+    do {                                                                                           \
+        if (recv)                                                                                  \
+            hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, L, G, true>), grid, block, 0, st, args);  \
+        else                                                                                       \
+            hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, L, G, false>), grid, block, 0, st, args); \
     } while (0)
         if (c.lsrk) {
             if (gfl) CMDG_TEND(true, true);
@@ -675,7 +596,6 @@ struct EngineT : EngineBase {
     int law_nder() const override { return P::HAS_SOURCE ? P::NDER : 0; }
     int law_nupd() const override { return P::HAS_UPDATE_AUX ? P::NUPD : 0; }
     int tendency_epb() const override { return TendencyShape<P, NQ_, NQV_>::EPB; }
-    bool law_pairable() const override { return TendencyShape<P, NQ_, NQV_>::PAIRABLE; }
     int law_state_read(int pass) const override { return law_reads<P>::state(pass); }
     int law_aux_read(int pass) const override { return law_reads<P>::aux(pass); }
     int init_derived() override

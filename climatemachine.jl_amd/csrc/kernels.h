@@ -19,15 +19,6 @@
 #include "cmdg_common.h"
 
 // minimum waves per SIMD requested from the register allocator (tuning knobs)
-// Memory round trips of the tendency pass issued as early as they can be (bits: 1 = the old tendency
-// of all states in one batch instead of one dependent load per state inside the contraction; 2 =
-// the metric rows with the state, before the flux arithmetic, where that does not cost residency).
-// The pass is bound by its chain of dependent loads, not by bytes (profiles/r04_ab_tendency_hoist.txt;
-// pinning every plus-side gather of a face node before the first-order flux was the third candidate
-// and lost).
-#ifndef CMDG_TEND_HOIST
-#define CMDG_TEND_HOIST 3
-#endif
 #ifndef CMDG_TEND_MINW
 #define CMDG_TEND_MINW 1
 #endif
@@ -50,30 +41,6 @@
 #endif
 #ifndef CMDG_LAP_MINW
 #define CMDG_LAP_MINW 1
-#endif
-// paired work-groups of the tendency pass (TendencyShape<..., PAIR>, CMDG_OPT_TENDENCY_PAIRS): the
-// round-4 structural experiment, measured and rejected (profiles/r04_ab_tendency_pairs.txt), kept
-// buildable: make EXTRA=-DCMDG_TEND_PAIRS=1
-#ifndef CMDG_TEND_PAIRS
-#define CMDG_TEND_PAIRS 0
-#endif
-// four-wave work-groups for the tendency pass of large elements (k_tendency_big,
-// CMDG_OPT_TENDENCY_FOUR_WAVES): measured and rejected in round 4 (BOMEX k_tendency 596 -> 869 us,
-// profiles/r04_ab_tendency_four_waves.txt), kept buildable: make EXTRA=-DCMDG_TEND_FOUR_WAVES=1
-#ifndef CMDG_TEND_FOUR_WAVES
-#define CMDG_TEND_FOUR_WAVES 0
-#endif
-// tendency pass of large elements (N >= 5) in two launches, volume then interface + update
-// (see TendencyShape::SPLIT; off: measured slower than two elements per work-group), and the
-// register budgets asked for the two halves (waves per SIMD)
-#ifndef CMDG_TEND_SPLIT_LARGE
-#define CMDG_TEND_SPLIT_LARGE 0
-#endif
-#ifndef CMDG_TENDV_MINW
-#define CMDG_TENDV_MINW 4
-#endif
-#ifndef CMDG_TENDF_MINW
-#define CMDG_TENDF_MINW 4
 #endif
 
 namespace cmdg {
@@ -229,15 +196,12 @@ struct has_flux_wavespeed<P, std::void_t<decltype(P::HAS_FLUX_WAVESPEED)>> : std
 // The dry atmosphere takes it (10 columns gathered on the plus side of every face node; the moist
 // law was measured and keeps the reference layout, physics_moist.h); laws whose hooks work on the
 // array in the reference layout do not.
-#ifndef CMDG_GF_NODE_MAJOR
-#define CMDG_GF_NODE_MAJOR 1
-#endif
 template <class P, class = void>
 struct gf_node_major : std::false_type {
 };
 template <class P>
 struct gf_node_major<P, std::void_t<decltype(P::GF_NODE_MAJOR)>>
-    : std::integral_constant<bool, P::GF_NODE_MAJOR && CMDG_GF_NODE_MAJOR != 0 && (P::NGF > 0)> {
+    : std::integral_constant<bool, P::GF_NODE_MAJOR && (P::NGF > 0)> {
 };
 template <class P, int Np>
 __device__ __forceinline__ int64_t gf_at(int n, int s, int64_t e)
@@ -412,41 +376,19 @@ struct grad_min_waves<P, std::void_t<decltype(P::GRAD_MIN_WAVES)>> : std::integr
 // carry twice the work and a second six-wave work-group does not become resident above 128
 // VGPRs (profiles/r02_lds_occupancy.jsonl).  Two elements per work-group (686 threads, eleven
 // waves, 3-3-3-2) even that out; the minus side of the faces is then read from memory instead
-// of being staged, so that both elements' flux buffers fit the LDS of a CU.
-//
-// SPLIT (large elements): the pass in two launches with separate register budgets, as the
-// reference has them (volume_tendency! / dgsem_interface_tendency!, DGModel_kernels.jl:64-548 /
-// :588-901) -- k_tendency<..., TEND_VOLUME> forms the volume part and stores it, k_tendency<...,
-// TEND_FACES> reads it back, adds the lifted face fluxes in the same order and applies the fused
-// update.  Measured on BOMEX (N = 6, 8 192 elements, profiles/r03_ab_bomex_split.txt): the two
-// launches take 727 us against 603 us for the fused two-element work-group -- the interface half
-// still needs 167-181 VGPRs and 73 KB of LDS (two six-wave work-groups per CU at best, no more
-// waves than the fused kernel's eleven), and the round trip of the tendency comes on top.  Kept
-// behind CMDG_TEND_SPLIT_LARGE as the recorded loser.
-//
-// PAIR (round 4, the structural experiment): the two elements of a work-group are horizontal
-// neighbours across a xi1 face -- element 0's face 2 (xi1+) is element 1's face 1 (xi1-), node for
-// node -- and that face never goes to memory: its plus side is the partner's staged minus side
-// (state out of sQ, face fields out of sM or, for large elements, out of the face-plane buffer sP).
-// The xi1 faces are the expensive gathers (stride Nq doubles: every line of the neighbour's column
-// is touched for one value in Nq), so a pair removes 1/2 of them.  The host builds the pair lists
-// at create (EngineBase::build_pairs): entries (e0, e1) 1-based, e1 < 0 for two unrelated elements
-// sharing a work-group, 0 for none.  Small elements keep the minus side staged (two 192-thread
-// halves, wave aligned); large ones read it from memory as the unpaired two-element shape does.
-enum { TEND_FUSED = 0, TEND_VOLUME = 1, TEND_FACES = 2 };
-template <class P, int NQ, int NQV, bool PAIR = false>
+// of being staged, so that both elements' flux buffers fit the LDS of a CU.  A law with a node
+// cache takes one element per work-group at every order.  The other shapes measured -- the pass
+// in two launches (volume, then interface + update), paired work-groups that keep a shared xi1
+// face on chip, four-wave work-groups for large elements -- lost and were removed (DESIGN.md
+// Appendix A).
+template <class P, int NQ, int NQV>
 struct TendencyShape {
     using KD = KDims<NQ, NQV>;
-    static constexpr bool PAIRABLE = CMDG_TEND_PAIRS != 0 && node_cache_size<P>::value == 0 && NQ == NQV;
-    static constexpr bool SPLIT = KD::Np > 125 && node_cache_size<P>::value == 0 && CMDG_TEND_SPLIT_LARGE != 0 && !PAIR;
-    static constexpr int EPB = PAIR ? 2
-                                    : (node_cache_size<P>::value != 0 || SPLIT
-                                           ? 1
-                                           : (KD::Np > 125 ? CMDG_TEND_EPB_LARGE : CMDG_TEND_EPB_SMALL));
-    static constexpr bool STAGE_M = EPB == 1 || (PAIR && KD::Np <= 125);
-    static constexpr int NTE = EPB == 1 || (PAIR && KD::Np <= 125) ? KD::NT : (KD::Np > KD::NFT ? KD::Np : KD::NFT);
+    static constexpr int EPB =
+        node_cache_size<P>::value != 0 ? 1 : (KD::Np > 125 ? CMDG_TEND_EPB_LARGE : CMDG_TEND_EPB_SMALL);
+    static constexpr bool STAGE_M = EPB == 1;  // minus side of the faces staged in LDS
+    static constexpr int NTE = EPB == 1 ? KD::NT : (KD::Np > KD::NFT ? KD::Np : KD::NFT);  // threads per element
     static constexpr int NT = EPB == 1 ? KD::NT : ((EPB * NTE + 63) / 64) * 64;
-    static constexpr int NTV = ((KD::Np + 63) / 64) * 64;  // threads of the volume half
     static int64_t blocks(int64_t nelems) { return (nelems + EPB - 1) / EPB; }
 };
 
@@ -457,92 +399,47 @@ struct TendencyShape {
 // handle whose exchanges are not unpacked).  A variant of its own: the second addressing mode
 // costs the Held-Suarez instantiation 24 VGPRs (128 -> 150, one wave per SIMD less), which the
 // interior launches and single-rank handles do not pay.
-template <class P, int NQ, int NQV, int MODE, bool PAIR = false>
-constexpr int tendency_threads()
-{
-    return MODE == TEND_VOLUME ? TendencyShape<P, NQ, NQV, PAIR>::NTV : TendencyShape<P, NQ, NQV, PAIR>::NT;
-}
-// doubles of LDS a paired fused launch takes (what tendency_body lays out; checked there)
-template <class P, int NQ, int NQV, bool USE_GF, bool PAIR>
-struct TendencyLds {
-    using KD = KDims<NQ, NQV>;
-    using SH = TendencyShape<P, NQ, NQV, PAIR>;
-    static constexpr int NPLANE = P::NFAUX + (USE_GF ? P::NGF : 0) + P::NHYP;
-    static constexpr int NMF = (SH::STAGE_M ? NPLANE : 0) + node_cache_size<P>::value;
-    static constexpr int doubles =
-        NQ * NQ + (NQV == NQ ? 0 : NQV * NQV) + SH::EPB * 3 * P::NS * KD::Np +
-        SH::EPB * (NMF > 0 ? NMF : 1) * (NMF > 0 ? SurfDims<NQ, NQV>::NSURF : 1) + SH::EPB * P::NS * KD::Np +
-        (PAIR && !SH::STAGE_M && NPLANE > 0 ? 2 * NPLANE * KD::Nfph : 1);
-};
-
-template <class P, int NQ, int NQV, bool LSRK, bool USE_GF, bool RECV = false, int MODE = TEND_FUSED,
-          bool PAIR = false, bool DYNLDS = false>
+// The pass is bound by its chain of dependent loads, not by bytes, so its memory round trips are
+// issued as early as registers allow: the metric rows go out with the state, before the flux
+// arithmetic (METRICS_FIRST), and the old tendency of all states in one batch ahead of the
+// contraction instead of one dependent load per state inside it (profiles/r04_ab_tendency_hoist.txt;
+// gathering every plus-side value of a face node before the first-order flux lost).
+template <class P, int NQ, int NQV, bool LSRK, bool USE_GF, bool RECV = false>
 __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
 {
     using KD = KDims<NQ, NQV>;
     const double a_t = a.tptr ? *a.tptr : a.t;  // (uniform: one scalar load)
-    using SH = TendencyShape<P, NQ, NQV, PAIR>;
+    using SH = TendencyShape<P, NQ, NQV>;
     constexpr int EPB = SH::EPB;
-    constexpr bool VOL = MODE != TEND_FACES, FACES = MODE != TEND_VOLUME;
-    static_assert(MODE == TEND_FUSED || (EPB == 1 && node_cache_size<P>::value == 0),
-                  "the two-launch form takes one element per work-group and no node cache");
-    static_assert(!PAIR || (MODE == TEND_FUSED && SH::PAIRABLE), "paired work-groups: fused form, one order, no node cache");
     constexpr bool STAGE_M = SH::STAGE_M;
     constexpr int Np = KD::Np, NS = P::NS, NAUX = P::NAUX, NGF = P::NGF,
                   NHYP = P::NHYP, NHG = 3 * P::NGL, NFA = P::NFAUX,
                   NSURF = SurfDims<NQ, NQV>::NSURF, NGFS = USE_GF ? NGF : 0,
                   NCA = node_cache_size<P>::value,
-                  NMF = (STAGE_M && FACES ? NFA + NGFS + NHYP : 0) + NCA, OCA = NMF - NCA;
-    // LDS: sD derivative matrices; sF_ contravariant flux [d][s][ijk], later the accumulator
-    // (interface half alone: the accumulator); sM_ minus side, surface nodes [field][sidx]; sQ_ the
-    // prognostic state of every node (minus side of the faces, and the "Q" of the fused update at the
-    // end: re-reading it from memory 20 us after the first read misses L2); sP_ (PAIR, minus side
-    // not staged) the face fields of the nodes of the shared face [elem][field][n].
-    // DYNLDS: the same arrays carved out of the launch's dynamic LDS -- the compiler then does not
-    // know the footprint and cannot relax a register budget on its account (k_tendency_pair_small).
-    constexpr int NPF = PAIR && !STAGE_M ? NFA + NGFS + NHYP : 0, NPL = KD::Nfph;
-    constexpr int LD = VOL ? NQ * NQ + (NQV == NQ ? 0 : NQV * NQV) : 1, LF = EPB * (VOL ? 3 : 1) * NS * Np,
-                  LM = EPB * (NMF > 0 ? NMF : 1) * (NMF > 0 ? NSURF : 1), LQ = FACES ? EPB * NS * Np : 1,
-                  LP = NPF > 0 ? 2 * NPF * NPL : 1;
-    static_assert(!DYNLDS || TendencyLds<P, NQ, NQV, USE_GF, PAIR>::doubles == LD + LF + LM + LQ + LP,
-                  "TendencyLds out of step with the kernel");
-    double *sD, *sF_, *sM_, *sQ_, *sP_;
-    if constexpr (DYNLDS) {
-        extern __shared__ double cmdg_dyn_lds[];
-        sD = cmdg_dyn_lds;
-        sF_ = sD + LD;
-        sM_ = sF_ + LF;
-        sQ_ = sM_ + LM;
-        sP_ = sQ_ + LQ;
-    } else {
-        __shared__ double aD[LD], aF[LF], aM[LM], aQ[LQ], aP[LP];
-        sD = aD, sF_ = aF, sM_ = aM, sQ_ = aQ, sP_ = aP;
-    }
+                  NMF = (STAGE_M ? NFA + NGFS + NHYP : 0) + NCA, OCA = NMF - NCA;
+    // LDS: sD derivative matrices; sF_ contravariant flux [d][s][ijk], later the accumulator; sM_ minus
+    // side, surface nodes [field][sidx]; sQ_ the prognostic state of every node (minus side of the
+    // faces, and the "Q" of the fused update at the end: re-reading it from memory 20 us after the
+    // first read misses L2).  (Reached through pointers, and the body kept out of the kernel: either
+    // change alters the generated code, though not the results.)
+    __shared__ double aD[NQ * NQ + (NQV == NQ ? 0 : NQV * NQV)], aF[EPB * 3 * NS * Np],
+        aM[EPB * (NMF > 0 ? NMF : 1) * (NMF > 0 ? NSURF : 1)], aQ[EPB * NS * Np];
+    double *sD = aD, *sF_ = aF, *sM_ = aM, *sQ_ = aQ;
     const double *const sDv = sD + (NQV == NQ ? 0 : NQ * NQ);  // vertical derivative matrix
     // this thread's element of the work-group and its index there
     const int sub = EPB == 1 ? 0 : (int)threadIdx.x / SH::NTE;
     const int tid = EPB == 1 ? (int)threadIdx.x : (int)threadIdx.x - sub * SH::NTE;
     const int64_t li = (int64_t)EPB * xcd_remap(blockIdx.x, gridDim.x) + sub;
-    // PAIR: entry (e0, e1) of the pair list; e1 > 0: the two share e0's xi1+ face
-    int64_t raw = 0;
-    bool paired = false;
-    if constexpr (PAIR) {
-        const int64_t r1 = a.elems[li - sub + 1];
-        paired = r1 > 0;
-        raw = sub == 0 ? a.elems[li - sub] : (sub == 1 ? (r1 < 0 ? -r1 : r1) : 0);
-    }
-    const bool live = PAIR ? raw != 0 : (EPB == 1 || (sub < EPB && li < a.nelems));
-    const int64_t e = live ? (PAIR ? raw : a.elems[li]) - 1 : 0;
+    const bool live = EPB == 1 || (sub < EPB && li < a.nelems);
+    const int64_t e = live ? a.elems[li] - 1 : 0;
     const int lsub = live ? sub : 0;
-    double *const sF = sF_ + lsub * ((VOL ? 3 : 1) * NS * Np);
+    double *const sF = sF_ + lsub * (3 * NS * Np);
     double *const sM = sM_ + lsub * ((NMF > 0 ? NMF : 1) * (NMF > 0 ? NSURF : 1));
-    double *const sQ = sQ_ + (FACES ? lsub * (NS * Np) : 0);
+    double *const sQ = sQ_ + lsub * (NS * Np);
     double *const sT = sF;              // tendency accumulator [s][ijk] (aliases sF after phase 2)
-    if constexpr (VOL) {
-        if (threadIdx.x < NQ * NQ) sD[threadIdx.x] = a.g.D[threadIdx.x];
-        if constexpr (NQV != NQ) {
-            if (threadIdx.x < NQV * NQV) sD[NQ * NQ + threadIdx.x] = a.g.Dv[threadIdx.x];
-        }
+    if (threadIdx.x < NQ * NQ) sD[threadIdx.x] = a.g.D[threadIdx.x];
+    if constexpr (NQV != NQ) {
+        if (threadIdx.x < NQV * NQV) sD[NQ * NQ + threadIdx.x] = a.g.Dv[threadIdx.x];
     }
     const bool hz = a.direction != DIR_VERTICAL, vt = a.direction != DIR_HORIZONTAL;
     // USE_GF: does flux_second_order depend on the gradient-flux state at all?  With zero
@@ -550,44 +447,13 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
     // zeros, so the host picks the instantiation that does not read them (identical results).
     constexpr bool use_gf = NGF > 0 && USE_GF;
     int32_t f_idP = 0;
-    int f_bctag = 0;
-    bool face_on = false;
-    if constexpr (FACES) {
-        int f_f = 0, f_n = 0;
-        KD::face_task(tid, f_f, f_n);
-        face_on = live && tid < KD::NFT && (f_f < 4 ? hz : vt);
-        // (the shared face of a pair has no table entry to load: interior, plus side in LDS)
-        if (face_on && !(PAIR && paired && f_f == 1 - lsub)) face_index<NQ, NQV>(a.g, e, tid, f_f, f_idP, f_bctag);
-    }
+    int f_bctag = 0, f_f = 0, f_n = 0;
+    KD::face_task(tid, f_f, f_n);
+    const bool face_on = live && tid < KD::NFT && (f_f < 4 ? hz : vt);
+    if (face_on) face_index<NQ, NQV>(a.g, e, tid, f_f, f_idP, f_bctag);
     Vec<NS> S;
     double MI = 0;
-    if constexpr (MODE == TEND_FACES) {
-        // interface half: the volume part of the tendency (the other launch stored it), the
-        // state, and the minus side of the surface nodes
-        if (live && tid < Np) {
-            const int sidx = surf_index<NQ, NQV>(tid);
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int64_t o = tid + (int64_t)Np * (s + (int64_t)NS * e);
-                sT[s * Np + tid] = a.tendency[o];
-                sQ[s * Np + tid] = a.Q[o];
-            }
-            if (sidx >= 0) {
-#pragma unroll
-                for (int s = 0; s < NFA; ++s)
-                    sM[s * NSURF + sidx] = a.aux[tid + (int64_t)Np * (P::face_aux(s) + (int64_t)NAUX * e)];
-                if (use_gf) {
-#pragma unroll
-                    for (int s = 0; s < NGF; ++s)
-                        sM[(NFA + s) * NSURF + sidx] = a.gf[gf_at<P, Np>(tid, s, e)];
-                }
-#pragma unroll
-                for (int s = 0; s < NHYP; ++s)
-                    sM[(NFA + NGFS + s) * NSURF + sidx] = a.hypgrad[hg_at<NHG, Np>(tid, s, e)];
-            }
-        }
-    }
-    if (VOL && live && tid < Np) {
+    if (live && tid < Np) {
         const double *vg = a.g.vgeo + (int64_t)Np * a.g.nvgeo * e + tid;
         const double M = vg[VM * Np];
         MI = vg[VMI * Np];
@@ -600,7 +466,7 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
         // residency: the hyperdiffusive inviscid instantiation at N <= 4 (Held-Suarez) sits at 126
         // VGPRs, five work-groups per CU; with nine more doubles live across the flux arithmetic it
         // takes 148 and runs on four (661 us against 636; rising bubble 132 -> 124 us, BOMEX 589 -> 578)
-        constexpr bool METRICS_FIRST = (CMDG_TEND_HOIST & 2) != 0 && !(NHYP > 0 && !use_gf && Np <= 125 && NS >= 5);
+        constexpr bool METRICS_FIRST = !(NHYP > 0 && !use_gf && Np <= 125 && NS >= 5);
         if constexpr (METRICS_FIRST) {
             if (hz) {
                 x11 = vg[XI1X1 * Np], x12 = vg[XI1X2 * Np], x13 = vg[XI1X3 * Np];
@@ -618,24 +484,9 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
             lhyp[s] = a.hypgrad[hg_at<NHG, Np>(tid, s, e)];
         if constexpr (METRICS_FIRST) __builtin_amdgcn_sched_barrier(0);  // (all of them in flight here)
         const int sidx = surf_index<NQ, NQV>(tid);
-        if constexpr (FACES) {
 #pragma unroll
-            for (int s = 0; s < NS; ++s) sQ[s * Np + tid] = lQ[s];
-        }
-        if constexpr (NPF > 0) {  // the shared face's fields, for the partner's plus side
-            if (paired && tid % NQ == (lsub == 0 ? NQ - 1 : 0)) {
-                double *sP = sP_ + lsub * (NPF * NPL) + tid / NQ;
-#pragma unroll
-                for (int s = 0; s < NFA; ++s) sP[s * NPL] = laux[P::face_aux(s)];
-                if (use_gf) {
-#pragma unroll
-                    for (int s = 0; s < NGF; ++s) sP[(NFA + s) * NPL] = lgf[s];
-                }
-#pragma unroll
-                for (int s = 0; s < NHYP; ++s) sP[(NFA + NGFS + s) * NPL] = lhyp[s];
-            }
-        }
-        if (FACES && STAGE_M && sidx >= 0) {  // stage the minus side of the interface phase
+        for (int s = 0; s < NS; ++s) sQ[s * Np + tid] = lQ[s];
+        if (STAGE_M && sidx >= 0) {  // stage the minus side of the interface phase
 #pragma unroll
             for (int s = 0; s < NFA; ++s) sM[s * NSURF + sidx] = laux[P::face_aux(s)];
             if (use_gf) {
@@ -696,23 +547,19 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
     }
     __syncthreads();
     Vec<NS> Tv;
-    if (VOL && live && tid < Np) {
+    if (live && tid < Np) {
         const int i = tid % NQ, j = (tid / NQ) % NQ, k = tid / (NQ * NQ);
-        Vec<NS> Tprev;
-        if constexpr ((CMDG_TEND_HOIST & 1) != 0) {
+        Vec<NS> Tprev;  // the old tendency, one batch of loads
 #pragma unroll
-            for (int s = 0; s < NS; ++s) Tprev[s] = 0.0;
-            if (a.beta != 0) {
+        for (int s = 0; s < NS; ++s) Tprev[s] = 0.0;
+        if (a.beta != 0) {
 #pragma unroll
-                for (int s = 0; s < NS; ++s) Tprev[s] = a.tendency[tid + (int64_t)Np * (s + (int64_t)NS * e)];
-            }
+            for (int s = 0; s < NS; ++s) Tprev[s] = a.tendency[tid + (int64_t)Np * (s + (int64_t)NS * e)];
         }
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             double T = 0.0;
-            const double Told = (CMDG_TEND_HOIST & 1) != 0
-                                    ? Tprev[s]
-                                    : (a.beta != 0 ? a.tendency[tid + (int64_t)Np * (s + (int64_t)NS * e)] : 0.0);
+            const double Told = Tprev[s];
             if (hz) {  // generic kernel called with HorizontalDirection() (:64-309)
                 double lt = 0.0;
                 if (a.direction == DIR_HORIZONTAL && P::HAS_SOURCE) lt += S[s];
@@ -747,19 +594,10 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
             Tv[s] = T;
         }
     }
-    if constexpr (MODE == TEND_VOLUME) {  // volume half: store, the interface launch goes on from here
-        if (live && tid < Np) {
+    __syncthreads();  // every read of sF is done: it becomes the accumulator sT
+    if (live && tid < Np) {
 #pragma unroll
-            for (int s = 0; s < NS; ++s) a.tendency[tid + (int64_t)Np * (s + (int64_t)NS * e)] = Tv[s];
-        }
-        return;
-    }
-    if constexpr (MODE == TEND_FUSED) {
-        __syncthreads();  // every read of sF is done: it becomes the accumulator sT
-        if (live && tid < Np) {
-#pragma unroll
-            for (int s = 0; s < NS; ++s) sT[s * Np + tid] = Tv[s];
-        }
+        for (int s = 0; s < NS; ++s) sT[s * Np + tid] = Tv[s];
     }
     // ---- faces: dgsem_interface_tendency! ------------------------------------------
     Vec<NS> lift;
@@ -794,9 +632,7 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
                             : a.aux[fp.vidM + (int64_t)Np * (P::face_aux(s) + (int64_t)NAUX * e)];
 #pragma unroll
             for (int s = 0; s < NGF; ++s) gfM[s] = gfP[s] = 0.0;
-            // PAIR: the face this element shares with its partner in the work-group
-            const bool shared_face = PAIR && paired && f == 1 - lsub;
-            const int gslot = RECV && !shared_face ? ghost_slot<Np>(a.h, fp.eP, fp.vidP) : -1;
+            const int gslot = RECV ? ghost_slot<Np>(a.h, fp.eP, fp.vidP) : -1;
             if (use_gf) {
                 if constexpr (STAGE_M) {
 #pragma unroll
@@ -811,42 +647,12 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
                                   : a.hypgrad[hg_at<NHG, Np>(fp.vidM, s, e)];
 #pragma unroll
             for (int s = 0; s < NAUX; ++s) auxPn[s] = 0;
-            if (shared_face) {  // plus side = the partner's staged minus side at the same face node
-                const int psub = 1 - lsub, vidP = face_vid<NQ, NQV>(f ^ 1, n);
-                const double *sQp = sQ_ + psub * (NS * Np);
+            if (use_gf) load_plus_gf<P, Np>(gfP, a.gf, a.h.recvGF, gslot, fp.vidP, fp.eP);
+            load_plus<NS, Np, NS>(QPn, a.Q, a.h.recvQ, gslot, fp.vidP, fp.eP);
 #pragma unroll
-                for (int s = 0; s < NS; ++s) QPn[s] = sQp[s * Np + vidP];
-                if constexpr (STAGE_M) {
-                    const double *sMp = sM_ + psub * ((NMF > 0 ? NMF : 1) * (NMF > 0 ? NSURF : 1));
-                    const int sidxP = surf_index<NQ, NQV>(vidP);
-#pragma unroll
-                    for (int s = 0; s < NFA; ++s) auxPn[P::face_aux(s)] = sMp[s * NSURF + sidxP];
-                    if (use_gf) {
-#pragma unroll
-                        for (int s = 0; s < NGF; ++s) gfP[s] = sMp[(NFA + s) * NSURF + sidxP];
-                    }
-#pragma unroll
-                    for (int s = 0; s < NHYP; ++s) hypP[s] = sMp[(NFA + NGFS + s) * NSURF + sidxP];
-                } else if constexpr (NPF > 0) {
-                    const double *sPp = sP_ + psub * (NPF * NPL) + n;
-#pragma unroll
-                    for (int s = 0; s < NFA; ++s) auxPn[P::face_aux(s)] = sPp[s * NPL];
-                    if (use_gf) {
-#pragma unroll
-                        for (int s = 0; s < NGF; ++s) gfP[s] = sPp[(NFA + s) * NPL];
-                    }
-#pragma unroll
-                    for (int s = 0; s < NHYP; ++s) hypP[s] = sPp[(NFA + NGFS + s) * NPL];
-                }
-            } else {
-                if (use_gf) load_plus_gf<P, Np>(gfP, a.gf, a.h.recvGF, gslot, fp.vidP, fp.eP);
-                load_plus<NS, Np, NS>(QPn, a.Q, a.h.recvQ, gslot, fp.vidP, fp.eP);
-#pragma unroll
-                for (int s = 0; s < NFA; ++s)
-                    auxPn[P::face_aux(s)] =
-                        a.aux[fp.vidP + (int64_t)Np * (P::face_aux(s) + (int64_t)NAUX * fp.eP)];
-                load_plus_hg<NHG, Np, NHYP>(hypP, a.hypgrad, a.h.recvHG, gslot, fp.vidP, fp.eP);
-            }
+            for (int s = 0; s < NFA; ++s)
+                auxPn[P::face_aux(s)] = a.aux[fp.vidP + (int64_t)Np * (P::face_aux(s) + (int64_t)NAUX * fp.eP)];
+            load_plus_hg<NHG, Np, NHYP>(hypP, a.hypgrad, a.h.recvHG, gslot, fp.vidP, fp.eP);
 #pragma unroll
             for (int s = 0; s < NS; ++s) QPd[s] = QPn[s];
 #pragma unroll
@@ -934,349 +740,14 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
             });
     }
 }
-
-template <class P, int NQ, int NQV, bool LSRK, bool USE_GF, bool RECV = false, int MODE = TEND_FUSED,
-          bool PAIR = false>
-__global__ void __launch_bounds__((tendency_threads<P, NQ, NQV, MODE, PAIR>()),
-                                   (MODE == TEND_FUSED ? CMDG_TEND_MINW
-                                                       : (MODE == TEND_VOLUME ? CMDG_TENDV_MINW : CMDG_TENDF_MINW)))
-    k_tendency(const PassArgs<P> a)
+template <class P, int NQ, int NQV, bool LSRK, bool USE_GF, bool RECV = false>
+__global__ void __launch_bounds__((TendencyShape<P, NQ, NQV>::NT), CMDG_TEND_MINW) k_tendency(const PassArgs<P> a)
 {
-    tendency_body<P, NQ, NQV, LSRK, USE_GF, RECV, MODE, PAIR>(a);
-}
-// Paired work-groups of small elements: 384 threads are six waves, which a CU places 2-1-2-1 over its
-// SIMDs, so a second work-group is resident only at <= 128 VGPRs (profiles/r02_lds_occupancy.jsonl;
-// unconstrained the Held-Suarez instantiation takes 154 and runs at half the occupancy, twice the
-// time: profiles/r04_ab_tendency_pairs.txt).  Neither a waves-per-SIMD request nor amdgpu_num_vgpr
-// gets there with static LDS -- the compiler relaxes both to what 62 KB of LDS per work-group
-// allow, three waves per SIMD ("failed to meet occupancy target") -- so this kernel takes its LDS
-// dynamically: the footprint is then unknown at compile time and four waves per SIMD are honoured.
-template <class P, int NQ, int NQV, bool LSRK, bool USE_GF, bool RECV>
-__global__ void __launch_bounds__((tendency_threads<P, NQ, NQV, TEND_FUSED, true>()), 4)
-    k_tendency_pair_small(const PassArgs<P> a)
-{
-    tendency_body<P, NQ, NQV, LSRK, USE_GF, RECV, TEND_FUSED, true, true>(a);
-}
-
-// ---------------------------------------------------------------------------------
-// Tendency pass of LARGE elements (Np > 125) on four-wave work-groups (round 4).  The fused
-// two-element shape above keeps ONE eleven-wave work-group on a CU (132 KB of LDS, 167 VGPRs):
-// its phases -- loads, 2 800 fp64 VALU instructions per wave, barrier, contraction, gathers, flux,
-// lift -- overlap with nobody's, and the kernel is bound by their latencies, not by bytes
-// (profiles/r04_bomex_n6_8192_pmc_sq.json, r04_ab_tendency_pairs.txt).  A second SIX-wave
-// work-group is resident only at <= 128 VGPRs (they are placed 2-1-2-1 over the SIMDs), which the
-// moist law's interface phase cannot meet.  FOUR-wave work-groups are placed 1-1-1-1: three share
-// a CU at <= 168 VGPRs if each takes <= 53 KB of LDS.  So: 256 threads per element, every thread
-// owns node tid and node tid + 256 (the second round is 87 nodes = two waves at N = 6), face tasks
-// likewise in two rounds; LDS holds the three contravariant fluxes only (49 KB) -- the state is
-// not staged (the minus side of the faces and the fused update read it again, L2-warm) and the
-// source is kept in registers.  Arithmetic and summation order are those of tendency_body.
-// Measured (BOMEX, N = 6): 869 us against 596 us for the shape above -- three independent work-groups
-// per CU do not make up for 204 B of scratch per thread, the state read three times instead of once
-// and second rounds that fill a quarter of the lanes.  Not compiled in by default (CMDG_TEND_FOUR_WAVES).
-template <class P, int NQ, int NQV, bool LSRK, bool USE_GF, bool RECV>
-__global__ void __launch_bounds__(256, 3) k_tendency_big(const PassArgs<P> a)
-{
-    using KD = KDims<NQ, NQV>;
-    static_assert(node_cache_size<P>::value == 0, "no node cache in the four-wave shape");
-    const double a_t = a.tptr ? *a.tptr : a.t;
-    constexpr int Np = KD::Np, NS = P::NS, NAUX = P::NAUX, NGF = P::NGF, NHYP = P::NHYP, NHG = 3 * P::NGL,
-                  NFA = P::NFAUX, NT = 256, RV = (Np + NT - 1) / NT, RF = (KD::NFT + NT - 1) / NT;
-    static_assert(RV <= 2 && RF <= 2, "two rounds at most");
-    constexpr bool use_gf = NGF > 0 && USE_GF;
-    __shared__ double sD[NQ * NQ + (NQV == NQ ? 0 : NQV * NQV)];
-    const double *const sDv = sD + (NQV == NQ ? 0 : NQ * NQ);
-    __shared__ double sF[3 * NS * Np];  // [d][s][ijk]; afterwards the accumulator sT[s][ijk]
-    double *const sT = sF;
-    const int tid = threadIdx.x;
-    const int64_t e = a.elems[xcd_remap(blockIdx.x, gridDim.x)] - 1;
-    if (tid < NQ * NQ) sD[tid] = a.g.D[tid];
-    if constexpr (NQV != NQ) {
-        if (tid < NQV * NQV) sD[NQ * NQ + tid] = a.g.Dv[tid];
-    }
-    const bool hz = a.direction != DIR_VERTICAL, vt = a.direction != DIR_HORIZONTAL;
-    Vec<NS> S[RV];
-    double MI[RV];
-    // ---- phase 1: pointwise physics of the nodes of both rounds
-#pragma unroll
-    for (int r = 0; r < RV; ++r) {
-        const int node = tid + NT * r;
-        MI[r] = 0;
-        S[r].negzero();
-        if (node < Np) {
-            const double *vg = a.g.vgeo + (int64_t)Np * a.g.nvgeo * e + node;
-            const double M = vg[VM * Np];
-            MI[r] = vg[VMI * Np];
-            Vec<NS> lQ;
-            Vec<NAUX> laux;
-            Vec<NGF> lgf;
-            Vec<NHYP> lhyp;
-            load_state<NS, Np>(lQ, a.Q, node, e);
-            load_state<NAUX, Np>(laux, a.aux, node, e);
-#pragma unroll
-            for (int s = 0; s < NGF; ++s) lgf[s] = 0.0;
-            if (use_gf) load_gf<P, Np>(lgf, a.gf, node, e);
-#pragma unroll
-            for (int s = 0; s < NHYP; ++s) lhyp[s] = a.hypgrad[hg_at<NHG, Np>(node, s, e)];
-            Vec<3 * NS> F, F2;
-            F.negzero();
-            P::flux_first_order(a.prm, F, lQ, laux, a_t, a.model_dir);
-            F2.negzero();
-            P::flux_second_order(a.prm, F2, lQ, lgf, lhyp, laux, a_t);
-#pragma unroll
-            for (int q = 0; q < 3 * NS; ++q) F[q] += F2[q];
-            if (hz) {
-                const double x11 = vg[XI1X1 * Np], x12 = vg[XI1X2 * Np], x13 = vg[XI1X3 * Np];
-                const double x21 = vg[XI2X1 * Np], x22 = vg[XI2X2 * Np], x23 = vg[XI2X3 * Np];
-#pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    const double F1 = F[3 * s], F2_ = F[3 * s + 1], F3 = F[3 * s + 2];
-                    sF[(0 * NS + s) * Np + node] = M * (x11 * F1 + x12 * F2_ + x13 * F3);
-                    sF[(1 * NS + s) * Np + node] = M * (x21 * F1 + x22 * F2_ + x23 * F3);
-                }
-            }
-            if (vt) {
-                const double x31 = vg[XI3X1 * Np], x32 = vg[XI3X2 * Np], x33 = vg[XI3X3 * Np];
-#pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    const double F1 = F[3 * s], F2_ = F[3 * s + 1], F3 = F[3 * s + 2];
-                    sF[(2 * NS + s) * Np + node] = M * (x31 * F1 + x32 * F2_ + x33 * F3);
-                }
-            }
-            if constexpr (P::HAS_SOURCE) {
-                Vec<P::NDER> lder;
-                load_state<P::NDER, Np>(lder, a.derived, node, e);
-                P::source(a.prm, S[r], lQ, lgf, laux, lder, a_t, a.model_dir);
-            }
-        }
-    }
-    __syncthreads();
-    // ---- phase 2: contractions (reference order: horizontal part, then vertical with the source)
-    Vec<NS> Tv[RV];
-#pragma unroll
-    for (int r = 0; r < RV; ++r) {
-        const int node = tid + NT * r;
-        if (node < Np) {
-            const int i = node % NQ, j = (node / NQ) % NQ, k = node / (NQ * NQ);
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                double T = 0.0;
-                const double Told = a.beta != 0 ? a.tendency[node + (int64_t)Np * (s + (int64_t)NS * e)] : 0.0;
-                if (hz) {
-                    double lt = 0.0;
-                    if (a.direction == DIR_HORIZONTAL && P::HAS_SOURCE) lt += S[r][s];
-#pragma unroll
-                    for (int n = 0; n < NQ; ++n) {
-                        lt += MI[r] * sD[n + NQ * i] * sF[(0 * NS + s) * Np + n + NQ * (j + NQ * k)];
-                        lt += MI[r] * sD[n + NQ * j] * sF[(1 * NS + s) * Np + i + NQ * (n + NQ * k)];
-                    }
-                    T = a.beta != 0 ? a.alpha * lt + a.beta * Told : a.alpha * lt;
-                }
-                if (vt) {
-                    double lt = 0.0;
-#pragma unroll
-                    for (int kk = 0; kk < NQV; ++kk) {
-                        lt += MI[r] * sDv[kk + NQV * k] * sF[(2 * NS + s) * Np + i + NQ * (j + NQ * kk)];
-                        if (kk == k && P::HAS_SOURCE) lt += S[r][s];
-                    }
-                    if (hz)
-                        T = a.alpha * lt + T;
-                    else
-                        T = a.beta != 0 ? a.alpha * lt + a.beta * Told : a.alpha * lt;
-                }
-                Tv[r][s] = T;
-            }
-        }
-    }
-    __syncthreads();  // every read of sF is done: it becomes the accumulator sT
-#pragma unroll
-    for (int r = 0; r < RV; ++r) {
-        const int node = tid + NT * r;
-        if (node < Np) {
-#pragma unroll
-            for (int s = 0; s < NS; ++s) sT[s * Np + node] = Tv[r][s];
-        }
-    }
-    __syncthreads();
-    // ---- faces, one round of tasks at a time; a round's lifts are applied before the next round
-    // (pair by pair: opposite faces touch disjoint nodes, and every node still receives its pairs in
-    // the order 1-2, 3-4, 5-6 -- the second round holds tasks of the last face only)
-    static_assert(RF == 1 || (RF - 1) * NT >= 4 * KD::Nfph, "later rounds must hold tasks of faces 5, 6 only");
-#pragma unroll
-    for (int r = 0; r < RF; ++r) {
-        const int t = tid + NT * r;
-        Vec<NS> lift;
-        int vidM = 0, fpair = -1;
-        if (t < KD::NFT) {
-            int f, n;
-            KD::face_task(t, f, n);
-            if (f < 4 ? hz : vt) {
-                const int facedir = f < 4 ? DIR_HORIZONTAL : DIR_VERTICAL;
-                FacePt fp;
-                face_setup<NQ, NQV>(a.g, e, t, f, n, fp);
-                Vec<NS> QM, QPn, QPd, flux;
-                Vec<NAUX> auxM, auxPn, auxPd;
-                Vec<NGF> gfM, gfP;
-                Vec<NHYP> hypM, hypP;
-#pragma unroll
-                for (int s = 0; s < NAUX; ++s) auxM[s] = 0;
-                load_state<NS, Np>(QM, a.Q, fp.vidM, e);
-#pragma unroll
-                for (int s = 0; s < NFA; ++s)
-                    auxM[P::face_aux(s)] = a.aux[fp.vidM + (int64_t)Np * (P::face_aux(s) + (int64_t)NAUX * e)];
-#pragma unroll
-                for (int s = 0; s < NGF; ++s) gfM[s] = gfP[s] = 0.0;
-                const int gslot = RECV ? ghost_slot<Np>(a.h, fp.eP, fp.vidP) : -1;
-                if (use_gf) {
-                    load_gf<P, Np>(gfM, a.gf, fp.vidM, e);
-                    load_plus_gf<P, Np>(gfP, a.gf, a.h.recvGF, gslot, fp.vidP, fp.eP);
-                }
-#pragma unroll
-                for (int s = 0; s < NHYP; ++s)
-                    hypM[s] = a.hypgrad[hg_at<NHG, Np>(fp.vidM, s, e)];
-                load_plus<NS, Np, NS>(QPn, a.Q, a.h.recvQ, gslot, fp.vidP, fp.eP);
-#pragma unroll
-                for (int s = 0; s < NAUX; ++s) auxPn[s] = 0;
-#pragma unroll
-                for (int s = 0; s < NFA; ++s)
-                    auxPn[P::face_aux(s)] =
-                        a.aux[fp.vidP + (int64_t)Np * (P::face_aux(s) + (int64_t)NAUX * fp.eP)];
-                load_plus_hg<NHG, Np, NHYP>(hypP, a.hypgrad, a.h.recvHG, gslot, fp.vidP, fp.eP);
-#pragma unroll
-                for (int s = 0; s < NS; ++s) QPd[s] = QPn[s];
-#pragma unroll
-                for (int s = 0; s < NAUX; ++s) auxPd[s] = auxPn[s];
-                flux.negzero();
-                if (fp.bctag == 0) {
-                    nf_first_order<P>(a.prm, a.nf_first, flux, fp.n, QM, auxM, QPn, auxPn, a_t, facedir, nullptr);
-                    Vec<3 * NS> FM, FP;
-                    FM.negzero();
-                    P::flux_second_order(a.prm, FM, QM, gfM, hypM, auxM, a_t);
-                    FP.negzero();
-                    P::flux_second_order(a.prm, FP, QPd, gfP, hypP, auxPd, a_t);
-                    const double nh0 = fp.n[0] / 2, nh1 = fp.n[1] / 2, nh2 = fp.n[2] / 2;
-#pragma unroll
-                    for (int s = 0; s < NS; ++s)
-                        flux[s] += (FM[3 * s] + FP[3 * s]) * nh0 + (FM[3 * s + 1] + FP[3 * s + 1]) * nh1 +
-                                   (FM[3 * s + 2] + FP[3 * s + 2]) * nh2;
-                } else {
-                    load_state<NAUX, Np>(auxM, a.aux, fp.vidM, e);
-#pragma unroll
-                    for (int s = 0; s < NAUX; ++s) auxPn[s] = auxPd[s] = auxM[s];
-                    Vec<NS> Q1;
-                    Vec<NAUX> aux1;
-                    Vec<NGF> gf1;
-                    for (int s = 0; s < NS; ++s) Q1[s] = 0;
-                    for (int s = 0; s < NAUX; ++s) aux1[s] = 0;
-                    for (int s = 0; s < NGF; ++s) gf1[s] = 0;
-                    if (f == 4) {
-                        load_state<NS, Np>(Q1, a.Q, n + NQ * NQ, e);
-                        load_state<NAUX, Np>(aux1, a.aux, n + NQ * NQ, e);
-                        if (use_gf) load_gf<P, Np>(gf1, a.gf, n + NQ * NQ, e);
-                    }
-                    P::boundary_state(a.prm, BS_FIRST, fp.bctag, QPn, auxPn, fp.n, QM, auxM, a_t, Q1, aux1);
-                    nf_first_order<P>(a.prm, a.nf_first, flux, fp.n, QM, auxM, QPn, auxPn, a_t, facedir, nullptr);
-                    Vec<3 * NS> FP;
-                    FP.negzero();
-                    P::boundary_flux_second_order(a.prm, fp.bctag, FP, QPd, gfP, hypP, auxPd, fp.n, QM, gfM,
-                                                  hypM, auxM, a_t, Q1, gf1, aux1);
-#pragma unroll
-                    for (int s = 0; s < NS; ++s)
-                        flux[s] += FP[3 * s] * fp.n[0] + FP[3 * s + 1] * fp.n[1] + FP[3 * s + 2] * fp.n[2];
-                }
-#pragma unroll
-                for (int s = 0; s < NS; ++s) lift[s] = a.alpha * fp.vMI * fp.sM * flux[s];
-                vidM = fp.vidM;
-                fpair = f / 2;
-            }
-        }
-#pragma unroll
-        for (int pp = 0; pp < 3; ++pp) {
-            if (fpair == pp) {
-#pragma unroll
-                for (int s = 0; s < NS; ++s) sT[s * Np + vidM] -= lift[s];
-            }
-            __syncthreads();
-        }
-    }
-    // ---- store, with the LSRK update fused in
-#pragma unroll
-    for (int r = 0; r < RV; ++r) {
-        const int node = tid + NT * r;
-        if (node < Np) {
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int64_t o = node + (int64_t)Np * (s + (int64_t)NS * e);
-                const double T = sT[s * Np + node];
-                if constexpr (LSRK) {
-                    a.Qout[o] = a.Q[o] + a.rkb_dt * T;
-                    a.tendency[o] = T * a.rka_next;
-                } else {
-                    a.tendency[o] = T;
-                }
-            }
-        }
-    }
-    if constexpr (LSRK)
-        send_nodes<NS, NS>(a.h, 0, e, tid, NT, [&](int s, int n) {
-            return a.Q[n + (int64_t)Np * (s + (int64_t)NS * e)] + a.rkb_dt * sT[s * Np + n];
-        });
+    tendency_body<P, NQ, NQV, LSRK, USE_GF, RECV>(a);
 }
 
 // ---------------------------------------------------------------------------------
 // Gradient pass: volume_gradients! (:934-1328) + dgsem_interface_gradients! (:1365-1651)
-#ifdef CMDG_MFMA_GRAD
-// A/B variant (not the default, see DESIGN.md "MFMA"): the (N+1)-point derivative contractions of
-// the gradient pass on the matrix pipe, v_mfma_f64_16x16x4_f64.  One 16x16x16 product (four
-// instructions) applies blockdiag(D, D, D) to 3 x 16 lines of five values: 48 lines, 2 400 useful
-// of 8 192 issued flops (K = 5 does not tile the instruction).  Lines of direction dir (0: xi1,
-// 1: xi2, 2: xi3) of the active fields are taken from sG and the derivatives land in
-// sDer[dir][field][node]; thread = node then applies the metric terms as the VALU path does.
-typedef double cmdg_v4d __attribute__((ext_vector_type(4)));
-template <int NFLD>
-__device__ __forceinline__ void mfma_line_derivatives(const double *sD, const double *sG,
-                                                      double *sDer, unsigned fldpack, int nact,
-                                                      int ndir, unsigned dirpack, int tid, int nthreads)
-{
-    constexpr int NQ = 5, Np = 125;
-    const int lane = tid & 63, wave = tid >> 6, nwaves = nthreads >> 6;
-    const int nlines = 25 * nact, ngroups = (nlines + 47) / 48;
-    const int c = lane & 15, kr = lane >> 4;
-    double Aop[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-        const int ip = c, r = 4 * kk + kr;  // A[row ip][col r]
-        Aop[kk] = (ip < 15 && r < 15 && ip / 5 == r / 5) ? sD[(ip % 5) + NQ * (r % 5)] : 0.0;
-    }
-    for (int w = wave; w < ndir * ngroups; w += nwaves) {
-        const int dir = (dirpack >> (2 * (w / ngroups))) & 3, g = w % ngroups;
-        cmdg_v4d acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int r = 4 * kk + kr, L = 48 * g + 16 * (r / 5) + c, n = r % 5;
-            double b = 0.0;
-            if (r < 15 && L < nlines) {
-                const int aa = L % 25, s = (fldpack >> (4 * (L / 25))) & 15;
-                const int node = dir == 0 ? 5 * aa + n
-                                          : (dir == 1 ? (aa % 5) + 5 * n + 25 * (aa / 5) : aa + 25 * n);
-                b = sG[s * Np + node];
-            }
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Aop[kk], b, acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const int ip = kr + 4 * reg, L = 48 * g + 16 * (ip / 5) + c, i = ip % 5;
-            if (ip < 15 && L < nlines) {
-                const int aa = L % 25, s = (fldpack >> (4 * (L / 25))) & 15;
-                const int node = dir == 0 ? 5 * aa + i
-                                          : (dir == 1 ? (aa % 5) + 5 * i + 25 * (aa / 5) : aa + 25 * i);
-                sDer[(dir * NFLD + s) * Np + node] = acc[reg];
-            }
-        }
-    }
-}
-#endif
-
 // USE_GF = false: the law's second-order flux does not read the gradient-flux state (zero
 // viscosity): only the gradients the hyperdiffusion passes consume are formed and stored, and
 // state_gradient_flux is left untouched (cmdg_set_option(CMDG_OPT_KEEP_GRADFLUX) restores it).
@@ -1304,10 +775,6 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
     const double *const sDv = sD + (NQV == NQ ? 0 : NQ * NQ);  // vertical derivative matrix
     __shared__ double sG[(NGRAD > 0 ? NGRAD : 1) * Np];
     __shared__ double sA[(NACC > 0 ? NACC : 1) * Np];  // [gf..., hypgrad...][ijk]
-#ifdef CMDG_MFMA_GRAD
-    constexpr bool MFMA = NQ == 5 && NQV == 5 && NGRAD > 0;
-    __shared__ double sDer[MFMA ? 3 * NGRAD * Np : 1];
-#endif
     const int tid = threadIdx.x;
     const int64_t e = a.elems[xcd_remap(blockIdx.x, gridDim.x)] - 1;
     if (tid < NQ * NQ) sD[tid] = a.g.D[tid];
@@ -1337,20 +804,6 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
             if (GMASK >> s & 1) sG[s * Np + tid] = G[s];
     }
     __syncthreads();
-#ifdef CMDG_MFMA_GRAD
-    if constexpr (MFMA) {
-        static_assert(NGRAD <= 8, "field ordinals are packed four bits each");
-        unsigned fldpack = 0, dirpack = 0;  // active fields / directions, packed
-        int nact = 0, ndir = 0;
-#pragma unroll
-        for (int s = 0; s < NGRAD; ++s)
-            if (GMASK >> s & 1) fldpack |= (unsigned)s << (4 * nact++);
-        if (hz) dirpack |= 0u << (2 * ndir++), dirpack |= 1u << (2 * ndir++);
-        if (vt) dirpack |= 2u << (2 * ndir++);
-        mfma_line_derivatives<NGRAD>(sD, sG, sDer, fldpack, nact, ndir, dirpack, tid, KD::NT);
-        __syncthreads();
-    }
-#endif
     if (tid < Np) {
         const int i = tid % NQ, j = (tid / NQ) % NQ, k = tid / (NQ * NQ);
         const double *vg = a.g.vgeo + (int64_t)Np * a.g.nvgeo * e + tid;
@@ -1364,12 +817,7 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
             for (int s = 0; s < NGRAD; ++s) {
                 if (!(GMASK >> s & 1)) continue;
                 double G1 = 0.0, G2 = 0.0;
-#if defined(CMDG_MFMA_GRAD)
-                if constexpr (MFMA) {
-                    G1 = sDer[(0 * NGRAD + s) * Np + tid];
-                    G2 = sDer[(1 * NGRAD + s) * Np + tid];
-                } else
-#elif defined(CMDG_DBG_NOCONTRACT)
+#ifdef CMDG_DBG_NOCONTRACT
                 // ablation: the contraction's share of the kernel (results are wrong)
                 G1 = sD[i] * sG[s * Np + tid], G2 = sD[j] * sG[s * Np + tid];
                 if (false)
@@ -1393,11 +841,7 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
             for (int s = 0; s < NGRAD; ++s) {
                 if (!(GMASK >> s & 1)) continue;
                 double G3 = -0.0;
-#if defined(CMDG_MFMA_GRAD)
-                if constexpr (MFMA) {
-                    G3 = sDer[(2 * NGRAD + s) * Np + tid];
-                } else
-#elif defined(CMDG_DBG_NOCONTRACT)
+#ifdef CMDG_DBG_NOCONTRACT
                 G3 = sDv[k] * sG[s * Np + tid];
                 if (false)
 #endif
@@ -1524,15 +968,10 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
             for (int s = 0; s < NGF; ++s)
                 a.gf[tid + (int64_t)Np * (s + (int64_t)P::NGF * e)] = sA[s * Np + tid];
         }
-        if constexpr (!CMDG_HG_NODE_MAJOR) {
-#pragma unroll
-            for (int s = 0; s < NHG; ++s)
-                a.hypgrad[hg_at<NHG, Np>(tid, s, e)] = sA[(NGF + s) * Np + tid];
-        }
     }
     if constexpr (gf_node_major<P>::value && NGF > 0)
         store_node_major<P::NGF, Np, NGF>(a.gf, e, tid, (int)blockDim.x, sA);
-    if constexpr (CMDG_HG_NODE_MAJOR && NHG > 0)
+    if constexpr (NHG > 0)
         store_node_major<NHG, Np, NHG>(a.hypgrad, e, tid, (int)blockDim.x, sA + NGF * Np);
     if constexpr (NGF > 0)
         send_nodes<P::NGF, NGF>(a.h, 0, e, tid, (int)blockDim.x, [&](int s, int n) { return sA[s * Np + n]; });
@@ -1797,13 +1236,7 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT), CMDG_LAP_MINW) k_gradlap
         }
         __syncthreads();
     }
-    if constexpr (CMDG_HG_NODE_MAJOR) {
-        if constexpr (NHYP > 0) store_node_major<NHG, Np, NHYP>(a.hypgrad, e, tid, (int)blockDim.x, sA);
-    } else if (tid < Np) {
-#pragma unroll
-        for (int s = 0; s < NHYP; ++s)
-            a.hypgrad[hg_at<NHG, Np>(tid, s, e)] = sA[s * Np + tid];
-    }
+    if constexpr (NHYP > 0) store_node_major<NHG, Np, NHYP>(a.hypgrad, e, tid, (int)blockDim.x, sA);
     if constexpr (NHYP > 0)
         send_nodes<NHG, NHYP>(a.h, 0, e, tid, (int)blockDim.x, [&](int s, int n) { return sA[s * Np + n]; });
 }

@@ -236,15 +236,7 @@ int cmdg_synchronize(cmdg_handle h);
  *   library therefore begins such a capture on the halo stream (the groups' stream) and forks the
  *   compute stream.  Runs a capture cannot hold stay eager: profiling, filters, hooks, a nodal
  *   update_auxiliary_state! kernel of its own, the local transport, exchanges that are packed.
- * CMDG_OPT_TENDENCY_PAIRS (default 0; environment CMDG_TENDENCY_PAIRS=1): the tendency pass takes
- *   horizontally adjacent elements two to a work-group and reads the xi1 face they share out of
- *   LDS instead of gathering it (laws with one polynomial order and no node cache; the pairs are
- *   found from vmap+ at create: faces that meet node for node).  Results are bit-identical.
- * CMDG_OPT_TENDENCY_FOUR_WAVES (environment CMDG_TENDENCY_FOUR_WAVES): elements above N = 4 -- the
- *   tendency pass on 256-thread work-groups, two nodes per thread, three work-groups per CU
- *   (k_tendency_big) instead of two elements per eleven-wave work-group.  Bit-identical; a
- *   recorded experiment like CMDG_OPT_TENDENCY_PAIRS (slower; effective only in a library built
- *   with -DCMDG_TEND_FOUR_WAVES=1 / -DCMDG_TEND_PAIRS=1, a no-op otherwise).
+ * CMDG_OPT_TENDENCY_PAIRS, CMDG_OPT_TENDENCY_FOUR_WAVES: retired; accepted and have no effect.
  * CMDG_OPT_ASYNC_RUN (default 0): cmdg_lsrk_run hands the run to a thread the handle owns and
  *   returns at once (the tableau is copied, Q and dQ must stay valid): the calling thread is not the
  *   one that spends ~1 ms per step of a partitioned run inside hipGraphLaunch or posting RCCL
@@ -260,8 +252,8 @@ int cmdg_synchronize(cmdg_handle h);
 enum {
     CMDG_OPT_KEEP_GRADFLUX = 1, CMDG_OPT_STACK_HEIGHT = 2, CMDG_OPT_REFERENCE_HALO = 3,
     CMDG_OPT_HALO_PIPELINE = 4, CMDG_OPT_STEP_GRAPH = 5, CMDG_OPT_STREAM_PRIORITY = 6,
-    CMDG_OPT_TENDENCY_PAIRS = 7, CMDG_OPT_ASYNC_RUN = 8,
-    CMDG_OPT_TENDENCY_FOUR_WAVES = 9
+    CMDG_OPT_TENDENCY_PAIRS = 7 /* retired */, CMDG_OPT_ASYNC_RUN = 8,
+    CMDG_OPT_TENDENCY_FOUR_WAVES = 9 /* retired */
 };
 int cmdg_set_option(cmdg_handle h, int32_t option, int32_t value);
 
@@ -284,7 +276,7 @@ enum {
     CMDG_Q_HOST_POST_NS = 10,   /* host nanoseconds spent posting exchanges (RCCL group calls) ... */
     CMDG_Q_HOST_POST_COUNT = 11, /* ... and how many were posted, since the handle was created */
     CMDG_Q_GRAPH_STEPS = 12,     /* steps cmdg_lsrk_run replayed from a captured graph */
-    CMDG_Q_TENDENCY_PAIRS = 13,  /* work-groups of the tendency pass that share a face (-1: option off) */
+    CMDG_Q_TENDENCY_PAIRS = 13,  /* retired with CMDG_OPT_TENDENCY_PAIRS: always -1 (option off) */
     CMDG_Q_STATE_READ = 16, CMDG_Q_AUX_READ = 20
 };
 int cmdg_query(cmdg_handle h, int32_t what, int64_t *out);

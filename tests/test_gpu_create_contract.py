@@ -80,3 +80,27 @@ def test_gradient_flux_copies_are_refused_on_a_node_major_law(cm, torch):
     with pytest.raises(RuntimeError, match="node-major"):
         dg.set_rhs_hooks(gradflux_to_aux=[(0, law.naux - 1, 1.0)])
     dg.close()
+
+
+def test_retired_tendency_options_are_accepted_and_change_nothing(cm, torch):
+    """CMDG_OPT_TENDENCY_PAIRS (7) and CMDG_OPT_TENDENCY_FOUR_WAVES (9) are retired (include/cmdg.h):
+    cmdg_set_option still accepts them and does nothing, and CMDG_Q_TENDENCY_PAIRS (13) reports -1
+    (option off).  Steps taken after setting them have the bits of steps without them."""
+    from helpers import pseudo1d_setup
+    assert (cm._lib.OPT_TENDENCY_PAIRS, cm._lib.OPT_TENDENCY_FOUR_WAVES, cm._lib.CMDG_Q["TENDENCY_PAIRS"]) == (7, 9, 13)
+    out = []
+    for retired in (False, True):
+        law, grid, dt = pseudo1d_setup(Ne=2)
+        dg = cm.dgmodel.DGModel(law, grid)
+        if retired:
+            dg.set_option(7, 1)
+            dg.set_option(9, 1)
+        assert dg.query("TENDENCY_PAIRS") == -1
+        Q = dg.init_ode_state(0.0)
+        solver = cm.odesolvers.LSRK54CarpenterKennedy(dg, Q, dt=dt)
+        solver.dostep(Q, nsteps=2)
+        dg.synchronize()
+        out.append(Q[:grid.nreal].cpu().numpy().copy())
+        dg.close()
+    assert np.isfinite(out[0]).all() and np.abs(out[0]).max() > 0
+    assert np.array_equal(out[0], out[1])

@@ -116,6 +116,68 @@ int dbg_sync()
 
 hipError_t ev_record(hipEvent_t &e, hipStream_t s) { return hipEventRecord(e, s); }
 
+int EngineBase::launch_status(const char *what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(CMDG_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    return CMDG_OK;
+}
+
+int EngineBase::order(hipStream_t earlier, hipStream_t later)
+{
+    if (earlier == later) return CMDG_OK;
+    if (dbg_sync() & 1) (void)hipStreamSynchronize(earlier);
+    if (ev_record(ev_comp, earlier) != hipSuccess || hipStreamWaitEvent(later, ev_comp, 0) != hipSuccess)
+        return fail(CMDG_ERR_HIP, "stream ordering failed");
+    return CMDG_OK;
+}
+
+int EngineBase::ensure_Imat(const double *host)
+{
+    if (d_Imat) return CMDG_OK;
+    if (!host) return fail(CMDG_ERR_INVALID, "Imat is NULL");
+    if (hipMalloc(&d_Imat, sizeof(double) * NQ * NQ) != hipSuccess ||
+        hipMemcpy(d_Imat, host, sizeof(double) * NQ * NQ, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(CMDG_ERR_HIP, "Imat upload failed");
+    return CMDG_OK;
+}
+
+int set_err(cmdg_handle h, int code)
+{
+    if (h && h->eng && code != CMDG_OK) h->err = h->eng->err;
+    return code;
+}
+
+GroupCall::GroupCall(cmdg_handle *h, cmdg_handle *h2, int n, bool pairs)
+{
+    if (!h || (pairs && !h2) || n < 1) return;
+    for (int i = 0; i < n; ++i)
+        if (!h[i] || (pairs && !h2[i])) return;
+    for (int i = 0; i < n; ++i) {  // (members in order, each with the prefix of its message)
+        const std::string r = std::to_string(i);
+        members.push_back({h[i], pairs ? "pair " + r + " (slow): " : "rank " + r + ": "});
+        if (pairs) members.push_back({h2[i], "pair " + r + " (fast): "});
+    }
+    for (auto &m : members) {
+        if (m.first->eng->worker) m.first->eng->worker->wait_idle();
+        m.first->eng->err.clear();
+    }
+    dev.emplace(h[0]->eng);
+}
+
+int GroupCall::finish(int rc)
+{
+    if (rc == CMDG_OK) return rc;
+    std::string msg = cmdg_status_string(rc);
+    for (auto &m : members)
+        if (!m.first->eng->err.empty()) {
+            msg = m.second + m.first->eng->err;
+            break;
+        }
+    for (auto &m : members) m.first->err = msg;
+    return rc;
+}
+
 // ---------------------------------------------------------------------------------
 EngineBase::~EngineBase()
 {
@@ -888,17 +950,15 @@ int EngineBase::rhs_segment(int seg, const RhsCtx &c)
         if (tendency_filter) TRY(filter_apply(tendency_filter, c.tendency, ns));  // (:417-425)
         if (c.update_after) {
             const int64_t n = (int64_t)Np * ns * nreal;
-            hipLaunchKernelGGL(k_lsrk_update, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65535)),
-                               dim3(256), 0, s_comp, c.tendency, c.Qin, c.rka_next, c.rkb_dt, n);
+            hipLaunchKernelGGL(k_lsrk_update, dim3(nblocks(n)), dim3(256), 0, s_comp, c.tendency, c.Qin,
+                               c.rka_next, c.rkb_dt, n);
         }
         break;
     default: break;
     }
 #undef TRY
     if (dbg_sync() & 512) HIPCHK(hipDeviceSynchronize());
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(CMDG_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return CMDG_OK;
+    return launch_status("kernel launch");
 }
 
 int EngineBase::rhs_async(const RhsCtx &c)
@@ -955,8 +1015,10 @@ int group_rhs(std::vector<EngineBase *> &g, std::vector<RhsCtx> &c, bool keep_fr
             if (int r = g[i]->run_pre_hooks_a(c[i], cc[i])) return r;
             ch.push_back(g[i]->hooks.pre_rhs_handle->eng);
         }
+        for (auto *e : ch) e->err.clear();
         if (int r = group_rhs(ch, cc)) {
-            g[0]->err = "nested operator: " + ch[0]->err;
+            for (size_t i = 0; i < ch.size(); ++i)
+                if (!ch[i]->err.empty()) return g[i]->fail(r, "nested operator: " + ch[i]->err);
             return r;
         }
         for (size_t i = 0; i < g.size(); ++i) {
@@ -1263,9 +1325,7 @@ int EngineBase::stack_integral(bool reverse, const double *Q, int nstate, double
 #undef CMDG_STACK_CASE
         prof_end(s_comp);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(CMDG_ERR_HIP, std::string("stack integral launch: ") + hipGetErrorString(e));
-    return CMDG_OK;
+    return launch_status("stack integral launch");
 }
 
 // ---- law-specific update_auxiliary_state! / update_auxiliary_state_gradient! as hooks ----
@@ -1418,9 +1478,9 @@ int EngineBase::run_pre_hooks_b(const RhsCtx &c)
         HIPCHK(ev_record(ch->ev_comp, ch->s_comp));
         HIPCHK(hipStreamWaitEvent(s_comp, ch->ev_comp, 0));
         const int64_t n = nreal * Np;
-        hipLaunchKernelGGL(k_scaled_column_copy, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65535)),
-                           dim3(256), 0, s_comp, aux, naux, hooks.pre_rhs_dst_aux_col, (const double *)d_preT,
-                           ch->ns, hooks.pre_rhs_src_col, 1.0, Np, (int64_t)0, nreal);
+        hipLaunchKernelGGL(k_scaled_column_copy, dim3(nblocks(n)), dim3(256), 0, s_comp, aux, naux,
+                           hooks.pre_rhs_dst_aux_col, (const double *)d_preT, ch->ns, hooks.pre_rhs_src_col,
+                           1.0, Np, (int64_t)0, nreal);
     }
     if (hooks.ops_before_gradients)
         if (int r = run_column_ops(c, 0, nreal)) return r;
@@ -1469,10 +1529,9 @@ int EngineBase::flow_deviation(double *Q, int64_t h0, int64_t nh)
     }
     if (int r = integrate_velocity(Q, ns, hooks.flow_u_col, hooks.nvertelem, h0, nh)) return r;
     const int64_t n = nh * hooks.nvertelem * Np;
-    hipLaunchKernelGGL(k_column_minus_top_over_H, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65535)),
-                       dim3(256), 0, s_comp, aux, naux, hooks.flow_ud_col, (const double *)Q, ns,
-                       hooks.flow_u_col, (const double *)d_flowint, hooks.flow_H, NQ * NQ, NQ,
-                       hooks.nvertelem, h0, nh);
+    hipLaunchKernelGGL(k_column_minus_top_over_H, dim3(nblocks(n)), dim3(256), 0, s_comp, aux, naux,
+                       hooks.flow_ud_col, (const double *)Q, ns, hooks.flow_u_col, (const double *)d_flowint,
+                       hooks.flow_H, NQ * NQ, NQ, hooks.nvertelem, h0, nh);
     return CMDG_OK;
 }
 
@@ -1499,7 +1558,7 @@ int EngineBase::run_gradient_hooks(const RhsCtx &c, int64_t e0, int64_t e1)
     if (e1 <= e0) return CMDG_OK;
     if (!hooks.ops_before_gradients && column_chain(c, e0, e1, true)) return CMDG_OK;
     const int64_t n = (e1 - e0) * Np;
-    const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 65535);
+    const unsigned nb = nblocks(n);
     for (int i = 0; i < hooks.ncopy; ++i)
         hipLaunchKernelGGL(k_scaled_column_copy, dim3(nb), dim3(256), 0, s_comp, aux, naux,
                            hooks.copy_aux_col[i], gf, ngf, hooks.copy_gf_col[i], hooks.copy_scale[i],
@@ -1612,7 +1671,7 @@ int EngineBase::run_column_ops(const RhsCtx &c, int64_t e0, int64_t e1)
     if (e1 <= e0) return CMDG_OK;
     if (column_chain(c, e0, e1, false)) return CMDG_OK;
     const int64_t n = (e1 - e0) * Np;
-    const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 65535);
+    const unsigned nb = nblocks(n);
     const int nv = hooks.nvertelem;
     if (hooks.has_integral)
         if (int r = stack_integral(false, c.Qin, ns, aux, naux, nv, nullptr, &hooks.integral, e0 / nv,
@@ -1760,9 +1819,7 @@ int EngineBase::filter_apply(const FilterObj *f, double *Q, int nstate)
         }
         prof_end(s_comp);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(CMDG_ERR_HIP, std::string("filter launch: ") + hipGetErrorString(e));
-    return CMDG_OK;
+    return launch_status("filter launch");
 }
 
 int EngineBase::wsum2(const double *A, const double *B, int nvar, int weighted, double *out)
@@ -1855,11 +1912,6 @@ EngineBase *plugin_engine(const cmdg_desc *d, std::string &err)
 }
 }  // namespace
 
-static int set_err(cmdg_handle h, int code)
-{
-    if (h && h->eng && code != CMDG_OK) h->err = h->eng->err;
-    return code;
-}
 
 extern "C" {
 
@@ -2270,13 +2322,13 @@ int cmdg_comm_selftest(cmdg_handle h, int64_t count)
 
 int cmdg_comm_connect_local(cmdg_handle *handles, int32_t n)
 {
-    if (!handles || n < 1) return CMDG_ERR_INVALID;
+    GroupCall gc(handles, n);
+    if (!gc.ok()) return CMDG_ERR_INVALID;
     std::vector<EngineBase *> g;
     for (int i = 0; i < n; ++i) {
-        if (!handles[i]) return CMDG_ERR_INVALID;
         g.push_back(handles[i]->eng);
         if (g[i]->dev != g[0]->dev)
-            return set_err(handles[i], g[i]->fail(CMDG_ERR_INVALID, "local transport: the handles of a group live on one device"));
+            return gc.finish(g[i]->fail(CMDG_ERR_INVALID, "local transport: the handles of a group live on one device"));
     }
     for (int i = 0; i < n; ++i) {
         g[i]->group = g;
@@ -2284,7 +2336,7 @@ int cmdg_comm_connect_local(cmdg_handle *handles, int32_t n)
         g[i]->nranks = n;
         g[i]->transport = TRANSPORT_LOCAL;
         for (int r : g[i]->nabrtorank)
-            if (r < 0 || r >= n) return set_err(handles[i], g[i]->fail(CMDG_ERR_COMM, "neighbour rank outside the local group"));
+            if (r < 0 || r >= n) return gc.finish(g[i]->fail(CMDG_ERR_COMM, "neighbour rank outside the local group"));
     }
     return CMDG_OK;
 }
@@ -2292,10 +2344,11 @@ int cmdg_comm_connect_local(cmdg_handle *handles, int32_t n)
 int cmdg_group_rhs(cmdg_handle *handles, int32_t n, double **tendency, double **Q, double t,
                    double alpha, double beta)
 {
-    if (!handles || n < 1 || !tendency || !Q) return CMDG_ERR_INVALID;
+    if (!tendency || !Q) return CMDG_ERR_INVALID;
     for (int i = 0; i < n; ++i)
-        if (!handles[i] || !tendency[i] || !Q[i]) return CMDG_ERR_INVALID;
-    DevGuard guard_(handles[0]->eng);
+        if (!tendency[i] || !Q[i]) return CMDG_ERR_INVALID;
+    GroupCall gc(handles, n);
+    if (!gc.ok()) return CMDG_ERR_INVALID;
     std::vector<EngineBase *> g;
     std::vector<RhsCtx> c(n);
     for (int i = 0; i < n; ++i) {
@@ -2306,25 +2359,23 @@ int cmdg_group_rhs(cmdg_handle *handles, int32_t n, double **tendency, double **
         c[i].alpha = alpha;
         c[i].beta = beta;
     }
-    int r = group_rhs(g, c);
-    if (r)
-        for (int i = 0; i < n; ++i) set_err(handles[i], r);
-    return r;
+    return gc.finish(group_rhs(g, c));
 }
 
 int cmdg_group_halo(cmdg_handle *handles, int32_t n, double **arrays, int32_t nstate)
 {
-    if (!handles || n < 1 || !arrays) return CMDG_ERR_INVALID;
+    if (!arrays) return CMDG_ERR_INVALID;
     for (int i = 0; i < n; ++i)
-        if (!handles[i] || !arrays[i]) return CMDG_ERR_INVALID;
-    DevGuard guard_(handles[0]->eng);
+        if (!arrays[i]) return CMDG_ERR_INVALID;
+    GroupCall gc(handles, n);
+    if (!gc.ok()) return CMDG_ERR_INVALID;
     for (int i = 0; i < n; ++i) handles[i]->eng->invalidate_sends();
     for (int i = 0; i < n; ++i)
-        if (int r = handles[i]->eng->halo_begin(SLOT_Q, arrays[i], nstate)) return set_err(handles[i], r);
+        if (int r = handles[i]->eng->halo_begin(SLOT_Q, arrays[i], nstate)) return gc.finish(r);
     for (int i = 0; i < n; ++i)
-        if (int r = handles[i]->eng->halo_end(SLOT_Q, arrays[i], nstate)) return set_err(handles[i], r);
+        if (int r = handles[i]->eng->halo_end(SLOT_Q, arrays[i], nstate)) return gc.finish(r);
     for (int i = 0; i < n; ++i)
-        if (int r = handles[i]->eng->synchronize()) return set_err(handles[i], r);
+        if (int r = handles[i]->eng->synchronize()) return gc.finish(r);
     return CMDG_OK;
 }
 
@@ -2332,19 +2383,15 @@ int cmdg_group_lsrk_run(cmdg_handle *handles, int32_t n, double **Q, double **dQ
                         double dt, int64_t nsteps, int32_t nstages, const double *rka,
                         const double *rkb, const double *rkc)
 {
-    if (!handles || n < 1 || !Q || !dQ || !rka || !rkb || !rkc) return CMDG_ERR_INVALID;
+    if (!Q || !dQ || !rka || !rkb || !rkc) return CMDG_ERR_INVALID;
     for (int i = 0; i < n; ++i)
-        if (!handles[i] || !Q[i] || !dQ[i]) return CMDG_ERR_INVALID;
-    DevGuard guard_(handles[0]->eng);
+        if (!Q[i] || !dQ[i]) return CMDG_ERR_INVALID;
+    GroupCall gc(handles, n);
+    if (!gc.ok()) return CMDG_ERR_INVALID;
     std::vector<EngineBase *> g;
     for (int i = 0; i < n; ++i) g.push_back(handles[i]->eng);
-    for (int64_t s = 0; s < nsteps; ++s, t += dt) {
-        int r = group_lsrk_step(g, Q, dQ, t, dt, nstages, rka, rkb, rkc, s > 0);
-        if (r) {
-            for (int i = 0; i < n; ++i) set_err(handles[i], r);
-            return r;
-        }
-    }
+    for (int64_t s = 0; s < nsteps; ++s, t += dt)
+        if (int r = group_lsrk_step(g, Q, dQ, t, dt, nstages, rka, rkb, rkc, s > 0)) return gc.finish(r);
     return CMDG_OK;
 }
 
@@ -2431,26 +2478,24 @@ int cmdg_reduce(cmdg_handle h, const cmdg_reduce_desc *d, const double *A, const
 int cmdg_group_reduce(cmdg_handle *handles, int32_t n, const cmdg_reduce_desc *d, const double **A,
                       const double **B, double *out_host)
 {
-    if (!handles || n < 1 || !A || !out_host) return CMDG_ERR_INVALID;
-    for (int i = 0; i < n; ++i)
-        if (!handles[i]) return CMDG_ERR_INVALID;
+    if (!A || !out_host) return CMDG_ERR_INVALID;
+    GroupCall gc(handles, n);
+    if (!gc.ok()) return CMDG_ERR_INVALID;
     EngineBase *e0 = handles[0]->eng;
     for (int i = 0; i < n; ++i) {
         EngineBase *e = handles[i]->eng;
         if (n > 1 && (e->transport != TRANSPORT_LOCAL || e->nranks != n || e->rank != i))
-            return set_err(handles[i], e->fail(CMDG_ERR_INVALID, "cmdg_group_reduce: handle i must be rank i of "
-                                                                 "one group of n connected with cmdg_comm_connect_local"));
+            return gc.finish(e->fail(CMDG_ERR_INVALID, "cmdg_group_reduce: handle i must be rank i of "
+                                                       "one group of n connected with cmdg_comm_connect_local"));
     }
     std::string err;
-    if (reduce_check(d, err)) return set_err(handles[0], e0->fail(CMDG_ERR_INVALID, err));
+    if (reduce_check(d, err)) return gc.finish(e0->fail(CMDG_ERR_INVALID, err));
     const size_t per = 2 * (size_t)reduce_nout(d);
     std::vector<double> parts(per * n);
-    for (int i = 0; i < n; ++i) {
-        DevGuard guard_(handles[i]->eng);
+    for (int i = 0; i < n; ++i)
         if (int r = reduce_to_host(handles[i]->eng, d, A[i], B ? B[i] : nullptr, parts.data() + per * i))
-            return set_err(handles[i], r);
-    }
-    if (reduce_combine(d, parts.data(), n, out_host, err)) return set_err(handles[0], e0->fail(CMDG_ERR_INVALID, err));
+            return gc.finish(r);
+    if (reduce_combine(d, parts.data(), n, out_host, err)) return gc.finish(e0->fail(CMDG_ERR_INVALID, err));
     return CMDG_OK;
 }
 

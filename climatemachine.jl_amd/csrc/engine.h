@@ -7,10 +7,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <condition_variable>
 #include <deque>
 #include <functional>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -73,6 +75,8 @@ void roctx_pop();
 //   256 device synchronize before every group_rhs   512 device synchronize after every segment
 int dbg_sync();
 hipError_t ev_record(hipEvent_t &e, hipStream_t s);
+// work-groups of 256 for a grid-stride launch over n items
+inline unsigned nblocks(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 65535); }
 struct Range {
     explicit Range(const char *name) { roctx_push(name); }
     ~Range() { roctx_pop(); }
@@ -208,6 +212,10 @@ struct EngineBase {
         err = msg;
         return code;
     }
+    // hipGetLastError after the launches of a call (per thread: one check covers a whole group)
+    int launch_status(const char *what);
+    // make stream `later` wait for everything enqueued so far on `earlier` (through ev_comp)
+    int order(hipStream_t earlier, hipStream_t later);
     bool communicate() const { return !nabrtorank.empty(); }
 
     // physics / order specific launches; `exterior`: the launch of the exterior element list of a
@@ -414,6 +422,7 @@ struct EngineBase {
     bool filter_pair(double *Q);
     int run_gradient_hooks(const RhsCtx &c, int64_t e0, int64_t e1);
     double *d_Imat = nullptr;
+    int ensure_Imat(const double *host);  // the steppers' Imat (NQ x NQ): uploaded if absent
     double *d_Dv = nullptr;  // vertical derivative matrix when the vertical order differs
     int filter_create(const cmdg_filter_desc *d, FilterObj **out);
     int filter_apply(const FilterObj *f, double *Q, int nstate);
@@ -451,6 +460,27 @@ struct DevGuard {
     DevGuard(const DevGuard &) = delete;
     DevGuard &operator=(const DevGuard &) = delete;
 };
+
+// The prologue and the one error path of the entries that take several handles (include/cmdg.h,
+// at cmdg_comm_connect_local): ok() false means a NULL list, n < 1 or a NULL member, and nothing
+// was done.  Otherwise every engine's deferred run is idle, the first engine's device is current
+// until the call returns, and every engine's err was cleared, so that a set err marks a member
+// that failed in this call.  finish(rc) returns rc, on failure with that member's message on
+// every handle.
+struct GroupCall {
+    GroupCall(cmdg_handle *handles, int n) : GroupCall(handles, nullptr, n, false) {}
+    GroupCall(cmdg_handle *slow, cmdg_handle *fast, int n) : GroupCall(slow, fast, n, true) {}
+    bool ok() const { return !members.empty(); }
+    int finish(int rc);
+
+  private:
+    GroupCall(cmdg_handle *h, cmdg_handle *h2, int n, bool pairs);
+    std::vector<std::pair<cmdg_handle, std::string>> members;
+    std::optional<DevGuard> dev;
+};
+
+// the handle's cmdg_last_error takes the engine's message when code is a failure
+int set_err(cmdg_handle h, int code);
 }  // namespace cmdg
 
 namespace cmdg {

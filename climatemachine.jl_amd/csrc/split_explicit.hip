@@ -15,29 +15,10 @@ using namespace cmdg;
 
 namespace {
 
-int set_err2(cmdg_handle h, int code)
-{
-    if (h && h->eng && code != CMDG_OK) h->err = h->eng->err;
-    return code;
-}
+const char *const LAUNCH = "split explicit launch";
 
-unsigned nblocks(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 65535); }
-
-// make stream `later` wait for everything enqueued so far on `earlier`
-int order(EngineBase *e, hipStream_t earlier, hipStream_t later)
+int check(EngineBase *s, EngineBase *f, const cmdg_ocean_coupling_desc *d)
 {
-    if (earlier == later) return CMDG_OK;
-    if (dbg_sync() & 1) (void)hipStreamSynchronize(earlier);
-    if (ev_record(e->ev_comp, earlier) != hipSuccess ||
-        hipStreamWaitEvent(later, e->ev_comp, 0) != hipSuccess)
-        return e->fail(CMDG_ERR_HIP, "split explicit: stream ordering failed");
-    return CMDG_OK;
-}
-
-int check(cmdg_handle slow, cmdg_handle fast, const cmdg_ocean_coupling_desc *d)
-{
-    if (!slow || !fast || !d) return CMDG_ERR_INVALID;
-    EngineBase *s = slow->eng, *f = fast->eng;
     if (!s->stacked || d->nvertelem < 1 || s->nreal % d->nvertelem)
         return s->fail(CMDG_ERR_INVALID, "ocean coupling: slow grid is not stacked by nvertelem");
     if (f->nreal != s->nreal / d->nvertelem)
@@ -51,14 +32,7 @@ int check(cmdg_handle slow, cmdg_handle fast, const cmdg_ocean_coupling_desc *d)
         d->fast_U_col + 2 > f->ns || d->fast_GU_col < 0 || d->fast_GU_col + 2 > f->naux ||
         d->fast_du_col < 0 || d->fast_du_col + 2 > f->naux)
         return s->fail(CMDG_ERR_INVALID, "ocean coupling: column out of range");
-    if (!s->d_Imat) {
-        if (!d->Imat) return s->fail(CMDG_ERR_INVALID, "ocean coupling: Imat is NULL");
-        if (hipMalloc(&s->d_Imat, sizeof(double) * s->NQ * s->NQ) != hipSuccess ||
-            hipMemcpy(s->d_Imat, d->Imat, sizeof(double) * s->NQ * s->NQ, hipMemcpyHostToDevice) !=
-                hipSuccess)
-            return s->fail(CMDG_ERR_HIP, "ocean coupling: Imat upload failed");
-    }
-    return CMDG_OK;
+    return s->ensure_Imat(d->Imat);
 }
 
 int initialize_states(EngineBase *s, const cmdg_ocean_coupling_desc *d)
@@ -74,14 +48,14 @@ int slow_to_fast(EngineBase *s, EngineBase *f, const cmdg_ocean_coupling_desc *d
     const int Nij = s->NQ * s->NQ, nv = d->nvertelem, Nqk2 = f->Np / Nij;
     const int64_t nh = s->nreal / nv;
     if (int r = s->integrate_velocity(dQ, s->ns, d->slow_u_col, d->nvertelem)) return r;
-    if (int r = order(s, f->s_comp, s->s_comp)) return r;
+    if (int r = s->order(f->s_comp, s->s_comp)) return r;
     hipLaunchKernelGGL(k_top_to_layer, dim3(nblocks(nh * f->Np)), dim3(256), 0, s->s_comp, f->aux,
                        f->naux, d->fast_GU_col, (const double *)s->d_flowint, Nij, s->NQ, nv, Nqk2, nh);
     hipLaunchKernelGGL(k_column_minus_top_over_H, dim3(nblocks((int64_t)s->nreal * s->Np)), dim3(256),
                        0, s->s_comp, s->aux, s->naux, d->slow_dGu_col, (const double *)s->aux, s->naux,
                        d->slow_dGu_col, (const double *)s->d_flowint, d->H, Nij, s->NQ, nv,
                        (int64_t)0, nh);
-    return order(s, s->s_comp, f->s_comp);
+    return s->order(s->s_comp, f->s_comp);
 }
 
 int fast_to_slow(EngineBase *s, EngineBase *f, const cmdg_ocean_coupling_desc *d, double *Q3,
@@ -90,14 +64,14 @@ int fast_to_slow(EngineBase *s, EngineBase *f, const cmdg_ocean_coupling_desc *d
     if (int r = s->integrate_velocity(Q3, s->ns, d->slow_u_col, d->nvertelem)) return r;
     const int Nij = s->NQ * s->NQ, nv = d->nvertelem, Nqk2 = f->Np / Nij;
     const int64_t nh = s->nreal / nv;
-    if (int r = order(s, f->s_comp, s->s_comp)) return r;
+    if (int r = s->order(f->s_comp, s->s_comp)) return r;
     hipLaunchKernelGGL(k_reconcile_layer, dim3(nblocks(nh * f->Np)), dim3(256), 0, s->s_comp, f->aux,
                        f->naux, d->fast_du_col, Q2, f->ns, d->fast_U_col,
                        (const double *)s->d_flowint, d->H, Nij, s->NQ, nv, Nqk2, nh);
     hipLaunchKernelGGL(k_reconcile_column, dim3(nblocks((int64_t)s->nreal * s->Np)), dim3(256), 0,
                        s->s_comp, Q3, s->ns, d->slow_u_col, d->slow_eta_col, Q2, f->ns, d->fast_U_col,
                        d->fast_eta_col, (const double *)s->d_flowint, d->H, Nij, s->NQ, nv, Nqk2, nh);
-    return order(s, s->s_comp, f->s_comp);
+    return s->order(s->s_comp, f->s_comp);
 }
 
 int lsrk_update(EngineBase *e, double *dQ, double *Q, double rka_next, double rkb_dt)
@@ -137,44 +111,41 @@ __global__ void k_fill(double *__restrict__ a, double v, int64_t n)
         a[i] = v;
 }
 
-int launch_status(EngineBase *e)
-{
-    hipError_t r = hipGetLastError();
-    if (r != hipSuccess) return e->fail(CMDG_ERR_HIP, std::string("split explicit launch: ") + hipGetErrorString(r));
-    return CMDG_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 int cmdg_ocean_initialize_states(cmdg_handle slow, cmdg_handle fast, const cmdg_ocean_coupling_desc *d)
 {
-    if (int r = check(slow, fast, d)) return set_err2(slow, r);
-    DevGuard guard_(slow->eng);
+    if (!d) return CMDG_ERR_INVALID;
+    GroupCall gc(&slow, &fast, 1);
+    if (!gc.ok()) return CMDG_ERR_INVALID;
+    if (int r = check(slow->eng, fast->eng, d)) return gc.finish(r);
     initialize_states(slow->eng, d);
-    return set_err2(slow, launch_status(slow->eng));
+    return gc.finish(slow->eng->launch_status(LAUNCH));
 }
 
 int cmdg_ocean_tendency_from_slow_to_fast(cmdg_handle slow, cmdg_handle fast,
                                           const cmdg_ocean_coupling_desc *d, const double *dQ_slow)
 {
-    if (int r = check(slow, fast, d)) return set_err2(slow, r);
-    DevGuard guard_(slow->eng);
-    if (!dQ_slow) return CMDG_ERR_INVALID;
-    if (int r = slow_to_fast(slow->eng, fast->eng, d, dQ_slow)) return set_err2(slow, r);
-    return set_err2(slow, launch_status(slow->eng));
+    if (!d || !dQ_slow) return CMDG_ERR_INVALID;
+    GroupCall gc(&slow, &fast, 1);
+    if (!gc.ok()) return CMDG_ERR_INVALID;
+    if (int r = check(slow->eng, fast->eng, d)) return gc.finish(r);
+    if (int r = slow_to_fast(slow->eng, fast->eng, d, dQ_slow)) return gc.finish(r);
+    return gc.finish(slow->eng->launch_status(LAUNCH));
 }
 
 int cmdg_ocean_reconcile_from_fast_to_slow(cmdg_handle slow, cmdg_handle fast,
                                            const cmdg_ocean_coupling_desc *d, double *Q_slow,
                                            const double *Q_fast)
 {
-    if (int r = check(slow, fast, d)) return set_err2(slow, r);
-    DevGuard guard_(slow->eng);
-    if (!Q_slow || !Q_fast) return CMDG_ERR_INVALID;
-    if (int r = fast_to_slow(slow->eng, fast->eng, d, Q_slow, Q_fast)) return set_err2(slow, r);
-    return set_err2(slow, launch_status(slow->eng));
+    if (!d || !Q_slow || !Q_fast) return CMDG_ERR_INVALID;
+    GroupCall gc(&slow, &fast, 1);
+    if (!gc.ok()) return CMDG_ERR_INVALID;
+    if (int r = check(slow->eng, fast->eng, d)) return gc.finish(r);
+    if (int r = fast_to_slow(slow->eng, fast->eng, d, Q_slow, Q_fast)) return gc.finish(r);
+    return gc.finish(slow->eng->launch_status(LAUNCH));
 }
 
 int cmdg_lsrk_update(cmdg_handle h, double *dQ, double *Q, double rka_next, double rkb_dt)
@@ -182,7 +153,7 @@ int cmdg_lsrk_update(cmdg_handle h, double *dQ, double *Q, double rka_next, doub
     if (!h || !dQ || !Q) return CMDG_ERR_INVALID;
     DevGuard guard_(h->eng);
     lsrk_update(h->eng, dQ, Q, rka_next, rkb_dt);
-    return set_err2(h, launch_status(h->eng));
+    return set_err(h, h->eng->launch_status(LAUNCH));
 }
 
 int cmdg_ls3n_step(cmdg_handle h, double *Q, double *dQ, double *dR, double t, double dt,
@@ -200,12 +171,12 @@ int cmdg_ls3n_step(cmdg_handle h, double *Q, double *dQ, double *dR, double t, d
         c.t = t + rkc[s] * dt;
         c.alpha = 1.0;
         c.beta = 1.0;  // increment = true
-        if (int r = e->rhs_async(c)) return set_err2(h, r);
+        if (int r = e->rhs_async(c)) return set_err(h, r);
         const int sn = (s + 1) % nstages;
         hipLaunchKernelGGL(k_ls3n_update, dim3(nblocks(n)), dim3(256), 0, e->s_comp, dQ, dR, Q,
                            rka[2 * sn], rka[2 * sn + 1], rkb[2 * s], rkb[2 * s + 1], dt, n);
     }
-    return set_err2(h, launch_status(e));
+    return set_err(h, e->launch_status(LAUNCH));
 }
 
 int cmdg_ssprk_step(cmdg_handle h, double *Q, double *Rstage, double *Qstage, double t, double dt,
@@ -216,7 +187,7 @@ int cmdg_ssprk_step(cmdg_handle h, double *Q, double *Rstage, double *Qstage, do
     EngineBase *e = h->eng;
     const int64_t n = (int64_t)e->Np * e->ns * e->nreal;
     if (hipMemcpyAsync(Qstage, Q, sizeof(double) * n, hipMemcpyDeviceToDevice, e->s_comp) != hipSuccess)
-        return set_err2(h, e->fail(CMDG_ERR_HIP, "ssprk: copy failed"));
+        return set_err(h, e->fail(CMDG_ERR_HIP, "ssprk: copy failed"));
     for (int s = 0; s < nstages; ++s) {
         RhsCtx c;
         c.tendency = Rstage;
@@ -224,19 +195,19 @@ int cmdg_ssprk_step(cmdg_handle h, double *Q, double *Rstage, double *Qstage, do
         c.t = t + rkc[s] * dt;
         c.alpha = 1.0;
         c.beta = 0.0;
-        if (int r = e->rhs_async(c)) return set_err2(h, r);
+        if (int r = e->rhs_async(c)) return set_err(h, r);
         hipLaunchKernelGGL(k_ssprk_update, dim3(nblocks(n)), dim3(256), 0, e->s_comp,
                            (const double *)Rstage, (const double *)Q, Qstage, rka[2 * s],
                            rka[2 * s + 1], rkb[s], dt, n);
     }
     if (hipMemcpyAsync(Q, Qstage, sizeof(double) * n, hipMemcpyDeviceToDevice, e->s_comp) != hipSuccess)
-        return set_err2(h, e->fail(CMDG_ERR_HIP, "ssprk: copy failed"));
-    return set_err2(h, launch_status(e));
+        return set_err(h, e->fail(CMDG_ERR_HIP, "ssprk: copy failed"));
+    return set_err(h, e->launch_status(LAUNCH));
 }
 
 // dostep!(Qslow, split::SplitExplicitSolver, param, time) for n (slow, fast) pairs in lock step:
 // one pair per rank.  With the RCCL transport a process drives its own pair (n = 1); handles
-// connected by cmdg_comm_connect_local are driven together by one host thread.
+// connected by cmdg_comm_connect_local are driven together by one host thread (GroupCall: the caller).
 static int group_split_explicit_step(int n, cmdg_handle *slow, cmdg_handle *fast,
                                      const cmdg_ocean_coupling_desc *d, int coupled, double **Q3,
                                      double **dQ3, double **dQ2fast, double **Q2, double **dQ2,
@@ -244,22 +215,11 @@ static int group_split_explicit_step(int n, cmdg_handle *slow, cmdg_handle *fast
                                      const double *rka, const double *rkb, const double *rkc)
 {
     std::vector<EngineBase *> S(n), F(n);
-    if (!slow[0]) return CMDG_ERR_INVALID;
-    DevGuard guard_(slow[0]->eng);
     for (int i = 0; i < n; ++i) {
-        if (int r = check(slow[i], fast[i], d)) return set_err2(slow[i], r);
-        if (!Q3[i] || !dQ3[i] || !dQ2fast[i] || !Q2[i] || !dQ2[i]) return CMDG_ERR_INVALID;
         S[i] = slow[i]->eng;
         F[i] = fast[i]->eng;
+        if (int r = check(S[i], F[i], d)) return r;
     }
-    auto bail = [&](std::vector<EngineBase *> &E, int r) {
-        for (int i = 0; i < n; ++i)
-            if (!E[i]->err.empty()) {
-                S[0]->err = E[i]->err;
-                break;
-            }
-        return set_err2(slow[0], r);
-    };
     std::vector<RhsCtx> c(n);
     for (int st = 0; st < nstages; ++st) {
         const double ts = t + rkc[st] * dt;
@@ -272,28 +232,28 @@ static int group_split_explicit_step(int n, cmdg_handle *slow, cmdg_handle *fast
             c[i].tendency = dQ2fast[i];  // slow.rhs!(dQ2fast, Qslow, ...; increment = false)
             c[i].beta = 0.0;
         }
-        if (int r = group_rhs(S, c)) return bail(S, r);
+        if (int r = group_rhs(S, c)) return r;
         for (int i = 0; i < n; ++i) {
             if (coupled)
-                if (int r = slow_to_fast(S[i], F[i], d, dQ2fast[i])) return bail(S, r);
+                if (int r = slow_to_fast(S[i], F[i], d, dQ2fast[i])) return r;
             c[i].tendency = dQ3[i];  // slow.rhs!(dQslow, Qslow, ...; increment = true)
             c[i].beta = 1.0;
         }
-        if (int r = group_rhs(S, c)) return bail(S, r);
+        if (int r = group_rhs(S, c)) return r;
         // fractional time for the fast sub-steps of this stage
         const double gamma = st == nstages - 1 ? 1 - rkc[st] : rkc[st + 1] - rkc[st];
         const int nsub = dt_fast > 0 ? (int)std::ceil(gamma * dt / dt_fast) : 1;
         const double fdt = gamma * dt / nsub;
         for (int sub = 0; sub < nsub; ++sub)
             if (int r = group_lsrk_step(F, Q2, dQ2, ts + sub * fdt, fdt, nstages, rka, rkb, rkc))
-                return bail(F, r);
+                return r;
         for (int i = 0; i < n; ++i) {
             lsrk_update(S[i], dQ3[i], Q3[i], rka[(st + 1) % nstages], rkb[st] * dt);
             if (coupled)
-                if (int r = fast_to_slow(S[i], F[i], d, Q3[i], Q2[i])) return bail(S, r);
+                if (int r = fast_to_slow(S[i], F[i], d, Q3[i], Q2[i])) return r;
         }
     }
-    return set_err2(slow[0], launch_status(S[0]));
+    return S[0]->launch_status(LAUNCH);
 }
 
 int cmdg_split_explicit_step(cmdg_handle slow, cmdg_handle fast, const cmdg_ocean_coupling_desc *d,
@@ -301,13 +261,16 @@ int cmdg_split_explicit_step(cmdg_handle slow, cmdg_handle fast, const cmdg_ocea
                              double *dQ2, double t, double dt, double dt_fast, int32_t nstages,
                              const double *rka, const double *rkb, const double *rkc)
 {
-    if (!slow || !fast || !d || !rka || !rkb || !rkc || nstages < 1) return CMDG_ERR_INVALID;
+    if (!slow || !fast || !d || !Q3 || !dQ3 || !dQ2fast || !Q2 || !dQ2 || !rka || !rkb || !rkc ||
+        nstages < 1)
+        return CMDG_ERR_INVALID;
     if (slow->eng->transport == TRANSPORT_LOCAL && slow->eng->communicate())
-        return set_err2(slow, slow->eng->fail(CMDG_ERR_INVALID,
-                                              "handles connected locally must be driven by "
-                                              "cmdg_group_split_explicit_step"));
-    return group_split_explicit_step(1, &slow, &fast, d, coupled, &Q3, &dQ3, &dQ2fast, &Q2, &dQ2, t,
-                                     dt, dt_fast, nstages, rka, rkb, rkc);
+        return set_err(slow, slow->eng->fail(CMDG_ERR_INVALID,
+                                             "handles connected locally must be driven by "
+                                             "cmdg_group_split_explicit_step"));
+    GroupCall gc(&slow, &fast, 1);
+    return gc.finish(group_split_explicit_step(1, &slow, &fast, d, coupled, &Q3, &dQ3, &dQ2fast, &Q2, &dQ2,
+                                               t, dt, dt_fast, nstages, rka, rkb, rkc));
 }
 
 int cmdg_group_split_explicit_step(cmdg_handle *slow, cmdg_handle *fast, int32_t n,
@@ -316,13 +279,14 @@ int cmdg_group_split_explicit_step(cmdg_handle *slow, cmdg_handle *fast, int32_t
                                    double t, double dt, double dt_fast, int32_t nstages,
                                    const double *rka, const double *rkb, const double *rkc)
 {
-    if (!slow || !fast || n < 1 || !d || !Q3 || !dQ3 || !dQ2fast || !Q2 || !dQ2 || !rka || !rkb ||
-        !rkc || nstages < 1)
+    if (!d || !Q3 || !dQ3 || !dQ2fast || !Q2 || !dQ2 || !rka || !rkb || !rkc || nstages < 1)
         return CMDG_ERR_INVALID;
     for (int i = 0; i < n; ++i)
-        if (!slow[i] || !fast[i]) return CMDG_ERR_INVALID;
-    return group_split_explicit_step(n, slow, fast, d, coupled, Q3, dQ3, dQ2fast, Q2, dQ2, t, dt,
-                                     dt_fast, nstages, rka, rkb, rkc);
+        if (!Q3[i] || !dQ3[i] || !dQ2fast[i] || !Q2[i] || !dQ2[i]) return CMDG_ERR_INVALID;
+    GroupCall gc(slow, fast, n);
+    if (!gc.ok()) return CMDG_ERR_INVALID;
+    return gc.finish(group_split_explicit_step(n, slow, fast, d, coupled, Q3, dQ3, dQ2fast, Q2, dQ2, t, dt,
+                                               dt_fast, nstages, rka, rkb, rkc));
 }
 
 }  // extern "C"

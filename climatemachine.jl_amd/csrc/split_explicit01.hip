@@ -18,17 +18,6 @@ using namespace cmdg;
 
 namespace {
 
-unsigned nblocks01(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 65535); }
-
-int order01(EngineBase *e, hipStream_t earlier, hipStream_t later)
-{
-    if (earlier == later) return CMDG_OK;
-    if (ev_record(e->ev_comp, earlier) != hipSuccess ||
-        hipStreamWaitEvent(later, e->ev_comp, 0) != hipSuccess)
-        return e->fail(CMDG_ERR_HIP, "split explicit 01: stream ordering failed");
-    return CMDG_OK;
-}
-
 // dst[:, dcol .. dcol + ncol - 1, e] (op)= src[:, scol .., e]   op: 0 copy, 1 add
 __global__ void k01_cols(double *__restrict__ dst, int ndst, int dcol, const double *__restrict__ src,
                          int nsrc, int scol, int ncol, int op, int Np, int64_t nelems)
@@ -107,13 +96,6 @@ __global__ void k01_reconcile_column(double *__restrict__ Q3, const double *__re
     }
 }
 
-int launch_status01(EngineBase *e)
-{
-    hipError_t r = hipGetLastError();
-    if (r != hipSuccess) return e->fail(CMDG_ERR_HIP, std::string("split explicit 01 launch: ") + hipGetErrorString(r));
-    return CMDG_OK;
-}
-
 }  // namespace
 
 // dostep!(Qslow, ::SplitExplicitLSRK2nSolver, param, time) for n (slow, fast) pairs in lock step: one
@@ -121,7 +103,8 @@ int launch_status01(EngineBase *e)
 // by cmdg_comm_connect_local (slow models, fast models and the nested continuity operators, each
 // among themselves) are driven together by one host thread.  Every exchange function acts on a
 // rank's real columns; the ghost stacks' flow deviation and kinematic pressure come from the
-// operator itself (EngineBase::rhs_segment, segment 1).
+// operator itself (EngineBase::rhs_segment, segment 1).  Checks of a pair fail on its slow engine;
+// the caller's GroupCall reports what fails.
 static int group_split_explicit01_step(int n, cmdg_handle *slow, cmdg_handle *fast, const cmdg_ocean01_desc *d,
                                        double **Q3, double **dQ3, double **dQ2fast, double **Q2,
                                        double **dQ2, double t, double dt, double dt_fast,
@@ -131,37 +114,23 @@ static int group_split_explicit01_step(int n, cmdg_handle *slow, cmdg_handle *fa
     using B = BarotropicSE01;
     using O = OceanSE01;
     std::vector<EngineBase *> S(n), F(n);
-    if (!slow[0]) return CMDG_ERR_INVALID;
-    DevGuard guard_(slow[0]->eng);
-    auto bad = [&](const char *msg) {
-        slow[0]->eng->fail(CMDG_ERR_INVALID, msg);
-        slow[0]->err = slow[0]->eng->err;
-        return CMDG_ERR_INVALID;
-    };
     for (int i = 0; i < n; ++i) {
-        if (!slow[i] || !fast[i] || !Q3[i] || !dQ3[i] || !dQ2fast[i] || !Q2[i] || !dQ2[i]) return CMDG_ERR_INVALID;
         S[i] = slow[i]->eng;
         F[i] = fast[i]->eng;
         if (S[i]->ns != O::NS || S[i]->naux != O::NAUX || S[i]->ngf != O::NGF || F[i]->ns != B::NS ||
             F[i]->naux != B::NAUX)
-            return bad("split explicit 01: handles are not the OceanModel / BarotropicModel pair");
+            return S[i]->fail(CMDG_ERR_INVALID, "split explicit 01: handles are not the OceanModel / BarotropicModel pair");
         if (!S[i]->stacked || d->nvertelem < 1 || S[i]->nreal % d->nvertelem ||
             F[i]->nreal != S[i]->nreal / d->nvertelem)
-            return bad("split explicit 01: the fast grid holds one element per stack of the slow grid");
+            return S[i]->fail(CMDG_ERR_INVALID, "split explicit 01: the fast grid holds one element per stack of the slow grid");
         if (F[i]->Np % (S[i]->NQ * S[i]->NQ) || S[i]->Np != S[i]->NQ * S[i]->NQ * S[i]->NQ || !(d->H > 0) ||
             d->add_fast_substeps < 0)
-            return bad("split explicit 01: grids / parameters");
+            return S[i]->fail(CMDG_ERR_INVALID, "split explicit 01: grids / parameters");
         if (F[i]->dev != S[i]->dev)  // the fast launches and the events between the two engines assume one device
-            return bad("split explicit 01: the slow and the fast handle live on one device");
+            return S[i]->fail(CMDG_ERR_INVALID, "split explicit 01: the slow and the fast handle live on one device");
         if (n > 1 && (S[i]->transport != TRANSPORT_LOCAL || F[i]->transport != TRANSPORT_LOCAL))
-            return bad("split explicit 01: several pairs in one call need the local transport");
-        if (!S[i]->d_Imat) {
-            if (!d->Imat) return bad("split explicit 01: Imat is NULL");
-            if (hipMalloc(&S[i]->d_Imat, sizeof(double) * S[i]->NQ * S[i]->NQ) != hipSuccess ||
-                hipMemcpy(S[i]->d_Imat, d->Imat, sizeof(double) * S[i]->NQ * S[i]->NQ, hipMemcpyHostToDevice) !=
-                    hipSuccess)
-                return bad("split explicit 01: Imat upload failed");
-        }
+            return S[i]->fail(CMDG_ERR_INVALID, "split explicit 01: several pairs in one call need the local transport");
+        if (int r = S[i]->ensure_Imat(d->Imat)) return r;
     }
     // dostep!(Qfast, fast, ...) runs the FAST solver's scheme (SplitExplicitLSRK2nMethod.jl:150-165):
     // its own tableau when the caller gives one, the slow solver's otherwise
@@ -170,22 +139,14 @@ static int group_split_explicit01_step(int n, cmdg_handle *slow, cmdg_handle *fa
     const double *rkb_f = d->nstages_fast > 0 ? d->rkb_fast : rkb;
     const double *rkc_f = d->nstages_fast > 0 ? d->rkc_fast : rkc;
     if (d->nstages_fast < 0 || (d->nstages_fast > 0 && (!rka_f || !rkb_f || !rkc_f)))
-        return bad("split explicit 01: the fast solver's tableau");
+        return S[0]->fail(CMDG_ERR_INVALID, "split explicit 01: the fast solver's tableau");
     const int Nij = S[0]->NQ * S[0]->NQ, nv = d->nvertelem, Nqk2 = F[0]->Np / Nij, Np2 = F[0]->Np, Np3 = S[0]->Np;
     auto fcols = [&](int i, double *dst, int ndst, int dcol, const double *src, int nsrc, int scol, int ncol,
                      int op, hipStream_t st) {
         const int64_t nh = F[i]->nreal;
         if (nh == 0) return;
-        hipLaunchKernelGGL(k01_cols, dim3(nblocks01(nh * ncol * Np2)), dim3(256), 0, st, dst, ndst, dcol,
+        hipLaunchKernelGGL(k01_cols, dim3(nblocks(nh * ncol * Np2)), dim3(256), 0, st, dst, ndst, dcol,
                            src, nsrc, scol, ncol, op, Np2, nh);
-    };
-    auto fail_from = [&](std::vector<EngineBase *> &E, int r) {
-        for (int i = 0; i < n; ++i)
-            if (!E[i]->err.empty()) {
-                slow[0]->err = E[i]->err;
-                break;
-            }
-        return r;
     };
     std::vector<RhsCtx> c(n);
     for (int s = 0; s < nstages; ++s) {
@@ -209,7 +170,7 @@ static int group_split_explicit01_step(int n, cmdg_handle *slow, cmdg_handle *fa
         for (int i = 0; i < n; ++i) {
             const int64_t nh = F[i]->nreal, n3 = S[i]->nreal;
             if (nh > 0)
-                hipLaunchKernelGGL(k_fill_columns, dim3(nblocks01(nh * 3 * Np2)), dim3(256), 0, F[i]->s_comp,
+                hipLaunchKernelGGL(k_fill_columns, dim3(nblocks(nh * 3 * Np2)), dim3(256), 0, F[i]->s_comp,
                                    F[i]->aux, B::NAUX, (int)B::AUC, 3, -0.0, Np2, nh);  // U_c, eta_c (adjacent columns)
             if (!first) {  // set fast-state to previously stored value
                 fcols(i, Q2[i], B::NS, B::ETA, F[i]->aux, B::NAUX, B::AETAS, 1, 0, F[i]->s_comp);
@@ -217,7 +178,7 @@ static int group_split_explicit01_step(int n, cmdg_handle *slow, cmdg_handle *fa
             }
             // ---- initialize_adjustment!: dG_u = 0
             if (n3 > 0)
-                hipLaunchKernelGGL(k_fill_columns, dim3(nblocks01(n3 * 2 * Np3)), dim3(256), 0, S[i]->s_comp,
+                hipLaunchKernelGGL(k_fill_columns, dim3(nblocks(n3 * 2 * Np3)), dim3(256), 0, S[i]->s_comp,
                                    S[i]->aux, O::NAUX, (int)O::ADGU, 2, 0.0, Np3, n3);
             // ---- slow.rhs!(dQ2fast, Qslow, ...; increment = false)
             c[i] = RhsCtx();
@@ -227,38 +188,38 @@ static int group_split_explicit01_step(int n, cmdg_handle *slow, cmdg_handle *fa
             c[i].tendency = dQ2fast[i];
             c[i].beta = 0.0;
         }
-        if (int r = group_rhs(S, c)) return fail_from(S, r);
+        if (int r = group_rhs(S, c)) return r;
         for (int i = 0; i < n; ++i) {
             const int64_t nh = F[i]->nreal, n3 = S[i]->nreal;
             // ---- tendency_from_slow_to_fast! (Communication.jl:166-224)
-            if (int r = S[i]->integrate_velocity(dQ2fast[i], O::NS, O::U, nv)) return fail_from(S, r);
-            if (int r = order01(S[i], F[i]->s_comp, S[i]->s_comp)) return fail_from(S, r);
+            if (int r = S[i]->integrate_velocity(dQ2fast[i], O::NS, O::U, nv)) return r;
+            if (int r = S[i]->order(F[i]->s_comp, S[i]->s_comp)) return r;
             if (nh > 0) {
-                hipLaunchKernelGGL(k_top_to_layer, dim3(nblocks01(nh * Np2)), dim3(256), 0, S[i]->s_comp,
+                hipLaunchKernelGGL(k_top_to_layer, dim3(nblocks(nh * Np2)), dim3(256), 0, S[i]->s_comp,
                                    F[i]->aux, B::NAUX, (int)B::AGU, (const double *)S[i]->d_flowint, Nij,
                                    S[i]->NQ, nv, Nqk2, nh);
-                hipLaunchKernelGGL(k_column_minus_top_over_H, dim3(nblocks01(n3 * Np3)), dim3(256), 0,
+                hipLaunchKernelGGL(k_column_minus_top_over_H, dim3(nblocks(n3 * Np3)), dim3(256), 0,
                                    S[i]->s_comp, S[i]->aux, O::NAUX, (int)O::ADGU, (const double *)S[i]->aux,
                                    O::NAUX, (int)O::ADGU, (const double *)S[i]->d_flowint, d->H, Nij, S[i]->NQ,
                                    nv, (int64_t)0, n3 / nv);
             }
-            if (int r = order01(S[i], S[i]->s_comp, F[i]->s_comp)) return fail_from(S, r);
+            if (int r = S[i]->order(S[i]->s_comp, F[i]->s_comp)) return r;
             // ---- slow.rhs!(dQslow, Qslow, ...; increment = true)
             c[i].tendency = dQ3[i];
             c[i].beta = 1.0;
         }
-        if (int r = group_rhs(S, c)) return fail_from(S, r);
+        if (int r = group_rhs(S, c)) return r;
         for (int i = 0; i < n; ++i) {  // ... and update!
             const int64_t nn = (int64_t)Np3 * O::NS * S[i]->nreal;
             if (nn > 0)
-                hipLaunchKernelGGL(k_lsrk_update, dim3(nblocks01(nn)), dim3(256), 0, S[i]->s_comp, dQ3[i], Q3[i],
+                hipLaunchKernelGGL(k_lsrk_update, dim3(nblocks(nn)), dim3(256), 0, S[i]->s_comp, dQ3[i], Q3[i],
                                    rka[(s + 1) % nstages], rkb[s] * dt, nn);
         }
         // ---- barotropic sub-steps with cummulate_fast_solution! (Communication.jl:226-252)
         for (int sub = 1; sub <= fs3; ++sub) {
             const double fast_time = stage_time + (sub - 1) * fdt;
             if (int r = group_lsrk_step(F, Q2, dQ2, fast_time, fdt, nst_f, rka_f, rkb_f, rkc_f))
-                return fail_from(F, r);
+                return r;
             for (int i = 0; i < n; ++i) {
                 if (sub >= fs1) {
                     fcols(i, F[i]->aux, B::NAUX, B::AUC, Q2[i], B::NS, B::U1, 2, 1, F[i]->s_comp);
@@ -275,27 +236,25 @@ static int group_split_explicit01_step(int n, cmdg_handle *slow, cmdg_handle *fa
         for (int i = 0; i < n; ++i) {
             const int64_t nh = F[i]->nreal, n3 = S[i]->nreal;
             if (nh > 0)
-                hipLaunchKernelGGL(k01_scale, dim3(nblocks01(nh * 3 * Np2)), dim3(256), 0, F[i]->s_comp, F[i]->aux,
+                hipLaunchKernelGGL(k01_scale, dim3(nblocks(nh * 3 * Np2)), dim3(256), 0, F[i]->s_comp, F[i]->aux,
                                    B::NAUX, (int)B::AUC, 3, 1 / count, Np2, nh);
-            if (int r = S[i]->integrate_velocity(Q3[i], O::NS, O::U, nv)) return fail_from(S, r);
-            if (int r = order01(S[i], F[i]->s_comp, S[i]->s_comp)) return fail_from(S, r);
+            if (int r = S[i]->integrate_velocity(Q3[i], O::NS, O::U, nv)) return r;
+            if (int r = S[i]->order(F[i]->s_comp, S[i]->s_comp)) return r;
             if (nh > 0) {
-                hipLaunchKernelGGL(k01_reconcile_layer, dim3(nblocks01(nh * Np2)), dim3(256), 0, S[i]->s_comp,
+                hipLaunchKernelGGL(k01_reconcile_layer, dim3(nblocks(nh * Np2)), dim3(256), 0, S[i]->s_comp,
                                    F[i]->aux, (const double *)Q3[i], (const double *)S[i]->d_flowint, d->H,
                                    (int)last, Nij, S[i]->NQ, nv, Nqk2, nh);
-                hipLaunchKernelGGL(k01_reconcile_column, dim3(nblocks01(n3 * Np3)), dim3(256), 0, S[i]->s_comp,
+                hipLaunchKernelGGL(k01_reconcile_column, dim3(nblocks(n3 * Np3)), dim3(256), 0, S[i]->s_comp,
                                    Q3[i], (const double *)F[i]->aux, (int)last, Nij, S[i]->NQ, nv, Nqk2, nh);
             }
             if (last) {  // reset fast-state to end of time-step value
                 fcols(i, Q2[i], B::NS, B::ETA, F[i]->aux, B::NAUX, B::AETAS, 1, 0, S[i]->s_comp);
                 fcols(i, Q2[i], B::NS, B::U1, F[i]->aux, B::NAUX, B::AUS, 2, 0, S[i]->s_comp);
             }
-            if (int r = order01(S[i], S[i]->s_comp, F[i]->s_comp)) return fail_from(S, r);
+            if (int r = S[i]->order(S[i]->s_comp, F[i]->s_comp)) return r;
         }
     }
-    int r = launch_status01(S[0]);
-    if (r) slow[0]->err = S[0]->err;
-    return r;
+    return S[0]->launch_status("split explicit 01 launch");
 }
 
 extern "C" int cmdg_split_explicit01_step(cmdg_handle slow, cmdg_handle fast, const cmdg_ocean01_desc *d,
@@ -307,13 +266,12 @@ extern "C" int cmdg_split_explicit01_step(cmdg_handle slow, cmdg_handle fast, co
     if (!slow || !fast || !d || !Q3 || !dQ3 || !dQ2fast || !Q2 || !dQ2 || !rka || !rkb || !rkc ||
         nstages < 1)
         return CMDG_ERR_INVALID;
-    if (slow->eng->transport == TRANSPORT_LOCAL && slow->eng->communicate()) {
-        slow->eng->fail(CMDG_ERR_INVALID, "handles connected locally must be driven by cmdg_group_split_explicit01_step");
-        slow->err = slow->eng->err;
-        return CMDG_ERR_INVALID;
-    }
-    return group_split_explicit01_step(1, &slow, &fast, d, &Q3, &dQ3, &dQ2fast, &Q2, &dQ2, t, dt, dt_fast,
-                                       nstages, rka, rkb, rkc);
+    if (slow->eng->transport == TRANSPORT_LOCAL && slow->eng->communicate())
+        return set_err(slow, slow->eng->fail(CMDG_ERR_INVALID, "handles connected locally must be driven by "
+                                                               "cmdg_group_split_explicit01_step"));
+    GroupCall gc(&slow, &fast, 1);
+    return gc.finish(group_split_explicit01_step(1, &slow, &fast, d, &Q3, &dQ3, &dQ2fast, &Q2, &dQ2, t, dt,
+                                                 dt_fast, nstages, rka, rkb, rkc));
 }
 
 extern "C" int cmdg_group_split_explicit01_step(cmdg_handle *slow, cmdg_handle *fast, int32_t n,
@@ -322,11 +280,12 @@ extern "C" int cmdg_group_split_explicit01_step(cmdg_handle *slow, cmdg_handle *
                                                 double dt, double dt_fast, int32_t nstages,
                                                 const double *rka, const double *rkb, const double *rkc)
 {
-    if (!slow || !fast || n < 1 || !d || !Q3 || !dQ3 || !dQ2fast || !Q2 || !dQ2 || !rka || !rkb || !rkc ||
-        nstages < 1)
+    if (!d || !Q3 || !dQ3 || !dQ2fast || !Q2 || !dQ2 || !rka || !rkb || !rkc || nstages < 1)
         return CMDG_ERR_INVALID;
     for (int i = 0; i < n; ++i)
-        if (!slow[i] || !fast[i]) return CMDG_ERR_INVALID;
-    return group_split_explicit01_step(n, slow, fast, d, Q3, dQ3, dQ2fast, Q2, dQ2, t, dt, dt_fast, nstages,
-                                       rka, rkb, rkc);
+        if (!Q3[i] || !dQ3[i] || !dQ2fast[i] || !Q2[i] || !dQ2[i]) return CMDG_ERR_INVALID;
+    GroupCall gc(slow, fast, n);
+    if (!gc.ok()) return CMDG_ERR_INVALID;
+    return gc.finish(group_split_explicit01_step(n, slow, fast, d, Q3, dQ3, dQ2fast, Q2, dQ2, t, dt, dt_fast,
+                                                 nstages, rka, rkb, rkc));
 }

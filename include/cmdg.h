@@ -324,7 +324,15 @@ int cmdg_comm_selftest(cmdg_handle h, int64_t count);
 /* Single-process: connect n handles (handle r plays rank r) through device copies. */
 int cmdg_comm_connect_local(cmdg_handle *handles, int32_t n);
 
-/* Lock-step drivers for handles connected with cmdg_comm_connect_local (one host thread
+/* Entries that take several handles -- cmdg_comm_connect_local, the cmdg_group_* calls,
+ * cmdg_group_reduce, the split-explicit steppers (one or n (slow, fast) pairs) and the three
+ * cmdg_ocean_* calls (slow, fast) -- refuse a NULL handle list, n < 1 or a NULL handle with
+ * CMDG_ERR_INVALID and no message.  Otherwise they first wait for the deferred CMDG_OPT_ASYNC_RUN
+ * run of EVERY handle passed.  On failure every handle passed carries the message: the reason,
+ * prefixed with the member that failed -- "rank i: " for a list of handles, "pair i (slow): " or
+ * "pair i (fast): " for (slow, fast) pairs -- or the bare status string when no member gave one.
+ *
+ * Lock-step drivers for handles connected with cmdg_comm_connect_local (one host thread
  * plays every rank): arrays of n per-rank pointers. */
 int cmdg_group_rhs(cmdg_handle *handles, int32_t n, double **tendency, double **Q, double t,
                    double alpha, double beta);

@@ -249,6 +249,40 @@ def test_partitioned_split_explicit_matches_single_rank(cm, torch, size, priorit
         d2.close()
 
 
+def test_group_step_failure_names_the_pair(cm, torch):
+    """A fast handle of the wrong grid as pair 1 (the one-rank barotropic operator next to a rank-1
+    slow model): the coupling check of pair 1 fails before anything is launched, and every handle
+    of the call -- the wrapper reads slows[0] -- carries the reason and the pair that failed."""
+    O = cm.ocean
+    central = cm.balancelaws.CentralNumericalFluxFirstOrder
+    law2, g2 = split_explicit_setup(True, Nx=4, Ny=3, Nz=3)[2:]
+    dg2 = cm.dgmodel.DGModel(law2, g2, numerical_flux_first_order=central)
+    slows, fasts, keeps = [], [], []
+    for r in range(2):
+        l3, gr3, l2, gr2 = split_explicit_setup(True, Nx=4, Ny=3, Nz=3, rank=r, size=2)
+        slows.append(cm.dgmodel.DGModel(l3, gr3))
+        keeps.append(O.install_hydrostatic_boussinesq_hooks(slows[-1]))
+        fasts.append(cm.dgmodel.DGModel(l2, gr2, numerical_flux_first_order=central))
+    cm.dgmodel.connect_local(slows)
+    cm.dgmodel.connect_local(fasts)
+    pair_fast = [fasts[0], dg2]
+    Q3s = [d.create_state() for d in slows]
+    Q2s = [d.create_state() for d in pair_fast]
+    solvers = [O.SplitExplicitSolver(d3, d2, q3, q2, 1800.0, 300.0)
+               for d3, d2, q3, q2 in zip(slows, pair_fast, Q3s, Q2s)]
+    with pytest.raises(cm._lib.CmdgError) as err:
+        O.SplitExplicitSolver.group_dostep(solvers, Q3s, Q2s, 1)
+    msg = str(err.value)
+    assert "one element per stack" in msg and "pair 1" in msg, msg
+    for d3, k in zip(slows, keeps):
+        d3.set_rhs_hooks()
+        for f in k:
+            f.close()
+        d3.close()
+    for d2 in fasts + [dg2]:
+        d2.close()
+
+
 def test_priority_halo_streams_first_use_in_a_process():
     """Round 3's ordering failure showed only on the FIRST partitioned step of a process (later
     handles found the freed work states' pages still holding valid numbers): a fresh process with

@@ -4,6 +4,8 @@ SplitExplicit/simple_box_2dt.jl: 20 x 20 x 20 elements, N = 4, eighty slow steps
 days) with 240 s barotropic sub-steps and the fast-step averaging window -- against the StateCheck
 table test/Ocean/refvals/simple_box_2dt_refvals.jl (28 fields x min / max / mean / std, 12 digits
 except where the reference itself asks for 8 - 10)."""
+import collections
+
 import numpy as np
 import pytest
 
@@ -154,6 +156,53 @@ def test_partitioned_split_explicit01_matches_single_rank(cm, torch, size):
         o.close()
     for d in dg2s + [dg2]:
         d.close()
+
+
+def _zero_pairs(cm, torch):
+    """two ranks of the 3 x 3 x 3 box with zero states: for calls that fail before they compute"""
+    zero = collections.defaultdict(float)
+    odgs, dg2s, Q3s, Q2s, _ = _partitioned_pairs(cm, torch, 2, 3, 3, 3, zero, zero)
+    return odgs, dg2s, Q3s, Q2s
+
+
+def _close_pairs(odgs, dg2s):
+    for o in odgs:
+        o.close()
+    for d in dg2s:
+        d.close()
+
+
+def test_group_step_failure_names_the_pair(cm, torch):
+    """A handle of the wrong law as fast[1] (rank 1's continuity operator): the check of pair 1
+    fails before anything is launched, and the message every handle carries -- the wrapper reads
+    slows[0] -- names pair 1."""
+    O1 = cm.ocean01
+    odgs, dg2s, Q3s, Q2s = _zero_pairs(cm, torch)
+    pair_fast = [dg2s[0], odgs[1].conti3d_dg]
+    solvers = [O1.SplitExplicitLSRK2nSolver01(o, d2, q3, q2, 5400.0, 240.0)
+               for o, d2, q3, q2 in zip(odgs, pair_fast, Q3s, Q2s)]
+    with pytest.raises(cm._lib.CmdgError) as err:
+        O1.SplitExplicitLSRK2nSolver01.group_dostep(solvers, Q3s, Q2s, 1)
+    msg = str(err.value)
+    assert "not the OceanModel / BarotropicModel pair" in msg and "pair 1" in msg, msg
+    _close_pairs(odgs, dg2s)
+
+
+def test_group_step_without_nested_operator_on_one_rank_names_it(cm, torch):
+    """Rank 1's slow model without its hooks: the nested continuity operators can no longer run
+    in lock step, group_rhs refuses before any exchange is posted, and the message read from
+    slows[0] says why and names rank 1 (pair 1)."""
+    O1 = cm.ocean01
+    odgs, dg2s, Q3s, Q2s = _zero_pairs(cm, torch)
+    solvers = [O1.SplitExplicitLSRK2nSolver01(o, d2, q3, q2, 5400.0, 240.0)
+               for o, d2, q3, q2 in zip(odgs, dg2s, Q3s, Q2s)]
+    odgs[1].dg.set_rhs_hooks()
+    with pytest.raises(cm._lib.CmdgError) as err:
+        O1.SplitExplicitLSRK2nSolver01.group_dostep(solvers, Q3s, Q2s, 1)
+    msg = str(err.value)
+    assert "every rank needs the nested operator" in msg and "pair 1" in msg, msg
+    torch.cuda.synchronize()
+    _close_pairs(odgs, dg2s)
 
 
 def test_simple_box_2dt_reference_table_on_two_ranks(cm, torch):

@@ -20,6 +20,7 @@
 
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "engine.h"
 
@@ -286,6 +287,21 @@ int cmdg_columnlu_create(cmdg_handle linear, int32_t nvertelem, double alpha, cm
         return lu_fail(&tmp, CMDG_ERR_UNSUPPORTED, "vertical order not compiled in (have N = 4, 5)");
     if (e->nreal % nvertelem != 0)
         return lu_fail(&tmp, CMDG_ERR_INVALID, "the real elements are not whole stacks");
+    {
+        // a vertically periodic stack couples its top and bottom elements, which the band cannot
+        // hold: every stack's bottom (face 5) and top (face 6) must be boundary faces
+        std::vector<int64_t> etb((size_t)6 * e->nreal);
+        if (int r = hip_ok(&tmp, hipMemcpy(etb.data(), e->g.elemtobndy, etb.size() * sizeof(int64_t),
+                                           hipMemcpyDefault),
+                           "hipMemcpy(elemtobndy)"))
+            return r;
+        for (int64_t h = 0; h < e->nreal / nvertelem; ++h)
+            if (etb[4 + 6 * (h * nvertelem)] == 0 || etb[5 + 6 * (h * nvertelem + nvertelem - 1)] == 0)
+                return lu_fail(&tmp, CMDG_ERR_UNSUPPORTED,
+                               "vertically periodic stacks are not supported (stack " + std::to_string(h) +
+                                   " has no boundary face at its bottom or top; the band cannot hold the "
+                                   "coupling of its top and bottom elements)");
+    }
     auto *lu = new cmdg_columnlu(tmp);
     lu->dev = e->dev;
     lu->nvert = nvertelem;

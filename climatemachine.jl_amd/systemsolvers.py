@@ -51,6 +51,7 @@ class ColumnLU:
         self.dg = linear_dg
         self.nvert = int(g.topology.stacksize)
         _check_stack_order(g, self.nvert)
+        _check_stack_ends(g, self.nvert)
         h = C.c_void_p()
         linear_dg._torch_ready()
         _lib.check(linear_dg.L.cmdg_columnlu_create(linear_dg.handle, self.nvert, float(alpha),
@@ -114,3 +115,14 @@ def _check_stack_order(grid, nvert):
     if not ok:
         raise _lib.CmdgError("ManyColumnLU: the real elements are not ordered bottom to top "
                              "within each stack")
+
+
+def _check_stack_ends(grid, nvert):
+    """Every stack ends in boundary faces, bottom and top.  A vertically periodic stack couples its
+    top and bottom elements; the band holds only neighbouring elements, so that coupling would be
+    dropped and the solve silently wrong (the library refuses it as well)."""
+    etb = np.asarray(grid.elemtobndy)[:grid.nreal].reshape(-1, nvert, 6)
+    if np.any(etb[:, 0, 4] == 0) or np.any(etb[:, -1, 5] == 0):
+        raise _lib.CmdgError("ManyColumnLU: vertically periodic stacks are not supported (a stack's "
+                             "bottom or top element has no boundary face; the band cannot hold "
+                             "the coupling of its top and bottom elements)")

@@ -671,7 +671,10 @@ int cmdg_profile_reset(cmdg_handle h);
  * A column solver owns the banded matrix I - alpha L of every column of a VerticalDirection DG
  * model `linear` on a stacked grid (CMDG_PHYSICS_ATMOS_LINEAR_AG; eband = 1, bandwidths
  * p = q = Nq_v nstate - 1).  A column is one horizontal node of one stack of `nvertelem` elements;
- * the real elements must be whole stacks, bottom first.  Assembly probes `linear` (3 Nq_v nstate
+ * the real elements must be whole stacks, bottom first.  Every stack must end in boundary faces:
+ * a vertically periodic stack (no boundary face at the bottom of its first or the top of its last
+ * element) is refused with CMDG_ERR_UNSUPPORTED, since the band cannot hold the coupling of its
+ * top and bottom elements.  Assembly probes `linear` (3 Nq_v nstate
  * evaluations at t = NaN, update_banded_matrix!); factorisation is band_lu! without pivoting.
  * The band lives on the device, ncol n (p + q + 1) doubles: cmdg_columnlu_create refuses
  * (CMDG_ERR_INVALID, message naming the size) when that does not fit in free device memory.

@@ -78,7 +78,8 @@ def lib():
         if hasattr(_LIB, "orc_atmos_new"):
             _LIB.orc_atmos_new.restype = C.POINTER(_Physics)
             _LIB.orc_atmos_new.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        for name in ("orc_ocean_se01_new", "orc_conti3d_se01_new", "orc_baro_se01_new"):
+        for name in ("orc_ocean_se01_new", "orc_conti3d_se01_new", "orc_baro_se01_new",
+                     "orc_atmos_linear_new"):
             getattr(_LIB, name).restype = C.POINTER(_Physics)
             getattr(_LIB, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _LIB.orc_physics_free.argtypes = [C.POINTER(_Physics)]
@@ -166,8 +167,11 @@ class OraclePhysics:
         self._dp = np.ascontiguousarray(dp, dtype=np.float64)
         ctor = {1: "orc_advdiff_new", 2: "orc_atmos_new", 3: "orc_ocean_new",
                 4: "orc_pgrad_new", 5: "orc_sw_new", 6: "orc_moist_new", 7: "orc_ocean_se01_new",
-                8: "orc_conti3d_se01_new", 9: "orc_baro_se01_new"}[law.physics_id]
+                8: "orc_conti3d_se01_new", 9: "orc_baro_se01_new",
+                10: "orc_atmos_linear_new"}[law.physics_id]
         self.c = getattr(lib(), ctor)(_p(self._ip), _p(self._dp), int(nf_first))
+        if not self.c:
+            raise ValueError("%s refuses this descriptor / numerical flux" % ctor)
         ph = self.c.contents
         if nf_first >= 2 and not ph.numerical_flux_law:
             raise ValueError("Roe / HLLC numerical fluxes are methods of the dry atmosphere law only")
@@ -904,3 +908,176 @@ def apply_filter(Q, target, grid, filt, direction=EVERY, state_auxiliary=None):
         else:
             L.orc_apply_mp_filter(dim, Nq, d, _p(Q), nstate, auxp, naux, C.byref(tg), _p(Fc),
                                   _p(vgeo), vgeo.shape[1], MCOL, nreal)
+
+
+# ---- ManyColumnLU (src/Numerics/SystemSolvers/columnwise_lu_solver.jl) -------------------
+# Bands are held in the device's layout: an (n, p + q + 1, ncol) array whose flat offset is
+# (col (p + q + 1) + d) ncol + c, d = row - col + q, c = h Nq^2 + i + Nq j (the column index
+# innermost; climatemachine.jl_amd.systemsolvers.band_offset).  Every operation below is an
+# elementwise numpy operation over the columns c, one per matrix entry, in the reference's order
+# and without contraction, so a device kernel that keeps that order agrees bit for bit.
+def column_shape(grid, nvert, ns=5):
+    """``(nh, nvert, ns, Nq_v, Nq_h^2)`` view shape of the real elements of a stacked grid."""
+    return (grid.nreal // nvert, nvert, ns, grid.Nq[2], grid.Nq[0] * grid.Nq[1])
+
+
+def to_columns(Q, grid, nvert):
+    """``(nelem, ns, Np)`` state -> ``(n, ncol)``, rows ``s + ns k + ns Nq_v v``."""
+    nh, nv, ns, nqv, nqh2 = column_shape(grid, nvert, Q.shape[1])
+    V = Q[:grid.nreal].reshape(nh, nv, ns, nqv, nqh2)
+    return np.ascontiguousarray(V.transpose(1, 3, 2, 0, 4)).reshape(nv * nqv * ns, nh * nqh2)
+
+
+def from_columns(X, Q, grid, nvert):
+    """Inverse of ``to_columns`` into the real elements of ``Q``."""
+    nh, nv, ns, nqv, nqh2 = column_shape(grid, nvert, Q.shape[1])
+    V = X.reshape(nv, nqv, ns, nh, nqh2).transpose(3, 0, 2, 1, 4)
+    Q[:grid.nreal] = V.reshape(grid.nreal, ns, grid.Np)
+
+
+def probe_band(f, grid, nvert, alpha, ns=5, eband=1):
+    """``update_banded_matrix!(A, EulerOperator(f, -alpha), dg, Q, dQ)`` (:404-480) with
+    ``kernel_set_banded_data!`` / ``kernel_set_banded_matrix!`` (:790-880): one unit per (state,
+    vertical node, element ``ev0 + (2 eband + 1) m``) in every column, ``dQ = Q + (-alpha) f(Q)``
+    (BackwardEulerSolvers.jl:26-29), each probed element's band rows taken from itself and its
+    ``eband`` neighbours.  ``f(dQ, Q)`` evaluates the operator with ``increment = false``."""
+    nh, nv, _, nqv, nqh2 = column_shape(grid, nvert, ns)
+    p = q = nqv * ns * eband - 1
+    n, ncol = ns * nqv * nvert, nh * nqh2
+    band = np.zeros((n, p + q + 1, ncol))
+    Q = np.zeros((grid.nelem, ns, grid.Np))
+    dQ = np.zeros_like(Q)
+    eps = -alpha
+    stride = 2 * eband + 1
+    for ev0 in range(min(nvert, stride)):
+        for s in range(ns):
+            for k in range(nqv):
+                Q[:] = 0.0
+                Q[:grid.nreal].reshape(nh, nv, ns, nqv, nqh2)[:, ev0::stride, s, k, :] = 1.0
+                dQ[:] = 0.0
+                f(dQ, Q)
+                E = Q + eps * dQ
+                V = E[:grid.nreal].reshape(nh, nv, ns, nqv, nqh2)
+                for evin in range(ev0, nvert, stride):
+                    jj = s + ns * k + ns * nqv * evin
+                    for ev in range(evin - eband, evin + eband + 1):
+                        if not 0 <= ev < nvert:
+                            continue
+                        for k2 in range(nqv):
+                            for s2 in range(ns):
+                                bb = s2 + ns * k2 + ns * nqv * ev - jj
+                                if -q <= bb <= p:
+                                    band[jj, bb + q] = V[:, ev, s2, k2, :].reshape(ncol)
+    return band, p, q
+
+
+def band_lu(band, p, q):
+    """``band_lu_kernel!`` (:555-600): band Gaussian elimination without pivoting, in place."""
+    n = band.shape[0]
+    for kk in range(n):
+        Aq = band[kk, q].copy()
+        band[kk, q + 1:q + p + 1] /= Aq
+        for jj in range(1, q + 1):
+            if jj + kk < n:
+                Ajj = band[kk + jj, q - jj].copy()
+                band[kk + jj, q + 1 - jj:q + p + 1 - jj] -= band[kk, q + 1:q + p + 1] * Ajj
+    return band
+
+
+def band_forward(band, b, p, q):
+    """``band_forward_kernel!`` (:615-690): ``L y = b`` for every column, ``b`` ``(n, ncol)``."""
+    n = band.shape[0]
+    y = np.zeros((n + p, b.shape[1]))
+    y[:n] = b
+    for jj in range(n):
+        y[jj + 1:jj + p + 1] -= band[jj, q + 1:q + p + 1] * y[jj]
+    return y[:n].copy()
+
+
+def band_back(band, y, p, q):
+    """``band_back_kernel!`` (:705-780): ``U x = y`` for every column."""
+    n = band.shape[0]
+    x = np.zeros((n + q, y.shape[1]))
+    x[q:] = y
+    for jj in range(n - 1, -1, -1):
+        x[jj + q] /= band[jj, q]
+        x[jj:jj + q] -= band[jj, 0:q] * x[jj + q]
+    return x[q:].copy()
+
+
+class OracleColumnLU:
+    """``LinearBackwardEulerSolver(ManyColumnLU(); isadjustable = true)`` over an oracle
+    vertical linear DG model ``lin`` (BackwardEulerSolvers.jl:108-190): the band of
+    ``I - alpha L`` probed, factored, and refactored by ``update`` when alpha changes."""
+
+    def __init__(self, lin, nvert, alpha):
+        self.lin, self.grid, self.nvert = lin, lin.grid, int(nvert)
+        self.update(alpha)
+
+    def assemble(self, alpha):
+        f = lambda dQ, Q: self.lin(dQ, Q, float("nan"), 1.0, 0.0)
+        self.band, self.p, self.q = probe_band(f, self.grid, self.nvert, alpha)
+        self.alpha = alpha
+
+    def update(self, alpha):
+        self.assemble(alpha)
+        band_lu(self.band, self.p, self.q)
+
+    def solve(self, X, B):
+        """``X = (I - alpha L)^-1 B`` on the real elements (``(nelem, 5, Np)`` arrays)."""
+        b = to_columns(B, self.grid, self.nvert)
+        x = band_back(self.band, band_forward(self.band, b, self.p, self.q), self.p, self.q)
+        from_columns(x, X, self.grid, self.nvert)
+        return X
+
+
+def ark_step(full, lin, lu, Q, t, dt, tableau, split):
+    """``dostep!(Q, ark, p, time, ::LowStorageVariant)`` (AdditiveRungeKuttaMethod.jl:415-523) with
+    ``stage_update!`` (:565-605) and ``solution_update!`` (:670-690) on the real elements of
+    ``Q``.  ``full`` is the explicit operator (every direction), ``lin`` the vertical linear
+    model and ``lu`` an ``OracleColumnLU`` of it; the solver is refactored when ``dt a_ii``
+    differs from its alpha (``besolver!`` with ``isadjustable = true``).  ``tableau`` is
+    ``(RKA_explicit, RKA_implicit, RKB, RKC)`` (``odesolvers.ark2gkc_tableau``).
+
+    With ``split`` the explicit operator is "full minus linear", computed as two evaluations (the
+    full one, then the linear one with alpha = -1 and increment), as the device does.  The
+    reference evaluates the remainder in one fused ``RemBL`` kernel; the two differ only in the
+    summation order, at rounding level."""
+    A_e, A_i, B, Cc = [np.asarray(a, dtype=np.float64) for a in tableau]
+    ns = len(B)
+    nr = full.grid.nreal
+    Qs = [Q] + [np.zeros_like(Q) for _ in range(ns - 1)]
+    R = [np.zeros_like(Q) for _ in range(ns)]
+
+    def rhs(Rs, Qst, time):
+        full(Rs, Qst, time, 1.0, 0.0)
+        if split:
+            lin(Rs, Qst, time, -1.0, 1.0)
+
+    rhs(R[0], Qs[0], t + Cc[0] * dt)
+    Qtt = np.zeros_like(Q)
+    for i in range(1, ns):
+        stagetime = t + Cc[i] * dt
+        Qhat = Q.copy()
+        Qst = np.full_like(Q[:nr], -0.0)
+        for j in range(i):
+            if split:
+                rkcoeff = A_i[i, j] / A_i[i, i]
+            else:
+                rkcoeff = (A_i[i, j] - A_e[i, j]) / A_i[i, i]
+            common = rkcoeff * Qs[j][:nr]
+            Qhat[:nr] += common + (dt * A_e[i, j]) * R[j][:nr]
+            Qst -= common
+        Qs[i][:nr] = Qst
+        alpha = dt * A_i[i, i]
+        if alpha != lu.alpha:
+            lu.update(alpha)
+        lu.solve(Qtt, Qhat)
+        Qs[i][:nr] += Qtt[:nr]
+        rhs(R[i], Qs[i], stagetime)
+    if split:
+        for i in range(ns):
+            lin(R[i], Qs[i], t + Cc[i] * dt, 1.0, 1.0)
+    for i in range(ns):
+        Q[:nr] += (B[i] * dt) * R[i][:nr]
+    return Q

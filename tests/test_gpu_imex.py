@@ -10,112 +10,10 @@ import numpy as np
 import pytest
 
 from helpers import held_suarez_setup
+from imex_cases import (ACOUSTIC_GOLDEN, HORIZONTAL, VERTICAL, acoustic_setup, band_to_dense,
+                        column_nodes, make_pair, ref_state, small_sphere, smooth_perturbation)
 
 pytestmark = pytest.mark.gpu
-
-VERTICAL, HORIZONTAL = 2, 1
-# acousticwave_1d_imex.jl:65, expected_result[Float64]
-ACOUSTIC_GOLDEN = 9.5073452847149594e+13
-
-
-class AcousticWaveSetup:
-    """``AcousticWaveSetup{Float64}()`` (acousticwave_1d_imex.jl:284-317): domain height 10 km,
-    T_ref 300 K, alpha 3, gamma 100, nv 1; the passive tracer is not carried (see the golden test)."""
-
-    def __init__(self, ps, domain_height=10e3, T_ref=300.0, alpha=3.0, gamma=100.0, nv=1):
-        self.ps, self.H, self.T_ref, self.alpha, self.gamma, self.nv = ps, domain_height, T_ref, alpha, gamma, nv
-
-    def __call__(self, law, aux, coord, t):
-        ps = self.ps
-        x, y, z3 = coord
-        lam = np.arctan2(y, x)
-        phi = np.arcsin(z3 / np.sqrt(x * x + y * y + z3 * z3))
-        z = aux[:, law.off_phi, :] / ps.grav
-        beta = np.minimum(1.0, self.alpha * np.arccos(np.cos(phi) * np.cos(lam)))
-        f = (1 + np.cos(np.pi * beta)) / 2
-        g = np.sin(self.nv * np.pi * z / self.H)
-        p = aux[:, law.off_ref + 1, :] + self.gamma * f * g
-        rho = p / (ps.R_d * self.T_ref)                       # PhaseDry_pT
-        e_int = ps.cv_d * (self.T_ref - ps.T_0)
-        e_pot = aux[:, law.off_phi, :]
-        zero = 0.0 * rho
-        return rho, [zero, zero, zero], rho * (e_int + e_pot)
-
-
-def acoustic_setup(cm, n_horz=10, n_vert=5, N=5):
-    M, A = cm.mesh, cm.atmos
-    ps = A.PlanetParameters()
-    a = ps.planet_radius
-    topl = M.StackedCubedSphereTopology(n_horz, np.linspace(a, a + 10e3, n_vert + 1), boundary=(1, 2))
-    grid = M.DiscontinuousSpectralElementGrid(topl, N, meshwarp=M.equiangular_cubed_sphere_warp)
-    law = A.DryAtmosModel(AcousticWaveSetup(ps), orientation=A.ORIENT_SPHERICAL,
-                          ref_state=A.IsothermalProfile(ps, 300.0), viscosity=0.0,
-                          dynamic_viscosity=True, sources=A.SRC_GRAVITY,
-                          boundary_conditions=(A.BC_ATMOS_DEFAULT, A.BC_ATMOS_DEFAULT), param_set=ps,
-                          discrete_hydrostatic_balance=True)
-    return law, grid
-
-
-def make_pair(cm, law, grid):
-    dg = cm.dgmodel.DGModel(law, grid, direction=0)
-    lin = cm.dgmodel.DGModel(cm.atmos.AtmosAcousticGravityLinearModel(law), grid, direction=VERTICAL,
-                             state_auxiliary=dg.state_auxiliary)
-    return dg, lin
-
-
-def small_sphere(cm, N=4, hyper=False):
-    """2 x 2 x 6 x 3 stacked cubed sphere, the full law with viscosity 0, Gravity, a reference state."""
-    M, A = cm.mesh, cm.atmos
-    ps = A.PlanetParameters()
-    a = ps.planet_radius
-    topl = M.StackedCubedSphereTopology(2, np.linspace(a, a + 30e3, 4), boundary=(1, 2))
-    grid = M.DiscontinuousSpectralElementGrid(topl, N, meshwarp=M.equiangular_cubed_sphere_warp)
-    law = A.DryAtmosModel(A.HeldSuarezSetup(ps), orientation=A.ORIENT_SPHERICAL,
-                          ref_state=A.DecayingTemperatureProfile(ps, 290.0, 220.0, 8e3), viscosity=0.0,
-                          hyperdiffusion_timescale=8 * 3600.0 if hyper else None,
-                          sources=A.SRC_GRAVITY, boundary_conditions=(A.BC_ATMOS_DEFAULT, A.BC_ATMOS_DEFAULT),
-                          param_set=ps)
-    return law, grid
-
-
-def ref_state(law, aux):
-    """Q0 = the reference state at rest."""
-    Q0 = np.zeros((aux.shape[0], 5, aux.shape[2]))
-    Q0[:, 0] = aux[:, law.off_ref]
-    Q0[:, 4] = aux[:, law.off_ref + 3]
-    return Q0
-
-
-def smooth_perturbation(grid, aux, seed=3):
-    rng = np.random.default_rng(seed)
-    x = [aux[:, d, :] / 6.4e6 for d in range(3)]
-    r = np.sqrt(x[0] ** 2 + x[1] ** 2 + x[2] ** 2)
-    zeta = (r * 6.4e6 - 6.371e6) / 30e3               # 0 at the bottom wall, 1 at the top
-    out = np.zeros((aux.shape[0], 5, aux.shape[2]))
-    for s in range(5):
-        c = rng.uniform(0.5, 1.5, 6)
-        out[:, s] = (np.sin(c[0] * 3 * x[0] + c[1]) * np.cos(c[2] * 2 * x[1] + c[3])
-                     * np.sin(c[4] * 4 * zeta + c[5]))
-    # rho u tangential at the bottom and top walls: the radial part fades out there
-    rhat = [xd / r for xd in x]
-    un = sum(out[:, 1 + d] * rhat[d] for d in range(3))
-    fade = np.sin(np.pi * np.clip(zeta, 0.0, 1.0))
-    for d in range(3):
-        out[:, 1 + d] += (fade - 1.0) * un * rhat[d]
-    return out
-
-
-def column_nodes(grid, nvert, column):
-    """(element, node) of every matrix row of one column, rows ordered (state, k, v) -> n."""
-    Nq, Nqv = grid.N[0] + 1, grid.N[2] + 1
-    nqh2 = Nq * Nq
-    h, ij = divmod(column, nqh2)
-    rows = []
-    for v in range(nvert):
-        for k in range(Nqv):
-            for s in range(5):
-                rows.append((h * nvert + v, s, ij + nqh2 * k))
-    return rows
 
 
 def dense_column(cm, torch, lin, grid, nvert, column, alpha):
@@ -132,17 +30,6 @@ def dense_column(cm, torch, lin, grid, nvert, column, alpha):
         Tn = T.cpu().numpy()
         for i, (e2, s2, node2) in enumerate(rows):
             A[i, j] = (1.0 if i == j else 0.0) + (-alpha) * Tn[e2, s2, node2]
-    return A
-
-
-def band_to_dense(band, p, q):
-    P, n = band.shape
-    A = np.zeros((n, n))
-    for col in range(n):
-        for d in range(P):
-            row = col + d - q
-            if 0 <= row < n:
-                A[row, col] = band[d, col]
     return A
 
 

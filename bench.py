@@ -11,6 +11,12 @@ evaluations of the DG right-hand side on the rank's elements.  ``value`` is the 
 DOF-updates/s: nodes x prognostic states x 5 stages x K steps / wall time (max over
 ranks), with every input resident in HBM before the timed region.  Rank 0 prints ONE JSON
 line (see DESIGN.md "Measurement").
+
+A plain run does only what that line's headline needs: set-up, the W warm-up and K timed steps,
+``--dump-outputs`` and the line.  ``--full`` adds everything else the benchmark checks or
+measures: the GPU vs oracle parity check, the per-kernel event pass (``kernels_ms``,
+``roofline``, ``halo``), the secondary sizes and the one-GPU reference of a multi-GPU job, and
+the CPU baseline.
 """
 import argparse
 import json
@@ -483,9 +489,125 @@ def committed_traffic(workload, nreal, dom):
     return 1024.0 * (2.0 * pm["FETCH_SIZE"] + pm["WRITE_SIZE"]), "profiles/" + name
 
 
+def event_pass(cm, args, dg, law, grid, direction, solver, Q, sync_all, rank, world, with_halo,
+               dofs, el):
+    """``--full``: the same K steps again with a HIP event pair around every kernel launch
+    (recorded on the launch stream): per-kernel durations for the roofline and, on partitioned
+    runs, the halo figures.  The events themselves cost ~10 % of a step at this size, hence the
+    separate pass.  ``dofs`` / ``el``: the timed region's DOF updates and seconds.  Returns rank
+    0's fields of the JSON line."""
+    import torch
+    dg.profile_reset()
+    if not args.no_events:
+        dg.profile_enable(True)
+    sync_all()
+    t1 = time.perf_counter()
+    solver.dostep(Q, nsteps=args.steps)
+    dg.synchronize()
+    torch.cuda.synchronize()
+    el_events = time.perf_counter() - t1
+    dg.profile_enable(False)
+    if rank != 0:
+        return None
+    kern = {}
+    ext = {}
+    for k in ("GRADIENTS", "DIVGRAD", "GRADLAP", "TENDENCY", "PACK", "UNPACK", "FILTER"):
+        ms, n = dg.profile_get(k)
+        if k + "_EXT" in cm._lib.CMDG_K:          # interior + exterior launches of the pass
+            ms_e, n_e = dg.profile_get(k + "_EXT")
+            if n_e:
+                ext[k] = {"interior_avg_ms": ms / max(n, 1), "exterior_avg_ms": ms_e / n_e}
+            ms, n = ms + ms_e, n + n_e
+        if n:
+            kern[k] = (ms / n, n)
+    out = {"kernels_ms": {k: {"avg_ms": v[0], "launches": v[1]} for k, v in kern.items()}}
+    # partitioned runs: rank 0's ghost exchange as the event pass saw it -- the RCCL group of
+    # each exchange on the halo stream, and the time the compute stream had nothing left to
+    # do but wait for the exterior pipeline / an exchange (zero when hidden)
+    if with_halo:
+        halo = {"rank": 0, "real_elements": int(grid.nreal),
+                "ghost_elements": int(grid.nelem - grid.nreal),
+                "interior_elements": int(len(grid.interiorelems)),
+                "exterior_elements": int(len(grid.exteriorelems)),
+                "neighbours": [int(r) for r in grid.nabrtorank],
+                "send_nodes": int(len(grid.vmapsend)),
+                "exchange": {k.lower(): dg.query(k) for k in
+                             ("DIRECT_SEND", "DIRECT_RECV", "HALO_PIPELINE")},
+                "step_graph": bool(args.step_graph), "async_run": bool(args.async_run),
+                "graph_steps_replayed": int(dg.query("GRAPH_STEPS"))}
+        for key, name in (("TRANSPORT", "rccl_group"), ("HALO_EXPOSED", "exposed")):
+            ms, n = dg.profile_get(key)
+            if n:
+                halo[name + "_avg_us"] = 1e3 * ms / n
+                halo[name + "_ms_per_step"] = ms / args.steps
+                halo["exchanges_per_step"] = n / args.steps
+        halo["passes"] = ext
+        out["halo"] = halo
+    passes = [k for k in kern if k in ("GRADIENTS", "DIVGRAD", "GRADLAP", "TENDENCY")]
+    if passes:
+        info = kernel_info(dg, law, grid, direction)
+        dom = max(passes, key=lambda k: kern[k][0] * kern[k][1])
+        avg_ms, nl = kern[dom]
+        elems_per_launch = grid.nreal * 5 * args.steps / nl   # interior/exterior launches split
+        nodes = grid.Np * elems_per_launch
+        needed = needed_bytes_per_node(info, dom)
+        achieved = needed * nodes / (avg_ms * 1e-3) / 1e9
+        traffic, traffic_src = (None, None)
+        if world == 1 and not args.filter:
+            traffic, traffic_src = committed_traffic(args.workload, grid.nreal, dom)
+        survey = algorithmic_bytes_per_node(law, dom, grid.N[0] + 1)
+        out["roofline"] = {
+            "bound": "hbm", "kernel": "k_%s" % dom.lower(), "achieved": achieved,
+            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+            "traffic": traffic,
+            "traffic_over_needed": (traffic / (needed * nodes)) if traffic else None,
+            "traffic_source": ("committed rocprofv3 --pmc profile of this command on these "
+                               "kernel sources, not measured in this run: " + traffic_src)
+            if traffic else traffic_src,
+            "algorithmic_bytes_per_launch": needed * nodes,
+            "algorithmic_bytes_per_node": needed,
+            "bytes_model": "what the shipped instantiation reads and writes, each distinct "
+                           "array element once (bench.needed_bytes_per_node)",
+            "survey_formula_bytes_per_node": survey,
+            "frac_on_survey_formula": survey * nodes / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "avg_launch_ms": avg_ms,
+            "per_kernel": {k: {"needed_bytes_per_node": needed_bytes_per_node(info, k),
+                               "frac": needed_bytes_per_node(info, k) * grid.Np * grid.nreal * 5
+                               * args.steps / kern[k][1] / (kern[k][0] * 1e-3) / 1e9 / HBM_PEAK_GBS}
+                           for k in passes},
+            "timing": "HIP events on the launch stream, second pass of the same "
+                      "%d steps (%.3f ms/step with events)" % (
+                          args.steps, 1e3 * el_events / args.steps)}
+        # SURVEY section 8(d): flops of the (N+1)-point derivative contractions alone (2 (N+1) per
+        # node, differentiated scalar and direction): gradient arguments, the two hyperdiffusion
+        # passes, the tendency.  Secondary figure: the path is HBM bound (< 1 flop/B), the
+        # contraction runs on fp64 VALU out of LDS, not on MFMA (DESIGN.md section 3).
+        cf = 6 * (grid.N[0] + 1) * (law.ngrad + 2 * law.ngradlap + law.ns)
+        out["contraction"] = {
+            "flops_per_node_update": cf,
+            "achieved_TFLOPs": cf * (dofs / law.ns) / el / 1e12,
+            "unit": "fp64 VALU out of LDS (v_mul_f64 + v_add_f64, no contraction of a*b+c)",
+            # the shipped kernels issue no MFMA; measured on this chip (profiles/r02_*):
+            "mfma_util": 0.0,
+            "measured_fp64_peaks_TFLOPs": {"v_mfma_f64_16x16x4_f64": 47.7, "v_mfma_f64_4x4x4_4b_f64": 72.7,
+                                           "v_fma_f64": 64.8, "v_mul_f64+v_add_f64": 34.0},
+            "mfma_variant": "k_gradients with the contraction on v_mfma_f64_16x16x4_f64: +70 % time, "
+                            "5.1 % matrix-pipe busy (SQ_VALU_MFMA_BUSY_CYCLES); contraction removed "
+                            "altogether: -2.1 % per step",
+            "evidence": ["profiles/r02_fp64_peak.jsonl", "profiles/r02_ab_mfma_contraction.txt",
+                         "profiles/r02_mfma_variant_pmc_per_launch.json"]}
+    if "FILTER" in kern:
+        # Q read + written (5 fields each) and the two reference-state columns
+        fb = 8 * (2 * law.ns + 2) * grid.Np * grid.nreal
+        out["filter_kernel"] = {"avg_launch_ms": kern["FILTER"][0],
+                                "algorithmic_bytes_per_node": 8 * (2 * law.ns + 2),
+                                "achieved_GBs": fb / (kern["FILTER"][0] * 1e-3) / 1e9}
+    return out
+
+
 def measure(cm, args, workload_args, rank, world, distributed, dev, with_halo, dump=None):
-    """Builds one workload on this rank, runs the timed region and the event pass, and (rank 0)
-    returns the fields of the JSON line for it.  ``dump``: directory for rank 0's state after the
+    """Builds one workload on this rank, runs the timed region (and with ``--full`` the event
+    pass), and (rank 0) returns the fields of the JSON line for it.  ``dump``: directory for rank 0's state after the
     timed steps (``--dump-outputs``)."""
     import torch
     import torch.distributed as dist
@@ -542,119 +664,18 @@ def measure(cm, args, workload_args, rank, world, distributed, dev, with_halo, d
         total_elems = grid.nreal
     if dump and rank == 0:
         log("[dump] %s" % json.dumps(dump_outputs(dump, {"state": Q[:grid.nreal]})))
-    # ---- same K steps again with a HIP event pair around every kernel launch (recorded on
-    # the launch stream): per-kernel durations for the roofline.  The events themselves cost
-    # ~10 % of a step at this size, hence the separate pass.
-    dg.profile_reset()
-    if not args.no_events:
-        dg.profile_enable(True)
-    sync_all()
-    t1 = time.perf_counter()
-    solver.dostep(Q, nsteps=args.steps)
-    dg.synchronize()
-    torch.cuda.synchronize()
-    el_events = time.perf_counter() - t1
-    dg.profile_enable(False)
     finite = bool(torch.isfinite(Q[:grid.nreal]).all().item())
+    dofs = total_elems * grid.Np * law.ns * 5 * args.steps
+    figures = None
+    if args.full:
+        figures = event_pass(cm, args, dg, law, grid, direction, solver, Q, sync_all, rank, world,
+                             with_halo, dofs, el)
     out = None
     if rank == 0:
-        dofs = total_elems * grid.Np * law.ns * 5 * args.steps
-        kern = {}
-        ext = {}
-        for k in ("GRADIENTS", "DIVGRAD", "GRADLAP", "TENDENCY", "PACK", "UNPACK", "FILTER"):
-            ms, n = dg.profile_get(k)
-            if k + "_EXT" in cm._lib.CMDG_K:          # interior + exterior launches of the pass
-                ms_e, n_e = dg.profile_get(k + "_EXT")
-                if n_e:
-                    ext[k] = {"interior_avg_ms": ms / max(n, 1), "exterior_avg_ms": ms_e / n_e}
-                ms, n = ms + ms_e, n + n_e
-            if n:
-                kern[k] = (ms / n, n)
         out = {"value": dofs / el, "ms_per_step": 1e3 * el / args.steps, "config": desc,
                "node_updates_per_s": dofs / el / law.ns, "state_finite": finite,
-               "elements_total": total_elems,
-               "kernels_ms": {k: {"avg_ms": v[0], "launches": v[1]} for k, v in kern.items()}}
-        # partitioned runs: rank 0's ghost exchange as the event pass saw it -- the RCCL group of
-        # each exchange on the halo stream, and the time the compute stream had nothing left to
-        # do but wait for the exterior pipeline / an exchange (zero when hidden)
-        if with_halo:
-            halo = {"rank": 0, "real_elements": int(grid.nreal),
-                    "ghost_elements": int(grid.nelem - grid.nreal),
-                    "interior_elements": int(len(grid.interiorelems)),
-                    "exterior_elements": int(len(grid.exteriorelems)),
-                    "neighbours": [int(r) for r in grid.nabrtorank],
-                    "send_nodes": int(len(grid.vmapsend)),
-                    "exchange": {k.lower(): dg.query(k) for k in
-                                 ("DIRECT_SEND", "DIRECT_RECV", "HALO_PIPELINE")},
-                    "step_graph": bool(args.step_graph), "async_run": bool(args.async_run),
-                    "graph_steps_replayed": int(dg.query("GRAPH_STEPS"))}
-            for key, name in (("TRANSPORT", "rccl_group"), ("HALO_EXPOSED", "exposed")):
-                ms, n = dg.profile_get(key)
-                if n:
-                    halo[name + "_avg_us"] = 1e3 * ms / n
-                    halo[name + "_ms_per_step"] = ms / args.steps
-                    halo["exchanges_per_step"] = n / args.steps
-            halo["passes"] = ext
-            out["halo"] = halo
-        passes = [k for k in kern if k in ("GRADIENTS", "DIVGRAD", "GRADLAP", "TENDENCY")]
-        if passes:
-            info = kernel_info(dg, law, grid, direction)
-            dom = max(passes, key=lambda k: kern[k][0] * kern[k][1])
-            avg_ms, nl = kern[dom]
-            elems_per_launch = grid.nreal * 5 * args.steps / nl   # interior/exterior launches split
-            nodes = grid.Np * elems_per_launch
-            needed = needed_bytes_per_node(info, dom)
-            achieved = needed * nodes / (avg_ms * 1e-3) / 1e9
-            traffic, traffic_src = (None, None)
-            if world == 1 and not args.filter:
-                traffic, traffic_src = committed_traffic(args.workload, grid.nreal, dom)
-            survey = algorithmic_bytes_per_node(law, dom, grid.N[0] + 1)
-            out["roofline"] = {
-                "bound": "hbm", "kernel": "k_%s" % dom.lower(), "achieved": achieved,
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "traffic_over_needed": (traffic / (needed * nodes)) if traffic else None,
-                "traffic_source": ("committed rocprofv3 --pmc profile of this command on these "
-                                   "kernel sources, not measured in this run: " + traffic_src)
-                if traffic else traffic_src,
-                "algorithmic_bytes_per_launch": needed * nodes,
-                "algorithmic_bytes_per_node": needed,
-                "bytes_model": "what the shipped instantiation reads and writes, each distinct "
-                               "array element once (bench.needed_bytes_per_node)",
-                "survey_formula_bytes_per_node": survey,
-                "frac_on_survey_formula": survey * nodes / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "avg_launch_ms": avg_ms,
-                "per_kernel": {k: {"needed_bytes_per_node": needed_bytes_per_node(info, k),
-                                   "frac": needed_bytes_per_node(info, k) * grid.Np * grid.nreal * 5
-                                   * args.steps / kern[k][1] / (kern[k][0] * 1e-3) / 1e9 / HBM_PEAK_GBS}
-                               for k in passes},
-                "timing": "HIP events on the launch stream, second pass of the same "
-                          "%d steps (%.3f ms/step with events)" % (
-                              args.steps, 1e3 * el_events / args.steps)}
-            # flops of the (N+1)-point derivative contractions alone (2 (N+1) per
-            # node, differentiated scalar and direction): gradient arguments, the two hyperdiffusion
-            # passes, the tendency.  Secondary figure: the path is HBM bound (< 1 flop/B), the
-            # contraction runs on fp64 VALU out of LDS, not on MFMA.
-            cf = 6 * (grid.N[0] + 1) * (law.ngrad + 2 * law.ngradlap + law.ns)
-            out["contraction"] = {
-                "flops_per_node_update": cf,
-                "achieved_TFLOPs": cf * (dofs / law.ns) / el / 1e12,
-                "unit": "fp64 VALU out of LDS (v_mul_f64 + v_add_f64, no contraction of a*b+c)",
-                # the shipped kernels issue no MFMA; measured on this chip (profiles/r02_*):
-                "mfma_util": 0.0,
-                "measured_fp64_peaks_TFLOPs": {"v_mfma_f64_16x16x4_f64": 47.7, "v_mfma_f64_4x4x4_4b_f64": 72.7,
-                                               "v_fma_f64": 64.8, "v_mul_f64+v_add_f64": 34.0},
-                "mfma_variant": "k_gradients with the contraction on v_mfma_f64_16x16x4_f64: +70 % time, "
-                                "5.1 % matrix-pipe busy (SQ_VALU_MFMA_BUSY_CYCLES); contraction removed "
-                                "altogether: -2.1 % per step",
-                "evidence": ["profiles/r02_fp64_peak.jsonl", "profiles/r02_ab_mfma_contraction.txt",
-                             "profiles/r02_mfma_variant_pmc_per_launch.json"]}
-        if "FILTER" in kern:
-            # Q read + written (5 fields each) and the two reference-state columns
-            fb = 8 * (2 * law.ns + 2) * grid.Np * grid.nreal
-            out["filter_kernel"] = {"avg_launch_ms": kern["FILTER"][0],
-                                    "algorithmic_bytes_per_node": 8 * (2 * law.ns + 2),
-                                    "achieved_GBs": fb / (kern["FILTER"][0] * 1e-3) / 1e9}
+               "elements_total": total_elems}
+        out.update(figures or {})
         out["_cpu_inputs"] = (law, grid, direction, dt)
     if step_filter is not None:
         dg.set_filters()
@@ -729,16 +750,22 @@ def parse_args(argv):
                          "configs[2] split over the GPUs, weak = 43 200 elements per GPU (n_horz "
                          "30/42/60/85 at 1/2/4/8 GPUs), weak-small = ~5 400 elements per GPU (n_horz "
                          "11/15/21/30); both (default) = strong as the headline and weak under "
-                         "'secondary' of the same line.  On one GPU all but weak-small are the "
-                         "same 43 200-element sphere")
-    ap.add_argument("--no-parity", action="store_true", help="skip the in-run GPU vs oracle check")
+                         "'secondary' of the same line (with --full).  On one GPU all but "
+                         "weak-small are the same 43 200-element sphere")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, check and measure everything else: the GPU vs "
+                         "oracle parity check, the per-kernel event pass (kernels_ms, roofline, "
+                         "halo), the secondary sizes (one GPU: n_horz = 11; N GPUs: the weak family "
+                         "and rank 0's one-GPU reference) and the CPU baseline.  A plain run only "
+                         "sets up, warms up, times the steps, dumps and prints the line")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the in-run GPU vs oracle check")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary measurement (one GPU: n_horz = 11; N GPUs: the weak family)")
+                    help="--full: skip the secondary measurement (one GPU: n_horz = 11; N GPUs: the weak family)")
     ap.add_argument("--no-n1-reference", action="store_true",
-                    help="N > 1: skip rank 0's one-GPU run of the 43 200-element sphere that "
+                    help="--full, N > 1: skip rank 0's one-GPU run of the 43 200-element sphere that "
                          "efficiency_vs_n1 is computed against")
     ap.add_argument("--nvert", type=int, default=8, help="heldsuarez: vertical elements")
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU baseline")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full: seconds of CPU baseline")
     ap.add_argument("--filter", action="store_true",
                     help="heldsuarez: exponential filter of the perturbations after every step "
                          "(experiments/AtmosGCM/heldsuarez.jl:261-272); off for the headline "
@@ -747,8 +774,10 @@ def parse_args(argv):
                     help="record one LSRK step into a HIP graph and replay it (CMDG_OPT_STEP_GRAPH)")
     ap.add_argument("--async-run", action="store_true",
                     help="the handle's own thread enqueues the run (CMDG_OPT_ASYNC_RUN)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-events", action="store_true", help="time without per-kernel HIP events")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="--full: skip the CPU baseline (and, on one GPU, the parity check)")
+    ap.add_argument("--no-events", action="store_true",
+                    help="--full: run the second pass without per-kernel HIP events")
     ap.add_argument("--dry-launch", action="store_true",
                     help="start the ranks as usual, but each only prints its launch environment "
                          "(no torch, no GPU): checks the launcher itself")
@@ -812,7 +841,7 @@ def main(argv=None):
         gloo = dist.new_group(backend="gloo")    # long waits without a spinning RCCL kernel
 
     parity = None
-    if rank == 0 and world == 1 and not args.no_parity and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_parity and not args.no_cpu:
         parity = parity_check(cm, args, dev)
         log("[parity] %s" % json.dumps(parity))
 
@@ -827,10 +856,10 @@ def main(argv=None):
     res = measure(cm, args, main_args, rank, world, distributed, dev,
                   with_halo=multi or bool(os.environ.get("BENCH_HALO_BLOCK")), dump=args.dump_outputs)
     sec = None
-    if both and not args.no_secondary:
+    if args.full and both and not args.no_secondary:
         sec = measure(cm, args, with_scaling(args, "weak"), rank, world, distributed, dev, with_halo=True)
     n1 = None
-    if multi and distributed and hs and not args.no_n1_reference and not args.nhorz:
+    if args.full and multi and distributed and hs and not args.no_n1_reference and not args.nhorz:
         # the one-GPU value both families are scaled against, measured by rank 0 alone on its GPU
         # while the others wait (CPU barrier): the 43 200-element sphere of BASELINE configs[2]
         if rank == 0:
@@ -862,7 +891,7 @@ def main(argv=None):
             if n1 is not None:
                 s2["efficiency_vs_n1"] = sec["value"] / (world * n1["value"])
             out["secondary"] = s2
-        elif (world == 1 and hs and not args.nhorz and not args.filter
+        elif (args.full and world == 1 and hs and not args.nhorz and not args.filter
                 and args.scaling != "weak-small" and not args.no_secondary):
             # the round-1 headline size (SURVEY section 8(d)'s weak-scaling base of ~5 400 elements
             # per GPU), so that numbers of that family stay comparable
@@ -870,7 +899,7 @@ def main(argv=None):
             r2 = measure(cm, args, a2, 0, 1, False, dev, with_halo=False)
             out["secondary"] = {"workload": r2["config"]["workload"], "elements": r2["elements_total"],
                                 "value": r2["value"], "ms_per_step": r2["ms_per_step"]}
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(cm, law, grid, direction, dt, args.cpu_budget, args)
         emit(out)
         if not out["state_finite"]:
@@ -966,21 +995,22 @@ def main_ocean(args, rank, world, local):
         dist.all_reduce(mx, op=dist.ReduceOp.MAX)
         dist.all_reduce(tt, op=dist.ReduceOp.SUM)
         el, total3 = float(mx[0].item()), int(round(tt[1].item()))
-    for d in (dg3, dg2):
-        d.profile_reset()
-        if not args.no_events:
-            d.profile_enable(True)
-    t1 = time.perf_counter()
-    se.dostep(Q3, Q2, args.steps)
-    dg3.synchronize(), dg2.synchronize()
-    torch.cuda.synchronize()
-    el_ev = time.perf_counter() - t1
-    for d in (dg3, dg2):
-        d.profile_enable(False)
+    finite = bool(torch.isfinite(Q3[:g3.nreal]).all().item() and torch.isfinite(Q2[:g2.nreal]).all().item())
+    if args.full:          # the same steps again with HIP events around every launch
+        for d in (dg3, dg2):
+            d.profile_reset()
+            if not args.no_events:
+                d.profile_enable(True)
+        t1 = time.perf_counter()
+        se.dostep(Q3, Q2, args.steps)
+        dg3.synchronize(), dg2.synchronize()
+        torch.cuda.synchronize()
+        el_ev = time.perf_counter() - t1
+        for d in (dg3, dg2):
+            d.profile_enable(False)
     RKC = se.RKC
     nsub = sum(int(np.ceil(((1 - RKC[s]) if s == 4 else (RKC[s + 1] - RKC[s])) * dt_slow / dt_fast))
                for s in range(5))
-    finite = bool(torch.isfinite(Q3[:g3.nreal]).all().item() and torch.isfinite(Q2[:g2.nreal]).all().item())
     dofs = total3 * g3.Np * law3.ns * 5 * args.steps
     if distributed and rank != 0:
         del keep
@@ -988,13 +1018,6 @@ def main_ocean(args, rank, world, local):
         dist.barrier()
         dist.destroy_process_group()
         return
-    kernels = {}
-    for name, d in (("slow", dg3), ("fast", dg2)):
-        for kn in ("GRADIENTS", "TENDENCY", "FILTER", "STACK_INTEGRAL"):
-            ms, n = d.profile_get(kn)
-            if n:
-                kernels["%s_%s" % (name, kn.lower())] = {
-                    "avg_ms": ms / n, "launches_per_step": n / args.steps, "ms_per_step": ms / args.steps}
     out = {"metric": "DG RHS DOF-updates/sec", "value": dofs / el, "unit": "DOF-updates/s",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True, "scaling": "weak",
@@ -1007,8 +1030,17 @@ def main_ocean(args, rank, world, local):
                       "elements": int(total3), "nodes_per_element": int(g3.Np), "states": law3.ns,
                       "parallelism": "element partition (Hilbert, whole columns, both models alike), "
                                      "%d rank(s), RCCL p2p halo" % world},
-           "node_updates_per_s": dofs / el / law3.ns, "state_finite": finite, "kernels_ms": kernels}
-    if "slow_tendency" in kernels:
+           "node_updates_per_s": dofs / el / law3.ns, "state_finite": finite}
+    if args.full:
+        kernels = {}
+        for name, d in (("slow", dg3), ("fast", dg2)):
+            for kn in ("GRADIENTS", "TENDENCY", "FILTER", "STACK_INTEGRAL"):
+                ms, n = d.profile_get(kn)
+                if n:
+                    kernels["%s_%s" % (name, kn.lower())] = {
+                        "avg_ms": ms / n, "launches_per_step": n / args.steps, "ms_per_step": ms / args.steps}
+        out["kernels_ms"] = kernels
+    if args.full and "slow_tendency" in kernels:
         info = kernel_info(dg3, law3, g3, (0, 0))
         avg_ms = kernels["slow_tendency"]["avg_ms"]
         needed = needed_bytes_per_node(info, "TENDENCY") - 8 * 1.5 * law3.ns
@@ -1022,7 +1054,7 @@ def main_ocean(args, rank, world, local):
                            "algorithmic_bytes_per_node": needed, "avg_launch_ms": avg_ms,
                            "timing": "HIP events on the launch stream, second pass of the same %d "
                                      "steps (%.3f ms/step with events)" % (args.steps, 1e3 * el_ev / args.steps)}
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         from oracle import oracle as OR
         OR.build()
         host = host_cpu_info()

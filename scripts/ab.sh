@@ -3,7 +3,7 @@
 args="$1"; shift
 for lib in "$@"; do
   if [ "$lib" = "default" ]; then unset CMDG_LIB; else export CMDG_LIB=$PWD/build/libcmdg_$lib.so; fi
-  python bench.py $args --no-cpu 2>/dev/null | python -c "
+  python bench.py --full $args --no-cpu 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = d['kernels_ms']

@@ -3,7 +3,7 @@
 args="$1"; shift
 for kv in "$@"; do
   if [ "$kv" = "-" ]; then pre=""; else pre="$kv"; fi
-  env $pre python bench.py $args --no-cpu 2>/dev/null | python -c "
+  env $pre python bench.py --full $args --no-cpu 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['kernels_ms']

@@ -55,3 +55,20 @@ def test_dump_of_the_split_explicit_ocean(tmp_path):
         assert q.dtype == np.float64 and np.isfinite(q).all()
         assert np.array_equal(q, np.load(tmp_path / "b" / name))
     assert np.load(tmp_path / "a" / "state_3d.npy").shape[0] == 5 * 5 * 8
+
+
+@pytest.mark.gpu
+def test_full_adds_the_extras_around_the_same_timed_steps(tmp_path):
+    """A plain run prints the headline alone; ``--full`` adds the parity check, the event pass and
+    the CPU baseline around the same timed steps, so it dumps the plain run's state."""
+    small = ["--nhorz", "3", "--nvert", "2", "--steps", "2", "--warmup", "1"]
+    plain = _bench(tmp_path / "plain", *small)
+    full = _bench(tmp_path / "full", "--full", "--cpu-budget", "0.1", *small)
+    extras = ("parity", "kernels_ms", "roofline", "cpu_baseline")
+    assert not [k for k in extras if k in plain], sorted(plain)
+    assert all(k in full for k in extras), sorted(full)
+    assert full["parity"]["ok"] and plain["state_finite"] and full["state_finite"]
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "elements_total"):
+        assert plain[k] == full[k], k
+    assert np.array_equal(np.load(tmp_path / "plain" / "state.npy"),
+                          np.load(tmp_path / "full" / "state.npy"))

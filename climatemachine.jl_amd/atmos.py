@@ -25,7 +25,7 @@ grad^3 h_tot (3)``.
 """
 import numpy as np
 
-from .balancelaws import PHYSICS_ATMOS_LINEAR_AG, PHYSICS_DRY_ATMOS
+from .balancelaws import PHYSICS_ATMOS_LINEAR_AG, PHYSICS_DRY_ATMOS, PHYSICS_MOIST_ATMOS, PHYSICS_MOIST_LINEAR_AG
 from .mesh import grids as G
 
 __all__ = ["PlanetParameters", "DryAtmosModel", "IsentropicVortexSetup", "HeldSuarezSetup",
@@ -424,10 +424,25 @@ class AtmosAcousticGravityLinearModel:
     rho Phi)``, source ``-rho grad Phi`` (vertical and every direction), Rusanov wavespeed
     ``soundspeed(ref.T)``, ``AtmosBC()`` on every boundary.  It reads the full model's auxiliary
     state: build it as ``DGModel(linear, grid, direction=VerticalDirection,
-    state_auxiliary=dg.state_auxiliary)``.  Device functor: csrc/physics_atmos_linear.h."""
+    state_auxiliary=dg.state_auxiliary)``.  Device functor: csrc/physics_atmos_linear.h.
+
+    Of a ``moist.MoistAtmosModel`` (``EquilMoist``, linear.jl:57-72) it carries the sixth state
+    ``rho q_tot`` (no flux, no source), ``p_lin`` gains ``- rho q_tot e_int_v0``, the auxiliary state
+    is the moist model's 19 columns and the physics id is ``PHYSICS_MOIST_LINEAR_AG``."""
     physics_id = PHYSICS_ATMOS_LINEAR_AG
 
     def __init__(self, atmos):
+        if atmos.physics_id == PHYSICS_MOIST_ATMOS:
+            if atmos.no_orientation or atmos.ref_state is None:
+                raise ValueError("AtmosAcousticGravityLinearModel needs a moist model with an "
+                                 "orientation and a reference state (this one has no_orientation)")
+            self.atmos = atmos
+            self.ps = atmos.ps
+            self.physics_id = PHYSICS_MOIST_LINEAR_AG
+            self.off_phi, self.off_ref = atmos.off_phi, atmos.off_ref
+            self.ns, self.naux = 6, atmos.naux
+            self.ngrad = self.ngradflux = self.ngradlap = self.nhyper = 0
+            return
         if atmos.ref_state is None:
             raise ValueError("AtmosAcousticGravityLinearModel needs a model with a reference state")
         if atmos.orientation == ORIENT_NONE:

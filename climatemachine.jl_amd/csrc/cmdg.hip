@@ -1950,6 +1950,7 @@ int cmdg_physics_counts(int32_t physics_id, const int32_t *iparam, int32_t out[6
     case CMDG_PHYSICS_SHALLOW_WATER: return counts_sw(iparam, out);
     case CMDG_PHYSICS_MOIST_ATMOS: return counts_moist(iparam, out);
     case CMDG_PHYSICS_ATMOS_LINEAR_AG: return counts_atmos_linear(iparam, out);
+    case CMDG_PHYSICS_MOIST_LINEAR_AG: return counts_moist_linear(iparam, out);
     case CMDG_PHYSICS_OCEAN_SE01:
     case CMDG_PHYSICS_CONTINUITY3D_SE01:
     case CMDG_PHYSICS_BAROTROPIC_SE01: return counts_se01(physics_id, out);
@@ -1992,6 +1993,7 @@ int cmdg_create(const cmdg_desc *d, cmdg_handle *out)
     case CMDG_PHYSICS_SHALLOW_WATER: e = make_engine_sw(d, err); break;
     case CMDG_PHYSICS_MOIST_ATMOS: e = make_engine_moist(d, err); break;
     case CMDG_PHYSICS_ATMOS_LINEAR_AG: e = make_engine_atmos_linear(d, err); break;
+    case CMDG_PHYSICS_MOIST_LINEAR_AG: e = make_engine_moist_linear(d, err); break;
     case CMDG_PHYSICS_OCEAN_SE01:
     case CMDG_PHYSICS_CONTINUITY3D_SE01:
     case CMDG_PHYSICS_BAROTROPIC_SE01: e = make_engine_se01(d, err); break;

@@ -1,8 +1,8 @@
 // ManyColumnLU (src/Numerics/SystemSolvers/columnwise_lu_solver.jl) and the low-storage additive
 // Runge-Kutta step that uses it (AdditiveRungeKuttaMethod.jl, LowStorageVariant).
 //
-// The operator is I - alpha L of a vertical-direction DG model on a stacked grid: a banded matrix
-// per column, one column = one horizontal node (i, j) of one stack of elements, n = Nq_v nstate
+// The operator is I - alpha L of a vertical-direction DG model on a stacked grid (the dry linear
+// law, nstate = 5, or the moist one, nstate = 6): a banded matrix per column, one column = one horizontal node (i, j) of one stack of elements, n = Nq_v nstate
 // nvert unknowns ordered (state, vertical node, element) fastest first, bandwidths
 // p = q = Nq_v nstate - 1 (eband = 1, an inviscid law: columnwise_lu_solver.jl:56-74, :339-349).
 //
@@ -27,11 +27,9 @@
 namespace cmdg {
 namespace {
 
-constexpr int NS = 5;  // the dry law's prognostic states
-
 unsigned blocks(int64_t n, int nt = 256) { return (unsigned)((n + nt - 1) / nt); }
 
-__global__ void k_probe_set(double *Q, int64_t nreal, int Np, int nqh2, int nvert, int kin,
+__global__ void k_probe_set(double *Q, int64_t nreal, int Np, int NS, int nqh2, int nvert, int kin,
                             int sin_, int ev0)
 {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -45,7 +43,7 @@ __global__ void k_probe_set(double *Q, int64_t nreal, int Np, int nqh2, int nver
 
 // every real node of dQ belongs to the band of the probed column in its own or an adjacent element
 __global__ void k_probe_scatter(double *band, const double *Q, const double *dQ, int64_t nreal,
-                                int Np, int nqh2, int nqv, int nvert, int kin, int sin_, int ev0,
+                                int Np, int NS, int nqh2, int nqv, int nvert, int kin, int sin_, int ev0,
                                 int p, int q, int64_t ncol, double eps)
 {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -90,8 +88,9 @@ __global__ void k_band_lu(double *A, int64_t ncol, int64_t n, int p, int q)
 
 // band_forward_kernel! then band_back_kernel! on one matrix column per lane.  W = p + 1 = q + 1 =
 // NQV * NS: the row loaded ahead (behind) is the same (node, state) of the next (previous)
-// element, so the window indices are static once the rows of an element are unrolled.
-template <int NQV>
+// element.  The window shifts by one register per row, so its indices are static; it stays in
+// registers for every compiled (NQV, NS) (scratch 0).
+template <int NQV, int NS>
 __global__ void __launch_bounds__(64) k_band_solve(double *X, const double *B, const double *A, int64_t ncol,
                                                    int nvert, int nqh2)
 {
@@ -112,7 +111,9 @@ __global__ void __launch_bounds__(64) k_band_solve(double *X, const double *B, c
 #pragma unroll
     for (int r = 0; r < W; ++r) lb[r] = B[idx(0, r)];
     for (int v = 0; v < nvert; ++v) {
-#pragma unroll
+        // one row per iteration: unrolling the rows of an element hoisted every row's p band
+        // loads at once and spilled the window to scratch
+#pragma unroll 1
         for (int r = 0; r < W; ++r) {
             const int64_t jj = (int64_t)v * W + r;
 #pragma unroll
@@ -127,7 +128,7 @@ __global__ void __launch_bounds__(64) k_band_solve(double *X, const double *B, c
 #pragma unroll
     for (int r = 0; r < W; ++r) lb[r] = X[idx(nvert - 1, r)];
     for (int v = nvert - 1; v >= 0; --v) {
-#pragma unroll
+#pragma unroll 1
         for (int r = W - 1; r >= 0; --r) {
             const int64_t jj = (int64_t)v * W + r;
             lb[q] /= L(jj, q);
@@ -185,7 +186,7 @@ using namespace cmdg;
 struct cmdg_columnlu {
     cmdg_handle lin = nullptr;
     int dev = 0;  // the linear handle's device (destroy does not need the handle any more)
-    int nvert = 0, nqh2 = 0, nqv = 0, p = 0, q = 0, P = 0;
+    int nvert = 0, nqh2 = 0, nqv = 0, ns = 0, p = 0, q = 0, P = 0;
     int64_t ncol = 0, n = 0;
     double alpha = 0;
     int state = 0;  // 0 empty, 1 assembled (I - alpha L), 2 factored
@@ -195,6 +196,11 @@ struct cmdg_columnlu {
 };
 
 namespace {
+
+// the (vertical order, state count) pairs k_band_solve is compiled for
+bool compiled(int nqv, int ns) { return ns == 5 ? (nqv == 5 || nqv == 6) : ns == 6 && (nqv == 5 || nqv == 7); }
+const char *const compiled_pairs =
+    "vertical order / state count not compiled in (have N = 4, 5 with five states, N = 4, 6 with six)";
 
 int lu_fail(cmdg_columnlu *lu, int code, const std::string &msg)
 {
@@ -220,6 +226,7 @@ int assemble(cmdg_columnlu *lu, double alpha)
 {
     EngineBase *e = lu->lin->eng;
     hipStream_t st = e->s_comp;
+    const int NS = lu->ns;
     const int64_t len = e->nreal * NS * e->Np;
     const size_t bytes = (size_t)lu->n * lu->P * lu->ncol * sizeof(double);
     if (int r = hip_ok(lu, hipMemsetAsync(lu->band, 0, bytes, st), "hipMemsetAsync")) return r;
@@ -228,10 +235,10 @@ int assemble(cmdg_columnlu *lu, double alpha)
         for (int s = 0; s < NS; ++s)
             for (int k = 0; k < lu->nqv; ++k) {
                 hipLaunchKernelGGL(k_probe_set, dim3(blocks(len)), dim3(256), 0, st, lu->probe, e->nreal,
-                                   e->Np, lu->nqh2, lu->nvert, k, s, ev0);
+                                   e->Np, NS, lu->nqh2, lu->nvert, k, s, ev0);
                 if (int r = cmdg_rhs_async(lu->lin, lu->dprobe, lu->probe, NAN, 1.0, 0.0)) return r;
                 hipLaunchKernelGGL(k_probe_scatter, dim3(blocks(len)), dim3(256), 0, st, lu->band,
-                                   lu->probe, lu->dprobe, e->nreal, e->Np, lu->nqh2, lu->nqv, lu->nvert,
+                                   lu->probe, lu->dprobe, e->nreal, e->Np, NS, lu->nqh2, lu->nqv, lu->nvert,
                                    k, s, ev0, lu->p, lu->q, lu->ncol, -alpha);
             }
     lu->alpha = alpha;
@@ -259,11 +266,16 @@ int solve(cmdg_columnlu *lu, double *X, const double *B)
     if (lu->state != 2) return lu_fail(lu, CMDG_ERR_INVALID, "the band is not factored");
     hipStream_t st = lu->lin->eng->s_comp;
     const dim3 g(blocks(lu->ncol, 64)), b(64);
-    switch (lu->nqv) {
-    case 5: hipLaunchKernelGGL(k_band_solve<5>, g, b, 0, st, X, B, lu->band, lu->ncol, lu->nvert, lu->nqh2); break;
-    case 6: hipLaunchKernelGGL(k_band_solve<6>, g, b, 0, st, X, B, lu->band, lu->ncol, lu->nvert, lu->nqh2); break;
-    default: return lu_fail(lu, CMDG_ERR_UNSUPPORTED, "vertical order not compiled in (have N = 4, 5)");
-    }
+    if (lu->ns == 5 && lu->nqv == 5)
+        hipLaunchKernelGGL((k_band_solve<5, 5>), g, b, 0, st, X, B, lu->band, lu->ncol, lu->nvert, lu->nqh2);
+    else if (lu->ns == 5 && lu->nqv == 6)
+        hipLaunchKernelGGL((k_band_solve<6, 5>), g, b, 0, st, X, B, lu->band, lu->ncol, lu->nvert, lu->nqh2);
+    else if (lu->ns == 6 && lu->nqv == 5)
+        hipLaunchKernelGGL((k_band_solve<5, 6>), g, b, 0, st, X, B, lu->band, lu->ncol, lu->nvert, lu->nqh2);
+    else if (lu->ns == 6 && lu->nqv == 7)
+        hipLaunchKernelGGL((k_band_solve<7, 6>), g, b, 0, st, X, B, lu->band, lu->ncol, lu->nvert, lu->nqh2);
+    else
+        return lu_fail(lu, CMDG_ERR_UNSUPPORTED, compiled_pairs);
     return hip_ok(lu, hipGetLastError(), "band solve");
 }
 
@@ -281,10 +293,10 @@ int cmdg_columnlu_create(cmdg_handle linear, int32_t nvertelem, double alpha, cm
     tmp.lin = linear;
     if (e->direction != DIR_VERTICAL || !e->stacked)
         return lu_fail(&tmp, CMDG_ERR_INVALID, "the operator must be a VerticalDirection DG model on a stacked grid");
-    if (e->ns != NS || e->ngf != 0)
-        return lu_fail(&tmp, CMDG_ERR_UNSUPPORTED, "five prognostic states and no second-order terms (eband = 1) only");
-    if (e->NQV != 5 && e->NQV != 6)
-        return lu_fail(&tmp, CMDG_ERR_UNSUPPORTED, "vertical order not compiled in (have N = 4, 5)");
+    if ((e->ns != 5 && e->ns != 6) || e->ngf != 0)
+        return lu_fail(&tmp, CMDG_ERR_UNSUPPORTED,
+                       "five or six prognostic states and no second-order terms (eband = 1) only");
+    if (!compiled(e->NQV, e->ns)) return lu_fail(&tmp, CMDG_ERR_UNSUPPORTED, compiled_pairs);
     if (e->nreal % nvertelem != 0)
         return lu_fail(&tmp, CMDG_ERR_INVALID, "the real elements are not whole stacks");
     {
@@ -307,6 +319,8 @@ int cmdg_columnlu_create(cmdg_handle linear, int32_t nvertelem, double alpha, cm
     lu->nvert = nvertelem;
     lu->nqh2 = e->NQ * e->NQ;
     lu->nqv = e->NQV;
+    lu->ns = e->ns;
+    const int NS = lu->ns;
     lu->p = lu->q = lu->nqv * NS - 1;  // lower_bandwidth(N, nstate, eband = 1)
     lu->P = lu->p + lu->q + 1;
     lu->ncol = (e->nreal / nvertelem) * lu->nqh2;
@@ -318,9 +332,9 @@ int cmdg_columnlu_create(cmdg_handle linear, int32_t nvertelem, double alpha, cm
     if (!r && band + states + (64u << 20) > freeb) {
         char msg[256];
         snprintf(msg, sizeof msg,
-                 "the band needs %.3f GB (%lld columns x %lld rows x %d diagonals x 8 B) plus %.3f GB of "
-                 "probe states; %.3f GB of device memory are free",
-                 band / 1e9, (long long)lu->ncol, (long long)lu->n, lu->P, states / 1e9, freeb / 1e9);
+                 "the band needs %.3f GB (%lld columns x %lld rows (%d states) x %d diagonals x 8 B) plus "
+                 "%.3f GB of probe states; %.3f GB of device memory are free",
+                 band / 1e9, (long long)lu->ncol, (long long)lu->n, NS, lu->P, states / 1e9, freeb / 1e9);
         r = lu_fail(lu, CMDG_ERR_INVALID, msg);
     }
     if (!r) r = hip_ok(lu, hipMalloc(&lu->band, band), "hipMalloc(band)");
@@ -423,7 +437,11 @@ int cmdg_ark_step(cmdg_handle full, cmdg_columnlu_handle lu, double *Q, double *
     if (!full || !lu || !Q || !work || !rka_explicit || !rka_implicit || !rkb || !rkc) return CMDG_ERR_INVALID;
     if (nstages < 2 || nstages > 4) return lu_fail(lu, CMDG_ERR_INVALID, "ark: 2 to 4 stages");
     EngineBase *ef = full->eng, *el = lu->lin->eng;
-    if (ef->nreal != el->nreal || ef->Np != el->Np || ef->ns != NS)
+    if (ef->ns != lu->ns)
+        return lu_fail(lu, CMDG_ERR_INVALID,
+                       "ark: the full model has " + std::to_string(ef->ns) + " states, the linear model " +
+                           std::to_string(lu->ns) + "; they must be the same");
+    if (ef->nreal != el->nreal || ef->Np != el->Np)
         return lu_fail(lu, CMDG_ERR_INVALID, "ark: the full and the linear model live on different grids");
     DevGuard guard_(ef);
     const int ns = nstages;
@@ -433,7 +451,7 @@ int cmdg_ark_step(cmdg_handle full, cmdg_columnlu_handle lu, double *Q, double *
     for (int i = 1; i < ns; ++i) Qs[i] = work[i - 1];
     for (int i = 0; i < ns; ++i) R[i] = work[ns - 1 + i];
     double *Qhat = work[2 * ns - 1], *Qtt = work[2 * ns];
-    const int64_t len = ef->nreal * NS * ef->Np;
+    const int64_t len = ef->nreal * lu->ns * ef->Np;
     hipStream_t sf = ef->s_comp, sl = el->s_comp;
     // device tables: Qs (4), R (4), then per stage rkcoeff (4) and dt A (4), then b dt (4)
     double host[64] = {0};

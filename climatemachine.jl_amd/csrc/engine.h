@@ -684,5 +684,7 @@ int counts_se01(int32_t physics_id, int32_t out[6]);
 int counts_pgrad(const int32_t *iparam, int32_t out[6]);
 EngineBase *make_engine_atmos_linear(const cmdg_desc *d, std::string &err);
 int counts_atmos_linear(const int32_t *iparam, int32_t out[6]);
+EngineBase *make_engine_moist_linear(const cmdg_desc *d, std::string &err);
+int counts_moist_linear(const int32_t *iparam, int32_t out[6]);
 
 }  // namespace cmdg

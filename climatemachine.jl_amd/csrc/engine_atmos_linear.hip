@@ -1,7 +1,8 @@
 // Engine instantiations for AtmosAcousticGravityLinearModel (physics_atmos_linear.h).  The law
-// shares the full DryAtmosModel's auxiliary array, so the count comes from the full model's
+// shares the full model's auxiliary array.  Of the dry law the count comes from the full model's
 // parameter block: orientation and reference state are required, hyperdiffusion or
-// SmagorinskyLilly add one column each.
+// SmagorinskyLilly add one column each.  Of the moist LES law (CMDG_PHYSICS_MOIST_LINEAR_AG) it is
+// always MoistAtmos's 19, at the orders the moist law is compiled for.
 #include "engine.h"
 #include "physics_atmos_linear.h"
 
@@ -50,6 +51,35 @@ EngineBase *make_engine_atmos_linear(const cmdg_desc *d, std::string &err)
     case 5: return pick<6>(d, err);
     default:
         err = "AtmosAcousticGravityLinearModel: polynomial order not compiled in (have N = 4, 5)";
+        return nullptr;
+    }
+}
+
+int counts_moist_linear(const int32_t *, int32_t out[6])
+{
+    out[0] = 6;
+    out[1] = 19;
+    out[2] = out[3] = out[4] = out[5] = 0;
+    return CMDG_OK;
+}
+
+EngineBase *make_engine_moist_linear(const cmdg_desc *d, std::string &err)
+{
+    // moist.py descriptor(): iparam[4] marks NoOrientation + NoReferenceState
+    if (d->iparam[4] != 0) {
+        err = "AtmosAcousticGravityLinearModel needs a moist model with an orientation and a reference "
+              "state (this one has no_orientation)";
+        return nullptr;
+    }
+    if (d->nf_first != CMDG_RUSANOV && d->nf_first != CMDG_CENTRAL_FIRST_ORDER) {
+        err = "AtmosAcousticGravityLinearModel (EquilMoist): Rusanov or central first-order flux only";
+        return nullptr;
+    }
+    switch (d->N[0]) {
+    case 4: return make_engine<AtmosLinearAG<19, true>, 5>(d);
+    case 6: return make_engine<AtmosLinearAG<19, true>, 7>(d);
+    default:
+        err = "AtmosAcousticGravityLinearModel (EquilMoist): polynomial order not compiled in (have N = 4, 6)";
         return nullptr;
     }
 }

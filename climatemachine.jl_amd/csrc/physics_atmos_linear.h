@@ -1,16 +1,22 @@
-// Device functor for AtmosAcousticGravityLinearModel (dry), the linear balance law the reference's
-// IMEX configurations solve implicitly in the vertical.  Restates, term by term and in the
-// reference's summation order:
-//   src/Atmos/Model/linear.jl:17-55 (linearized_air_pressure, DryModel), :95-345 (state
+// Device functor for AtmosAcousticGravityLinearModel, the linear balance law the reference's
+// IMEX configurations solve implicitly in the vertical, of the dry law (MOIST = false) and of the
+// moist LES law with EquilMoist (MOIST = true).  Restates, term by term and in the reference's
+// summation order:
+//   src/Atmos/Model/linear.jl:17-72 (linearized_air_pressure, DryModel / EquilMoist), :95-345 (state
 //       layout shared with the full model, no second-order terms, wavespeed soundspeed(ref.T),
 //       AtmosBC boundary), linear_atmos_tendencies.jl (which terms),
 //   linear_tendencies.jl (Advect, LinearPressureGradient, LinearEnergyFlux, Gravity source).
-// The auxiliary array is the full DryAtmosModel's (Phi, grad Phi, reference state ...), shared
-// with it (DGModel(...; state_auxiliary = dg.state_auxiliary)): NAUX is the full model's count.
+// The auxiliary array is the full model's (Phi, grad Phi, reference state ...), shared with it
+// (DGModel(...; state_auxiliary = dg.state_auxiliary)): NAUX is the full model's count.  The moist
+// law's first 15 columns are the dry layout (MoistAtmosModel.init_state_auxiliary), so Phi and the
+// reference state sit in the same columns for both.
 //
-// Parameter block: the full model's (climatemachine.jl_amd/atmos.py); this law reads
-// dparam[2..6] R_d cp_d cv_d T_0 grav.  Boundaries: every tag is AtmosBC() (Impenetrable
-// FreeSlip, Insulating), boundary_conditions(::AtmosLinearModel) at linear.jl:215-216.
+// Parameter block: the full model's (climatemachine.jl_amd/atmos.py, moist.py); this law reads
+// dparam[2..6] R_d cp_d cv_d T_0 grav, and the moist one dparam[16] R_v, [20] LH_v0, [21] LH_s0.
+// Moist: the sixth state rho q_tot has no flux and no source (linear_atmos_tendencies.jl:17-23,
+// 34) and enters only p_lin.  Boundaries: every tag is AtmosBC() (Impenetrable FreeSlip,
+// Insulating; the plus side's rho q_tot is the minus side's), boundary_conditions(
+// ::AtmosLinearModel) at linear.jl:215-216.
 #pragma once
 #include "cmdg_common.h"
 
@@ -18,14 +24,16 @@ namespace cmdg {
 
 struct AtmosLinearParams {
     double R_d, cp_d, cv_d, T_0;
+    double e_int_v0, e_int_i0;  // EquilMoist only
 };
 
-template <int NAUX_FULL>
+template <int NAUX_FULL, bool MOIST = false>
 struct AtmosLinearAG {
     using Params = AtmosLinearParams;
-    // auxiliary layout of DryAtmos with orientation and reference state (physics_atmos.h)
+    // auxiliary layout of DryAtmos with orientation and reference state (physics_atmos.h), which
+    // MoistAtmos keeps in its first 15 columns (physics_moist.h)
     static constexpr int OPHI = 3, OREF = 7;
-    static constexpr int NS = 5, NAUX = NAUX_FULL, NGRAD = 0, NGF = 0, NGL = 0, NHYP = 0;
+    static constexpr int NS = MOIST ? 6 : 5, NAUX = NAUX_FULL, NGRAD = 0, NGF = 0, NGL = 0, NHYP = 0;
     static constexpr bool HAS_UPDATE_AUX = false, FUSE_UPDATE_AUX = false, HAS_SOURCE = true;
     static constexpr bool HAS_COURANT = false, HAS_PENALTY = false;
     static constexpr int NUPD = 0, NDER = 0;
@@ -41,12 +49,20 @@ struct AtmosLinearAG {
         p.cp_d = dp[3];
         p.cv_d = dp[4];
         p.T_0 = dp[5];
+        // e_int_v0 = LH_v0 - R_v T_0, e_int_i0 = LH_s0 - LH_v0 (physics_moist.h)
+        p.e_int_v0 = MOIST ? dp[20] - dp[16] * dp[5] : 0.0;
+        p.e_int_i0 = MOIST ? dp[21] - dp[20] : 0.0;
     }
-    // linearized_air_pressure (linear.jl:17-36) for DryModel: the moisture terms are zeros
+    // linearized_air_pressure (linear.jl:17-36): DryModel passes no moisture terms; EquilMoist
+    // (:57-72) passes rho q_tot, with rho q_liq = rho q_ice = 0 kept in the reference's order
     __device__ static double p_lin(const Params &m, const double *Q, const double *aux)
     {
         const double rhoe_pot = Q[0] * aux[OPHI];
-        return Q[0] * m.R_d * m.T_0 + m.R_d / m.cv_d * (Q[4] - rhoe_pot);
+        if constexpr (MOIST)
+            return Q[0] * m.R_d * m.T_0 +
+                   m.R_d / m.cv_d * (Q[4] - rhoe_pot - (Q[5] - 0.0) * m.e_int_v0 + 0.0 * (m.e_int_i0 + m.e_int_v0));
+        else
+            return Q[0] * m.R_d * m.T_0 + m.R_d / m.cv_d * (Q[4] - rhoe_pot);
     }
     __device__ static double soundspeed(const Params &m, double T)
     {
@@ -78,6 +94,7 @@ struct AtmosLinearAG {
     {
         S[0] = 0;
         S[4] = 0;
+        if constexpr (MOIST) S[5] = 0;
 #pragma unroll
         for (int d = 0; d < 3; ++d) S[1 + d] = direction == DIR_HORIZONTAL ? 0.0 : -Q[0] * aux[OPHI + 1 + d];
     }
@@ -100,14 +117,15 @@ struct AtmosLinearAG {
     {
         const double c = soundspeed(m, aux[OREF + 2]);
 #pragma unroll
-        for (int s = 0; s < 5; ++s) ws[s] = c;
+        for (int s = 0; s < NS; ++s) ws[s] = c;
     }
     __device__ static void update_penalty(const Params &, double *, const double *, const double *,
                                           const double *)
     {
     }
     // atmos_boundary_state! of AtmosBC(): Impenetrable(FreeSlip) reflects the normal momentum,
-    // Insulating leaves the energy; the plus-side auxiliary state is the minus side's
+    // Insulating leaves the energy, rho q_tot passes through; the plus-side auxiliary state is the
+    // minus side's
     __device__ static void boundary_state(const Params &, int, int, double *QP, double *,
                                           const double *n, const double *QM, const double *,
                                           double, const double *, const double *)

@@ -251,6 +251,7 @@ class MoistAtmosModel:
         ps = self.ps
         ip = np.zeros(16, dtype=np.int32)
         ip[0], ip[1], ip[2], ip[3] = self.closure, int(self.subtract_off), int(self.kinematic), self.maxiter
+        ip[4] = int(self.no_orientation)    # read by the linear law only (it refuses such a model)
         ip[5], ip[6] = self.sources, len(self.boundary_conditions)
         for i, bc in enumerate(self.boundary_conditions):
             ip[7 + i] = bc

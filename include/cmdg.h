@@ -73,7 +73,11 @@ enum {
     CMDG_PHYSICS_BAROTROPIC_SE01 = 9,
     /* AtmosAcousticGravityLinearModel of the dry AtmosModel (src/Atmos/Model/linear.jl), on the
      * full model's parameter block and auxiliary array (orientation + reference state) */
-    CMDG_PHYSICS_ATMOS_LINEAR_AG = 10
+    CMDG_PHYSICS_ATMOS_LINEAR_AG = 10,
+    /* AtmosAcousticGravityLinearModel of the moist AtmosModel (EquilMoist, linear.jl:57-72): six
+     * states, on the full CMDG_PHYSICS_MOIST_ATMOS model's parameter block and 19-column
+     * auxiliary array; N = 4, 6; Rusanov or central first-order flux */
+    CMDG_PHYSICS_MOIST_LINEAR_AG = 11
 };
 
 /* Construction record: the fields of `DGModel(balance_law, grid, nf1, nf2, nfgrad;
@@ -669,8 +673,9 @@ int cmdg_profile_reset(cmdg_handle h);
 
 /* ---- ManyColumnLU and the IMEX step (columnwise_lu_solver.jl, AdditiveRungeKuttaMethod.jl) ----
  * A column solver owns the banded matrix I - alpha L of every column of a VerticalDirection DG
- * model `linear` on a stacked grid (CMDG_PHYSICS_ATMOS_LINEAR_AG; eband = 1, bandwidths
- * p = q = Nq_v nstate - 1).  A column is one horizontal node of one stack of `nvertelem` elements;
+ * model `linear` on a stacked grid (CMDG_PHYSICS_ATMOS_LINEAR_AG with nstate = 5 or
+ * CMDG_PHYSICS_MOIST_LINEAR_AG with nstate = 6; eband = 1, bandwidths p = q = Nq_v nstate - 1;
+ * compiled for (N, nstate) = (4, 5), (5, 5), (4, 6), (6, 6)).  A column is one horizontal node of one stack of `nvertelem` elements;
  * the real elements must be whole stacks, bottom first.  Every stack must end in boundary faces:
  * a vertically periodic stack (no boundary face at the bottom of its first or the top of its last
  * element) is refused with CMDG_ERR_UNSUPPORTED, since the band cannot hold the coupling of its
@@ -686,7 +691,7 @@ int cmdg_columnlu_create(cmdg_handle linear, int32_t nvertelem, double alpha, cm
 int cmdg_columnlu_update(cmdg_columnlu_handle lu, double alpha);
 /* assemble I - alpha L only, unfactored (for cmdg_columnlu_export_band; a solve then refuses) */
 int cmdg_columnlu_assemble(cmdg_columnlu_handle lu, double alpha);
-/* Q = (I - alpha L)^-1 Qrhs, both (Np, 5, nelem) device arrays, real elements; Q may be Qrhs */
+/* Q = (I - alpha L)^-1 Qrhs, both (Np, nstate, nelem) device arrays, real elements; Q may be Qrhs */
 int cmdg_columnlu_solve(cmdg_columnlu_handle lu, double *Q, const double *Qrhs);
 /* out[8] = n, p, q, ncol, band bytes, state (1 assembled, 2 factored), nvertelem, Nq_v */
 int cmdg_columnlu_info(cmdg_columnlu_handle lu, int64_t *out);
@@ -703,7 +708,8 @@ int cmdg_columnlu_destroy(cmdg_columnlu_handle lu);
  * (0, c, ..., c).  work: 2 nstages + 1 device state arrays shaped like Q (Qstages[2..], Rstages,
  * Qhat, Qtt).  split_explicit_implicit != 0: the explicit operator is full minus linear,
  * evaluated as `full` followed by `linear` with alpha = -1 and increment.  The solver is refactored
- * when dt a_ii differs from its alpha.  Returns after the step has finished. */
+ * when dt a_ii differs from its alpha.  `full` and `linear` must have the same state count
+ * (CMDG_ERR_INVALID otherwise).  Returns after the step has finished. */
 int cmdg_ark_step(cmdg_handle full, cmdg_columnlu_handle lu, double *Q, double *const *work, double t,
                   double dt, int32_t nstages, const double *rka_explicit, const double *rka_implicit,
                   const double *rkb, const double *rkc, int32_t split_explicit_implicit);

@@ -99,6 +99,18 @@ class CmdgOceanCouplingDesc(C.Structure):
     ]
 
 
+MRI_MAXR, MRI_MAXGAMMA = 6, 4
+MRIGARK_EXPLICIT, MRIGARK_DECOUPLED_IMPLICIT = 0, 1
+
+
+class CmdgMrigarkDesc(C.Structure):
+    """``cmdg_mrigark_desc`` of include/cmdg.h."""
+    _fields_ = [("kind", C.c_int32), ("nstages", C.c_int32), ("ngamma", C.c_int32),
+                ("gamma", C.c_void_p), ("dc", C.c_void_p), ("fast_nstages", C.c_int32),
+                ("fast_rka", C.c_void_p), ("fast_rkb", C.c_void_p), ("fast_rkc", C.c_void_p),
+                ("fast_dt", C.c_double), ("lu_adjustable", C.c_int32)]
+
+
 RED_WEIGHTEDSUM, RED_SUM, RED_DOT, RED_DISTANCE, RED_NORM, RED_MAX, RED_MIN = range(7)
 
 
@@ -180,6 +192,9 @@ SYMBOLS = [
     ("cmdg_columnlu_export_band", C.c_int, [_vp, _i64, _vp]),
     ("cmdg_columnlu_destroy", C.c_int, [_vp]),
     ("cmdg_ark_step", C.c_int, [_vp, _vp, _vp, _vp, _d, _d, _i32, _vp, _vp, _vp, _vp, _i32]),
+    ("cmdg_mri_lsrk_update", C.c_int, [_vp, _vp, _vp, _d, _d, _i32, _vp, _vp]),
+    ("cmdg_mri_qhat", C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp]),
+    ("cmdg_mrigark_step", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d]),
 ]
 
 _LIB = None

@@ -165,6 +165,27 @@ GroupCall::GroupCall(cmdg_handle *h, cmdg_handle *h2, int n, bool pairs)
     dev.emplace(h[0]->eng);
 }
 
+GroupCall::GroupCall(const std::vector<std::pair<cmdg_handle, std::string>> &named)
+{
+    if (named.empty()) return;
+    for (auto &m : named)
+        if (!m.first) return;
+    for (auto &m : named) {
+        bool merged = false;
+        for (auto &have : members)
+            if (have.first == m.first) {
+                have.second = have.second.substr(0, have.second.size() - 2) + " / " + m.second + ": ";
+                merged = true;
+            }
+        if (!merged) members.push_back({m.first, m.second + ": "});
+    }
+    for (auto &m : members) {
+        if (m.first->eng->worker) m.first->eng->worker->wait_idle();
+        m.first->eng->err.clear();
+    }
+    dev.emplace(named[0].first->eng);
+}
+
 int GroupCall::finish(int rc)
 {
     if (rc == CMDG_OK) return rc;

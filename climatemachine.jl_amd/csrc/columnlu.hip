@@ -281,6 +281,25 @@ int solve(cmdg_columnlu *lu, double *X, const double *B)
 
 }  // namespace
 
+namespace cmdg {
+// for cmdg_mrigark_step (multirate.hip): enqueued on the linear handle's stream, errors also on
+// its engine (where GroupCall::finish looks)
+cmdg_handle columnlu_linear(cmdg_columnlu_handle lu) { return lu->lin; }
+double columnlu_alpha(cmdg_columnlu_handle lu) { return lu->state == 2 ? lu->alpha : NAN; }
+int columnlu_refactor_async(cmdg_columnlu_handle lu, double alpha)
+{
+    const int r = update(lu, alpha);
+    if (r) lu->lin->eng->err = lu->lin->err;
+    return r;
+}
+int columnlu_solve_async(cmdg_columnlu_handle lu, double *X, const double *B)
+{
+    const int r = solve(lu, X, B);
+    if (r) lu->lin->eng->err = lu->lin->err;
+    return r;
+}
+}  // namespace cmdg
+
 extern "C" {
 
 int cmdg_columnlu_create(cmdg_handle linear, int32_t nvertelem, double alpha, cmdg_columnlu_handle *out)

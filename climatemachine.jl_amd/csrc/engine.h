@@ -470,6 +470,9 @@ struct DevGuard {
 struct GroupCall {
     GroupCall(cmdg_handle *handles, int n) : GroupCall(handles, nullptr, n, false) {}
     GroupCall(cmdg_handle *slow, cmdg_handle *fast, int n) : GroupCall(slow, fast, n, true) {}
+    // members with a role each ("slow", "fast", ...); a handle named twice is one member whose
+    // message prefix carries both roles
+    explicit GroupCall(const std::vector<std::pair<cmdg_handle, std::string>> &named);
     bool ok() const { return !members.empty(); }
     int finish(int rc);
 

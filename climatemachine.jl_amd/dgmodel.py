@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from .balancelaws import EveryDirection, RusanovNumericalFlux
 
-__all__ = ["DGModel", "connect_local", "group_rhs", "group_lsrk_run", "group_halo",
+__all__ = ["DGModel", "RemainderDGModel", "remainder_DGModel", "connect_local", "group_rhs", "group_lsrk_run", "group_halo",
            "reference_pressure_gradient", "rccl_unique_id",
            "ADVECTIVE_COURANT", "NONDIFFUSIVE_COURANT", "DIFFUSIVE_COURANT"]
 
@@ -389,6 +389,66 @@ class DGModel:
                                            C.cast(C.byref(ms), C.c_void_p),
                                            C.cast(C.byref(n), C.c_void_p)), self.handle)
         return ms.value, n.value
+
+
+class RemainderDGModel:
+    """``remainder_DGModel(dg, (lin,))`` (src/Numerics/DGMethods/remainder.jl): the operator
+    ``dg - lin`` for the multirate solvers, as their slow or their fast operator.
+
+    It is evaluated as ``cmdg_ark_step`` evaluates its split form: ``dg`` first, then ``lin`` with
+    alpha = -1 and increment.  The reference evaluates the remainder in one fused ``RemBL`` kernel
+    that subtracts flux by flux; the two agree up to rounding (the summation order differs)."""
+
+    def __init__(self, dg, lin):
+        self.dg, self.lin = dg, lin
+        self.grid, self.balance_law, self.device, self.L = dg.grid, dg.balance_law, dg.device, dg.L
+        self.state_auxiliary = dg.state_auxiliary
+
+    @property
+    def handle(self):
+        return self.dg.handle
+
+    def create_state(self, nstate=None):
+        return self.dg.create_state(nstate)
+
+    def __call__(self, tendency, Q, t, alpha=1.0, beta=0.0, increment=None):
+        """``tendency = alpha (dg - lin)(Q) + beta tendency`` as two evaluations."""
+        if increment is not None:
+            alpha, beta = 1.0, float(bool(increment))
+        self.dg(tendency, Q, t, alpha, beta)
+        self.lin(tendency, Q, t, -alpha, 1.0)
+
+    def synchronize(self):
+        self.dg.synchronize()
+        self.lin.synchronize()
+
+    def _torch_ready(self):
+        self.dg._torch_ready()
+
+    def lsrk_run(self, *args, **kw):
+        raise _lib.CmdgError("a remainder model is stepped only as an operator of the multirate "
+                             "solvers (odesolvers.MRIGARKExplicit / MRIGARKDecoupledImplicit)")
+
+
+def remainder_DGModel(dg, subtract):
+    """``remainder_DGModel(dg, (lin,))``: exactly one subtracted model, a ``DGModel`` on the same
+    grid, with the same state count and the same auxiliary array as ``dg``."""
+    subtract = tuple(subtract)
+    if len(subtract) != 1:
+        raise _lib.CmdgError("remainder_DGModel: exactly one subtracted model is supported, not %d"
+                             % len(subtract))
+    lin = subtract[0]
+    if not isinstance(dg, DGModel) or not isinstance(lin, DGModel):
+        raise _lib.CmdgError("remainder_DGModel: the main and the subtracted model must be DGModels")
+    if lin.grid is not dg.grid:
+        raise _lib.CmdgError("remainder_DGModel: the subtracted model lives on another grid")
+    if lin.balance_law.ns != dg.balance_law.ns:
+        raise _lib.CmdgError("remainder_DGModel: the subtracted model has %d states, the main model %d"
+                             % (lin.balance_law.ns, dg.balance_law.ns))
+    if lin.state_auxiliary.data_ptr() != dg.state_auxiliary.data_ptr():
+        raise _lib.CmdgError("remainder_DGModel: the subtracted model must share the main model's "
+                             "auxiliary state (state_auxiliary = dg.state_auxiliary)")
+    return RemainderDGModel(dg, lin)
 
 
 def reference_pressure_gradient(grid, p, device="cuda:0"):

@@ -22,7 +22,11 @@ __all__ = ["LSRK54CarpenterKennedy", "LSRK144NiegemannDiehlBusch", "solve",
            "SSPRK22Heuns", "SSPRK22Ralstons", "SSPRK33ShuOsher", "SSPRK34SpiteriRuuth",
            "SSPRK_COEFFICIENTS", "LowStorageRungeKutta3N", "LS3NRK44Classic", "LS3NRK33Heuns",
            "LS3N_COEFFICIENTS", "AdditiveRungeKutta", "ARK2GiraldoKellyConstantinescu",
-           "ark2gkc_tableau", "LinearBackwardEulerSolver", "ManyColumnLU"]
+           "ark2gkc_tableau", "LinearBackwardEulerSolver", "ManyColumnLU", "MRIGARKExplicit",
+           "MRIGARKDecoupledImplicit", "MRIGARKERK33aSandu", "MRIGARKERK45aSandu",
+           "MRIGARKIRK21aSandu", "MRIGARKESDIRK23LSA", "MRIGARKESDIRK24LSA", "MRIGARKESDIRK34aSandu",
+           "MRIGARKESDIRK46aSandu", "MRIGARK_TABLEAUS", "mrigark_explicit_coefficients",
+           "mrigark_implicit_coefficients"]
 
 
 def _f(num, den):
@@ -190,14 +194,19 @@ LS3NRK44Classic, LS3NRK33Heuns = _ls3n("LS3NRK44Classic"), _ls3n("LS3NRK33Heuns"
 class LinearBackwardEulerSolver:
     """``LinearBackwardEulerSolver(solver; isadjustable = true)`` (BackwardEulerSolvers.jl:108-190):
     solves ``Q = Qhat + alpha L(Q)`` with a direct column solver, refactored whenever alpha
-    changes."""
+    changes.  With ``isadjustable = False`` the solver keeps the alpha it was first factored
+    for: a solve or ``updatedt`` that needs another alpha is refused (the reference's
+    ``@assert lin.isadjustable``)."""
 
     def __init__(self, solver, isadjustable=True):
         if not isinstance(solver, ManyColumnLU):
             raise TypeError("LinearBackwardEulerSolver: only ManyColumnLU() is implemented")
-        if not isadjustable:
-            raise ValueError("LinearBackwardEulerSolver: isadjustable = false is not implemented")
-        self.solver, self.isadjustable = solver, True
+        self.solver, self.isadjustable = solver, bool(isadjustable)
+
+
+def _refuse_alpha(lu, alpha):
+    raise ValueError("LinearBackwardEulerSolver(isadjustable = false) was factored for alpha = %r; "
+                     "alpha = %r would need a refactorisation" % (lu.alpha, alpha))
 
 
 def ark2gkc_tableau(paperversion=False):
@@ -244,15 +253,22 @@ class AdditiveRungeKutta:
         self.dt, self.t, self.steps = float(dt), t0, 0
         self.work = [dg.create_state(Q.shape[1]) for _ in range(2 * ns + 1)]
         self._ptrs = (C.c_void_p * len(self.work))(*[w.data_ptr() for w in self.work])
+        self.isadjustable = backward_euler_solver.isadjustable
+        self._diag = diag[1]
         self.lu = ColumnLU(linear_dg, self.dt * diag[1])
 
     def updatedt(self, dt):
-        """``updatedt!``: the next stage refactors the column matrices for ``dt a_ii``."""
+        """``updatedt!``: the next stage refactors the column matrices for ``dt a_ii`` (refused
+        when the solver is not adjustable and ``dt a_ii`` changes)."""
+        if not self.isadjustable and float(dt) * self._diag != self.lu.alpha:
+            _refuse_alpha(self.lu, float(dt) * self._diag)
         self.dt = float(dt)
 
     def dostep(self, Q, nsteps=1, dt=None):
         from . import _lib
         dt = self.dt if dt is None else dt
+        if not self.isadjustable and dt * self._diag != self.lu.alpha:
+            _refuse_alpha(self.lu, dt * self._diag)
         p = lambda a: C.c_void_p(a.ctypes.data)
         self.dg._torch_ready()
         for _ in range(int(nsteps)):
@@ -276,6 +292,376 @@ def ARK2GiraldoKellyConstantinescu(dg, linear_dg, backward_euler_solver, Q, dt=N
     return AdditiveRungeKutta(dg, linear_dg, backward_euler_solver, A_e, A_i, B, Cc, Q, dt=dt,
                               t0=t0, split_explicit_implicit=split_explicit_implicit)
 
+
+# -- multirate infinitesimal GARK (Sandu 2019) ----------------------------------------------------
+# MultirateInfinitesimalGARKExplicit.jl and MultirateInfinitesimalGARKDecoupledImplicit.jl.  The
+# rational tables are exact (Fraction) until the reference converts them to Float64; the tables
+# the reference builds in Float64 arithmetic are built here in the same operation order.
+
+def _rt(rows):
+    """Rows of ``"num/den"`` strings (``"0"`` for zero) as Fractions."""
+    return [[Fraction(x) for x in r.split()] for r in rows]
+
+
+def _isapprox(a, b, rtol=math.sqrt(2.0 ** -52), atol=0.0):
+    """Julia's ``isapprox`` (default rtol sqrt(eps)), on scalars or on arrays through the norm."""
+    import numpy as np
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    d = float(np.linalg.norm((a - b).ravel()))
+    return d <= max(atol, rtol * max(float(np.linalg.norm(a.ravel())), float(np.linalg.norm(b.ravel()))))
+
+
+def _erk33a(delta=Fraction(-1, 2)):
+    d = delta
+    G0 = [[Fraction(1, 3), Fraction(0), Fraction(0)],
+          [(-6 * d - 7) / 12, (6 * d + 11) / 12, Fraction(0)],
+          [Fraction(0), (6 * d - 5) / 12, (3 - 2 * d) / 4]]
+    G1 = [[Fraction(0)] * 3,
+          [(2 * d + 1) / 2, -(2 * d + 1) / 2, Fraction(0)],
+          [Fraction(1, 2), -(2 * d + 1) / 2, d]]
+    return (G0, G1), ([Fraction(1, 12), Fraction(-1, 3), Fraction(7, 12)], [Fraction(0)] * 3)
+
+
+def _erk45a():
+    G0 = _rt(["1/5 0 0 0 0", "-53/16 281/80 0 0 0",
+              "-36562993/71394880 34903117/17848720 -88770499/71394880 0 0",
+              "-7631593/71394880 -166232021/35697440 6068517/1519040 8644289/8924360 0",
+              "277061/303808 -209323/1139280 -1360217/1139280 -148789/56964 147889/45120"])
+    G1 = _rt(["0 0 0 0 0", "503/80 -503/80 0 0 0",
+              "-1365537/35697440 4963773/7139488 -1465833/2231090 0 0",
+              "66974357/35697440 21445367/7139488 -3 -8388609/4462180 0",
+              "-18227/7520 2 1 5 -41933/7520"])
+    g0 = _rt(["-1482837/759520 175781/71205 -790577/1139280 -6379/56964 47/96"])[0]
+    g1 = _rt(["6213/1880 -6213/1880 0 0 0"])[0]
+    return (G0, G1), (g0, g1)
+
+
+def _irk21a():
+    return (_rt(["1 0", "-1/2 1/2"]),), (_rt(["-1/2 1/2"])[0],)
+
+
+def _esdirk_lambda():
+    """``λ`` of ESDIRK34a / ESDIRK46a, with the reference's check of its cubic."""
+    mu = math.atan(1 / (2 * math.sqrt(2.0))) / 3            # acot(2 sqrt(2)) / 3
+    lam = 1 - math.cos(mu) / math.sqrt(2.0) + math.sqrt(1.5) * math.sin(mu)
+    assert _isapprox(-1 + 9 * lam - 18 * (lam * lam) + 6 * (lam * lam * lam), 0, atol=2 * 2.0 ** -52)
+    return lam
+
+
+def _esdirk34a():
+    lam = _esdirk_lambda()
+    l2 = lam * lam
+    G0 = [[float(Fraction(1, 3)), 0.0, 0.0, 0.0],
+          [-lam, lam, 0.0, 0.0],
+          [(3 - 10 * lam) / (24 * lam - 6), (5 - 18 * lam) / (6 - 24 * lam), 0.0, 0.0],
+          [(-24 * l2 + 6 * lam + 1) / (6 - 24 * lam), (-48 * l2 + 12 * lam + 1) / (24 * lam - 6), lam, 0.0],
+          [(3 - 16 * lam) / (12 - 48 * lam), (48 * l2 - 21 * lam + 2) / (12 * lam - 3), (3 - 16 * lam) / 4, 0.0],
+          [-lam, 0.0, 0.0, lam]]
+    return (G0,), ([0.0] * 4,)
+
+
+def _esdirk46a():
+    _esdirk_lambda()
+    G0 = _rt(["1/5 0 0 0 0 0", "-1/4 1/4 0 0 0 0",
+              "1771023115159/1929363690800 -1385150376999/1929363690800 0 0 0 0",
+              "914009/345800 -1000459/345800 1/4 0 0 0",
+              "18386293581909/36657910125200 5506531089/80566835440 -178423463189/482340922700 0 0 0",
+              "36036097/8299200 4621/118560 -38434367/8299200 1/4 0 0",
+              "-247809665162987/146631640500800 10604946373579/14663164050080 "
+              "10838126175385/5865265620032 -24966656214317/36657910125200 0 0",
+              "38519701/11618880 10517363/9682400 -23284701/19364800 -10018609/2904720 1/4 0",
+              "-52907807977903/33838070884800 74846944529257/73315820250400 "
+              "365022522318171/146631640500800 -20513210406809/109973730375600 "
+              "-2918009798/1870301537 0",
+              "19/100 -73/300 127/300 127/300 -313/300 1/4"])
+    G1 = _rt(["0 0 0 0 0 0", "0 0 0 0 0 0",
+              "-1674554930619/964681845400 1674554930619/964681845400 0 0 0 0",
+              "-1007739/172900 1007739/172900 0 0 0 0",
+              "-8450070574289/18328955062600 -39429409169/40283417720 173621393067/120585230675 0 0 0",
+              "-122894383/16598400 14501/237120 121879313/16598400 0 0 0",
+              "32410002731287/15434909526400 -46499276605921/29326328100160 "
+              "-34914135774643/11730531240064 45128506783177/18328955062600 0 0",
+              "-128357303/23237760 -35433927/19364800 71038479/38729600 8015933/1452360 0 0",
+              "136721604296777/67676141769600 -349632444539303/146631640500800 "
+              "-1292744859249609/293263281001600 8356250416309/54986865187800 "
+              "17282943803/3740603074 0",
+              "3/25 -29/300 71/300 71/300 -149/300 0"])
+    g0 = _rt(["-1/4 5595/8804 -2445/8804 -4225/8804 2205/4402 -567/4402"])[0]
+    return (G0, G1), (g0, [Fraction(0)] * 6)
+
+
+def _esdirk23lsa(delta=0):
+    rt2 = math.sqrt(2.0)
+    d = delta
+    G0 = [[2 - rt2, 0.0, 0.0],
+          [(1 - rt2) / rt2, (rt2 - 1) / rt2, 0.0],
+          [float(d), rt2 - 1 - d, 0.0],
+          [(3 - (2 * rt2) * (1 + d)) / (2 * rt2), (d * (2 * rt2) - 1) / (2 * rt2), (rt2 - 1) / rt2]]
+    dc = [sum(r) for r in G0]
+    assert _isapprox(G0[0][0], dc[0]) and _isapprox(G0[2][0] + G0[2][1], dc[2])
+    assert _isapprox(G0[1][0] + G0[1][1], 0, atol=2.0 ** -52)
+    assert _isapprox(G0[3][0] + G0[3][1] + G0[3][2], 0, atol=2.0 ** -52)
+    assert _isapprox(G0[0][0] + G0[1][0], 1 - 1 / rt2) and _isapprox(G0[1][1], 1 - 1 / rt2)
+    assert _isapprox(G0[0][0] + G0[1][0] + G0[2][0] + G0[3][0], 1 / (2 * rt2))
+    assert _isapprox(G0[1][1] + G0[2][1] + G0[3][1], 1 / (2 * rt2))
+    assert _isapprox(G0[3][2], 1 - 1 / rt2)
+    return (G0,), ([0.0] * 3,)
+
+
+def esdirk24lsa_base(gamma=0.2, c3=None, a32=0.2, alpha=-0.1, beta1=None, beta2=None):
+    """The L-stable, stiffly accurate ESDIRK behind ``MRIGARKESDIRK24LSA`` and its GARK table:
+    ``(A, Δc, Γ0)``, with the reference's checks."""
+    import numpy as np
+    g = gamma
+    c3 = (2 * g + 1) / 2 if c3 is None else c3
+    beta1 = c3 / 10 if beta1 is None else beta1
+    beta2 = c3 / 10 if beta2 is None else beta2
+    # L-stability (Kennedy and Carpenter 2016, Table 5) and increasing stage times
+    if not (0.1804253064293985641345831 <= g < 0.5):
+        raise ValueError("MRIGARKESDIRK24LSA: gamma must lie in [0.18042530642939856, 1/2)")
+    if not (2 * g < c3 < 1):
+        raise ValueError("MRIGARKESDIRK24LSA: 2 gamma < c3 < 1 is needed")
+    b3 = (2 * ((1 - g) * (1 - g)) - 1) / 4 / a32
+    b2 = (1 - 2 * g - 2 * b3 * c3) / (4 * g)
+    A = [[0.0, 0.0, 0.0, 0.0], [g, g, 0.0, 0.0], [c3 - a32 - g, a32, g, 0.0],
+         [1 - b2 - b3 - g, b2, b3, g]]
+    c = [sum(r) for r in A]
+    b = A[-1]
+    assert _isapprox(sum(b), 1)
+    assert _isapprox(2 * sum(float(np.dot(np.asarray(A).T[i], b)) for i in range(4)), 1)
+    dc = [c[1], 0.0, c[2] - c[1], 0.0, c[3] - c[2], 0.0]
+    G = [[0.0] * 4 for _ in range(6)]
+    G[0][0] = dc[0]
+    G[1][0] = A[1][0] - G[0][0]
+    G[1][1] = A[1][1]
+    G[2][0] = alpha
+    G[2][1] = dc[2] - G[2][0]
+    G[3][0] = A[2][0] - G[0][0] - G[1][0] - G[2][0]
+    G[3][1] = A[2][1] - G[0][1] - G[1][1] - G[2][1]
+    G[3][2] = A[2][2]
+    G[4][0] = beta1
+    G[4][1] = beta2
+    G[4][2] = dc[4] - G[4][0] - G[4][1]
+    for j in range(3):
+        G[5][j] = A[3][j] - G[0][j] - G[1][j] - G[2][j] - G[3][j] - G[4][j]
+    G[5][3] = A[3][3]
+    acc = np.cumsum(np.asarray(G), axis=0)
+    assert _isapprox(A, np.vstack([np.zeros((1, 4)), acc[1::2]]))
+    assert _isapprox(dc, [sum(r) for r in G])
+    return A, dc, G
+
+
+def _esdirk24lsa(**kw):
+    _, _, G0 = esdirk24lsa_base(**kw)
+    return (G0,), ([0.0] * 4,)
+
+
+# name -> (kind, raw table builder): the Γ and γ̂ as the reference passes them to the solver
+MRIGARK_TABLEAUS = {
+    "MRIGARKERK33aSandu": ("explicit", _erk33a),
+    "MRIGARKERK45aSandu": ("explicit", _erk45a),
+    "MRIGARKIRK21aSandu": ("implicit", _irk21a),
+    "MRIGARKESDIRK23LSA": ("implicit", _esdirk23lsa),
+    "MRIGARKESDIRK24LSA": ("implicit", _esdirk24lsa),
+    "MRIGARKESDIRK34aSandu": ("implicit", _esdirk34a),
+    "MRIGARKESDIRK46aSandu": ("implicit", _esdirk46a),
+}
+
+
+def _rowsum(row):
+    s = 0
+    for x in row:
+        s = s + x
+    return s
+
+
+def mrigark_explicit_coefficients(Gs, ghats):
+    """``MRIGARKExplicit``'s constructor: ``Δc = rowsum(Γ_0)``, ``Γ_k ./ Δc`` and ``γ̂_k / Δc[end]``
+    (exact when the tables are rational), then Float64.  Returns ``(Γs, γ̂s, Δc)`` as numpy
+    arrays."""
+    import numpy as np
+    dc = [_rowsum(r) for r in Gs[0]]
+    G = np.array([[[float(x / dc[i]) for x in row] for i, row in enumerate(Gk)] for Gk in Gs])
+    gh = np.array([[float(x / dc[-1]) for x in g] for g in ghats])
+    return G, gh, np.array([float(x) for x in dc])
+
+
+def mrigark_implicit_coefficients(Gs, ghats):
+    """``MRIGARKDecoupledImplicit``'s constructor: ``Δc = rowsum(Γ_0)`` (exact when rational), the
+    even rows' sums 0 to ``2 eps``, the odd rows' kept; ``Γ_k`` and ``γ̂_k`` as given, in Float64.
+    Returns ``(Γs, γ̂s, Δc)`` as numpy arrays."""
+    import numpy as np
+    dc = [float(_rowsum(r)) for r in Gs[0]]
+    if not all(abs(x) <= 2 * 2.0 ** -52 for x in dc[1::2]):
+        raise ValueError("MRIGARKDecoupledImplicit: the implicit rows of Gamma_0 must sum to 0")
+    dc = dc[0:len(dc) - 1:2]
+    ns = len(dc)
+    if not (ns == len(Gs[0][0]) - 1 and ns == len(Gs[0]) // 2):
+        raise ValueError("MRIGARKDecoupledImplicit: Gamma must be (2 nstages, nstages + 1)")
+    G = np.array([[[float(x) for x in row] for row in Gk] for Gk in Gs])
+    gh = np.array([[float(x) for x in g] for g in ghats])
+    return G, gh, np.array(dc)
+
+
+def _operator(op):
+    """(handle, subtracted handle or None, the DGModel that owns the device) of a solver operator:
+    a DGModel or a ``dgmodel.RemainderDGModel``."""
+    from .dgmodel import RemainderDGModel
+    if isinstance(op, RemainderDGModel):
+        return op.dg.handle, op.lin.handle, op.dg
+    return op.handle, None, op
+
+
+def _fast_solver(fastsolver, who):
+    if isinstance(fastsolver, (MRIGARKExplicit, MRIGARKDecoupledImplicit)):
+        raise TypeError("%s: nested (three-rate) MRI is not supported" % who)
+    if not isinstance(fastsolver, LowStorageRungeKutta2N):
+        raise TypeError("%s: the fast solver must be a LowStorageRungeKutta2N (LSRK54CarpenterKennedy "
+                        "or LSRK144NiegemannDiehlBusch), not %s" % (who, type(fastsolver).__name__))
+    if len(fastsolver.RKA) > 14:
+        raise ValueError("%s: fast 2N tableaus of at most 14 stages are supported" % who)
+    return fastsolver
+
+
+class _MRIGARK:
+    """What the two MRI-GARK kinds share: the descriptor of ``cmdg_mrigark_step`` and ``dostep``."""
+
+    KIND = None
+
+    def _setup(self, slow_rhs, fastsolver, G, gh, dc, Q, dt, t0, lu=None, adjustable=True):
+        import numpy as np
+        from . import _lib
+        self.slow_rhs, self.fastsolver = slow_rhs, fastsolver
+        self.Gammas, self.gammahats, self.dc = G, gh, dc
+        self.dt, self.t, self.steps = float(dt), float(t0), 0
+        self._slow = _operator(slow_rhs)
+        self._fast = _operator(fastsolver.dg)
+        self.dg = self._slow[2]
+        ns = len(dc)
+        self.Rstages = [self.dg.create_state(Q.shape[1]) for _ in range(ns)]
+        self.Qhat = self.dg.create_state(Q.shape[1]) if self.KIND == 1 else None
+        ptrs = [r.data_ptr() for r in self.Rstages] + [fastsolver.dQ.data_ptr(),
+                                                        self.Qhat.data_ptr() if self.Qhat is not None else 0]
+        self._work = (C.c_void_p * len(ptrs))(*ptrs)
+        self._G = np.ascontiguousarray(G, dtype=np.float64)
+        self._dc = np.ascontiguousarray(dc, dtype=np.float64)
+        self._fa = np.ascontiguousarray(fastsolver.RKA, dtype=np.float64)
+        self._fb = np.ascontiguousarray(fastsolver.RKB, dtype=np.float64)
+        self._fc = np.ascontiguousarray(fastsolver.RKC, dtype=np.float64)
+        d = _lib.CmdgMrigarkDesc()
+        d.kind, d.nstages, d.ngamma = self.KIND, ns, self._G.shape[0]
+        d.gamma, d.dc = self._G.ctypes.data, self._dc.ctypes.data
+        d.fast_nstages = len(self._fa)
+        d.fast_rka, d.fast_rkb, d.fast_rkc = self._fa.ctypes.data, self._fb.ctypes.data, self._fc.ctypes.data
+        d.lu_adjustable = int(adjustable)
+        self._desc = d
+        self.lu = lu
+
+    def updatedt(self, dt):
+        self.dt = float(dt)
+
+    def dostep(self, Q, nsteps=1, dt=None):
+        from . import _lib
+        dt = self.dt if dt is None else dt
+        self._desc.fast_dt = float(self.fastsolver.dt)
+        self.dg._torch_ready()
+        lu = self.lu.handle if self.lu is not None else None
+        for _ in range(int(nsteps)):
+            _lib.check(self.dg.L.cmdg_mrigark_step(
+                self._slow[0], self._slow[1], self._fast[0], self._fast[1], lu, C.byref(self._desc),
+                Q.data_ptr(), C.cast(self._work, C.c_void_p), float(self.t), float(dt)), self._slow[0])
+            # the fast solver's clock ends at the last stage's end (updatetime! in solve!)
+            ts = self.t
+            for c in self.dc:
+                ts += c * dt
+            self.fastsolver.t = ts
+            _advance(self, 1, dt)
+
+    def close(self):
+        if self.lu is not None:
+            self.lu.close()
+
+
+class MRIGARKExplicit(_MRIGARK):
+    """``MRIGARKExplicit(slowrhs!, fastsolver, Γs, γ̂s, Q, dt, t0)``
+    (MultirateInfinitesimalGARKExplicit.jl:100-160): ``slow_rhs`` is a DGModel or a
+    ``remainder_DGModel``, ``fastsolver`` an LSRK 2N solver whose operator is either as well.  One
+    step is one ``cmdg_mrigark_step``.  ``γ̂s`` (the embedded scheme) is carried, not used."""
+
+    KIND = 0
+
+    def __init__(self, slow_rhs, fastsolver, Gammas, gammahats, Q, dt, t0=0.0):
+        _fast_solver(fastsolver, "MRIGARKExplicit")
+        G, gh, dc = mrigark_explicit_coefficients(Gammas, gammahats)
+        self._setup(slow_rhs, fastsolver, G, gh, dc, Q, dt, t0)
+
+
+class MRIGARKDecoupledImplicit(_MRIGARK):
+    """``MRIGARKDecoupledImplicit(slowrhs!, backward_euler_solver, fastsolver, Γs, γ̂s, Q, dt, t0)``
+    (MultirateInfinitesimalGARKDecoupledImplicit.jl:60-200): the slow operator is the vertical
+    linear model, solved by ``LinearBackwardEulerSolver(ManyColumnLU())``, factored for
+    ``dt Γ_0[2, 2]``.  ``updatedt`` with another alpha is refused when the solver is not
+    adjustable."""
+
+    KIND = 1
+
+    def __init__(self, slow_rhs, backward_euler_solver, fastsolver, Gammas, gammahats, Q, dt, t0=0.0):
+        from .dgmodel import RemainderDGModel
+        from .systemsolvers import ColumnLU
+        _fast_solver(fastsolver, "MRIGARKDecoupledImplicit")
+        if not isinstance(backward_euler_solver, LinearBackwardEulerSolver):
+            raise TypeError("MRIGARKDecoupledImplicit: a LinearBackwardEulerSolver(ManyColumnLU()) is needed")
+        if isinstance(slow_rhs, RemainderDGModel):
+            raise TypeError("MRIGARKDecoupledImplicit: the implicit slow operator must be the vertical "
+                            "linear model itself, not a remainder")
+        G, gh, dc = mrigark_implicit_coefficients(Gammas, gammahats)
+        self.isadjustable = backward_euler_solver.isadjustable
+        lu = ColumnLU(slow_rhs, float(dt) * G[0][1][1])
+        self._setup(slow_rhs, fastsolver, G, gh, dc, Q, dt, t0, lu=lu, adjustable=self.isadjustable)
+
+    def updatedt(self, dt):
+        """``updatedt!``: ``@assert Δt_is_adjustable``; the next stage refactors for ``dt Γ_0[2, 2]``."""
+        alpha = float(dt) * self.Gammas[0][1][1]
+        if not self.isadjustable and alpha != self.lu.alpha:
+            _refuse_alpha(self.lu, alpha)
+        self.dt = float(dt)
+
+    def dostep(self, Q, nsteps=1, dt=None):
+        d = self.dt if dt is None else dt
+        if not self.isadjustable:
+            for s in range(len(self.dc)):
+                alpha = d * self.Gammas[0][2 * s + 1][s + 1]
+                if alpha != self.lu.alpha:
+                    _refuse_alpha(self.lu, alpha)
+        super().dostep(Q, nsteps, dt)
+
+
+def _mri_explicit_factory(name):
+    def make(slow_rhs, fastsolver, Q, dt=None, t0=0.0, **kw):
+        assert dt is not None
+        Gs, ghs = MRIGARK_TABLEAUS[name][1](**kw)
+        return MRIGARKExplicit(slow_rhs, fastsolver, Gs, ghs, Q, dt, t0)
+    make.__name__ = name
+    return make
+
+
+def _mri_implicit_factory(name):
+    def make(slow_rhs, backward_euler_solver, fastsolver, Q, dt=None, t0=0.0, **kw):
+        assert dt is not None
+        Gs, ghs = MRIGARK_TABLEAUS[name][1](**kw)
+        return MRIGARKDecoupledImplicit(slow_rhs, backward_euler_solver, fastsolver, Gs, ghs, Q, dt, t0)
+    make.__name__ = name
+    return make
+
+
+# MRIGARKERK33aSandu(slow, fast, Q; dt, t0, delta = -1/2) and the others, as the reference names them
+MRIGARKERK33aSandu = _mri_explicit_factory("MRIGARKERK33aSandu")
+MRIGARKERK45aSandu = _mri_explicit_factory("MRIGARKERK45aSandu")
+MRIGARKIRK21aSandu = _mri_implicit_factory("MRIGARKIRK21aSandu")
+MRIGARKESDIRK23LSA = _mri_implicit_factory("MRIGARKESDIRK23LSA")
+MRIGARKESDIRK24LSA = _mri_implicit_factory("MRIGARKESDIRK24LSA")
+MRIGARKESDIRK34aSandu = _mri_implicit_factory("MRIGARKESDIRK34aSandu")
+MRIGARKESDIRK46aSandu = _mri_implicit_factory("MRIGARKESDIRK46aSandu")
 
 def solve(Q, solver, timeend=None, numberofsteps=0, adjustfinalstep=True, callbacks=()):
     """``solve!(Q, solver; timeend, adjustfinalstep, numberofsteps, callbacks)``: steps are issued

@@ -613,6 +613,19 @@ int cmdg_group_split_explicit01_step(cmdg_handle *slow, cmdg_handle *fast, int32
 /* update!() of the LSRK methods on the handle's real elements (LowStorageRungeKuttaMethod.jl:
  * 146-166): Q += rkb_dt * dQ; dQ *= rka_next */
 int cmdg_lsrk_update(cmdg_handle h, double *dQ, double *Q, double rka_next, double rkb_dt);
+/* lsrk_mri_update!() of the LSRK methods as the fast solver of an MRI-GARK scheme
+ * (LowStorageRungeKuttaMethod.jl:206-225) on the handle's real elements:
+ * dq = dQ + sc[0] R[0] + ... + sc[nR-1] R[nR-1] (in that order); Q += rkb_dt dq; dQ = rka_next dq.
+ * R: HOST array of nR device arrays shaped like Q, 1 <= nR <= CMDG_MRI_MAXR; sc: HOST array of
+ * nR scalars (the reference's Horner sums in tau, computed by the caller).  Enqueued on the
+ * handle's stream; no copy to the device, no host wait. */
+#define CMDG_MRI_MAXR 6
+int cmdg_mri_lsrk_update(cmdg_handle h, double *dQ, double *Q, double rka_next, double rkb_dt, int32_t nR,
+                         const double *const *R, const double *sc);
+/* mri_create_Qhat! (MultirateInfinitesimalGARKDecoupledImplicit.jl:220-237) on the handle's real
+ * elements: Qhat = Q + sc[0] R[0] + ... + sc[nR-1] R[nR-1]; R and sc as above */
+int cmdg_mri_qhat(cmdg_handle h, double *Qhat, const double *Q, int32_t nR, const double *const *R,
+                  const double *sc);
 /* dostep!(Q, ssp::StrongStabilityPreservingRungeKutta, p, time)
  * (src/Numerics/ODESolvers/StrongStabilityPreservingRungeKuttaMethod.jl:117-165, update! kernel
  * :167-190): Qstage = Q; per stage Rstage = rhs(Qstage, t + rkc[s] dt) (increment = false) and
@@ -713,6 +726,45 @@ int cmdg_columnlu_destroy(cmdg_columnlu_handle lu);
 int cmdg_ark_step(cmdg_handle full, cmdg_columnlu_handle lu, double *Q, double *const *work, double t,
                   double dt, int32_t nstages, const double *rka_explicit, const double *rka_implicit,
                   const double *rkb, const double *rkc, int32_t split_explicit_implicit);
+
+/* One slow step of a multirate infinitesimal GARK scheme (Sandu 2019) whose fast method is a
+ * low-storage 2N Runge-Kutta method: dostep! of MultirateInfinitesimalGARKExplicit.jl (kind
+ * CMDG_MRIGARK_EXPLICIT) or of MultirateInfinitesimalGARKDecoupledImplicit.jl (kind
+ * CMDG_MRIGARK_DECOUPLED_IMPLICIT).  Each slow stage s evaluates the slow operator into
+ * Rstages[s], then runs the fast solve! loop from the stage time ts to ts + dc[s] dt with the
+ * fast dt, the last fast step shortened to end there (adjustfinalstep); every fast stage is one
+ * evaluation of the fast operator (increment) and one k_lsrk_mri_update.  The decoupled-implicit
+ * kind then forms Qhat (k_mri_qhat) and solves (I - alpha L) Q = Qhat with the column solver,
+ * alpha = dt gamma[0][2s+1][s+1]: when alpha differs from the solver's the solver is refactored
+ * if lu_adjustable, and the step is refused (CMDG_ERR_INVALID) otherwise. */
+#define CMDG_MRIGARK_EXPLICIT 0
+#define CMDG_MRIGARK_DECOUPLED_IMPLICIT 1
+#define CMDG_MRI_MAXGAMMA 4
+typedef struct cmdg_mrigark_desc {
+    int32_t kind;
+    int32_t nstages;  /* slow stages, 1 .. CMDG_MRI_MAXR */
+    int32_t ngamma;   /* coupling matrices Gamma_0 .. Gamma_{ngamma-1}, 1 .. CMDG_MRI_MAXGAMMA */
+    /* HOST, ngamma row-major matrices: explicit (nstages, nstages) holding Gamma_k ./ dc;
+     * decoupled implicit (2 nstages, nstages + 1) holding Gamma_k as given */
+    const double *gamma;
+    const double *dc;  /* HOST nstages: the explicit stages' time fractions */
+    int32_t fast_nstages;  /* the fast 2N tableau, 1 .. 14 stages */
+    const double *fast_rka, *fast_rkb, *fast_rkc;  /* HOST */
+    double fast_dt;
+    int32_t lu_adjustable;  /* decoupled implicit: LinearBackwardEulerSolver's isadjustable */
+} cmdg_mrigark_desc;
+/* The slow operator is `slow`, or `slow` minus `slow_minus` when that is not NULL (a remainder,
+ * evaluated as `slow` then `slow_minus` with alpha = -1 and increment); the same for `fast` and
+ * `fast_minus`.  All handles live on one grid with one state count.  lu: required for the
+ * decoupled-implicit kind, whose slow operator must be lu's linear model (no remainder), and NULL
+ * for the explicit kind.  work: HOST array of device arrays shaped like Q: Rstages[nstages], the
+ * fast dQ (zero on entry, zero again on return), Qhat (decoupled implicit only).  Refusals
+ * (CMDG_ERR_INVALID, the message naming the member): another grid or state count, nstages or
+ * ngamma out of range, a fast tableau longer than 14 stages, dt <= 0, fast_dt <= 0, a missing lu
+ * or work array.  Returns after the step has finished. */
+int cmdg_mrigark_step(cmdg_handle slow, cmdg_handle slow_minus, cmdg_handle fast, cmdg_handle fast_minus,
+                      cmdg_columnlu_handle lu, const cmdg_mrigark_desc *d, double *Q, double *const *work,
+                      double t, double dt);
 
 #ifdef __cplusplus
 }

@@ -195,6 +195,11 @@ SYMBOLS = [
     ("cmdg_mri_lsrk_update", C.c_int, [_vp, _vp, _vp, _d, _d, _i32, _vp, _vp]),
     ("cmdg_mri_qhat", C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp]),
     ("cmdg_mrigark_step", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d]),
+    ("cmdg_interp_create", C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    ("cmdg_interp_destroy", C.c_int, [_vp, _vp]),
+    ("cmdg_interp_apply", C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp]),
+    ("cmdg_interp_project", C.c_int, [_vp, _vp, _vp, _i32, _vp]),
+    ("cmdg_interp_scatter", C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp]),
 ]
 
 _LIB = None

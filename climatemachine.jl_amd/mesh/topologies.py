@@ -18,6 +18,7 @@ from . import brickmesh as bm
 __all__ = [
     "Topology", "BrickTopology", "StackedBrickTopology", "CubedShellTopology",
     "StackedCubedSphereTopology", "cubedshellmesh", "equiangular_cubed_sphere_warp",
+    "equiangular_cubed_sphere_unwarp",
 ]
 
 
@@ -44,6 +45,11 @@ class Topology:
         self.nabrtorecv = list(conn["nabrtorecv"])      # (first, last) 1-based
         self.nabrtosend = list(conn["nabrtosend"])
         self.globalelems = conn.get("globalelems")
+        # origsendorder (Topologies.jl:164): 1-based global number of every real element in local
+        # order; a stacked topology carries its base (2-D) topology's, as the reference does
+        self.origsendorder = conn.get("origsendorder")
+        if self.origsendorder is None and self.globalelems is not None:
+            self.origsendorder = np.asarray(self.globalelems[:self.nreal], dtype=np.int64)
         self.stacksize = stacksize
         self.periodicstack = periodicstack
         self.bndytoelem, self.bndytoface = bndytoelem, bndytoface
@@ -127,7 +133,7 @@ def _stack(base, stacksize, dim, elemtocoord, elemtoordr_map, vert_nbr, vert_bnd
                 elemtoelem=elemtoelem, elemtoface=elemtoface, elemtoordr=elemtoordr,
                 elemtobndy=elemtobndy, nabrtorank=base.nabrtorank,
                 nabrtorecv=nabrtorecv, nabrtosend=nabrtosend,
-                globalelems=gl)
+                globalelems=gl, origsendorder=base.origsendorder)
     return Topology(dim, conn, stacksize=stacksize, periodicstack=periodicstack,
                     bndytoelem=b2e, bndytoface=b2f, rank=rank, size=size)
 
@@ -312,3 +318,36 @@ def equiangular_cubed_sphere_warp(a, b, c, R=None):
         z = f(-R, b / c, a / c)
         x3[m], x2[m], x1[m] = z[0][m], z[1][m], z[2][m]
     return x1, x2, x3
+
+
+def equiangular_cubed_sphere_unwarp(x1, x2, x3):
+    """Vectorised ``cubed_sphere_unwarp(EquiangularCubedSphere(), x1, x2, x3)``, the inverse
+    of :func:`equiangular_cubed_sphere_warp`.  Reference: Topologies.jl:1315-1364
+    (same face branch order: ``argmax`` picks the first maximal |.|)."""
+    x1 = np.asarray(x1, dtype=np.float64)
+    x2 = np.asarray(x2, dtype=np.float64)
+    x3 = np.asarray(x3, dtype=np.float64)
+    R = np.sqrt(x1 * x1 + x2 * x2 + x3 * x3)
+    fdim = np.argmax(np.stack([np.abs(x1), np.abs(x2), np.abs(x3)]), axis=0)
+    a = np.full_like(R, np.nan)
+    b = np.full_like(R, np.nan)
+    c = np.full_like(R, np.nan)
+
+    def g(sR, X, Y):
+        return sR, sR * (np.arctan(X) * 4 / math.pi), sR * (np.arctan(Y) * 4 / math.pi)
+
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for m, sR, (n0, n1, n2), out in (
+                ((fdim == 0) & (x1 < 0), -R, (x1, x2, x3), (a, b, c)),
+                ((fdim == 1) & (x2 < 0), -R, (x2, x1, x3), (b, a, c)),
+                ((fdim == 0) & (x1 > 0), R, (x1, x2, x3), (a, b, c)),
+                ((fdim == 1) & (x2 > 0), R, (x2, x1, x3), (b, a, c)),
+                ((fdim == 2) & (x3 > 0), R, (x3, x2, x1), (c, b, a)),
+                ((fdim == 2) & (x3 < 0), -R, (x3, x2, x1), (c, b, a))):
+            if not m.any():
+                continue
+            z = g(sR[m], n1[m] / n0[m], n2[m] / n0[m])
+            out[0][m], out[1][m], out[2][m] = z
+    if np.isnan(a).any():
+        raise ValueError("invalid case for cubed_sphere_unwarp (a point at the origin)")
+    return a, b, c

@@ -489,6 +489,64 @@ int cmdg_filter_apply(cmdg_handle h, cmdg_filter f, double *Q, int32_t nstate);
 int cmdg_set_filters(cmdg_handle h, cmdg_filter gradient_filter, cmdg_filter tendency_filter,
                      cmdg_filter step_filter);
 
+/* ---- interpolation onto box and latitude-longitude grids (src/Numerics/Mesh/Interpolation.jl) ---
+ * InterpolationBrick (:132-376) and InterpolationCubedSphere (:700-1044) are host set-up
+ * (climatemachine.jl_amd/mesh/interpolation.py); the descriptor carries what they produce.  The
+ * library copies the point tables to the device and computes the barycentric weights of the nodes
+ * itself; the coincidence flags and the scaling the reference stores per point (flg, fac) are
+ * formed inside the kernel from xi.  Every pointer of the descriptor is a HOST pointer and need
+ * not outlive cmdg_interp_create.  Refused at create (CMDG_ERR_INVALID, message in
+ * cmdg_last_error(h)): an offset table that does not start at 0, decreases or does not end at
+ * npoints; a xi outside [-1 - 1e-10, 1 + 1e-10] (or NaN); an index triple outside the output grid;
+ * npoints or n1 n2 n3 beyond 2^31 - 1.  CMDG_ERR_UNSUPPORTED: Nq[0] != Nq[1], or an Nq outside 2..8.
+ * With offset, xi1, xi2 and xi3 all NULL the object holds index triples only (Nq, nelem and xi_nodes are
+ * not read): it serves cmdg_interp_project and cmdg_interp_scatter -- a root that scatters the gathered
+ * index vectors of every rank -- and cmdg_interp_apply refuses it.
+ *
+ * The cmdg_handle argument of every entry may be NULL.  With a handle the work is ordered on that
+ * handle's compute stream, after any deferred CMDG_OPT_ASYNC_RUN run, and the call returns without
+ * waiting (follow with cmdg_synchronize), as the filters do; errors go to cmdg_last_error(h).  With
+ * NULL the work runs on the default stream of the device the object was created on and the call
+ * returns when it is done; errors go to cmdg_last_error(NULL).  The object is not bound to a
+ * handle: polynomial orders no engine is compiled for, such as (5, 6), are served with NULL. */
+typedef struct cmdg_interp_s *cmdg_interp;
+typedef struct cmdg_interp_desc {
+    int32_t Nq[3];             /* points per direction of the grid, polynomialorders(grid) .+ 1 */
+    int64_t nelem;             /* length(topology.realelems) */
+    int64_t npoints;           /* Npl: output points of this rank */
+    const double *xi_nodes[3]; /* referencepoints(grid): Nq[d] LGL nodes per direction */
+    const int64_t *offset;     /* nelem + 1 prefix sums, 0-based: element e (0-based) owns the
+                                  points offset[e] .. offset[e + 1] - 1 */
+    const double *xi1, *xi2, *xi3; /* npoints reference coordinates each */
+    const int32_t *i1, *i2, *i3;   /* npoints 1-based indices into the output grid: x1i, x2i, x3i
+                                      of the brick; longi, lati, radi of the sphere */
+    int64_t n1, n2, n3;        /* output grid: (n1g, n2g, n3g) or (n_long, n_lat, n_rad) */
+    const double *lat_grd, *long_grd; /* sphere: n2 latitudes and n1 longitudes in degrees; NULL
+                                         for a brick (cmdg_interp_project then refuses) */
+} cmdg_interp_desc;
+int cmdg_interp_create(cmdg_handle h, const cmdg_interp_desc *d, cmdg_interp *out);
+/* waits for the handle h (if given) and for the device's default stream, then frees the tables: work
+ * that used the object through ANOTHER handle must have been synchronised by the caller, as for the
+ * filters.  No device-wide synchronisation. */
+int cmdg_interp_destroy(cmdg_handle h, cmdg_interp it);
+/* interpolate_local! (:397-570, :1265-1317): Q (Np, nstate, nelemQ) device array with
+ * nelemQ >= nelem, v (npoints, nstate) device array;
+ *   v[p, s] = sum_k l3_k(xi3) sum_j l2_j(xi2) sum_i l1_i(xi1) Q[i + Nq1 (j + Nq2 k), s, e]
+ * with the Lagrange basis l in barycentric form; a xi within 4 eps of a node picks that node. */
+int cmdg_interp_apply(cmdg_handle h, cmdg_interp it, const double *Q, int32_t nstate, int64_t nelemQ,
+                      double *v);
+/* project_cubed_sphere! (:1332-1414): the three 1-based columns uvwi of v (npoints, nstate), Cartesian
+ * components, become the components along the unit vectors in longitudinal, latitudinal and radial
+ * direction at each point's latitude and longitude.  A column outside 1..nstate or a column
+ * named twice is refused (CMDG_ERR_INVALID). */
+int cmdg_interp_project(cmdg_handle h, cmdg_interp it, double *v, int32_t nstate, const int32_t uvwi[3]);
+/* the device half of accumulate_interpolated_data! (:1453-1561) for the n ranks of one process:
+ * fiv[i1, i2, i3, s] = v[r][p, s] through the index triples of its[r], r = 0 .. n - 1 in order; fiv is
+ * (n1, n2, n3, nstate) column-major and the objects must agree on (n1, n2, n3).  its and v are HOST
+ * arrays of n objects / device arrays.  Gathering across processes is the caller's. */
+int cmdg_interp_scatter(cmdg_handle h, const cmdg_interp *its, int32_t n, const double *const *v,
+                        int32_t nstate, double *fiv);
+
 /* ---- law-specific update_auxiliary_state! / update_auxiliary_state_gradient! ----------- */
 /* Laws whose auxiliary state needs more than a nodal refresh override these two methods in
  * the reference (BalanceLaws/interface.jl:276-305; called at DGModel.jl:110-116,161-172 and

@@ -1,5 +1,5 @@
-// ManyColumnLU (src/Numerics/SystemSolvers/columnwise_lu_solver.jl) and the low-storage additive
-// Runge-Kutta step that uses it (AdditiveRungeKuttaMethod.jl, LowStorageVariant).
+// ManyColumnLU (src/Numerics/SystemSolvers/columnwise_lu_solver.jl): the banded column solver of
+// the implicit steppers (steppers.hip, multirate.hip).
 //
 // The operator is I - alpha L of a vertical-direction DG model on a stacked grid (the dry linear
 // law, nstate = 5, or the moist one, nstate = 6): a banded matrix per column, one column = one horizontal node (i, j) of one stack of elements, n = Nq_v nstate
@@ -18,16 +18,16 @@
 // the substitutions keep the p + 1 wide window of the solution in registers.
 #include <math.h>
 
-#include <cstring>
 #include <string>
 #include <vector>
 
-#include "engine.h"
+#include "stepping.h"
 
 namespace cmdg {
 namespace {
 
-unsigned blocks(int64_t n, int nt = 256) { return (unsigned)((n + nt - 1) / nt); }
+// work-groups of nt lanes for the band kernels: one matrix column per lane
+unsigned blocks(int64_t n, int nt) { return (unsigned)((n + nt - 1) / nt); }
 
 __global__ void k_probe_set(double *Q, int64_t nreal, int Np, int NS, int nqh2, int nvert, int kin,
                             int sin_, int ev0)
@@ -143,41 +143,6 @@ __global__ void __launch_bounds__(64) k_band_solve(double *X, const double *B, c
     }
 }
 
-// stage_update! (LowStorageVariant, AdditiveRungeKuttaMethod.jl:565-605) over the real elements
-__global__ void k_ark_stage(const double *Q, double *const *Qs, const double *const *R,
-                            double *Qhat, int is, const double *__restrict__ rkcoeff,
-                            const double *__restrict__ dtA, int64_t len)
-{
-    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (i >= len) return;
-    double Qhat_i = Q[i];
-    double Qst = -0.0;
-    for (int js = 0; js < is; ++js) {
-        const double common = rkcoeff[js] * (js == 0 ? Q[i] : Qs[js][i]);
-        Qhat_i += common + dtA[js] * R[js][i];
-        Qst -= common;
-    }
-    Qs[is][i] = Qst;
-    Qhat[i] = Qhat_i;
-}
-
-__global__ void k_add(double *a, const double *b, int64_t len)
-{
-    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (i < len) a[i] += b[i];
-}
-
-// solution_update! (LowStorageVariant, :670-690)
-__global__ void k_ark_solution(double *Q, const double *const *R, int nstages,
-                               const double *__restrict__ bdt, int64_t len)
-{
-    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (i >= len) return;
-    double q = Q[i];
-    for (int is = 0; is < nstages; ++is) q += bdt[is] * R[is][i];
-    Q[i] = q;
-}
-
 }  // namespace
 }  // namespace cmdg
 
@@ -191,8 +156,6 @@ struct cmdg_columnlu {
     double alpha = 0;
     int state = 0;  // 0 empty, 1 assembled (I - alpha L), 2 factored
     double *band = nullptr, *probe = nullptr, *dprobe = nullptr;
-    double *args = nullptr;  // device copies of the step's pointer tables and coefficients
-    hipEvent_t ev = nullptr;
 };
 
 namespace {
@@ -214,14 +177,6 @@ int hip_ok(cmdg_columnlu *lu, hipError_t r, const char *what)
     return lu_fail(lu, CMDG_ERR_HIP, std::string(what) + ": " + hipGetErrorString(r));
 }
 
-// make stream `later` wait for what has been enqueued on `earlier`
-int order(cmdg_columnlu *lu, hipStream_t earlier, hipStream_t later)
-{
-    if (earlier == later) return CMDG_OK;
-    if (int r = hip_ok(lu, hipEventRecord(lu->ev, earlier), "hipEventRecord")) return r;
-    return hip_ok(lu, hipStreamWaitEvent(later, lu->ev, 0), "hipStreamWaitEvent");
-}
-
 int assemble(cmdg_columnlu *lu, double alpha)
 {
     EngineBase *e = lu->lin->eng;
@@ -234,10 +189,10 @@ int assemble(cmdg_columnlu *lu, double alpha)
     for (int ev0 = 0; ev0 < nev; ++ev0)
         for (int s = 0; s < NS; ++s)
             for (int k = 0; k < lu->nqv; ++k) {
-                hipLaunchKernelGGL(k_probe_set, dim3(blocks(len)), dim3(256), 0, st, lu->probe, e->nreal,
+                hipLaunchKernelGGL(k_probe_set, dim3(grid_one_per_thread(len)), dim3(256), 0, st, lu->probe, e->nreal,
                                    e->Np, NS, lu->nqh2, lu->nvert, k, s, ev0);
                 if (int r = cmdg_rhs_async(lu->lin, lu->dprobe, lu->probe, NAN, 1.0, 0.0)) return r;
-                hipLaunchKernelGGL(k_probe_scatter, dim3(blocks(len)), dim3(256), 0, st, lu->band,
+                hipLaunchKernelGGL(k_probe_scatter, dim3(grid_one_per_thread(len)), dim3(256), 0, st, lu->band,
                                    lu->probe, lu->dprobe, e->nreal, e->Np, NS, lu->nqh2, lu->nqv, lu->nvert,
                                    k, s, ev0, lu->p, lu->q, lu->ncol, -alpha);
             }
@@ -282,8 +237,7 @@ int solve(cmdg_columnlu *lu, double *X, const double *B)
 }  // namespace
 
 namespace cmdg {
-// for cmdg_mrigark_step (multirate.hip): enqueued on the linear handle's stream, errors also on
-// its engine (where GroupCall::finish looks)
+// stepping.h: enqueued on the linear handle's stream, errors also on its engine
 cmdg_handle columnlu_linear(cmdg_columnlu_handle lu) { return lu->lin; }
 double columnlu_alpha(cmdg_columnlu_handle lu) { return lu->state == 2 ? lu->alpha : NAN; }
 int columnlu_refactor_async(cmdg_columnlu_handle lu, double alpha)
@@ -359,10 +313,8 @@ int cmdg_columnlu_create(cmdg_handle linear, int32_t nvertelem, double alpha, cm
     if (!r) r = hip_ok(lu, hipMalloc(&lu->band, band), "hipMalloc(band)");
     if (!r) r = hip_ok(lu, hipMalloc(&lu->probe, states / 2), "hipMalloc(probe)");
     if (!r) r = hip_ok(lu, hipMalloc(&lu->dprobe, states / 2), "hipMalloc(probe)");
-    if (!r) r = hip_ok(lu, hipMalloc(&lu->args, 64 * sizeof(double)), "hipMalloc(args)");
     if (!r) r = hip_ok(lu, hipMemset(lu->probe, 0, states / 2), "hipMemset");
     if (!r) r = hip_ok(lu, hipMemset(lu->dprobe, 0, states / 2), "hipMemset");
-    if (!r) r = hip_ok(lu, hipEventCreateWithFlags(&lu->ev, hipEventDisableTiming), "hipEventCreate");
     if (!r) r = update(lu, alpha);
     if (!r) r = hip_ok(lu, hipStreamSynchronize(e->s_comp), "hipStreamSynchronize");
     if (r) {
@@ -441,93 +393,10 @@ int cmdg_columnlu_destroy(cmdg_columnlu_handle lu)
         if (lu->band) (void)hipFree(lu->band);
         if (lu->probe) (void)hipFree(lu->probe);
         if (lu->dprobe) (void)hipFree(lu->dprobe);
-        if (lu->args) (void)hipFree(lu->args);
-        if (lu->ev) (void)hipEventDestroy(lu->ev);
         if (prev >= 0) (void)hipSetDevice(prev);
     }
     delete lu;
     return CMDG_OK;
-}
-
-int cmdg_ark_step(cmdg_handle full, cmdg_columnlu_handle lu, double *Q, double *const *work, double t,
-                  double dt, int32_t nstages, const double *rka_explicit, const double *rka_implicit,
-                  const double *rkb, const double *rkc, int32_t split_explicit_implicit)
-{
-    if (!full || !lu || !Q || !work || !rka_explicit || !rka_implicit || !rkb || !rkc) return CMDG_ERR_INVALID;
-    if (nstages < 2 || nstages > 4) return lu_fail(lu, CMDG_ERR_INVALID, "ark: 2 to 4 stages");
-    EngineBase *ef = full->eng, *el = lu->lin->eng;
-    if (ef->ns != lu->ns)
-        return lu_fail(lu, CMDG_ERR_INVALID,
-                       "ark: the full model has " + std::to_string(ef->ns) + " states, the linear model " +
-                           std::to_string(lu->ns) + "; they must be the same");
-    if (ef->nreal != el->nreal || ef->Np != el->Np)
-        return lu_fail(lu, CMDG_ERR_INVALID, "ark: the full and the linear model live on different grids");
-    DevGuard guard_(ef);
-    const int ns = nstages;
-    auto A = [&](const double *m, int i, int j) { return m[i * ns + j]; };  // row-major (stage, stage)
-    // work: Qstages[1..ns-1], Rstages[0..ns-1], Qhat, Qtt
-    double *Qs[4] = {Q, nullptr, nullptr, nullptr}, *R[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int i = 1; i < ns; ++i) Qs[i] = work[i - 1];
-    for (int i = 0; i < ns; ++i) R[i] = work[ns - 1 + i];
-    double *Qhat = work[2 * ns - 1], *Qtt = work[2 * ns];
-    const int64_t len = ef->nreal * lu->ns * ef->Np;
-    hipStream_t sf = ef->s_comp, sl = el->s_comp;
-    // device tables: Qs (4), R (4), then per stage rkcoeff (4) and dt A (4), then b dt (4)
-    double host[64] = {0};
-    std::memcpy(host, Qs, sizeof Qs);
-    std::memcpy(host + 4, R, sizeof R);
-    for (int is = 1; is < ns; ++is)
-        for (int js = 0; js < is; ++js) {
-            host[8 + 8 * is + js] = split_explicit_implicit
-                                        ? A(rka_implicit, is, js) / A(rka_implicit, is, is)
-                                        : (A(rka_implicit, is, js) - A(rka_explicit, is, js)) / A(rka_implicit, is, is);
-            host[12 + 8 * is + js] = dt * A(rka_explicit, is, js);
-        }
-    for (int is = 0; is < ns; ++is) host[48 + is] = rkb[is] * dt;
-    int r = hip_ok(lu, hipMemcpyAsync(lu->args, host, sizeof host, hipMemcpyHostToDevice, sf), "hipMemcpyAsync");
-    if (!r) r = hip_ok(lu, hipStreamSynchronize(sf), "hipStreamSynchronize");  // (host is a stack buffer)
-    if (r) return r;
-    double *const *dQs = (double *const *)lu->args;
-    const double *const *dR = (const double *const *)(lu->args + 4);
-    const unsigned g = blocks(len);
-    // the first stage's explicit tendency
-    if ((r = cmdg_rhs_async(full, R[0], Qs[0], t + rkc[0] * dt, 1.0, 0.0))) return r;
-    if (split_explicit_implicit) {
-        if ((r = order(lu, sf, sl))) return r;
-        if ((r = cmdg_rhs_async(lu->lin, R[0], Qs[0], t + rkc[0] * dt, -1.0, 1.0))) return r;
-        if ((r = order(lu, sl, sf))) return r;
-    }
-    for (int is = 1; is < ns; ++is) {
-        const double stagetime = t + rkc[is] * dt;
-        hipLaunchKernelGGL(k_ark_stage, dim3(g), dim3(256), 0, sf, Q, dQs, dR, Qhat, is,
-                           lu->args + 8 + 8 * is, lu->args + 12 + 8 * is, len);
-        if ((r = order(lu, sf, sl))) return r;
-        // Q_tt = Qhat + alpha L(Q_tt), alpha = dt a_ii; refactored when alpha changes
-        const double alpha = dt * A(rka_implicit, is, is);
-        if (alpha != lu->alpha || lu->state != 2) {
-            if ((r = update(lu, alpha))) return r;
-        }
-        if ((r = solve(lu, Qtt, Qhat))) return r;
-        hipLaunchKernelGGL(k_add, dim3(g), dim3(256), 0, sl, Qs[is], Qtt, len);
-        if ((r = order(lu, sl, sf))) return r;
-        if ((r = cmdg_rhs_async(full, R[is], Qs[is], stagetime, 1.0, 0.0))) return r;
-        if (split_explicit_implicit) {
-            // "full minus linear" as two evaluations (not the reference's fused RemBL kernel)
-            if ((r = order(lu, sf, sl))) return r;
-            if ((r = cmdg_rhs_async(lu->lin, R[is], Qs[is], stagetime, -1.0, 1.0))) return r;
-            if ((r = order(lu, sl, sf))) return r;
-        }
-    }
-    if (split_explicit_implicit) {
-        // rhs_implicit!(Rstages[is], Qstages[is], p, stagetime, increment = true)
-        if ((r = order(lu, sf, sl))) return r;
-        for (int is = 0; is < ns; ++is)
-            if ((r = cmdg_rhs_async(lu->lin, R[is], Qs[is], t + rkc[is] * dt, 1.0, 1.0))) return r;
-        if ((r = order(lu, sl, sf))) return r;
-    }
-    hipLaunchKernelGGL(k_ark_solution, dim3(g), dim3(256), 0, sf, Q, dR, ns, lu->args + 48, len);
-    if ((r = hip_ok(lu, hipGetLastError(), "ark kernels"))) return r;
-    return hip_ok(lu, hipStreamSynchronize(sf), "hipStreamSynchronize");
 }
 
 }  // extern "C"

@@ -16,21 +16,12 @@
 // consecutive operations on different streams are ordered by one event.
 #include <math.h>
 
-#include <string>
 #include <utility>
 #include <vector>
 
-#include "engine.h"
+#include "stepping.h"
 
 using namespace cmdg;
-
-namespace cmdg {
-// columnlu.hip: the column solver's pieces that the step drives on the linear handle's stream
-cmdg_handle columnlu_linear(cmdg_columnlu_handle lu);
-double columnlu_alpha(cmdg_columnlu_handle lu);
-int columnlu_refactor_async(cmdg_columnlu_handle lu, double alpha);
-int columnlu_solve_async(cmdg_columnlu_handle lu, double *X, const double *B);
-}  // namespace cmdg
 
 namespace {
 
@@ -71,11 +62,9 @@ __global__ void __launch_bounds__(256) k_mri_qhat(const MriArgs a)
     a.out[i] = qh;
 }
 
-unsigned grid_for(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 void launch_update(const MriArgs &a, int nR, hipStream_t st)
 {
-    const dim3 g(grid_for(a.n)), b(256);
+    const dim3 g(grid_one_per_thread(a.n)), b(256);
     switch (nR) {
         case 1: hipLaunchKernelGGL(k_lsrk_mri_update<1>, g, b, 0, st, a); break;
         case 2: hipLaunchKernelGGL(k_lsrk_mri_update<2>, g, b, 0, st, a); break;
@@ -88,7 +77,7 @@ void launch_update(const MriArgs &a, int nR, hipStream_t st)
 
 void launch_qhat(const MriArgs &a, int nR, hipStream_t st)
 {
-    const dim3 g(grid_for(a.n)), b(256);
+    const dim3 g(grid_one_per_thread(a.n)), b(256);
     switch (nR) {
         case 1: hipLaunchKernelGGL(k_mri_qhat<1>, g, b, 0, st, a); break;
         case 2: hipLaunchKernelGGL(k_mri_qhat<2>, g, b, 0, st, a); break;
@@ -98,8 +87,6 @@ void launch_qhat(const MriArgs &a, int nR, hipStream_t st)
         case 6: hipLaunchKernelGGL(k_mri_qhat<6>, g, b, 0, st, a); break;
     }
 }
-
-int64_t real_len(const EngineBase *e) { return e->nreal * (int64_t)e->ns * e->Np; }
 
 // the low-level entries' common checks and argument struct
 int low_level_args(cmdg_handle h, double *out, const double *Q, int nR, const double *const *R,
@@ -120,67 +107,6 @@ int low_level_args(cmdg_handle h, double *out, const double *Q, int nR, const do
     return CMDG_OK;
 }
 
-// Consecutive operations of one step on different streams: the later stream waits for
-// everything enqueued so far on the earlier one.
-struct Chain {
-    EngineBase *owner;  // takes the messages of ordering failures
-    hipEvent_t ev = nullptr;
-    hipStream_t cur = nullptr;
-    explicit Chain(EngineBase *e) : owner(e) {}
-    ~Chain()
-    {
-        if (ev) (void)hipEventDestroy(ev);
-    }
-    int create()
-    {
-        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
-            return owner->fail(CMDG_ERR_HIP, "mrigark: hipEventCreate failed");
-        return CMDG_OK;
-    }
-    int to(hipStream_t s)
-    {
-        if (cur && cur != s) {
-            if (hipEventRecord(ev, cur) != hipSuccess || hipStreamWaitEvent(s, ev, 0) != hipSuccess)
-                return owner->fail(CMDG_ERR_HIP, "mrigark: stream ordering failed");
-        }
-        cur = s;
-        return CMDG_OK;
-    }
-};
-
-// one operator: `h`, or `h` minus `minus` evaluated as h (alpha, beta) then minus (-alpha, 1)
-struct Op {
-    cmdg_handle h = nullptr, minus = nullptr;
-    int eval(Chain &ch, double *tendency, double *Q, double t, double beta) const
-    {
-        RhsCtx c;
-        c.tendency = tendency;
-        c.Qin = Q;
-        c.t = t;
-        c.alpha = 1.0;
-        c.beta = beta;
-        if (int r = ch.to(h->eng->s_comp)) return r;
-        if (int r = h->eng->rhs_async(c)) return r;
-        if (!minus) return CMDG_OK;
-        c.alpha = -1.0;
-        c.beta = 1.0;
-        if (int r = ch.to(minus->eng->s_comp)) return r;
-        return minus->eng->rhs_async(c);
-    }
-};
-
-int check_same_grid(EngineBase *ref, EngineBase *e, const char *what)
-{
-    if (e->nreal != ref->nreal || e->Np != ref->Np || e->NQ != ref->NQ || e->NQV != ref->NQV || e->dev != ref->dev)
-        return e->fail(CMDG_ERR_INVALID, std::string("mrigark: the ") + what +
-                                             " operator lives on another grid than the slow operator");
-    if (e->ns != ref->ns)
-        return e->fail(CMDG_ERR_INVALID, std::string("mrigark: the ") + what + " operator has " +
-                                             std::to_string(e->ns) + " states, the slow operator " +
-                                             std::to_string(ref->ns) + "; they must be the same");
-    return CMDG_OK;
-}
-
 int step(const Op &slow, const Op &fast, cmdg_columnlu_handle lu, const cmdg_mrigark_desc *d, double *Q,
          double *const *work, double t, double dt)
 {
@@ -192,7 +118,7 @@ int step(const Op &slow, const Op &fast, cmdg_columnlu_handle lu, const cmdg_mri
     auto G = [&](int k, int row, int col) { return d->gamma[((int64_t)k * nrows + row) * ncols + col]; };
     double *const *R = work;
     double *dQ = work[ns], *Qhat = work[ns + 1];
-    Chain ch(es);
+    Chain ch(es, "mrigark");
     if (int r = ch.create()) return r;
     EngineBase *elu = implicit ? columnlu_linear(lu)->eng : nullptr;
     MriArgs a{};
@@ -352,20 +278,15 @@ int cmdg_mrigark_step(cmdg_handle slow, cmdg_handle slow_minus, cmdg_handle fast
     if (!gc.ok()) return CMDG_ERR_INVALID;
     EngineBase *es = slow->eng;
     if (slow_minus)
-        if (int r = check_same_grid(es, slow_minus->eng, "subtracted slow")) return gc.finish(r);
-    if (int r = check_same_grid(es, fast->eng, "fast")) return gc.finish(r);
+        if (int r = check_same_grid("mrigark", es, slow_minus->eng, "subtracted slow")) return gc.finish(r);
+    if (int r = check_same_grid("mrigark", es, fast->eng, "fast")) return gc.finish(r);
     if (fast_minus)
-        if (int r = check_same_grid(es, fast_minus->eng, "subtracted fast")) return gc.finish(r);
+        if (int r = check_same_grid("mrigark", es, fast_minus->eng, "subtracted fast")) return gc.finish(r);
     if (int r = check_desc(slow, fast, lu, d, work, dt)) return gc.finish(r);
     if (lu && slow_minus)
         return gc.finish(es->fail(CMDG_ERR_INVALID,
                                   "mrigark: the decoupled-implicit slow operator cannot be a remainder"));
-    Op so, fo;
-    so.h = slow;
-    so.minus = slow_minus;
-    fo.h = fast;
-    fo.minus = fast_minus;
-    return gc.finish(step(so, fo, lu, d, Q, work, t, dt));
+    return gc.finish(step(Op{slow, slow_minus}, Op{fast, fast_minus}, lu, d, Q, work, t, dt));
 }
 
 }  // extern "C"

@@ -8,8 +8,7 @@
 #include <vector>
 
 #include "columns.h"
-#include "engine.h"
-#include "filters.h"
+#include "stepping.h"
 
 using namespace cmdg;
 
@@ -74,43 +73,6 @@ int fast_to_slow(EngineBase *s, EngineBase *f, const cmdg_ocean_coupling_desc *d
     return s->order(s->s_comp, f->s_comp);
 }
 
-int lsrk_update(EngineBase *e, double *dQ, double *Q, double rka_next, double rkb_dt)
-{
-    const int64_t n = (int64_t)e->Np * e->ns * e->nreal;
-    hipLaunchKernelGGL(k_lsrk_update, dim3(nblocks(n)), dim3(256), 0, e->s_comp, dQ, Q, rka_next,
-                       rkb_dt, n);
-    return CMDG_OK;
-}
-
-// update! of StrongStabilityPreservingRungeKuttaMethod.jl:167-190
-__global__ void k_ssprk_update(const double *__restrict__ R, const double *__restrict__ Q,
-                               double *__restrict__ Qstage, double rka1, double rka2, double rkb,
-                               double dt, int64_t n)
-{
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x)
-        Qstage[i] = rka1 * Q[i] + rka2 * Qstage[i] + dt * rkb * R[i];
-}
-
-// update! of LowStorageRungeKutta3NMethod.jl:201-226
-__global__ void k_ls3n_update(double *__restrict__ dQ, double *__restrict__ dR, double *__restrict__ Q,
-                              double rka1, double rka2, double rkb1, double rkb2, double dt,
-                              int64_t n)
-{
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        Q[i] += rkb1 * dt * dQ[i] + rkb2 * dt * dR[i];
-        dR[i] += rka2 * dQ[i];
-        dQ[i] *= rka1;
-    }
-}
-__global__ void k_fill(double *__restrict__ a, double v, int64_t n)
-{
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x)
-        a[i] = v;
-}
-
 }  // namespace
 
 extern "C" {
@@ -146,63 +108,6 @@ int cmdg_ocean_reconcile_from_fast_to_slow(cmdg_handle slow, cmdg_handle fast,
     if (int r = check(slow->eng, fast->eng, d)) return gc.finish(r);
     if (int r = fast_to_slow(slow->eng, fast->eng, d, Q_slow, Q_fast)) return gc.finish(r);
     return gc.finish(slow->eng->launch_status(LAUNCH));
-}
-
-int cmdg_lsrk_update(cmdg_handle h, double *dQ, double *Q, double rka_next, double rkb_dt)
-{
-    if (!h || !dQ || !Q) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    lsrk_update(h->eng, dQ, Q, rka_next, rkb_dt);
-    return set_err(h, h->eng->launch_status(LAUNCH));
-}
-
-int cmdg_ls3n_step(cmdg_handle h, double *Q, double *dQ, double *dR, double t, double dt,
-                   int32_t nstages, const double *rka, const double *rkb, const double *rkc)
-{
-    if (!h || !Q || !dQ || !dR || !rka || !rkb || !rkc || nstages < 1) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    EngineBase *e = h->eng;
-    const int64_t n = (int64_t)e->Np * e->ns * e->nreal;
-    hipLaunchKernelGGL(k_fill, dim3(nblocks(n)), dim3(256), 0, e->s_comp, dR, 0.0, n);  // `rv_dR .= -0`: integer -0, i.e. +0.0
-    for (int s = 0; s < nstages; ++s) {
-        RhsCtx c;
-        c.tendency = dQ;
-        c.Qin = Q;
-        c.t = t + rkc[s] * dt;
-        c.alpha = 1.0;
-        c.beta = 1.0;  // increment = true
-        if (int r = e->rhs_async(c)) return set_err(h, r);
-        const int sn = (s + 1) % nstages;
-        hipLaunchKernelGGL(k_ls3n_update, dim3(nblocks(n)), dim3(256), 0, e->s_comp, dQ, dR, Q,
-                           rka[2 * sn], rka[2 * sn + 1], rkb[2 * s], rkb[2 * s + 1], dt, n);
-    }
-    return set_err(h, e->launch_status(LAUNCH));
-}
-
-int cmdg_ssprk_step(cmdg_handle h, double *Q, double *Rstage, double *Qstage, double t, double dt,
-                    int32_t nstages, const double *rka, const double *rkb, const double *rkc)
-{
-    if (!h || !Q || !Rstage || !Qstage || !rka || !rkb || !rkc || nstages < 1) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    EngineBase *e = h->eng;
-    const int64_t n = (int64_t)e->Np * e->ns * e->nreal;
-    if (hipMemcpyAsync(Qstage, Q, sizeof(double) * n, hipMemcpyDeviceToDevice, e->s_comp) != hipSuccess)
-        return set_err(h, e->fail(CMDG_ERR_HIP, "ssprk: copy failed"));
-    for (int s = 0; s < nstages; ++s) {
-        RhsCtx c;
-        c.tendency = Rstage;
-        c.Qin = Qstage;
-        c.t = t + rkc[s] * dt;
-        c.alpha = 1.0;
-        c.beta = 0.0;
-        if (int r = e->rhs_async(c)) return set_err(h, r);
-        hipLaunchKernelGGL(k_ssprk_update, dim3(nblocks(n)), dim3(256), 0, e->s_comp,
-                           (const double *)Rstage, (const double *)Q, Qstage, rka[2 * s],
-                           rka[2 * s + 1], rkb[s], dt, n);
-    }
-    if (hipMemcpyAsync(Q, Qstage, sizeof(double) * n, hipMemcpyDeviceToDevice, e->s_comp) != hipSuccess)
-        return set_err(h, e->fail(CMDG_ERR_HIP, "ssprk: copy failed"));
-    return set_err(h, e->launch_status(LAUNCH));
 }
 
 // dostep!(Qslow, split::SplitExplicitSolver, param, time) for n (slow, fast) pairs in lock step:

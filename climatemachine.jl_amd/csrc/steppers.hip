@@ -1,0 +1,209 @@
+// The time steppers other than the fused LSRK run (cmdg.hip) and the multirate ones
+// (multirate.hip, split_explicit*.hip): the 2N update on its own, the strong-stability-preserving
+// and 3N low-storage Runge-Kutta steps over one operator, and the low-storage additive
+// Runge-Kutta step (AdditiveRungeKuttaMethod.jl, LowStorageVariant) over a full operator and the
+// column solver's linear one.
+#include "stepping.h"
+
+using namespace cmdg;
+
+namespace {
+
+const char *const LAUNCH = "stepper launch";
+
+// update! of StrongStabilityPreservingRungeKuttaMethod.jl:167-190
+__global__ void k_ssprk_update(const double *__restrict__ R, const double *__restrict__ Q,
+                               double *__restrict__ Qstage, double rka1, double rka2, double rkb,
+                               double dt, int64_t n)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x)
+        Qstage[i] = rka1 * Q[i] + rka2 * Qstage[i] + dt * rkb * R[i];
+}
+
+// update! of LowStorageRungeKutta3NMethod.jl:201-226
+__global__ void k_ls3n_update(double *__restrict__ dQ, double *__restrict__ dR, double *__restrict__ Q,
+                              double rka1, double rka2, double rkb1, double rkb2, double dt,
+                              int64_t n)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        Q[i] += rkb1 * dt * dQ[i] + rkb2 * dt * dR[i];
+        dR[i] += rka2 * dQ[i];
+        dQ[i] *= rka1;
+    }
+}
+__global__ void k_fill(double *__restrict__ a, double v, int64_t n)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x)
+        a[i] = v;
+}
+
+// The additive step's pointers and the coefficients of one launch, by value as the kernel
+// argument: Qs[0] is Q; rkcoeff and dtA are the stage's row, bdt is rkb dt.
+struct ArkArgs {
+    double *Qs[4];
+    const double *R[4];
+    double rkcoeff[4], dtA[4], bdt[4];
+    int64_t len;
+};
+
+// stage_update! (LowStorageVariant, AdditiveRungeKuttaMethod.jl:565-605) over the real elements
+__global__ void __launch_bounds__(256) k_ark_stage(const ArkArgs a, double *Qhat, int is)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= a.len) return;
+    double Qhat_i = a.Qs[0][i];
+    double Qst = -0.0;
+#pragma unroll
+    for (int js = 0; js < 3; ++js) {
+        if (js >= is) break;
+        const double common = a.rkcoeff[js] * a.Qs[js][i];
+        Qhat_i += common + a.dtA[js] * a.R[js][i];
+        Qst -= common;
+    }
+    a.Qs[is][i] = Qst;
+    Qhat[i] = Qhat_i;
+}
+
+__global__ void k_add(double *a, const double *b, int64_t len)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i < len) a[i] += b[i];
+}
+
+// solution_update! (LowStorageVariant, :670-690)
+__global__ void __launch_bounds__(256) k_ark_solution(const ArkArgs a, int nstages)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= a.len) return;
+    double q = a.Qs[0][i];
+#pragma unroll
+    for (int is = 0; is < 4; ++is) {
+        if (is >= nstages) break;
+        q += a.bdt[is] * a.R[is][i];
+    }
+    a.Qs[0][i] = q;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cmdg_lsrk_update(cmdg_handle h, double *dQ, double *Q, double rka_next, double rkb_dt)
+{
+    if (!h || !dQ || !Q) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    lsrk_update(h->eng, dQ, Q, rka_next, rkb_dt);
+    return set_err(h, h->eng->launch_status(LAUNCH));
+}
+
+int cmdg_ls3n_step(cmdg_handle h, double *Q, double *dQ, double *dR, double t, double dt,
+                   int32_t nstages, const double *rka, const double *rkb, const double *rkc)
+{
+    if (!h || !Q || !dQ || !dR || !rka || !rkb || !rkc || nstages < 1) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    EngineBase *e = h->eng;
+    const int64_t n = real_len(e);
+    Chain ch(e, "ls3n");
+    hipLaunchKernelGGL(k_fill, dim3(nblocks(n)), dim3(256), 0, e->s_comp, dR, 0.0, n);  // `rv_dR .= -0`: integer -0, i.e. +0.0
+    for (int s = 0; s < nstages; ++s) {
+        if (int r = Op{h}.eval(ch, dQ, Q, t + rkc[s] * dt, 1.0)) return set_err(h, r);  // increment = true
+        const int sn = (s + 1) % nstages;
+        hipLaunchKernelGGL(k_ls3n_update, dim3(nblocks(n)), dim3(256), 0, e->s_comp, dQ, dR, Q,
+                           rka[2 * sn], rka[2 * sn + 1], rkb[2 * s], rkb[2 * s + 1], dt, n);
+    }
+    return set_err(h, e->launch_status(LAUNCH));
+}
+
+int cmdg_ssprk_step(cmdg_handle h, double *Q, double *Rstage, double *Qstage, double t, double dt,
+                    int32_t nstages, const double *rka, const double *rkb, const double *rkc)
+{
+    if (!h || !Q || !Rstage || !Qstage || !rka || !rkb || !rkc || nstages < 1) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    EngineBase *e = h->eng;
+    const int64_t n = real_len(e);
+    Chain ch(e, "ssprk");
+    if (hipMemcpyAsync(Qstage, Q, sizeof(double) * n, hipMemcpyDeviceToDevice, e->s_comp) != hipSuccess)
+        return set_err(h, e->fail(CMDG_ERR_HIP, "ssprk: copy failed"));
+    for (int s = 0; s < nstages; ++s) {
+        if (int r = Op{h}.eval(ch, Rstage, Qstage, t + rkc[s] * dt, 0.0)) return set_err(h, r);
+        hipLaunchKernelGGL(k_ssprk_update, dim3(nblocks(n)), dim3(256), 0, e->s_comp,
+                           (const double *)Rstage, (const double *)Q, Qstage, rka[2 * s],
+                           rka[2 * s + 1], rkb[s], dt, n);
+    }
+    if (hipMemcpyAsync(Q, Qstage, sizeof(double) * n, hipMemcpyDeviceToDevice, e->s_comp) != hipSuccess)
+        return set_err(h, e->fail(CMDG_ERR_HIP, "ssprk: copy failed"));
+    return set_err(h, e->launch_status(LAUNCH));
+}
+
+// The full operator runs on its handle's stream, as do the stage and solution kernels; the linear
+// operator, the band solve and k_add run on the linear handle's.
+int cmdg_ark_step(cmdg_handle full, cmdg_columnlu_handle lu, double *Q, double *const *work, double t,
+                  double dt, int32_t nstages, const double *rka_explicit, const double *rka_implicit,
+                  const double *rkb, const double *rkc, int32_t split_explicit_implicit)
+{
+    if (!full || !lu || !Q || !work || !rka_explicit || !rka_implicit || !rkb || !rkc) return CMDG_ERR_INVALID;
+    const cmdg_handle lin = columnlu_linear(lu);
+    GroupCall gc({{full, "full"}, {lin, "linear"}});
+    if (!gc.ok()) return CMDG_ERR_INVALID;
+    EngineBase *ef = full->eng, *el = lin->eng;
+    if (nstages < 2 || nstages > 4) return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: 2 to 4 stages"));
+    if (ef->ns != el->ns)
+        return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: the full model has " + std::to_string(ef->ns) +
+                                                        " states, the linear model " + std::to_string(el->ns) +
+                                                        "; they must be the same"));
+    if (ef->nreal != el->nreal || ef->Np != el->Np || ef->dev != el->dev)
+        return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: the full and the linear model live on different grids"));
+    const int ns = nstages;
+    for (int i = 0; i < 2 * ns + 1; ++i)
+        if (!work[i]) return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: work array " + std::to_string(i) + " is NULL"));
+    auto A = [&](const double *m, int i, int j) { return m[i * ns + j]; };  // row-major (stage, stage)
+    // work: Qstages[1..ns-1], Rstages[0..ns-1], Qhat, Qtt
+    ArkArgs a{};
+    a.Qs[0] = Q;
+    for (int i = 1; i < ns; ++i) a.Qs[i] = work[i - 1];
+    for (int i = 0; i < ns; ++i) a.R[i] = work[ns - 1 + i];
+    double *const *Qs = a.Qs, *const *R = work + ns - 1;
+    double *Qhat = work[2 * ns - 1], *Qtt = work[2 * ns];
+    a.len = real_len(ef);
+    for (int is = 0; is < ns; ++is) a.bdt[is] = rkb[is] * dt;
+    const dim3 g(grid_one_per_thread(a.len)), b(256);
+    hipStream_t sf = ef->s_comp, sl = el->s_comp;
+    Chain ch(ef, "ark");
+    if (int r = ch.create()) return gc.finish(r);
+    // the explicit tendency: the full operator, or "full minus linear" as two evaluations (not the
+    // reference's fused RemBL kernel)
+    const Op expl{full, split_explicit_implicit ? lin : nullptr}, impl{lin};
+    if (int r = expl.eval(ch, R[0], Qs[0], t + rkc[0] * dt, 0.0)) return gc.finish(r);
+    for (int is = 1; is < ns; ++is) {
+        for (int js = 0; js < is; ++js) {
+            a.rkcoeff[js] = split_explicit_implicit
+                                ? A(rka_implicit, is, js) / A(rka_implicit, is, is)
+                                : (A(rka_implicit, is, js) - A(rka_explicit, is, js)) / A(rka_implicit, is, is);
+            a.dtA[js] = dt * A(rka_explicit, is, js);
+        }
+        if (int r = ch.to(sf)) return gc.finish(r);
+        hipLaunchKernelGGL(k_ark_stage, g, b, 0, sf, a, Qhat, is);
+        // Q_tt = Qhat + alpha L(Q_tt), alpha = dt a_ii; refactored when alpha changes
+        if (int r = ch.to(sl)) return gc.finish(r);
+        const double alpha = dt * A(rka_implicit, is, is);
+        if (alpha != columnlu_alpha(lu))
+            if (int r = columnlu_refactor_async(lu, alpha)) return gc.finish(r);
+        if (int r = columnlu_solve_async(lu, Qtt, Qhat)) return gc.finish(r);
+        hipLaunchKernelGGL(k_add, g, b, 0, sl, Qs[is], Qtt, a.len);
+        if (int r = expl.eval(ch, R[is], Qs[is], t + rkc[is] * dt, 0.0)) return gc.finish(r);
+    }
+    if (split_explicit_implicit)
+        // rhs_implicit!(Rstages[is], Qstages[is], p, stagetime, increment = true)
+        for (int is = 0; is < ns; ++is)
+            if (int r = impl.eval(ch, R[is], Qs[is], t + rkc[is] * dt, 1.0)) return gc.finish(r);
+    if (int r = ch.to(sf)) return gc.finish(r);
+    hipLaunchKernelGGL(k_ark_solution, g, b, 0, sf, a, ns);
+    if (int r = ef->launch_status("ark kernels")) return gc.finish(r);
+    if (hipStreamSynchronize(sf) != hipSuccess) return gc.finish(ef->fail(CMDG_ERR_HIP, "ark: hipStreamSynchronize"));
+    return CMDG_OK;
+}
+
+}  // extern "C"

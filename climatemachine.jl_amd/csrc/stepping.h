@@ -1,0 +1,94 @@
+// The parts the time steppers that run several operators are built from (steppers.hip,
+// multirate.hip): stream ordering, "an operator, or one minus another", the grid checks and the
+// column solver's internal interface.  Internal: not installed under include/.
+#pragma once
+#include <string>
+
+#include "engine.h"
+#include "filters.h"
+
+namespace cmdg {
+
+// columnlu.hip: the column solver's pieces that a step drives on the linear handle's stream;
+// errors land on that handle's engine (where GroupCall::finish looks)
+cmdg_handle columnlu_linear(cmdg_columnlu_handle lu);
+double columnlu_alpha(cmdg_columnlu_handle lu);  // NaN while the band is not factored
+int columnlu_refactor_async(cmdg_columnlu_handle lu, double alpha);
+int columnlu_solve_async(cmdg_columnlu_handle lu, double *X, const double *B);
+
+// Work-groups of 256 for a kernel that handles one item per thread and returns past n: every
+// item needs its own thread, so the count is not capped (nblocks, engine.h, is for grid-stride
+// kernels only).
+inline unsigned grid_one_per_thread(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+inline int64_t real_len(const EngineBase *e) { return e->nreal * (int64_t)e->ns * e->Np; }
+
+// update! of the 2N scheme over the real elements, on the engine's compute stream
+inline void lsrk_update(EngineBase *e, double *dQ, double *Q, double rka_next, double rkb_dt)
+{
+    const int64_t n = real_len(e);
+    hipLaunchKernelGGL(k_lsrk_update, dim3(nblocks(n)), dim3(256), 0, e->s_comp, dQ, Q, rka_next, rkb_dt, n);
+}
+
+// Consecutive operations of one step on different streams: the later stream waits for
+// everything enqueued so far on the earlier one.  A step that stays on one stream needs no create().
+struct Chain {
+    EngineBase *owner;  // takes the messages of ordering failures
+    std::string who;    // their prefix: the stepper's name
+    hipEvent_t ev = nullptr;
+    hipStream_t cur = nullptr;
+    Chain(EngineBase *e, const char *stepper) : owner(e), who(stepper) {}
+    ~Chain()
+    {
+        if (ev) (void)hipEventDestroy(ev);
+    }
+    int create()
+    {
+        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
+            return owner->fail(CMDG_ERR_HIP, who + ": hipEventCreate failed");
+        return CMDG_OK;
+    }
+    int to(hipStream_t s)
+    {
+        if (cur && cur != s) {
+            if (hipEventRecord(ev, cur) != hipSuccess || hipStreamWaitEvent(s, ev, 0) != hipSuccess)
+                return owner->fail(CMDG_ERR_HIP, who + ": stream ordering failed");
+        }
+        cur = s;
+        return CMDG_OK;
+    }
+};
+
+// one operator: `h`, or `h` minus `minus` evaluated as h (alpha, beta) then minus (-alpha, 1)
+struct Op {
+    cmdg_handle h = nullptr, minus = nullptr;
+    int eval(Chain &ch, double *tendency, double *Q, double t, double beta) const
+    {
+        RhsCtx c;
+        c.tendency = tendency;
+        c.Qin = Q;
+        c.t = t;
+        c.alpha = 1.0;
+        c.beta = beta;
+        if (int r = ch.to(h->eng->s_comp)) return r;
+        if (int r = h->eng->rhs_async(c)) return r;
+        if (!minus) return CMDG_OK;
+        c.alpha = -1.0;
+        c.beta = 1.0;
+        if (int r = ch.to(minus->eng->s_comp)) return r;
+        return minus->eng->rhs_async(c);
+    }
+};
+
+inline int check_same_grid(const char *stepper, EngineBase *ref, EngineBase *e, const char *what)
+{
+    const std::string the = std::string(stepper) + ": the " + what + " operator ";
+    if (e->nreal != ref->nreal || e->Np != ref->Np || e->NQ != ref->NQ || e->NQV != ref->NQV || e->dev != ref->dev)
+        return e->fail(CMDG_ERR_INVALID, the + "lives on another grid than the slow operator");
+    if (e->ns != ref->ns)
+        return e->fail(CMDG_ERR_INVALID, the + "has " + std::to_string(e->ns) + " states, the slow operator " +
+                                             std::to_string(ref->ns) + "; they must be the same");
+    return CMDG_OK;
+}
+
+}  // namespace cmdg

@@ -1,21 +1,29 @@
-"""Host-side mirror of the reference's explicit low-storage Runge-Kutta driver.
+"""Host-side mirrors of the reference's ODE solvers: tableaus and work arrays here, every stage
+loop inside libcmdg.
 
-Reference: ``LowStorageRungeKutta2N`` / ``dostep!`` / ``update!``
+Explicit low-storage 2N: ``LowStorageRungeKutta2N`` / ``dostep!`` / ``update!``
 ``src/Numerics/ODESolvers/LowStorageRungeKuttaMethod.jl:26-62,102-158``;
 ``LSRK54CarpenterKennedy`` ``:293-327`` (rational coefficients converted to Float64),
 ``LSRK144NiegemannDiehlBusch`` ``:349-410``;
 ``solve!`` / ``general_dostep!`` ``ODESolvers.jl:49-158``;
 ``StrongStabilityPreservingRungeKutta`` and its four tableaus
-``StrongStabilityPreservingRungeKuttaMethod.jl:27-285``.
+``StrongStabilityPreservingRungeKuttaMethod.jl:27-285`` (``cmdg_ssprk_step``);
+``LowStorageRungeKutta3N`` ``LowStorageRungeKutta3NMethod.jl`` (``cmdg_ls3n_step``);
+``AdditiveRungeKutta``, LowStorageVariant, ``AdditiveRungeKuttaMethod.jl`` (``cmdg_ark_step``);
+``MRIGARKExplicit`` / ``MRIGARKDecoupledImplicit`` ``MultirateInfinitesimalGARK*.jl``
+(``cmdg_mrigark_step``).
 
-The stage loop itself runs inside libcmdg (``cmdg_lsrk_run``): five fused
-RHS+update passes per step, enqueued without host synchronisation.
+The 2N stage loop is ``cmdg_lsrk_run``: five fused RHS+update passes per step, enqueued without
+host synchronisation.
 """
 import ctypes as C
 import math
 from fractions import Fraction
 
-from .systemsolvers import ManyColumnLU
+import numpy as np
+
+from . import _lib
+from .systemsolvers import ColumnLU, ManyColumnLU
 
 __all__ = ["LSRK54CarpenterKennedy", "LSRK144NiegemannDiehlBusch", "solve",
            "LowStorageRungeKutta2N", "LSRK144_COEFFICIENTS", "StrongStabilityPreservingRungeKutta",
@@ -38,6 +46,24 @@ def _advance(solver, nsteps, dt):
     for _ in range(int(nsteps)):
         solver.t += dt
     solver.steps += int(nsteps)
+
+
+def _tableau(x):
+    return np.ascontiguousarray(x, dtype=np.float64)
+
+
+def _ptr(a):
+    return C.c_void_p(a.ctypes.data)
+
+
+def _run(solver, nsteps, dt, call, handle=None):
+    """``nsteps`` library calls ``call(t, dt)``, each from the running sum of the time (as
+    cmdg_lsrk_run's steps start); a failure raises with the message of ``handle`` (``solver.dg``'s
+    by default)."""
+    solver.dg._torch_ready()
+    for _ in range(int(nsteps)):
+        _lib.check(call(float(solver.t), float(dt)), handle or solver.dg.handle)
+        _advance(solver, 1, dt)
 
 
 class LowStorageRungeKutta2N:
@@ -107,26 +133,15 @@ class StrongStabilityPreservingRungeKutta:
     (StrongStabilityPreservingRungeKuttaMethod.jl:27-75); the stage loop is ``cmdg_ssprk_step``."""
 
     def __init__(self, dg, RKA, RKB, RKC, Q, dt=0.0, t0=0.0):
-        import numpy as np
         self.dg, self.dt, self.t, self.steps = dg, dt, t0, 0
-        self.RKA = np.ascontiguousarray(RKA, dtype=np.float64)
-        self.RKB = np.ascontiguousarray(RKB, dtype=np.float64)
-        self.RKC = np.ascontiguousarray(RKC, dtype=np.float64)
+        self.RKA, self.RKB, self.RKC = _tableau(RKA), _tableau(RKB), _tableau(RKC)
         self.Rstage = dg.create_state(Q.shape[1])
         self.Qstage = dg.create_state(Q.shape[1])
 
     def dostep(self, Q, nsteps=1, dt=None):
-        import ctypes as C
-        from . import _lib
-        dt = self.dt if dt is None else dt
-        p = lambda a: C.c_void_p(a.ctypes.data)
-        self.dg._torch_ready()
-        for i in range(int(nsteps)):     # each step starts at the running sum, as cmdg_lsrk_run's do
-            _lib.check(self.dg.L.cmdg_ssprk_step(
-                self.dg.handle, Q.data_ptr(), self.Rstage.data_ptr(), self.Qstage.data_ptr(),
-                float(self.t), float(dt), len(self.RKB), p(self.RKA), p(self.RKB),
-                p(self.RKC)), self.dg.handle)
-            _advance(self, 1, dt)
+        _run(self, nsteps, self.dt if dt is None else dt, lambda t, dt: self.dg.L.cmdg_ssprk_step(
+            self.dg.handle, Q.data_ptr(), self.Rstage.data_ptr(), self.Qstage.data_ptr(), t, dt,
+            len(self.RKB), _ptr(self.RKA), _ptr(self.RKB), _ptr(self.RKC)))
 
 
 def _ssp(name):
@@ -157,26 +172,15 @@ class LowStorageRungeKutta3N:
     (LowStorageRungeKutta3NMethod.jl:60-120); the stage loop is ``cmdg_ls3n_step``."""
 
     def __init__(self, dg, RKA, RKB, RKC, Q, dt=0.0, t0=0.0):
-        import numpy as np
         self.dg, self.dt, self.t, self.steps = dg, dt, t0, 0
-        self.RKA = np.ascontiguousarray(RKA, dtype=np.float64)
-        self.RKB = np.ascontiguousarray(RKB, dtype=np.float64)
-        self.RKC = np.ascontiguousarray(RKC, dtype=np.float64)
+        self.RKA, self.RKB, self.RKC = _tableau(RKA), _tableau(RKB), _tableau(RKC)
         self.dQ = dg.create_state(Q.shape[1])
         self.dR = dg.create_state(Q.shape[1])
 
     def dostep(self, Q, nsteps=1, dt=None):
-        import ctypes as C
-        from . import _lib
-        dt = self.dt if dt is None else dt
-        p = lambda a: C.c_void_p(a.ctypes.data)
-        self.dg._torch_ready()
-        for i in range(int(nsteps)):
-            _lib.check(self.dg.L.cmdg_ls3n_step(
-                self.dg.handle, Q.data_ptr(), self.dQ.data_ptr(), self.dR.data_ptr(),
-                float(self.t), float(dt), len(self.RKC), p(self.RKA), p(self.RKB),
-                p(self.RKC)), self.dg.handle)
-            _advance(self, 1, dt)
+        _run(self, nsteps, self.dt if dt is None else dt, lambda t, dt: self.dg.L.cmdg_ls3n_step(
+            self.dg.handle, Q.data_ptr(), self.dQ.data_ptr(), self.dR.data_ptr(), t, dt,
+            len(self.RKC), _ptr(self.RKA), _ptr(self.RKB), _ptr(self.RKC)))
 
 
 def _ls3n(name):
@@ -233,13 +237,10 @@ class AdditiveRungeKutta:
 
     def __init__(self, dg, linear_dg, backward_euler_solver, RKA_explicit, RKA_implicit, RKB, RKC,
                  Q, dt=None, t0=0.0, split_explicit_implicit=False):
-        import numpy as np
-        from .systemsolvers import ColumnLU
         assert dt is not None
         if not isinstance(backward_euler_solver, LinearBackwardEulerSolver):
             raise TypeError("AdditiveRungeKutta: a LinearBackwardEulerSolver(ManyColumnLU()) is needed")
-        A_e = np.ascontiguousarray(RKA_explicit, dtype=np.float64)
-        A_i = np.ascontiguousarray(RKA_implicit, dtype=np.float64)
+        A_e, A_i = _tableau(RKA_explicit), _tableau(RKA_implicit)
         ns = A_e.shape[0]
         diag = [A_i[i, i] for i in range(ns)]
         # LowStorageVariant preconditions (:157-168): diagonal (0, c, ..., c)
@@ -247,8 +248,7 @@ class AdditiveRungeKutta:
             raise ValueError("LowStorageVariant needs an implicit diagonal (0, c, ..., c)")
         self.dg, self.linear_dg = dg, linear_dg
         self.RKA_explicit, self.RKA_implicit = A_e, A_i
-        self.RKB = np.ascontiguousarray(RKB, dtype=np.float64)
-        self.RKC = np.ascontiguousarray(RKC, dtype=np.float64)
+        self.RKB, self.RKC = _tableau(RKB), _tableau(RKC)
         self.split_explicit_implicit = bool(split_explicit_implicit)
         self.dt, self.t, self.steps = float(dt), t0, 0
         self.work = [dg.create_state(Q.shape[1]) for _ in range(2 * ns + 1)]
@@ -265,19 +265,13 @@ class AdditiveRungeKutta:
         self.dt = float(dt)
 
     def dostep(self, Q, nsteps=1, dt=None):
-        from . import _lib
         dt = self.dt if dt is None else dt
         if not self.isadjustable and dt * self._diag != self.lu.alpha:
             _refuse_alpha(self.lu, dt * self._diag)
-        p = lambda a: C.c_void_p(a.ctypes.data)
-        self.dg._torch_ready()
-        for _ in range(int(nsteps)):
-            _lib.check(self.dg.L.cmdg_ark_step(
-                self.dg.handle, self.lu.handle, Q.data_ptr(), C.cast(self._ptrs, C.c_void_p),
-                float(self.t), float(dt), len(self.RKB), p(self.RKA_explicit),
-                p(self.RKA_implicit), p(self.RKB), p(self.RKC),
-                int(self.split_explicit_implicit)), self.linear_dg.handle)
-            _advance(self, 1, dt)
+        _run(self, nsteps, dt, lambda t, dt: self.dg.L.cmdg_ark_step(
+            self.dg.handle, self.lu.handle, Q.data_ptr(), C.cast(self._ptrs, C.c_void_p), t, dt,
+            len(self.RKB), _ptr(self.RKA_explicit), _ptr(self.RKA_implicit), _ptr(self.RKB),
+            _ptr(self.RKC), int(self.split_explicit_implicit)), self.linear_dg.handle)
 
     def close(self):
         self.lu.close()
@@ -305,7 +299,6 @@ def _rt(rows):
 
 def _isapprox(a, b, rtol=math.sqrt(2.0 ** -52), atol=0.0):
     """Julia's ``isapprox`` (default rtol sqrt(eps)), on scalars or on arrays through the norm."""
-    import numpy as np
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     d = float(np.linalg.norm((a - b).ravel()))
     return d <= max(atol, rtol * max(float(np.linalg.norm(a.ravel())), float(np.linalg.norm(b.ravel()))))
@@ -411,7 +404,6 @@ def _esdirk23lsa(delta=0):
 def esdirk24lsa_base(gamma=0.2, c3=None, a32=0.2, alpha=-0.1, beta1=None, beta2=None):
     """The L-stable, stiffly accurate ESDIRK behind ``MRIGARKESDIRK24LSA`` and its GARK table:
     ``(A, Δc, Γ0)``, with the reference's checks."""
-    import numpy as np
     g = gamma
     c3 = (2 * g + 1) / 2 if c3 is None else c3
     beta1 = c3 / 10 if beta1 is None else beta1
@@ -479,7 +471,6 @@ def mrigark_explicit_coefficients(Gs, ghats):
     """``MRIGARKExplicit``'s constructor: ``Δc = rowsum(Γ_0)``, ``Γ_k ./ Δc`` and ``γ̂_k / Δc[end]``
     (exact when the tables are rational), then Float64.  Returns ``(Γs, γ̂s, Δc)`` as numpy
     arrays."""
-    import numpy as np
     dc = [_rowsum(r) for r in Gs[0]]
     G = np.array([[[float(x / dc[i]) for x in row] for i, row in enumerate(Gk)] for Gk in Gs])
     gh = np.array([[float(x / dc[-1]) for x in g] for g in ghats])
@@ -490,7 +481,6 @@ def mrigark_implicit_coefficients(Gs, ghats):
     """``MRIGARKDecoupledImplicit``'s constructor: ``Δc = rowsum(Γ_0)`` (exact when rational), the
     even rows' sums 0 to ``2 eps``, the odd rows' kept; ``Γ_k`` and ``γ̂_k`` as given, in Float64.
     Returns ``(Γs, γ̂s, Δc)`` as numpy arrays."""
-    import numpy as np
     dc = [float(_rowsum(r)) for r in Gs[0]]
     if not all(abs(x) <= 2 * 2.0 ** -52 for x in dc[1::2]):
         raise ValueError("MRIGARKDecoupledImplicit: the implicit rows of Gamma_0 must sum to 0")
@@ -529,8 +519,6 @@ class _MRIGARK:
     KIND = None
 
     def _setup(self, slow_rhs, fastsolver, G, gh, dc, Q, dt, t0, lu=None, adjustable=True):
-        import numpy as np
-        from . import _lib
         self.slow_rhs, self.fastsolver = slow_rhs, fastsolver
         self.Gammas, self.gammahats, self.dc = G, gh, dc
         self.dt, self.t, self.steps = float(dt), float(t0), 0
@@ -543,11 +531,8 @@ class _MRIGARK:
         ptrs = [r.data_ptr() for r in self.Rstages] + [fastsolver.dQ.data_ptr(),
                                                         self.Qhat.data_ptr() if self.Qhat is not None else 0]
         self._work = (C.c_void_p * len(ptrs))(*ptrs)
-        self._G = np.ascontiguousarray(G, dtype=np.float64)
-        self._dc = np.ascontiguousarray(dc, dtype=np.float64)
-        self._fa = np.ascontiguousarray(fastsolver.RKA, dtype=np.float64)
-        self._fb = np.ascontiguousarray(fastsolver.RKB, dtype=np.float64)
-        self._fc = np.ascontiguousarray(fastsolver.RKC, dtype=np.float64)
+        self._G, self._dc = _tableau(G), _tableau(dc)
+        self._fa, self._fb, self._fc = (_tableau(x) for x in (fastsolver.RKA, fastsolver.RKB, fastsolver.RKC))
         d = _lib.CmdgMrigarkDesc()
         d.kind, d.nstages, d.ngamma = self.KIND, ns, self._G.shape[0]
         d.gamma, d.dc = self._G.ctypes.data, self._dc.ctypes.data
@@ -561,21 +546,20 @@ class _MRIGARK:
         self.dt = float(dt)
 
     def dostep(self, Q, nsteps=1, dt=None):
-        from . import _lib
-        dt = self.dt if dt is None else dt
         self._desc.fast_dt = float(self.fastsolver.dt)
-        self.dg._torch_ready()
         lu = self.lu.handle if self.lu is not None else None
-        for _ in range(int(nsteps)):
-            _lib.check(self.dg.L.cmdg_mrigark_step(
+
+        def step(t, dt):
+            rc = self.dg.L.cmdg_mrigark_step(
                 self._slow[0], self._slow[1], self._fast[0], self._fast[1], lu, C.byref(self._desc),
-                Q.data_ptr(), C.cast(self._work, C.c_void_p), float(self.t), float(dt)), self._slow[0])
-            # the fast solver's clock ends at the last stage's end (updatetime! in solve!)
-            ts = self.t
-            for c in self.dc:
-                ts += c * dt
-            self.fastsolver.t = ts
-            _advance(self, 1, dt)
+                Q.data_ptr(), C.cast(self._work, C.c_void_p), t, dt)
+            if rc == 0:
+                # the fast solver's clock ends at the last stage's end (updatetime! in solve!)
+                for c in self.dc:
+                    t += c * dt
+                self.fastsolver.t = t
+            return rc
+        _run(self, nsteps, self.dt if dt is None else dt, step)
 
     def close(self):
         if self.lu is not None:
@@ -607,7 +591,6 @@ class MRIGARKDecoupledImplicit(_MRIGARK):
 
     def __init__(self, slow_rhs, backward_euler_solver, fastsolver, Gammas, gammahats, Q, dt, t0=0.0):
         from .dgmodel import RemainderDGModel
-        from .systemsolvers import ColumnLU
         _fast_solver(fastsolver, "MRIGARKDecoupledImplicit")
         if not isinstance(backward_euler_solver, LinearBackwardEulerSolver):
             raise TypeError("MRIGARKDecoupledImplicit: a LinearBackwardEulerSolver(ManyColumnLU()) is needed")

@@ -780,7 +780,8 @@ int cmdg_columnlu_destroy(cmdg_columnlu_handle lu);
  * Qhat, Qtt).  split_explicit_implicit != 0: the explicit operator is full minus linear,
  * evaluated as `full` followed by `linear` with alpha = -1 and increment.  The solver is refactored
  * when dt a_ii differs from its alpha.  `full` and `linear` must have the same state count
- * (CMDG_ERR_INVALID otherwise).  Returns after the step has finished. */
+ * (CMDG_ERR_INVALID otherwise).  A failure's message is on both handles.  Returns after the step
+ * has finished. */
 int cmdg_ark_step(cmdg_handle full, cmdg_columnlu_handle lu, double *Q, double *const *work, double t,
                   double dt, int32_t nstages, const double *rka_explicit, const double *rka_implicit,
                   const double *rkb, const double *rkc, int32_t split_explicit_implicit);

@@ -1,5 +1,5 @@
 """IMEX stepping on the bench-size Held-Suarez state: ARK2GiraldoKellyConstantinescu with
-LinearBackwardEulerSolver(ManyColumnLU()) (csrc/columnlu.hip) against explicit LSRK54.
+LinearBackwardEulerSolver(ManyColumnLU()) (csrc/columnlu.hip, the step in csrc/steppers.hip) against explicit LSRK54.
 6 x 30 x 30 x 8 = 43 200 elements, N = 4; the full physics as bench.py builds it (hyperdiffusion,
 Gravity, Coriolis, Held-Suarez forcing) and AtmosAcousticGravityLinearModel on the same auxiliary
 state.  Prints one JSON line.

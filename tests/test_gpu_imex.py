@@ -1,5 +1,5 @@
 """IMEX stepping on the device: AtmosAcousticGravityLinearModel (csrc/physics_atmos_linear.h),
-ManyColumnLU (csrc/columnlu.hip) and ARK2GiraldoKellyConstantinescu with
+ManyColumnLU (csrc/columnlu.hip) and ARK2GiraldoKellyConstantinescu (csrc/steppers.hip) with
 LinearBackwardEulerSolver(ManyColumnLU()) -- the Held-Suarez solver configuration of
 experiments/AtmosGCM/heldsuarez.jl:234-240 and the parity pin of
 test/Numerics/DGMethods/Euler/acousticwave_1d_imex.jl."""

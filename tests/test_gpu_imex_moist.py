@@ -164,6 +164,8 @@ def test_moist_linear_counts_and_refusals(cm, torch):
                                                 Q, dt=1.0)
     with pytest.raises(cm._lib.CmdgError, match="5 states, the linear model 6"):
         solver.dostep(Q, 1)
+    for h in (dry.handle, lin.handle):     # the refusal is on both members of the step
+        assert b"5 states, the linear model 6" in L.cmdg_last_error(h)
     solver.close()
     dry.close()
     lin.close()

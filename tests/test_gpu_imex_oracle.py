@@ -1,6 +1,6 @@
 """The device IMEX path against the oracle: the linear law's tendency (csrc/physics_atmos_linear.h
 vs oracle/physics_atmos_linear.c), the column band's assembly, factorisation and solve
-(csrc/columnlu.hip vs oracle.probe_band / band_lu / band_forward / band_back) and cmdg_ark_step
+(csrc/columnlu.hip vs oracle.probe_band / band_lu / band_forward / band_back) and cmdg_ark_step (csrc/steppers.hip)
 vs oracle.ark_step.  Errors are per state (rho, rho u, rho e), each against its own max-norm."""
 import ctypes as C
 

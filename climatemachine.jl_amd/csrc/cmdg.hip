@@ -221,6 +221,7 @@ EngineBase::~EngineBase()
     if (own_hd && hypdiv) hipFree(hypdiv);
     if (W[0]) hipFree(W[0]);
     if (W[1]) hipFree(W[1]);
+    if (garg) hipFree(garg);
     if (d_D) hipFree(d_D);
     if (d_interior_tiled) hipFree(d_interior_tiled);
     if (d_exterior_tiled) hipFree(d_exterior_tiled);
@@ -494,6 +495,19 @@ int EngineBase::ensure_work()
             HIPCHK(hipMemsetAsync(W[i], 0, sizeof(double) * n, s_comp));
             HIPCHK(hipStreamSynchronize(s_comp));
         }
+    return CMDG_OK;
+}
+
+// the records of CMDG_OPT_GRADARG_HANDOFF, allocated by the first run that uses them: the fill is
+// stream-ordered before the run's launches like that of the work states
+int EngineBase::ensure_garg()
+{
+    if (!garg) {
+        const size_t n = std::max<size_t>((size_t)Np * ngl * nelem, 1);
+        HIPCHK(hipMalloc(&garg, sizeof(double) * n));
+        HIPCHK(hipMemsetAsync(garg, 0, sizeof(double) * n, s_comp));
+        HIPCHK(hipStreamSynchronize(s_comp));
+    }
     return CMDG_OK;
 }
 
@@ -1087,6 +1101,11 @@ int group_lsrk_step(std::vector<EngineBase *> &g, double **Q, double **dQ, doubl
             x.update_after = !fused;
             x.rkb_dt = rkb[s] * dt;
             x.rka_next = rka[(s + 1) % nstages];
+            // CMDG_OPT_GRADARG_HANDOFF: every evaluation of a run but the first reads the gradient
+            // arguments the update before it left, every update but the last leaves them
+            const int ho = g[i]->handoff_step;
+            x.garg_in = (ho & 1) && !((ho & 2) && s == 0);
+            x.garg_out = (ho & 1) && !((ho & 4) && s == nstages - 1);
         }
         if (int r = group_rhs(g, c, s > 0 || continued)) return r;
     }
@@ -1206,6 +1225,7 @@ int EngineBase::run_steps(double *Q, double *dQ, double t, double dt, int64_t ns
 {
     // (the step times accumulate as the reference's updatetime! does: t += dt, ODESolvers.jl:96-98)
     int64_t i = 0;
+    handoff_used = false;
     if (nsteps >= 2 && nstages <= 16 && graph_eligible()) {
         if (int r = lsrk_step(Q, dQ, t, dt, nstages, rka, rkb, rkc, false)) return r;  // eager: packs Q
         t += dt;
@@ -1245,8 +1265,18 @@ int EngineBase::run_steps(double *Q, double *dQ, double t, double dt, int64_t ns
             if (int r = lsrk_step(Q, dQ, t, dt, nstages, rka, rkb, rkc, false)) return r;
         return CMDG_OK;
     }
-    for (; i < nsteps; ++i, t += dt)
-        if (int r = lsrk_step(Q, dQ, t, dt, nstages, rka, rkb, rkc, i > 0)) return r;
+    // the hand-off of the gradient arguments lives inside one run: its first evaluation and its
+    // last update are the existing kernels, so nothing is carried over from or into another call
+    const bool ho = handoff_eligible() && nsteps * nstages >= 2;
+    handoff_used = ho;
+    if (ho)
+        if (int r = ensure_garg()) return r;
+    for (; i < nsteps; ++i, t += dt) {
+        handoff_step = ho ? (1 | (i == 0 ? 2 : 0) | (i == nsteps - 1 ? 4 : 0)) : 0;
+        const int r = lsrk_step(Q, dQ, t, dt, nstages, rka, rkb, rkc, i > 0);
+        handoff_step = 0;
+        if (r) return r;
+    }
     return CMDG_OK;
 }
 
@@ -2187,6 +2217,7 @@ int cmdg_set_option(cmdg_handle h, int32_t option, int32_t value)
         return CMDG_OK;
     case CMDG_OPT_TENDENCY_PAIRS:
     case CMDG_OPT_TENDENCY_FOUR_WAVES: return CMDG_OK;  // retired: no effect
+    case CMDG_OPT_GRADARG_HANDOFF: e->gradarg_handoff = value != 0; return CMDG_OK;
     case CMDG_OPT_HALO_PIPELINE:
         if (int r = e->synchronize()) return set_err(h, r);
         e->drop_graph();
@@ -2212,6 +2243,7 @@ int cmdg_query(cmdg_handle h, int32_t what, int64_t *out)
     case CMDG_Q_TENDENCY_ELEMS_PER_GROUP: *out = e->tendency_epb(); return CMDG_OK;
     case CMDG_Q_GRAPH_STEPS: *out = e->graph_steps; return CMDG_OK;
     case CMDG_Q_TENDENCY_PAIRS: *out = -1; return CMDG_OK;  // retired option: always off
+    case CMDG_Q_GRADARG_HANDOFF: *out = e->handoff_used; return CMDG_OK;
     case CMDG_Q_HOST_POST_NS: *out = e->host_post_ns; return CMDG_OK;
     case CMDG_Q_HOST_POST_COUNT: *out = e->host_post_n; return CMDG_OK;
     case CMDG_Q_HALO_PIPELINE:

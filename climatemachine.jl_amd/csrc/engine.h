@@ -46,6 +46,9 @@ struct RhsCtx {
     const double *tptr = nullptr;  // time in device memory instead (captured steps)
     bool lsrk = false;         // fused update inside k_tendency
     bool update_after = false; // separate update!() after the (filtered) tendency
+    // CMDG_OPT_GRADARG_HANDOFF, set by cmdg_lsrk_run alone: the gradient pass reads the records the
+    // previous stage's update left / the fused update leaves them for the next stage
+    bool garg_in = false, garg_out = false;
     double rkb_dt = 0, rka_next = 0;
     // the law's update_auxiliary_state!(realelems) composition has run already (group_rhs runs the
     // nested operators of a local group in lock step before segment 0)
@@ -192,6 +195,22 @@ struct EngineBase {
     HaloSlot slot[NSLOT];
     int slot_nvar_max = 0;
     double *W[2] = {nullptr, nullptr};  // LSRK work states
+    // ---- CMDG_OPT_GRADARG_HANDOFF (kernels.h GradArgHandoff) --------------------------------
+    // (ngl, Np, nelem) gradient arguments of the next stage's input, written by the fused update
+    // and read by the next gradient pass of the same cmdg_lsrk_run; never trusted across calls
+    double *garg = nullptr;
+    bool gradarg_handoff = true;   // the option
+    bool handoff_used = false;     // did the last cmdg_lsrk_run use it (cmdg_query)
+    // the step cmdg_lsrk_run is enqueuing: bit 0 hand-off on, bit 1 first step, bit 2 last step of the run
+    int handoff_step = 0;
+    virtual bool garg_capable() const = 0;  // the law and order have the two instantiations
+    bool handoff_eligible() const
+    {
+        return gradarg_handoff && garg_capable() && !gf_live() && ngl > 0 && has_update_aux() &&
+               fused_update_aux() && !has_hooks && !step_filter && !tendency_filter && !gradient_filter &&
+               !step_graph && nghost == 0 && !communicate();
+    }
+    int ensure_garg();
     double *d_partial = nullptr;        // reduction scratch
     int transport = TRANSPORT_NONE;
     int rank = 0, nranks = 1;
@@ -513,6 +532,7 @@ struct EngineT : EngineBase {
         a.hypdiv = hypdiv;
         a.tendency = c.tendency;
         a.Qout = c.Qout;
+        a.garg = garg;
         a.t = c.t;
         a.tptr = c.tptr;
         a.alpha = c.alpha;
@@ -534,7 +554,12 @@ struct EngineT : EngineBase {
         PassArgs<P> args = make_args(c, elems, n, diffusion_direction);
         args.h = halo_dev(exterior, gf_live() ? slot[SLOT_GF].sendbuf : nullptr,
                           ngl > 0 ? slot[SLOT_HG].sendbuf : nullptr);
-        if (gf_live())
+        constexpr bool HO = GradArgHandoff<P, NQ_, NQV_>::value;
+        if (HO && c.garg_in) {  // (handoff_eligible: no gradient flux, no ghosts)
+            if constexpr (HO)
+                hipLaunchKernelGGL((k_gradients<P, NQ_, NQV_, false, true>), dim3((unsigned)n),
+                                   dim3(KDims<NQ_, NQV_>::NT), 0, st, args);
+        } else if (gf_live())
             hipLaunchKernelGGL((k_gradients<P, NQ_, NQV_, true>), dim3((unsigned)n), dim3(KDims<NQ_, NQV_>::NT), 0,
                                st, args);
         else
@@ -587,7 +612,11 @@ struct EngineT : EngineBase {
         else                                                                                       \
             hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, L, G, false>), grid, block, 0, st, args); \
     } while (0)
-        if (c.lsrk) {
+        constexpr bool HO = GradArgHandoff<P, NQ_, NQV_>::value;
+        if (HO && c.garg_out) {  // (handoff_eligible: fused update, no gradient flux, no ghosts)
+            if constexpr (HO)
+                hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, true, false, false, true>), grid, block, 0, st, args);
+        } else if (c.lsrk) {
             if (gfl) CMDG_TEND(true, true);
             else CMDG_TEND(true, false);
         } else {
@@ -626,6 +655,14 @@ struct EngineT : EngineBase {
     bool law_needs_gradflux() const override { return P::needs_gradflux(prm); }
     bool gf_node_major() const override { return cmdg::gf_node_major<P>::value; }
     bool fused_update_aux() const override { return P::HAS_UPDATE_AUX && P::FUSE_UPDATE_AUX; }
+    bool garg_capable() const override
+    {
+#ifdef CMDG_GF_ALWAYS
+        return false;
+#else
+        return GradArgHandoff<P, NQ_, NQV_>::value && !P::needs_gradflux(prm);
+#endif
+    }
     int law_nder() const override { return P::HAS_SOURCE ? P::NDER : 0; }
     int law_nupd() const override { return P::HAS_UPDATE_AUX ? P::NUPD : 0; }
     int tendency_epb() const override { return TendencyShape<P, NQ_, NQV_>::EPB; }

@@ -62,6 +62,7 @@ struct PassArgs {
     double *hypdiv;    // Qhypervisc_div
     double *tendency;  // tendency (== dQ when the LSRK update is fused)
     double *Qout;      // LSRK: updated state
+    double *garg;      // gradient arguments handed from a fused update to the next stage (GradArgHandoff)
     double t, alpha, beta;
     const double *tptr;  // time of the evaluation in device memory (a captured step is replayed
                          // with the time a one-thread kernel of the graph advances); NULL: t
@@ -393,6 +394,34 @@ struct TendencyShape {
 };
 
 // ---------------------------------------------------------------------------------
+// Hand-off of the gradient arguments inside cmdg_lsrk_run.  The input of stage s+1 is the Q+ the
+// fused update of stage s holds in LDS, and P::gradient_argument is a pure function of the node's
+// (Q, aux) whose time argument is unused.  A law that says `static constexpr bool GRADARG_HANDOFF =
+// true` gets two more instantiations: k_tendency<..., GARG_OUT> evaluates the argument of Q+ once
+// per node, stores the entries the USE_GF = false gradient pass consumes (those of
+// gradient_argument_mask<P, false>(), entry s = G[hv_indexmap(s)]) as one record per node in a
+// library-owned array, node-major like Qhypervisc_grad -- (NGL, Np, nelem) -- and does the nodal
+// auxiliary refresh for Q+; k_gradients<..., GARG_IN> of the next stage reads and gathers those
+// records instead of 9 columns of Q / aux per node and per interior face node.  Same expressions on
+// the same operands: every bit downstream is unchanged.  One element per work-group only.
+template <class P, class = void>
+struct law_gradarg_handoff : std::false_type {
+};
+template <class P>
+struct law_gradarg_handoff<P, std::void_t<decltype(P::GRADARG_HANDOFF)>>
+    : std::integral_constant<bool, P::GRADARG_HANDOFF && (P::NGL > 0) && P::HAS_UPDATE_AUX && P::FUSE_UPDATE_AUX> {
+};
+template <class P, int NQ, int NQV>
+struct GradArgHandoff {
+    static constexpr bool value = law_gradarg_handoff<P>::value && TendencyShape<P, NQ, NQV>::EPB == 1;
+};
+template <int NGL, int Np>
+__device__ __forceinline__ int64_t garg_at(int n, int64_t e)
+{
+    return (int64_t)NGL * (n + (int64_t)Np * e);
+}
+
+// ---------------------------------------------------------------------------------
 // Tendency pass: volume_tendency! (:64-548) + dgsem_interface_tendency! (:588-901),
 // optionally fused with the LSRK update! (LowStorageRungeKuttaMethod.jl:146-158).
 // RECV: the plus side of ghost neighbours comes from the receive buffers (exterior launches of a
@@ -404,9 +433,14 @@ struct TendencyShape {
 // arithmetic (METRICS_FIRST), and the old tendency of all states in one batch ahead of the
 // contraction instead of one dependent load per state inside it (profiles/r04_ab_tendency_hoist.txt;
 // gathering every plus-side value of a face node before the first-order flux lost).
-template <class P, int NQ, int NQV, bool LSRK, bool USE_GF, bool RECV = false>
+// GARG_OUT: the fused update also forms the next stage's gradient arguments and refreshes the
+// nodal auxiliary state for Q+ (GradArgHandoff).  The auxiliary columns both need are dead in
+// registers by then: they are loaded again after the face phase, in flight across the lift.
+template <class P, int NQ, int NQV, bool LSRK, bool USE_GF, bool RECV = false, bool GARG_OUT = false>
 __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
 {
+    static_assert(!GARG_OUT || (LSRK && !USE_GF && !RECV && TendencyShape<P, NQ, NQV>::EPB == 1),
+                  "the hand-off rides in the fused update of single-rank handles");
     using KD = KDims<NQ, NQV>;
     const double a_t = a.tptr ? *a.tptr : a.t;  // (uniform: one scalar load)
     using SH = TendencyShape<P, NQ, NQV>;
@@ -711,6 +745,10 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
             fpair = f / 2;
         }
     }
+    Vec<NAUX> gaux;  // (the compiler drops the columns neither function reads)
+    if constexpr (GARG_OUT) {
+        if (live && tid < Np) load_state<NAUX, Np>(gaux, a.aux, tid, e);
+    }
     __syncthreads();
 #pragma unroll
     for (int p = 0; p < 3; ++p) {  // opposite faces touch disjoint nodes (:898-899)
@@ -721,16 +759,31 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
         __syncthreads();
     }
     if (live && tid < Np) {
+        Vec<NS> Qn;  // the updated state of this node
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             const int64_t o = tid + (int64_t)Np * (s + (int64_t)NS * e);
             const double T = sT[s * Np + tid];
             if constexpr (LSRK) {  // update!: Q += rkb*dt*dQ; dQ *= rka
-                a.Qout[o] = sQ[s * Np + tid] + a.rkb_dt * T;
+                Qn[s] = sQ[s * Np + tid] + a.rkb_dt * T;
+                a.Qout[o] = Qn[s];
                 a.tendency[o] = T * a.rka_next;
             } else {
                 a.tendency[o] = T;
             }
+        }
+        if constexpr (GARG_OUT) {
+            Vec<P::NGRAD> G;
+            G.negzero();
+            P::gradient_argument(a.prm, G, Qn, gaux, a_t);
+            double *rec = a.garg + garg_at<P::NGL, Np>(tid, e);
+#pragma unroll
+            for (int s = 0; s < P::NGL; ++s) rec[s] = G[P::hv_indexmap(s)];
+            // kernel_nodal_update_auxiliary_state! for the next evaluation's input
+            P::update_aux(a.prm, Qn, gaux, a_t);
+#pragma unroll
+            for (int s = 0; s < P::NUPD; ++s)
+                a.aux_rw[tid + (int64_t)Np * (P::upd_aux(s) + (int64_t)NAUX * e)] = gaux[P::upd_aux(s)];
         }
     }
     if constexpr (LSRK) {  // the updated state of the nodes of vmapsend, straight to the send buffer
@@ -740,10 +793,10 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
             });
     }
 }
-template <class P, int NQ, int NQV, bool LSRK, bool USE_GF, bool RECV = false>
+template <class P, int NQ, int NQV, bool LSRK, bool USE_GF, bool RECV = false, bool GARG_OUT = false>
 __global__ void __launch_bounds__((TendencyShape<P, NQ, NQV>::NT), CMDG_TEND_MINW) k_tendency(const PassArgs<P> a)
 {
-    tendency_body<P, NQ, NQV, LSRK, USE_GF, RECV>(a);
+    tendency_body<P, NQ, NQV, LSRK, USE_GF, RECV, GARG_OUT>(a);
 }
 
 // ---------------------------------------------------------------------------------
@@ -760,7 +813,10 @@ __host__ __device__ constexpr unsigned gradient_argument_mask()
     return m;
 }
 
-template <class P, int NQ, int NQV = NQ, bool USE_GF = true>
+// GARG_IN (GradArgHandoff): the arguments of the volume nodes and of the plus side of interior
+// faces are read from the records the previous stage's fused update left; boundary faces keep
+// boundary_state on the element's own Q / aux; no auxiliary refresh (the update did it).
+template <class P, int NQ, int NQV = NQ, bool USE_GF = true, bool GARG_IN = false>
 // (six-wave work-groups of the large elements share a CU only at <= 128 VGPRs, see TendencyShape;
 // a launch bound of 1024 threads is the hard form of that request)
 __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LARGE : KDims<NQ, NQV>::NT),
@@ -771,6 +827,7 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
     constexpr int Np = KD::Np, NS = P::NS, NAUX = P::NAUX, NGRAD = P::NGRAD,
                   NGF = USE_GF ? P::NGF : 0, NGL = P::NGL, NHG = 3 * NGL, NACC = NGF + NHG;
     constexpr unsigned GMASK = gradient_argument_mask<P, USE_GF>();
+    static_assert(!GARG_IN || (!USE_GF && NGL > 0), "the hand-off feeds the USE_GF = false pass");
     __shared__ double sD[NQ * NQ + (NQV == NQ ? 0 : NQV * NQV)];
     const double *const sDv = sD + (NQV == NQ ? 0 : NQ * NQ);  // vertical derivative matrix
     __shared__ double sG[(NGRAD > 0 ? NGRAD : 1) * Np];
@@ -784,7 +841,13 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
     const bool hz = a.direction != DIR_VERTICAL, vt = a.direction != DIR_HORIZONTAL;
     Vec<NS> lQ;
     Vec<NAUX> laux;
-    if (tid < Np) {
+    if constexpr (GARG_IN) {
+        if (tid < Np) {
+            const double *rec = a.garg + garg_at<NGL, Np>(tid, e);
+#pragma unroll
+            for (int s = 0; s < NGL; ++s) sG[P::hv_indexmap(s) * Np + tid] = rec[s];
+        }
+    } else if (tid < Np) {
         load_state<NS, Np>(lQ, a.Q, tid, e);
         load_state<NAUX, Np>(laux, a.aux, tid, e);
         if constexpr (P::HAS_UPDATE_AUX && P::FUSE_UPDATE_AUX) {
@@ -888,8 +951,10 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
             Vec<NS> QM, QP;
             Vec<NAUX> auxM, auxP;
             Vec<NGRAD> GM, GP;
-            load_state<NS, Np>(QM, a.Q, fp.vidM, e);       // only kept if the law reads them
-            load_state<NAUX, Np>(auxM, a.aux, fp.vidM, e);  // (gradient_flux / boundary_state)
+            if constexpr (!GARG_IN) {
+                load_state<NS, Np>(QM, a.Q, fp.vidM, e);       // only kept if the law reads them
+                load_state<NAUX, Np>(auxM, a.aux, fp.vidM, e);  // (gradient_flux / boundary_state)
+            }
 #pragma unroll
             for (int s = 0; s < NGRAD; ++s)
                 GM[s] = (GMASK >> s & 1) ? sG[s * Np + fp.vidM] : 0.0;  // == G(Q-, aux-)
@@ -900,10 +965,16 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
             if (fp.bctag == 0) {  // CentralNumericalFluxGradient  NumericalFluxes.jl:67-83
                 // the plus side is read inside the branch that uses it: of the neighbour's
                 // auxiliary columns only those the law's gradient argument touches are gathered
-                load_plus<NS, Np, NS>(QP, a.Q, a.h.recvQ, ghost_slot<Np>(a.h, fp.eP, fp.vidP), fp.vidP,
-                                      fp.eP);
-                load_state<NAUX, Np>(auxP, a.aux, fp.vidP, fp.eP);
-                P::gradient_argument(a.prm, GP, QP, auxP, a_t);
+                if constexpr (GARG_IN) {
+                    const double *rec = a.garg + garg_at<NGL, Np>(fp.vidP, fp.eP);
+#pragma unroll
+                    for (int s = 0; s < NGL; ++s) GP[P::hv_indexmap(s)] = rec[s];
+                } else {
+                    load_plus<NS, Np, NS>(QP, a.Q, a.h.recvQ, ghost_slot<Np>(a.h, fp.eP, fp.vidP), fp.vidP,
+                                          fp.eP);
+                    load_state<NAUX, Np>(auxP, a.aux, fp.vidP, fp.eP);
+                    P::gradient_argument(a.prm, GP, QP, auxP, a_t);
+                }
 #pragma unroll
                 for (int s = 0; s < NGRAD; ++s)
 #pragma unroll
@@ -911,6 +982,10 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
             } else {  // numerical_boundary_flux_gradient!  NumericalFluxes.jl:85-123
                 // e+ = e-, vid+ = vid- on boundary faces (:686-692): the plus side starts as
                 // a copy of the minus side, already loaded
+                if constexpr (GARG_IN) {
+                    load_state<NS, Np>(QM, a.Q, fp.vidM, e);
+                    load_state<NAUX, Np>(auxM, a.aux, fp.vidM, e);
+                }
 #pragma unroll
                 for (int s = 0; s < NS; ++s) QP[s] = QM[s];
 #pragma unroll

@@ -60,6 +60,9 @@ struct DryAtmos {
     static constexpr bool FUSE_UPDATE_AUX = true;
     static constexpr int NUPD = 2;
     __host__ __device__ static constexpr int upd_aux(int i) { return OMOIST + i; }
+    // gradient_argument and update_aux are pure functions of the node's (Q, aux): inside
+    // cmdg_lsrk_run the fused update may form both for the next stage (kernels.h GradArgHandoff)
+    static constexpr bool GRADARG_HANDOFF = true;
     static constexpr bool HAS_SOURCE = true;
     // sin / cos of the latitude (heldsuarez.jl:134,147-149 recomputes them every call; they
     // only depend on aux.coord, so they are evaluated once with the same libm calls)

@@ -252,12 +252,21 @@ int cmdg_synchronize(cmdg_handle h);
  *   stream priority, -1 at the lowest.  Meant for a handle whose launches are small and form a long dependent chain
  *   next to another handle's bandwidth-bound launches (the barotropic model of the split-explicit
  *   ocean, whose sub-steps decide the length of a slow stage).  The handle must be idle; results
- *   do not depend on it. */
+ *   do not depend on it.
+ * CMDG_OPT_GRADARG_HANDOFF (default 1): inside cmdg_lsrk_run the fused update of a stage also forms
+ *   the gradient arguments of the updated state and does the nodal update_auxiliary_state! for
+ *   it, and the next stage's gradient pass reads those records instead of Q and state_auxiliary.
+ *   Taken only by single-rank handles (no ghost elements) of a law whose gradient-flux state is
+ *   not formed, with hyperdiffusion and a fused nodal refresh (Held-Suarez), without hooks,
+ *   filters or CMDG_OPT_STEP_GRAPH; the first evaluation and the last update of every run are the
+ *   ordinary kernels, so nothing is carried from one call to the next.  Q, dQ and every column
+ *   of state_auxiliary end a run bit-identical.  cmdg_query(CMDG_Q_GRADARG_HANDOFF) says whether
+ *   the last run used it. */
 enum {
     CMDG_OPT_KEEP_GRADFLUX = 1, CMDG_OPT_STACK_HEIGHT = 2, CMDG_OPT_REFERENCE_HALO = 3,
     CMDG_OPT_HALO_PIPELINE = 4, CMDG_OPT_STEP_GRAPH = 5, CMDG_OPT_STREAM_PRIORITY = 6,
     CMDG_OPT_TENDENCY_PAIRS = 7 /* retired */, CMDG_OPT_ASYNC_RUN = 8,
-    CMDG_OPT_TENDENCY_FOUR_WAVES = 9 /* retired */
+    CMDG_OPT_TENDENCY_FOUR_WAVES = 9 /* retired */, CMDG_OPT_GRADARG_HANDOFF = 10
 };
 int cmdg_set_option(cmdg_handle h, int32_t option, int32_t value);
 
@@ -281,6 +290,7 @@ enum {
     CMDG_Q_HOST_POST_COUNT = 11, /* ... and how many were posted, since the handle was created */
     CMDG_Q_GRAPH_STEPS = 12,     /* steps cmdg_lsrk_run replayed from a captured graph */
     CMDG_Q_TENDENCY_PAIRS = 13,  /* retired with CMDG_OPT_TENDENCY_PAIRS: always -1 (option off) */
+    CMDG_Q_GRADARG_HANDOFF = 14, /* did the last cmdg_lsrk_run use CMDG_OPT_GRADARG_HANDOFF */
     CMDG_Q_STATE_READ = 16, CMDG_Q_AUX_READ = 20
 };
 int cmdg_query(cmdg_handle h, int32_t what, int64_t *out);

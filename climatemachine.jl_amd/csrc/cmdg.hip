@@ -1106,6 +1106,11 @@ int group_lsrk_step(std::vector<EngineBase *> &g, double **Q, double **dQ, doubl
             const int ho = g[i]->handoff_step;
             x.garg_in = (ho & 1) && !((ho & 2) && s == 0);
             x.garg_out = (ho & 1) && !((ho & 4) && s == nstages - 1);
+            // the auxiliary refresh is seen only after the run's last hand-off update: stage
+            // nstages - 2 of the last step.  (A one-stage tableau has it in the step before the
+            // last; it refreshes in every update.)
+            x.garg_refresh = !g[i]->refresh_elidable() || nstages == 1 || ((ho & 4) && s == nstages - 2);
+            if (x.garg_out && x.garg_refresh) g[i]->handoff_refreshes += 1;
         }
         if (int r = group_rhs(g, c, s > 0 || continued)) return r;
     }
@@ -1226,6 +1231,7 @@ int EngineBase::run_steps(double *Q, double *dQ, double t, double dt, int64_t ns
     // (the step times accumulate as the reference's updatetime! does: t += dt, ODESolvers.jl:96-98)
     int64_t i = 0;
     handoff_used = false;
+    handoff_refreshes = 0;
     if (nsteps >= 2 && nstages <= 16 && graph_eligible()) {
         if (int r = lsrk_step(Q, dQ, t, dt, nstages, rka, rkb, rkc, false)) return r;  // eager: packs Q
         t += dt;
@@ -2244,6 +2250,7 @@ int cmdg_query(cmdg_handle h, int32_t what, int64_t *out)
     case CMDG_Q_GRAPH_STEPS: *out = e->graph_steps; return CMDG_OK;
     case CMDG_Q_TENDENCY_PAIRS: *out = -1; return CMDG_OK;  // retired option: always off
     case CMDG_Q_GRADARG_HANDOFF: *out = e->handoff_used; return CMDG_OK;
+    case CMDG_Q_GRADARG_REFRESHES: *out = e->handoff_refreshes; return CMDG_OK;
     case CMDG_Q_HOST_POST_NS: *out = e->host_post_ns; return CMDG_OK;
     case CMDG_Q_HOST_POST_COUNT: *out = e->host_post_n; return CMDG_OK;
     case CMDG_Q_HALO_PIPELINE:

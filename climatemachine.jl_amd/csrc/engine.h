@@ -49,6 +49,9 @@ struct RhsCtx {
     // CMDG_OPT_GRADARG_HANDOFF, set by cmdg_lsrk_run alone: the gradient pass reads the records the
     // previous stage's update left / the fused update leaves them for the next stage
     bool garg_in = false, garg_out = false;
+    // ... and that update also does the nodal auxiliary refresh (always, unless the law lets the
+    // unobservable ones go: refresh_elidable)
+    bool garg_refresh = true;
     double rkb_dt = 0, rka_next = 0;
     // the law's update_auxiliary_state!(realelems) composition has run already (group_rhs runs the
     // nested operators of a local group in lock step before segment 0)
@@ -201,9 +204,12 @@ struct EngineBase {
     double *garg = nullptr;
     bool gradarg_handoff = true;   // the option
     bool handoff_used = false;     // did the last cmdg_lsrk_run use it (cmdg_query)
+    int64_t handoff_refreshes = 0; // hand-off updates of the last run that carried the auxiliary refresh
     // the step cmdg_lsrk_run is enqueuing: bit 0 hand-off on, bit 1 first step, bit 2 last step of the run
     int handoff_step = 0;
     virtual bool garg_capable() const = 0;  // the law and order have the two instantiations
+    // the law's refreshed columns are read by no pass: only the run's last hand-off update refreshes
+    virtual bool refresh_elidable() const = 0;
     bool handoff_eligible() const
     {
         return gradarg_handoff && garg_capable() && !gf_live() && ngl > 0 && has_update_aux() &&
@@ -614,7 +620,12 @@ struct EngineT : EngineBase {
     } while (0)
         constexpr bool HO = GradArgHandoff<P, NQ_, NQV_>::value;
         if (HO && c.garg_out) {  // (handoff_eligible: fused update, no gradient flux, no ghosts)
-            if constexpr (HO)
+            constexpr bool ELIDE = GradArgHandoff<P, NQ_, NQV_>::elide_refresh;
+            if (ELIDE && !c.garg_refresh) {
+                if constexpr (ELIDE)
+                    hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, true, false, false, true, false>), grid, block, 0,
+                                       st, args);
+            } else if constexpr (HO)
                 hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, true, false, false, true>), grid, block, 0, st, args);
         } else if (c.lsrk) {
             if (gfl) CMDG_TEND(true, true);
@@ -663,6 +674,7 @@ struct EngineT : EngineBase {
         return GradArgHandoff<P, NQ_, NQV_>::value && !P::needs_gradflux(prm);
 #endif
     }
+    bool refresh_elidable() const override { return GradArgHandoff<P, NQ_, NQV_>::elide_refresh; }
     int law_nder() const override { return P::HAS_SOURCE ? P::NDER : 0; }
     int law_nupd() const override { return P::HAS_UPDATE_AUX ? P::NUPD : 0; }
     int tendency_epb() const override { return TendencyShape<P, NQ_, NQV_>::EPB; }

@@ -404,6 +404,12 @@ struct TendencyShape {
 // auxiliary refresh for Q+; k_gradients<..., GARG_IN> of the next stage reads and gathers those
 // records instead of 9 columns of Q / aux per node and per interior face node.  Same expressions on
 // the same operands: every bit downstream is unchanged.  One element per work-group only.
+// A run's hand-off launches follow one another with no hook, filter, exchange or caller in between,
+// so the columns the refresh writes are seen by somebody only after the last of them (it leaves the
+// auxiliary state of the final evaluation's input, as every run promises).  A law whose refreshed
+// columns are read by none of its pointwise functions in any pass says `GRADARG_REFRESH_UNREAD =
+// true`; its other hand-off launches then run k_tendency<..., GARG_OUT, false>, which neither
+// calls update_aux nor stores the columns.  Every other law refreshes in every update.
 template <class P, class = void>
 struct law_gradarg_handoff : std::false_type {
 };
@@ -411,9 +417,18 @@ template <class P>
 struct law_gradarg_handoff<P, std::void_t<decltype(P::GRADARG_HANDOFF)>>
     : std::integral_constant<bool, P::GRADARG_HANDOFF && (P::NGL > 0) && P::HAS_UPDATE_AUX && P::FUSE_UPDATE_AUX> {
 };
+template <class P, class = void>
+struct law_refresh_unread : std::false_type {
+};
+template <class P>
+struct law_refresh_unread<P, std::void_t<decltype(P::GRADARG_REFRESH_UNREAD)>>
+    : std::integral_constant<bool, P::GRADARG_REFRESH_UNREAD && law_gradarg_handoff<P>::value> {
+};
 template <class P, int NQ, int NQV>
 struct GradArgHandoff {
     static constexpr bool value = law_gradarg_handoff<P>::value && TendencyShape<P, NQ, NQV>::EPB == 1;
+    // may the refresh be left out of the hand-off launches nobody can observe
+    static constexpr bool elide_refresh = value && law_refresh_unread<P>::value;
 };
 template <int NGL, int Np>
 __device__ __forceinline__ int64_t garg_at(int n, int64_t e)
@@ -436,11 +451,15 @@ __device__ __forceinline__ int64_t garg_at(int n, int64_t e)
 // GARG_OUT: the fused update also forms the next stage's gradient arguments and refreshes the
 // nodal auxiliary state for Q+ (GradArgHandoff).  The auxiliary columns both need are dead in
 // registers by then: they are loaded again after the face phase, in flight across the lift.
-template <class P, int NQ, int NQV, bool LSRK, bool USE_GF, bool RECV = false, bool GARG_OUT = false>
+// GARG_REFRESH = false: the records alone (GradArgHandoff::elide_refresh).
+template <class P, int NQ, int NQV, bool LSRK, bool USE_GF, bool RECV = false, bool GARG_OUT = false,
+          bool GARG_REFRESH = true>
 __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
 {
     static_assert(!GARG_OUT || (LSRK && !USE_GF && !RECV && TendencyShape<P, NQ, NQV>::EPB == 1),
                   "the hand-off rides in the fused update of single-rank handles");
+    static_assert(GARG_REFRESH || (GARG_OUT && GradArgHandoff<P, NQ, NQV>::elide_refresh),
+                  "only a hand-off launch of a law that opts in may leave the refresh out");
     using KD = KDims<NQ, NQV>;
     const double a_t = a.tptr ? *a.tptr : a.t;  // (uniform: one scalar load)
     using SH = TendencyShape<P, NQ, NQV>;
@@ -779,11 +798,13 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
             double *rec = a.garg + garg_at<P::NGL, Np>(tid, e);
 #pragma unroll
             for (int s = 0; s < P::NGL; ++s) rec[s] = G[P::hv_indexmap(s)];
-            // kernel_nodal_update_auxiliary_state! for the next evaluation's input
-            P::update_aux(a.prm, Qn, gaux, a_t);
+            if constexpr (GARG_REFRESH) {
+                // kernel_nodal_update_auxiliary_state! for the next evaluation's input
+                P::update_aux(a.prm, Qn, gaux, a_t);
 #pragma unroll
-            for (int s = 0; s < P::NUPD; ++s)
-                a.aux_rw[tid + (int64_t)Np * (P::upd_aux(s) + (int64_t)NAUX * e)] = gaux[P::upd_aux(s)];
+                for (int s = 0; s < P::NUPD; ++s)
+                    a.aux_rw[tid + (int64_t)Np * (P::upd_aux(s) + (int64_t)NAUX * e)] = gaux[P::upd_aux(s)];
+            }
         }
     }
     if constexpr (LSRK) {  // the updated state of the nodes of vmapsend, straight to the send buffer
@@ -793,10 +814,11 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
             });
     }
 }
-template <class P, int NQ, int NQV, bool LSRK, bool USE_GF, bool RECV = false, bool GARG_OUT = false>
+template <class P, int NQ, int NQV, bool LSRK, bool USE_GF, bool RECV = false, bool GARG_OUT = false,
+          bool GARG_REFRESH = true>
 __global__ void __launch_bounds__((TendencyShape<P, NQ, NQV>::NT), CMDG_TEND_MINW) k_tendency(const PassArgs<P> a)
 {
-    tendency_body<P, NQ, NQV, LSRK, USE_GF, RECV, GARG_OUT>(a);
+    tendency_body<P, NQ, NQV, LSRK, USE_GF, RECV, GARG_OUT, GARG_REFRESH>(a);
 }
 
 // ---------------------------------------------------------------------------------

@@ -63,6 +63,13 @@ struct DryAtmos {
     // gradient_argument and update_aux are pure functions of the node's (Q, aux): inside
     // cmdg_lsrk_run the fused update may form both for the next stage (kernels.h GradArgHandoff)
     static constexpr bool GRADARG_HANDOFF = true;
+    // ... and may leave the refresh out of every such update but the run's last: theta_v / air_T
+    // (upd_aux) are read by no pointwise function of this law in any pass -- flux, source,
+    // gradient_argument (which forms theta_v itself where it needs it), boundary_state (which
+    // writes its own copy) -- so nothing sees them before the run's last hand-off update has
+    // written them again (aux_read counts the columns a pass does read; update_aux checks that
+    // they fit among the others).
+    static constexpr bool GRADARG_REFRESH_UNREAD = true;
     static constexpr bool HAS_SOURCE = true;
     // sin / cos of the latitude (heldsuarez.jl:134,147-149 recomputes them every call; they
     // only depend on aux.coord, so they are evaluated once with the same libm calls)
@@ -669,6 +676,10 @@ struct DryAtmos {
     // DryModel atmos_nodal_update_auxiliary_state! (moisture.jl:53-62)
     __device__ static void update_aux(const Params &m, const double *Q, double *aux, double)
     {
+        static_assert(!GRADARG_REFRESH_UNREAD ||
+                          (upd_aux(0) == NAUX - NUPD && aux_read(0) <= NAUX - NUPD &&
+                           aux_read(2) <= NAUX - NUPD && aux_read(3) <= NAUX - NUPD),
+                      "a pass that reads moisture.theta_v / air_T needs the refresh in every update");
         const double T = air_T(m, internal_energy(m, Q, aux));
         aux[OMOIST] = theta_v(m, T, Q[0]);
         aux[OMOIST + 1] = T;

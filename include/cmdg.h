@@ -259,7 +259,9 @@ int cmdg_synchronize(cmdg_handle h);
  *   Taken only by single-rank handles (no ghost elements) of a law whose gradient-flux state is
  *   not formed, with hyperdiffusion and a fused nodal refresh (Held-Suarez), without hooks,
  *   filters or CMDG_OPT_STEP_GRAPH; the first evaluation and the last update of every run are the
- *   ordinary kernels, so nothing is carried from one call to the next.  Q, dQ and every column
+ *   ordinary kernels, so nothing is carried from one call to the next.  Of these updates only the
+ *   run's last does the refresh when no pass of the law reads the refreshed columns (the dry
+ *   atmosphere's theta_v / air_T): the others would be overwritten unseen.  Q, dQ and every column
  *   of state_auxiliary end a run bit-identical.  cmdg_query(CMDG_Q_GRADARG_HANDOFF) says whether
  *   the last run used it. */
 enum {
@@ -291,6 +293,9 @@ enum {
     CMDG_Q_GRAPH_STEPS = 12,     /* steps cmdg_lsrk_run replayed from a captured graph */
     CMDG_Q_TENDENCY_PAIRS = 13,  /* retired with CMDG_OPT_TENDENCY_PAIRS: always -1 (option off) */
     CMDG_Q_GRADARG_HANDOFF = 14, /* did the last cmdg_lsrk_run use CMDG_OPT_GRADARG_HANDOFF */
+    CMDG_Q_GRADARG_REFRESHES = 15, /* ... and how many of its hand-off updates carried the nodal auxiliary
+                                      refresh: 1 for a law whose refreshed columns no pass reads (only the
+                                      last one is ever seen), else all of them; 0 without the hand-off */
     CMDG_Q_STATE_READ = 16, CMDG_Q_AUX_READ = 20
 };
 int cmdg_query(cmdg_handle h, int32_t what, int64_t *out);

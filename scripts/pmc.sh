@@ -1,7 +1,8 @@
 #!/bin/bash
 # PMC passes over the default bench (one --pmc set per pass, kernel trace only), then a
 # per-kernel per-launch summary.  Usage: scripts/pmc.sh "<bench args>" out.json "SET1" "SET2" ...
-# Run on the GPU box through gpurun; writes under gpurun_out/.
+# Every pass runs under its own time limit (PMC_TIMEOUT seconds, default 300); a pass that fails or
+# runs out of time ends the script.
 args="$1"; out="$2"; shift 2
 root=$PWD
 cd /tmp && export TMPDIR=/tmp
@@ -9,9 +10,9 @@ i=0
 for set in "$@"; do
   i=$((i+1))
   rm -rf /tmp/pmc_$i
-  rocprofv3 --kernel-trace --pmc $set -d /tmp/pmc_$i -o p --output-format csv -- python3 $root/bench.py $args --no-cpu --no-events > /tmp/pmc_$i.log 2>&1 || { tail -5 /tmp/pmc_$i.log; exit 1; }
+  timeout -k 10 ${PMC_TIMEOUT:-300} rocprofv3 --kernel-trace --pmc $set -d /tmp/pmc_$i -o p --output-format csv -- python3 $root/bench.py $args --no-cpu --no-events > /tmp/pmc_$i.log 2>&1 || { tail -5 /tmp/pmc_$i.log; exit 1; }
 done
-python3 - "$root/$out" "$i" <<'PY'
+python3 - "$root/$out" "$i" "$root" <<'PY'
 import csv, glob, json, os, sys, collections
 out, n = sys.argv[1], int(sys.argv[2])
 res = collections.defaultdict(dict)
@@ -31,7 +32,7 @@ for i in range(1, n + 1):
             res[k][c] = v / max(len(cnt[k]), 1)
         res[k]['launches'] = len(cnt[k])
 try:
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(out))))
+    sys.path.insert(0, sys.argv[3])  # bench.py lies in the directory the script is called from
     import bench
     res['kernel_source_digest'] = bench.kernel_source_digest()
 except Exception as e:          # the counters stand without it; bench.py then calls them stale

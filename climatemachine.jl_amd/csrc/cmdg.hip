@@ -8,20 +8,12 @@
 #include <new>
 #include <tuple>
 
-#include "engine.h"
-#include "filters.h"
+#include "stepping.h"
 #include "columns.h"
 #include "reductions.h"
 #include "interpolation.h"
 
 namespace cmdg {
-
-#define HIPCHK(call)                                                                     \
-    do {                                                                                 \
-        hipError_t e_ = (call);                                                          \
-        if (e_ != hipSuccess)                                                            \
-            return fail(CMDG_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 // ---- RCCL, resolved lazily so that single-GPU use has no link-time dependency -------
 namespace rccl {
@@ -803,14 +795,14 @@ int EngineBase::halo_end(int s, double *array, int nvar, bool unpack, bool on_ha
 // interior elements while the halo is in flight, exterior elements after it arrived.
 int EngineBase::rhs_segment(int seg, const RhsCtx &c)
 {
-    const bool comm = communicate() && !(stacked && direction == DIR_VERTICAL);  // (:104-108)
+    const bool comm = exchanges();
     const bool gfl = gf_live();  // is state_gradient_flux read by anybody?
     const bool grad = gfl || nhyp > 0;
     const bool hyper = nhyp > 0;
     // exterior launches write the send buffers / consumers read the receive buffers (HaloDev)
     const bool dsend = comm && direct_send(), unpack = !(comm && direct_recv());
     // exterior launches and exchanges on the halo stream, interior launches on the compute stream
-    const bool pipe = pipelined(comm) && !has_hooks;
+    const bool pipe = pipelined() && !has_hooks;
     hipStream_t s_ext = pipe ? s_comm : s_comp;
     // of Qhypervisc_div's nhyp columns the Laplacian pass writes, and the next pass reads, ngl
     const int nhd = ngl;
@@ -1010,25 +1002,6 @@ int EngineBase::rhs_async(const RhsCtx &c)
     return CMDG_OK;
 }
 
-// dostep!  LowStorageRungeKuttaMethod.jl:102-144.  The state rotates Q -> W0 -> W1 -> ...
-// -> Q so that the fused update never writes the array its neighbours still read.
-static void lsrk_stage_buffers(EngineBase *e, double *Q, int s, int nstages, double **in,
-                               double **out)
-{
-    *in = s == 0 ? Q : e->W[(s - 1) % 2];
-    *out = s == nstages - 1 ? Q : e->W[s % 2];
-}
-
-int EngineBase::lsrk_step(double *Q, double *dQ, double t, double dt, int nstages,
-                          const double *rka, const double *rkb, const double *rkc, bool continued)
-{
-    std::vector<EngineBase *> one{this};
-    double *Qs[1] = {Q}, *dQs[1] = {dQ};
-    if (transport == TRANSPORT_LOCAL && communicate())
-        return fail(CMDG_ERR_INVALID, "handles connected locally must be driven by the cmdg_group_* calls");
-    return group_lsrk_step(one, Qs, dQs, t, dt, nstages, rka, rkb, rkc, continued);
-}
-
 // keep_fresh: the state read is what the previous stage's fused update wrote (its exterior launch
 // filled the send buffer of Q already); otherwise nothing is known about the send buffers
 int group_rhs(std::vector<EngineBase *> &g, std::vector<RhsCtx> &c, bool keep_fresh)
@@ -1068,221 +1041,6 @@ int group_rhs(std::vector<EngineBase *> &g, std::vector<RhsCtx> &c, bool keep_fr
                 for (auto *e : g) e->abort_exchanges();
                 return r;
             }
-    return CMDG_OK;
-}
-
-// continued: this step follows the previous step of the same run with nothing in between
-int group_lsrk_step(std::vector<EngineBase *> &g, double **Q, double **dQ, double t, double dt,
-                    int nstages, const double *rka, const double *rkb, const double *rkc,
-                    bool continued, const double *stage_times_dev)
-{
-    if (nstages < 1) return g[0]->fail(CMDG_ERR_INVALID, "lsrk: nstages < 1");
-    for (auto *e : g)
-        if (int r = e->ensure_work()) return r;
-    std::vector<RhsCtx> c(g.size());
-    for (int s = 0; s < nstages; ++s) {
-        for (size_t i = 0; i < g.size(); ++i) {
-            RhsCtx &x = c[i];
-            // a tendency filter acts on dQ between rhs! and update!: no fused update then
-            const bool fused = g[i]->tendency_filter == nullptr;
-            if (fused) {
-                lsrk_stage_buffers(g[i], Q[i], s, nstages, &x.Qin, &x.Qout);
-                if (nstages == 1) x.Qout = g[i]->W[0];
-            } else {
-                x.Qin = Q[i];
-                x.Qout = nullptr;
-            }
-            x.tendency = dQ[i];
-            x.t = t + rkc[s] * dt;
-            x.tptr = stage_times_dev ? stage_times_dev + s : nullptr;
-            x.alpha = 1.0;  // rhs!(dQ, Q, p, time + RKC[s] * dt, increment = true)
-            x.beta = 1.0;
-            x.lsrk = fused;
-            x.update_after = !fused;
-            x.rkb_dt = rkb[s] * dt;
-            x.rka_next = rka[(s + 1) % nstages];
-            // CMDG_OPT_GRADARG_HANDOFF: every evaluation of a run but the first reads the gradient
-            // arguments the update before it left, every update but the last leaves them
-            const int ho = g[i]->handoff_step;
-            x.garg_in = (ho & 1) && !((ho & 2) && s == 0);
-            x.garg_out = (ho & 1) && !((ho & 4) && s == nstages - 1);
-            // the auxiliary refresh is seen only after the run's last hand-off update: stage
-            // nstages - 2 of the last step.  (A one-stage tableau has it in the step before the
-            // last; it refreshes in every update.)
-            x.garg_refresh = !g[i]->refresh_elidable() || nstages == 1 || ((ho & 4) && s == nstages - 2);
-            if (x.garg_out && x.garg_refresh) g[i]->handoff_refreshes += 1;
-        }
-        if (int r = group_rhs(g, c, s > 0 || continued)) return r;
-    }
-    for (size_t i = 0; i < g.size(); ++i) {
-        EngineBase *e = g[i];
-        if (nstages == 1 && e->tendency_filter == nullptr)
-            if (hipMemcpyAsync(Q[i], e->W[0], sizeof(double) * e->Np * e->ns * e->nreal,
-                               hipMemcpyDeviceToDevice, e->s_comp) != hipSuccess)
-                return e->fail(CMDG_ERR_HIP, "lsrk: copy back failed");
-        // user callback EveryXSimulationSteps(1) of heldsuarez.jl:261-272
-        if (e->step_filter) {
-            if (int r = e->filter_apply(e->step_filter, Q[i], e->ns)) return r;
-            e->invalidate_sends();
-        }
-    }
-    return CMDG_OK;
-}
-
-// ---- cmdg_lsrk_run: eager steps, or one captured step replayed (EngineBase::step_graph) -----
-namespace {
-struct StepTimesInit {
-    double t_next, dt;
-    int nstages;
-    double rkc[16];
-};
-// [t_next, dt, times[16], rkc[16]] <- the values of a run
-__global__ void k_step_times_init(double *g, StepTimesInit v)
-{
-    g[0] = v.t_next;
-    g[1] = v.dt;
-    for (int s = 0; s < v.nstages; ++s) g[18 + s] = v.rkc[s];
-}
-// head of the captured step: the stage times of this step, then t += dt (updatetime!)
-__global__ void k_step_times(double *g, int nstages)
-{
-    const double t = g[0], dt = g[1];
-    for (int s = 0; s < nstages; ++s) g[2 + s] = t + g[18 + s] * dt;
-    g[0] = t + dt;
-}
-}  // namespace
-
-bool EngineBase::graph_eligible() const
-{
-    const bool comm = communicate() && !(stacked && direction == DIR_VERTICAL);
-    // A handle that exchanges can be recorded when its exchanges need neither a pack nor an unpack
-    // launch from the compute stream (pipelined()) and travel through RCCL.  The groups must then sit
-    // on the capture's ORIGIN stream: on HIP 7.0.2 / RCCL 2.26.6 (the stack torch brings) a group
-    // recorded on a stream that joined the capture through an event crashes hipStreamEndCapture,
-    // whatever the capture mode; on ROCm 7.2 / RCCL 2.27.7 both forms work
-    // (scripts/probe/rccl_capture_probe.py, profiles/r04_rccl_capture_probes.txt).  The halo stream
-    // is therefore the origin of such a capture and the compute stream the forked one.
-    const bool comm_ok = !comm || (transport == TRANSPORT_RCCL && pipelined(comm));
-    return step_graph && !graph_failed && !profiling && !step_filter && !tendency_filter &&
-           !gradient_filter && !has_hooks && (!has_update_aux() || fused_update_aux()) && comm_ok;
-}
-
-int EngineBase::capture_step(double *Q, double *dQ, double dt, int nstages, const double *rka,
-                             const double *rkb, const double *rkc)
-{
-    const bool comm = communicate() && !(stacked && direction == DIR_VERTICAL);
-    if (graph_exec) {
-        hipGraphExecDestroy(graph_exec);
-        graph_exec = nullptr;
-    }
-    if (!d_gtime) HIPCHK(hipMalloc(&d_gtime, sizeof(double) * 34));
-    std::vector<EngineBase *> one{this};
-    double *Qs[1] = {Q}, *dQs[1] = {dQ};
-    if (4 * nstages + 1 > NGEV) return fail(CMDG_ERR_UNSUPPORTED, "step graph: too many stages");
-    for (int i = 0; i < NGEV; ++i) {  // (created on first use: most handles never capture)
-        if (!gev_int[i]) HIPCHK(hipEventCreateWithFlags(&gev_int[i], hipEventDisableTiming));
-        if (!gev_ext[i]) HIPCHK(hipEventCreateWithFlags(&gev_ext[i], hipEventDisableTiming));
-    }
-    capturing = true;
-    cap_interior = cap_exterior = cap_pass = 0;
-    hipGraph_t graph = nullptr;
-    int r = CMDG_OK;
-    // origin of the capture: the stream the RCCL groups are recorded on (graph_eligible)
-    const hipStream_t so = comm ? s_comm : s_comp;
-    if (hipStreamBeginCapture(so, hipStreamCaptureModeRelaxed) != hipSuccess) {
-        capturing = false;
-        return fail(CMDG_ERR_HIP, "step graph: hipStreamBeginCapture failed");
-    }
-    hipLaunchKernelGGL(k_step_times, dim3(1), dim3(1), 0, so, d_gtime, nstages);
-    if (comm) {  // the compute stream joins the capture
-        if (hipEventRecord(gev_fork, s_comm) != hipSuccess ||
-            hipStreamWaitEvent(s_comp, gev_fork, 0) != hipSuccess)
-            r = fail(CMDG_ERR_HIP, "step graph: fork of the compute stream failed");
-    }
-    if (!r) r = group_lsrk_step(one, Qs, dQs, 0.0, dt, nstages, rka, rkb, rkc, true, d_gtime + 2);
-    if (comm && !r) {  // ... and ends in the origin stream
-        if (hipEventRecord(gev_fork, s_comp) != hipSuccess ||
-            hipStreamWaitEvent(s_comm, gev_fork, 0) != hipSuccess)
-            r = fail(CMDG_ERR_HIP, "step graph: join of the compute stream failed");
-    }
-    const hipError_t ee = hipStreamEndCapture(so, &graph);
-    capturing = false;
-    if (r || ee != hipSuccess || !graph) {
-        if (graph) hipGraphDestroy(graph);
-        abort_exchanges();
-        (void)hipGetLastError();
-        graph_failed = true;
-        if (!r) r = fail(CMDG_ERR_HIP, std::string("step graph: hipStreamEndCapture: ") + hipGetErrorString(ee));
-        return r;
-    }
-    const hipError_t ie = hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    if (ie != hipSuccess) {
-        graph_exec = nullptr;
-        graph_failed = true;
-        return fail(CMDG_ERR_HIP, std::string("step graph: hipGraphInstantiate: ") + hipGetErrorString(ie));
-    }
-    return CMDG_OK;
-}
-
-int EngineBase::run_steps(double *Q, double *dQ, double t, double dt, int64_t nsteps, int nstages,
-                          const double *rka, const double *rkb, const double *rkc)
-{
-    // (the step times accumulate as the reference's updatetime! does: t += dt, ODESolvers.jl:96-98)
-    int64_t i = 0;
-    handoff_used = false;
-    handoff_refreshes = 0;
-    if (nsteps >= 2 && nstages <= 16 && graph_eligible()) {
-        if (int r = lsrk_step(Q, dQ, t, dt, nstages, rka, rkb, rkc, false)) return r;  // eager: packs Q
-        t += dt;
-        i = 1;
-        GraphKey key;
-        key.Q = Q, key.dQ = dQ, key.dt = dt, key.nstages = nstages;
-        key.comm = communicate() && !(stacked && direction == DIR_VERTICAL);
-        key.pipe = pipelined(key.comm);
-        for (int s = 0; s < nstages; ++s) key.coef[s] = rka[s], key.coef[16 + s] = rkb[s], key.coef[32 + s] = rkc[s];
-        if (!graph_exec || !(key == graph_key)) {
-            if (capture_step(Q, dQ, dt, nstages, rka, rkb, rkc) == CMDG_OK) graph_key = key;
-            else graph_failed = true;  // err says why; this run and the later ones go on eagerly
-        }
-        if (graph_exec && !graph_failed) {
-            StepTimesInit v{};
-            v.t_next = t, v.dt = dt, v.nstages = nstages;
-            for (int s = 0; s < nstages; ++s) v.rkc[s] = rkc[s];
-            const hipStream_t so = key.comm ? s_comm : s_comp;
-            if (key.comm) {  // the eager step's work on the compute stream comes first
-                HIPCHK(hipEventRecord(ev_comp, s_comp));
-                HIPCHK(hipStreamWaitEvent(s_comm, ev_comp, 0));
-            }
-            hipLaunchKernelGGL(k_step_times_init, dim3(1), dim3(1), 0, so, d_gtime, v);
-            for (; i < nsteps; ++i, t += dt) {
-                HIPCHK(hipGraphLaunch(graph_exec, so));
-                graph_steps += 1;
-            }
-            if (key.comm) {  // whatever the caller enqueues next on the compute stream follows the run
-                HIPCHK(hipEventRecord(ev_comp, s_comm));
-                HIPCHK(hipStreamWaitEvent(s_comp, ev_comp, 0));
-            }
-            return CMDG_OK;
-        }
-        // the capture left the exchange state of a continued step behind: start over from Q
-        invalidate_sends();
-        for (; i < nsteps; ++i, t += dt)
-            if (int r = lsrk_step(Q, dQ, t, dt, nstages, rka, rkb, rkc, false)) return r;
-        return CMDG_OK;
-    }
-    // the hand-off of the gradient arguments lives inside one run: its first evaluation and its
-    // last update are the existing kernels, so nothing is carried over from or into another call
-    const bool ho = handoff_eligible() && nsteps * nstages >= 2;
-    handoff_used = ho;
-    if (ho)
-        if (int r = ensure_garg()) return r;
-    for (; i < nsteps; ++i, t += dt) {
-        handoff_step = ho ? (1 | (i == 0 ? 2 : 0) | (i == nsteps - 1 ? 4 : 0)) : 0;
-        const int r = lsrk_step(Q, dQ, t, dt, nstages, rka, rkb, rkc, i > 0);
-        handoff_step = 0;
-        if (r) return r;
-    }
     return CMDG_OK;
 }
 
@@ -2139,36 +1897,6 @@ int cmdg_rhs(cmdg_handle h, double *tendency, double *Q, double t, double alpha,
     return set_err(h, h->eng->synchronize());
 }
 
-int cmdg_lsrk_step(cmdg_handle h, double *Q, double *dQ, double t, double dt, int32_t nstages,
-                   const double *rka, const double *rkb, const double *rkc)
-{
-    if (!h || !Q || !dQ || !rka || !rkb || !rkc) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    return set_err(h, h->eng->lsrk_step(Q, dQ, t, dt, nstages, rka, rkb, rkc));
-}
-
-int cmdg_lsrk_run(cmdg_handle h, double *Q, double *dQ, double t, double dt, int64_t nsteps,
-                  int32_t nstages, const double *rka, const double *rkb, const double *rkc)
-{
-    if (!h || !Q || !dQ || !rka || !rkb || !rkc) return CMDG_ERR_INVALID;
-    EngineBase *e = h->eng;
-    if (e->worker && nstages >= 1 && nstages <= 16) {  // CMDG_OPT_ASYNC_RUN: the handle's own thread enqueues
-        std::vector<double> a(rka, rka + nstages), b(rkb, rkb + nstages), c(rkc, rkc + nstages);
-        e->worker->submit([=]() {
-            DevGuard guard_(e);
-            const int r = e->run_steps(Q, dQ, t, dt, nsteps, nstages, a.data(), b.data(), c.data());
-            if (r) {
-                std::lock_guard<std::mutex> lk(e->worker->m);
-                if (e->worker->deferred_err.empty()) e->worker->deferred_err = e->err;
-            }
-            return r;
-        });
-        return CMDG_OK;
-    }
-    DevGuard guard_(e);
-    return set_err(h, e->run_steps(Q, dQ, t, dt, nsteps, nstages, rka, rkb, rkc));
-}
-
 int cmdg_synchronize(cmdg_handle h)
 {
     if (!h) return CMDG_ERR_INVALID;
@@ -2253,9 +1981,7 @@ int cmdg_query(cmdg_handle h, int32_t what, int64_t *out)
     case CMDG_Q_GRADARG_REFRESHES: *out = e->handoff_refreshes; return CMDG_OK;
     case CMDG_Q_HOST_POST_NS: *out = e->host_post_ns; return CMDG_OK;
     case CMDG_Q_HOST_POST_COUNT: *out = e->host_post_n; return CMDG_OK;
-    case CMDG_Q_HALO_PIPELINE:
-        *out = e->pipelined(e->communicate() && !(e->stacked && e->direction == DIR_VERTICAL)) && !e->has_hooks;
-        return CMDG_OK;
+    case CMDG_Q_HALO_PIPELINE: *out = e->pipelined() && !e->has_hooks; return CMDG_OK;
     default:
         if (what >= CMDG_Q_STATE_READ && what < CMDG_Q_STATE_READ + 4) {
             *out = e->law_state_read(what - CMDG_Q_STATE_READ);
@@ -2439,22 +2165,6 @@ int cmdg_group_halo(cmdg_handle *handles, int32_t n, double **arrays, int32_t ns
         if (int r = handles[i]->eng->halo_end(SLOT_Q, arrays[i], nstate)) return gc.finish(r);
     for (int i = 0; i < n; ++i)
         if (int r = handles[i]->eng->synchronize()) return gc.finish(r);
-    return CMDG_OK;
-}
-
-int cmdg_group_lsrk_run(cmdg_handle *handles, int32_t n, double **Q, double **dQ, double t,
-                        double dt, int64_t nsteps, int32_t nstages, const double *rka,
-                        const double *rkb, const double *rkc)
-{
-    if (!Q || !dQ || !rka || !rkb || !rkc) return CMDG_ERR_INVALID;
-    for (int i = 0; i < n; ++i)
-        if (!Q[i] || !dQ[i]) return CMDG_ERR_INVALID;
-    GroupCall gc(handles, n);
-    if (!gc.ok()) return CMDG_ERR_INVALID;
-    std::vector<EngineBase *> g;
-    for (int i = 0; i < n; ++i) g.push_back(handles[i]->eng);
-    for (int64_t s = 0; s < nsteps; ++s, t += dt)
-        if (int r = group_lsrk_step(g, Q, dQ, t, dt, nstages, rka, rkb, rkc, s > 0)) return gc.finish(r);
     return CMDG_OK;
 }
 

@@ -38,6 +38,16 @@ struct HaloSlot {
     int fresh_nvar = 0;
 };
 
+// where a step of cmdg_lsrk_run stands in the run, for the steps that hand gradient arguments from
+// stage to stage (CMDG_OPT_GRADARG_HANDOFF); a step that is given none does not hand anything on
+struct StepInRun {
+    bool first_step, last_step;
+};
+
+// what the fused update of a stage leaves for the next stage's gradient pass: nothing (the ordinary
+// kernel), the gradient-argument records alone, or the records and the nodal auxiliary refresh
+enum class GargOut { none, records, records_refresh };
+
 struct RhsCtx {
     double *tendency = nullptr;
     double *Qin = nullptr;   // state read by this evaluation (ghosts refreshed in place)
@@ -46,12 +56,10 @@ struct RhsCtx {
     const double *tptr = nullptr;  // time in device memory instead (captured steps)
     bool lsrk = false;         // fused update inside k_tendency
     bool update_after = false; // separate update!() after the (filtered) tendency
-    // CMDG_OPT_GRADARG_HANDOFF, set by cmdg_lsrk_run alone: the gradient pass reads the records the
-    // previous stage's update left / the fused update leaves them for the next stage
-    bool garg_in = false, garg_out = false;
-    // ... and that update also does the nodal auxiliary refresh (always, unless the law lets the
-    // unobservable ones go: refresh_elidable)
-    bool garg_refresh = true;
+    // CMDG_OPT_GRADARG_HANDOFF, set by cmdg_lsrk_run alone (handoff_stage, lsrk_run.hip): the gradient
+    // pass reads the records the previous stage's update left / what the fused update leaves
+    bool garg_in = false;
+    GargOut garg_out = GargOut::none;
     double rkb_dt = 0, rka_next = 0;
     // the law's update_auxiliary_state!(realelems) composition has run already (group_rhs runs the
     // nested operators of a local group in lock step before segment 0)
@@ -157,6 +165,14 @@ struct RunWorker {
     }
 };
 
+// inside a member of EngineBase: a failed HIP call ends the function with the engine's message set
+#define HIPCHK(call)                                                                     \
+    do {                                                                                 \
+        hipError_t e_ = (call);                                                          \
+        if (e_ != hipSuccess)                                                            \
+            return fail(CMDG_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
 struct EngineBase {
     RunWorker *worker = nullptr;  // CMDG_OPT_ASYNC_RUN
     // ---- configuration (copied from cmdg_desc) ---------------------------------------
@@ -205,8 +221,6 @@ struct EngineBase {
     bool gradarg_handoff = true;   // the option
     bool handoff_used = false;     // did the last cmdg_lsrk_run use it (cmdg_query)
     int64_t handoff_refreshes = 0; // hand-off updates of the last run that carried the auxiliary refresh
-    // the step cmdg_lsrk_run is enqueuing: bit 0 hand-off on, bit 1 first step, bit 2 last step of the run
-    int handoff_step = 0;
     virtual bool garg_capable() const = 0;  // the law and order have the two instantiations
     // the law's refreshed columns are read by no pass: only the run's last hand-off update refreshes
     virtual bool refresh_elidable() const = 0;
@@ -242,6 +256,9 @@ struct EngineBase {
     // make stream `later` wait for everything enqueued so far on `earlier` (through ev_comp)
     int order(hipStream_t earlier, hipStream_t later);
     bool communicate() const { return !nabrtorank.empty(); }
+    // does an evaluation of this handle exchange ghosts (DGModel.jl:104-108: not the vertical
+    // operator of a stacked mesh)
+    bool exchanges() const { return communicate() && !(stacked && direction == DIR_VERTICAL); }
 
     // physics / order specific launches; `exterior`: the launch of the exterior element list of a
     // handle with neighbours (writes the send buffers of what it produces, see HaloDev)
@@ -325,9 +342,9 @@ struct EngineBase {
     int64_t host_post_ns = 0, host_post_n = 0;  // host time inside halo_post (RCCL group calls)
     hipEvent_t prof_ext_done = nullptr;  // profiling: end of the last exterior launch
     bool no_pipeline = false;  // CMDG_OPT_HALO_PIPELINE = 0
-    bool pipelined(bool comm) const
+    bool pipelined() const
     {
-        return comm && !no_pipeline && direct_send() && direct_recv() && !gradient_filter &&
+        return exchanges() && !no_pipeline && direct_send() && direct_recv() && !gradient_filter &&
                !tendency_filter && (!has_update_aux() || fused_update_aux());
     }
     void invalidate_sends()
@@ -398,7 +415,8 @@ struct EngineBase {
     int rhs_segment(int seg, const RhsCtx &c);
     int rhs_async(const RhsCtx &c);
     int lsrk_step(double *Q, double *dQ, double t, double dt, int nstages, const double *rka,
-                  const double *rkb, const double *rkc, bool continued = false);
+                  const double *rkb, const double *rkc, bool continued = false,
+                  const StepInRun *handoff = nullptr);
     // (nvar columns per packed position = the leading columns of the ncol-column array; ncol = 0:
     // the whole array, nvar == ncol, as the reference packs)
     // on_halo_stream (pipelined()): producer and consumer are launches of the halo stream itself
@@ -509,20 +527,14 @@ struct GroupCall {
 
 // the handle's cmdg_last_error takes the engine's message when code is a failure
 int set_err(cmdg_handle h, int code);
-}  // namespace cmdg
-
-namespace cmdg {
-
-int group_rhs(std::vector<EngineBase *> &g, std::vector<RhsCtx> &c, bool keep_fresh = false);
-int group_lsrk_step(std::vector<EngineBase *> &g, double **Q, double **dQ, double t, double dt,
-                    int nstages, const double *rka, const double *rkb, const double *rkc,
-                    bool continued = false, const double *stage_times_dev = nullptr);
 
 // ---------------------------------------------------------------------------------
 template <class P, int NQ_, int NQV_ = NQ_>
 struct EngineT : EngineBase {
     typename P::Params prm;
-    PassArgs<P> make_args(const RhsCtx &c, const int64_t *elems, int64_t n, int dir) const
+    // send0 / send1: the send buffers of what an exterior launch produces (halo_dev)
+    PassArgs<P> make_args(const RhsCtx &c, const int64_t *elems, int64_t n, int dir, bool exterior, double *send0,
+                          double *send1) const
     {
         PassArgs<P> a;
         a.prm = prm;
@@ -548,94 +560,90 @@ struct EngineT : EngineBase {
         a.direction = dir;
         a.model_dir = direction;
         a.nf_first = nf_first;
-        a.h = HaloDev{};
-        a.h.nreal = nreal;
+        a.h = halo_dev(exterior, send0, send1);
         return a;
+    }
+    // ---- the four passes ---------------------------------------------------------------------
+    using Kernel = void (*)(PassArgs<P>);
+    static constexpr bool HO = GradArgHandoff<P, NQ_, NQV_>::value;
+    static constexpr bool ELIDE = GradArgHandoff<P, NQ_, NQV_>::elide_refresh;
+    struct Pass {
+        const char *range, *range_ext;  // roctx range of the interior / exterior launch
+        int prof, prof_ext;             // ... and its profiling id
+    };
+    static constexpr Pass GRADIENTS{"cmdg:gradients", "cmdg:gradients:exterior", CMDG_K_GRADIENTS, CMDG_K_GRADIENTS_EXT};
+    static constexpr Pass DIVGRAD{"cmdg:divgrad", "cmdg:divgrad:exterior", CMDG_K_DIVGRAD, CMDG_K_DIVGRAD_EXT};
+    static constexpr Pass GRADLAP{"cmdg:gradlap", "cmdg:gradlap:exterior", CMDG_K_GRADLAP, CMDG_K_GRADLAP_EXT};
+    static constexpr Pass TENDENCY{"cmdg:tendency", "cmdg:tendency:exterior", CMDG_K_TENDENCY, CMDG_K_TENDENCY_EXT};
+    // What every launch of a pass shares: nothing for an empty element list, else the roctx range and
+    // the profiling bracket of the interior or exterior launch around what `enqueue` puts on st.
+    template <class Enqueue>
+    void in_pass(const Pass &p, int64_t n, bool exterior, hipStream_t st, Enqueue enqueue)
+    {
+        if (n <= 0) return;
+        Range range_(exterior ? p.range_ext : p.range);
+        prof_begin(exterior ? p.prof_ext : p.prof, st);
+        enqueue();
+        prof_end(st);
+    }
+    // The instantiation of a pass kernel for the flags of a launch.  A combination the law does not
+    // instantiate (GradArgHandoff) is not named for it; the flags never ask for one (handoff_eligible).
+    static Kernel pick_gradients(bool gf_live, bool garg_in)
+    {
+        if constexpr (HO)  // (handoff_eligible: no gradient flux, no ghosts)
+            if (garg_in) return k_gradients<P, NQ_, NQV_, false, true>;
+        return gf_live ? k_gradients<P, NQ_, NQV_, true> : k_gradients<P, NQ_, NQV_, false>;
+    }
+    template <bool LSRK, bool GF>
+    static Kernel tendency_recv(bool recv)
+    {
+        return recv ? k_tendency<P, NQ_, NQV_, LSRK, GF, true> : k_tendency<P, NQ_, NQV_, LSRK, GF, false>;
+    }
+    static Kernel pick_tendency(bool lsrk, bool gf, bool recv, GargOut out)
+    {
+        if constexpr (HO)  // (handoff_eligible: fused update, no gradient flux, no ghosts)
+            if (out != GargOut::none) {
+                if constexpr (ELIDE)
+                    if (out == GargOut::records) return k_tendency<P, NQ_, NQV_, true, false, false, true, false>;
+                return k_tendency<P, NQ_, NQV_, true, false, false, true>;
+            }
+        if (lsrk) return gf ? tendency_recv<true, true>(recv) : tendency_recv<true, false>(recv);
+        return gf ? tendency_recv<false, true>(recv) : tendency_recv<false, false>(recv);
     }
     void launch_gradients(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
     {
-        if (n <= 0) return;
-        Range range_(exterior ? "cmdg:gradients:exterior" : "cmdg:gradients");
-        prof_begin(exterior ? CMDG_K_GRADIENTS_EXT : CMDG_K_GRADIENTS, st);
-        PassArgs<P> args = make_args(c, elems, n, diffusion_direction);
-        args.h = halo_dev(exterior, gf_live() ? slot[SLOT_GF].sendbuf : nullptr,
-                          ngl > 0 ? slot[SLOT_HG].sendbuf : nullptr);
-        constexpr bool HO = GradArgHandoff<P, NQ_, NQV_>::value;
-        if (HO && c.garg_in) {  // (handoff_eligible: no gradient flux, no ghosts)
-            if constexpr (HO)
-                hipLaunchKernelGGL((k_gradients<P, NQ_, NQV_, false, true>), dim3((unsigned)n),
-                                   dim3(KDims<NQ_, NQV_>::NT), 0, st, args);
-        } else if (gf_live())
-            hipLaunchKernelGGL((k_gradients<P, NQ_, NQV_, true>), dim3((unsigned)n), dim3(KDims<NQ_, NQV_>::NT), 0,
+        in_pass(GRADIENTS, n, exterior, st, [&] {
+            const PassArgs<P> args = make_args(c, elems, n, diffusion_direction, exterior,
+                                               gf_live() ? slot[SLOT_GF].sendbuf : nullptr,
+                                               ngl > 0 ? slot[SLOT_HG].sendbuf : nullptr);
+            hipLaunchKernelGGL(pick_gradients(gf_live(), c.garg_in), dim3((unsigned)n), dim3(KDims<NQ_, NQV_>::NT), 0,
                                st, args);
-        else
-            hipLaunchKernelGGL((k_gradients<P, NQ_, NQV_, false>), dim3((unsigned)n), dim3(KDims<NQ_, NQV_>::NT), 0,
-                               st, args);
-        prof_end(st);
+        });
     }
     void launch_divgrad(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
     {
-        if (n <= 0) return;
-        Range range_(exterior ? "cmdg:divgrad:exterior" : "cmdg:divgrad");
-        prof_begin(exterior ? CMDG_K_DIVGRAD_EXT : CMDG_K_DIVGRAD, st);
-        PassArgs<P> args = make_args(c, elems, n, diffusion_direction);
-        args.h = halo_dev(exterior, slot[SLOT_HD].sendbuf, nullptr);
-        hipLaunchKernelGGL((k_divgrad<P, NQ_, NQV_>), dim3((unsigned)n), dim3(KDims<NQ_, NQV_>::NT), 0, st,
-                           args);
-        prof_end(st);
+        in_pass(DIVGRAD, n, exterior, st, [&] {
+            const PassArgs<P> args = make_args(c, elems, n, diffusion_direction, exterior, slot[SLOT_HD].sendbuf, nullptr);
+            hipLaunchKernelGGL((k_divgrad<P, NQ_, NQV_>), dim3((unsigned)n), dim3(KDims<NQ_, NQV_>::NT), 0, st, args);
+        });
     }
     void launch_gradlap(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
     {
-        if (n <= 0) return;
-        Range range_(exterior ? "cmdg:gradlap:exterior" : "cmdg:gradlap");
-        prof_begin(exterior ? CMDG_K_GRADLAP_EXT : CMDG_K_GRADLAP, st);
-        PassArgs<P> args = make_args(c, elems, n, diffusion_direction);
-        args.h = halo_dev(exterior, slot[SLOT_HG].sendbuf, nullptr);
-        hipLaunchKernelGGL((k_gradlap<P, NQ_, NQV_>), dim3((unsigned)n), dim3(KDims<NQ_, NQV_>::NT), 0, st,
-                           args);
-        prof_end(st);
+        in_pass(GRADLAP, n, exterior, st, [&] {
+            const PassArgs<P> args = make_args(c, elems, n, diffusion_direction, exterior, slot[SLOT_HG].sendbuf, nullptr);
+            hipLaunchKernelGGL((k_gradlap<P, NQ_, NQV_>), dim3((unsigned)n), dim3(KDims<NQ_, NQV_>::NT), 0, st, args);
+        });
     }
     void launch_tendency(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
     {
-        if (n <= 0) return;
-        Range range_(exterior ? "cmdg:tendency:exterior" : "cmdg:tendency");
-        prof_begin(exterior ? CMDG_K_TENDENCY_EXT : CMDG_K_TENDENCY, st);
-#ifdef CMDG_GF_ALWAYS
-        const bool gfl = true;
-#else
-        const bool gfl = P::needs_gradflux(prm);
-#endif
-        using SH = TendencyShape<P, NQ_, NQV_>;
-        PassArgs<P> args = make_args(c, elems, n, direction);
-        args.h = halo_dev(exterior, c.lsrk ? slot[SLOT_Q].sendbuf : nullptr, nullptr);
-        const bool recv = args.h.ghostslot != nullptr && exterior;  // (interior elements have no ghost neighbour)
-        if (!recv) args.h.ghostslot = nullptr;
-        const dim3 grid((unsigned)SH::blocks(n)), block(SH::NT);
-#define CMDG_TEND(L, G)                                                                            \
-    do {                                                                                           \
-        if (recv)                                                                                  \
-            hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, L, G, true>), grid, block, 0, st, args);  \
-        else                                                                                       \
-            hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, L, G, false>), grid, block, 0, st, args); \
-    } while (0)
-        constexpr bool HO = GradArgHandoff<P, NQ_, NQV_>::value;
-        if (HO && c.garg_out) {  // (handoff_eligible: fused update, no gradient flux, no ghosts)
-            constexpr bool ELIDE = GradArgHandoff<P, NQ_, NQV_>::elide_refresh;
-            if (ELIDE && !c.garg_refresh) {
-                if constexpr (ELIDE)
-                    hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, true, false, false, true, false>), grid, block, 0,
-                                       st, args);
-            } else if constexpr (HO)
-                hipLaunchKernelGGL((k_tendency<P, NQ_, NQV_, true, false, false, true>), grid, block, 0, st, args);
-        } else if (c.lsrk) {
-            if (gfl) CMDG_TEND(true, true);
-            else CMDG_TEND(true, false);
-        } else {
-            if (gfl) CMDG_TEND(false, true);
-            else CMDG_TEND(false, false);
-        }
-#undef CMDG_TEND
-        prof_end(st);
+        in_pass(TENDENCY, n, exterior, st, [&] {
+            using SH = TendencyShape<P, NQ_, NQV_>;
+            PassArgs<P> args = make_args(c, elems, n, direction, exterior, c.lsrk ? slot[SLOT_Q].sendbuf : nullptr, nullptr);
+            const bool recv = args.h.ghostslot != nullptr && exterior;  // (interior elements have no ghost neighbour)
+            if (!recv) args.h.ghostslot = nullptr;
+            hipLaunchKernelGGL(pick_tendency(c.lsrk, P::needs_gradflux(prm), recv, c.garg_out),
+                               dim3((unsigned)SH::blocks(n)), dim3(SH::NT), 0, st, args);
+        });
     }
     void launch_update_aux(const RhsCtx &c, int64_t e0, int64_t e1) override
     {
@@ -666,15 +674,8 @@ struct EngineT : EngineBase {
     bool law_needs_gradflux() const override { return P::needs_gradflux(prm); }
     bool gf_node_major() const override { return cmdg::gf_node_major<P>::value; }
     bool fused_update_aux() const override { return P::HAS_UPDATE_AUX && P::FUSE_UPDATE_AUX; }
-    bool garg_capable() const override
-    {
-#ifdef CMDG_GF_ALWAYS
-        return false;
-#else
-        return GradArgHandoff<P, NQ_, NQV_>::value && !P::needs_gradflux(prm);
-#endif
-    }
-    bool refresh_elidable() const override { return GradArgHandoff<P, NQ_, NQV_>::elide_refresh; }
+    bool garg_capable() const override { return HO && !P::needs_gradflux(prm); }
+    bool refresh_elidable() const override { return ELIDE; }
     int law_nder() const override { return P::HAS_SOURCE ? P::NDER : 0; }
     int law_nupd() const override { return P::HAS_UPDATE_AUX ? P::NUPD : 0; }
     int tendency_epb() const override { return TendencyShape<P, NQ_, NQV_>::EPB; }

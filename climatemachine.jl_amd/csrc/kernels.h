@@ -590,13 +590,11 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
             }
         }
         S.negzero();
-#ifndef CMDG_DBG_NOSRC
         if constexpr (P::HAS_SOURCE) {
             Vec<P::NDER> lder;
             load_state<P::NDER, Np>(lder, a.derived, tid, e);
             P::source(a.prm, S, lQ, lgf, laux, lder, a_t, a.model_dir);
         }
-#endif
     }
     __syncthreads();
     Vec<NS> Tv;
@@ -616,10 +614,6 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
             if (hz) {  // generic kernel called with HorizontalDirection() (:64-309)
                 double lt = 0.0;
                 if (a.direction == DIR_HORIZONTAL && P::HAS_SOURCE) lt += S[s];
-#ifdef CMDG_DBG_NOCONTRACT
-                lt += MI * sD[i] * sF[(0 * NS + s) * Np + tid] + MI * sD[j] * sF[(1 * NS + s) * Np + tid];
-                if (false)
-#endif
 #pragma unroll
                 for (int n = 0; n < NQ; ++n) {
                     lt += MI * sD[n + NQ * i] * sF[(0 * NS + s) * Np + n + NQ * (j + NQ * k)];
@@ -630,10 +624,6 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
             if (vt) {  // ::VerticalDirection kernel (:312-548); beta = true after the
                        // horizontal call in EveryDirection (SpaceDiscretization.jl:1192)
                 double lt = 0.0;
-#ifdef CMDG_DBG_NOCONTRACT
-                lt += MI * sDv[k] * sF[(2 * NS + s) * Np + tid] + S[s];
-                if (false)
-#endif
 #pragma unroll
                 for (int kk = 0; kk < NQV; ++kk) {
                     lt += MI * sDv[kk + NQV * k] * sF[(2 * NS + s) * Np + i + NQ * (j + NQ * kk)];
@@ -655,11 +645,7 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
     // ---- faces: dgsem_interface_tendency! ------------------------------------------
     Vec<NS> lift;
     int vidM = 0, fpair = -1;
-#ifdef CMDG_DBG_NOFACE
-    if (false) {
-#else
     if (tid < KD::NFT) {
-#endif
         int f, n;  // recomputed: cheaper than two registers live across the volume phases
         KD::face_task(tid, f, n);
         if (face_on) {
@@ -902,11 +888,6 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
             for (int s = 0; s < NGRAD; ++s) {
                 if (!(GMASK >> s & 1)) continue;
                 double G1 = 0.0, G2 = 0.0;
-#ifdef CMDG_DBG_NOCONTRACT
-                // ablation: the contraction's share of the kernel (results are wrong)
-                G1 = sD[i] * sG[s * Np + tid], G2 = sD[j] * sG[s * Np + tid];
-                if (false)
-#endif
 #pragma unroll
                 for (int n = 0; n < NQ; ++n) {
                     G1 += sD[i + NQ * n] * sG[s * Np + n + NQ * (j + NQ * k)];
@@ -926,10 +907,6 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
             for (int s = 0; s < NGRAD; ++s) {
                 if (!(GMASK >> s & 1)) continue;
                 double G3 = -0.0;
-#ifdef CMDG_DBG_NOCONTRACT
-                G3 = sDv[k] * sG[s * Np + tid];
-                if (false)
-#endif
 #pragma unroll
                 for (int n = 0; n < NQV; ++n)
                     G3 += sDv[k + NQV * n] * sG[s * Np + i + NQ * (j + NQ * n)];

@@ -10,8 +10,7 @@
 #include <vector>
 
 #include "columns.h"
-#include "engine.h"
-#include "filters.h"
+#include "stepping.h"
 #include "physics_ocean01.h"
 
 using namespace cmdg;

@@ -1,4 +1,4 @@
-// The time steppers other than the fused LSRK run (cmdg.hip) and the multirate ones
+// The time steppers other than the fused LSRK run (lsrk_run.hip) and the multirate ones
 // (multirate.hip, split_explicit*.hip): the 2N update on its own, the strong-stability-preserving
 // and 3N low-storage Runge-Kutta steps over one operator, and the low-storage additive
 // Runge-Kutta step (AdditiveRungeKuttaMethod.jl, LowStorageVariant) over a full operator and the

@@ -1,6 +1,7 @@
-// The parts the time steppers that run several operators are built from (steppers.hip,
-// multirate.hip): stream ordering, "an operator, or one minus another", the grid checks and the
-// column solver's internal interface.  Internal: not installed under include/.
+// The parts the time steppers are built from (lsrk_run.hip, steppers.hip, multirate.hip,
+// split_explicit*.hip): an evaluation and a fused LSRK step over a local group, stream ordering,
+// "an operator, or one minus another", the grid checks and the column solver's internal
+// interface.  Internal: not installed under include/.
 #pragma once
 #include <string>
 
@@ -8,6 +9,15 @@
 #include "filters.h"
 
 namespace cmdg {
+
+// cmdg.hip: one evaluation over the handles of a local group, in lock step
+int group_rhs(std::vector<EngineBase *> &g, std::vector<RhsCtx> &c, bool keep_fresh = false);
+// lsrk_run.hip: one fused LSRK step over them.  continued: this step follows the previous step of
+// the same run with nothing in between; handoff: see EngineBase::lsrk_step
+int group_lsrk_step(std::vector<EngineBase *> &g, double **Q, double **dQ, double t, double dt,
+                    int nstages, const double *rka, const double *rkb, const double *rkc,
+                    bool continued = false, const double *stage_times_dev = nullptr,
+                    const StepInRun *handoff = nullptr);
 
 // columnlu.hip: the column solver's pieces that a step drives on the linear handle's stream;
 // errors land on that handle's engine (where GroupCall::finish looks)

@@ -9,7 +9,6 @@
 #include <tuple>
 
 #include "stepping.h"
-#include "columns.h"
 #include "reductions.h"
 #include "interpolation.h"
 
@@ -107,7 +106,7 @@ int dbg_sync()
     return v;
 }
 
-hipError_t ev_record(hipEvent_t &e, hipStream_t s) { return hipEventRecord(e, s); }
+hipError_t ev_record(hipEvent_t e, hipStream_t s) { return hipEventRecord(e, s); }
 
 int EngineBase::launch_status(const char *what)
 {
@@ -129,7 +128,7 @@ int EngineBase::ensure_Imat(const double *host)
 {
     if (d_Imat) return CMDG_OK;
     if (!host) return fail(CMDG_ERR_INVALID, "Imat is NULL");
-    if (hipMalloc(&d_Imat, sizeof(double) * NQ * NQ) != hipSuccess ||
+    if (d_Imat.alloc(NQ * NQ) != hipSuccess ||
         hipMemcpy(d_Imat, host, sizeof(double) * NQ * NQ, hipMemcpyHostToDevice) != hipSuccess)
         return fail(CMDG_ERR_HIP, "Imat upload failed");
     return CMDG_OK;
@@ -193,6 +192,7 @@ int GroupCall::finish(int rc)
 }
 
 // ---------------------------------------------------------------------------------
+// What has an order; the members' destructors free everything else, the two streams last.
 EngineBase::~EngineBase()
 {
     delete worker;  // (drains its queue first)
@@ -200,51 +200,8 @@ EngineBase::~EngineBase()
     if (s_comp) hipStreamSynchronize(s_comp);
     if (s_comm) hipStreamSynchronize(s_comm);
     prof_collect();
-    for (auto &s : slot) {
-        if (s.sendbuf) hipFree(s.sendbuf);
-        if (s.recvbuf) hipFree(s.recvbuf);
-        if (s.ev_packed) hipEventDestroy(s.ev_packed);
-        if (s.ev_done) hipEventDestroy(s.ev_done);
-        if (s.ev_pulled) hipEventDestroy(s.ev_pulled);
-    }
-    if (own_gf && gf) hipFree(gf);
-    if (gf_scratch) hipFree(gf_scratch);
-    if (hypgrad) hipFree(hypgrad);
-    if (own_hd && hypdiv) hipFree(hypdiv);
-    if (W[0]) hipFree(W[0]);
-    if (W[1]) hipFree(W[1]);
-    if (garg) hipFree(garg);
-    if (d_D) hipFree(d_D);
-    if (d_interior_tiled) hipFree(d_interior_tiled);
-    if (d_exterior_tiled) hipFree(d_exterior_tiled);
-    if (d_faceP) hipFree(d_faceP);
-    if (d_faceG) hipFree(d_faceG);
-    if (d_sendoff) hipFree(d_sendoff);
-    if (d_sendent) hipFree(d_sendent);
-    if (d_ghostslot) hipFree(d_ghostslot);
-    if (derived) hipFree(derived);
-    if (d_partial) hipFree(d_partial);
-    if (d_elemred) hipFree(d_elemred);
-    if (d_Imat) hipFree(d_Imat);
-    if (d_flowint) hipFree(d_flowint);
-    if (d_preT) hipFree(d_preT);
-    if (d_Dv) hipFree(d_Dv);
-    if (ev_comp) hipEventDestroy(ev_comp);
-    if (prof_ext_done) hipEventDestroy(prof_ext_done);
     if (graph_exec) hipGraphExecDestroy(graph_exec);
-    if (d_gtime) hipFree(d_gtime);
-    if (gev_fork) hipEventDestroy(gev_fork);
-    for (int i = 0; i < NGEV; ++i) {
-        if (gev_int[i]) hipEventDestroy(gev_int[i]);
-        if (gev_ext[i]) hipEventDestroy(gev_ext[i]);
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (ev_int[i]) hipEventDestroy(ev_int[i]);
-        if (ev_ext[i]) hipEventDestroy(ev_ext[i]);
-    }
     if (nccl_comm && rccl::CommDestroy) rccl::CommDestroy(nccl_comm);
-    if (s_comp) hipStreamDestroy(s_comp);
-    if (s_comm) hipStreamDestroy(s_comm);
 }
 
 int EngineBase::init(const cmdg_desc *d)
@@ -296,7 +253,7 @@ int EngineBase::init(const cmdg_desc *d)
         nabrrecv.assign(d->nabrtovmaprecv, d->nabrtovmaprecv + 2 * d->nnabr);
     }
     HIPCHK(hipGetDevice(&dev));
-    HIPCHK(hipStreamCreateWithFlags(&s_comp, hipStreamNonBlocking));
+    HIPCHK(s_comp.create(hipStreamNonBlocking));
     {
         // CMDG_HALO_PRIORITY=1: the halo stream (the latency chain of a partitioned run: exchange ->
         // exterior launch -> exchange ...) as a high-priority stream, so that its small kernels go
@@ -308,23 +265,23 @@ int EngineBase::init(const cmdg_desc *d)
         int lo = 0, hi = 0;
         const char *pv = getenv("CMDG_HALO_PRIORITY");
         if (communicate() && pv && *pv == '1' && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi < lo)
-            HIPCHK(hipStreamCreateWithPriority(&s_comm, hipStreamNonBlocking, hi));
+            HIPCHK(s_comm.create(hipStreamNonBlocking, hi));
         else
-            HIPCHK(hipStreamCreateWithFlags(&s_comm, hipStreamNonBlocking));
+            HIPCHK(s_comm.create(hipStreamNonBlocking));
     }
     for (int i = 0; i < 2; ++i) {
-        HIPCHK(hipEventCreateWithFlags(&ev_int[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ev_ext[i], hipEventDisableTiming));
+        HIPCHK(ev_int[i].create(hipEventDisableTiming));
+        HIPCHK(ev_ext[i].create(hipEventDisableTiming));
     }
-    HIPCHK(hipEventCreateWithFlags(&gev_fork, hipEventDisableTiming));
+    HIPCHK(gev_fork.create(hipEventDisableTiming));
     if (const char *v = getenv("CMDG_STEP_GRAPH")) step_graph = *v && *v != '0';
-    HIPCHK(hipEventCreateWithFlags(&ev_comp, hipEventDisableTiming));
-    HIPCHK(hipMalloc(&d_D, sizeof(double) * NQ * NQ));
+    HIPCHK(ev_comp.create(hipEventDisableTiming));
+    HIPCHK(d_D.alloc(NQ * NQ));
     HIPCHK(hipMemcpy(d_D, d->D, sizeof(double) * NQ * NQ, hipMemcpyHostToDevice));
     g.D = d_D;
     g.Dv = d_D;
     if (NQV != NQ) {
-        HIPCHK(hipMalloc(&d_Dv, sizeof(double) * NQV * NQV));
+        HIPCHK(d_Dv.alloc(NQV * NQV));
         HIPCHK(hipMemcpy(d_Dv, d->Dv, sizeof(double) * NQV * NQV, hipMemcpyHostToDevice));
         g.Dv = d_Dv;
     }
@@ -332,19 +289,19 @@ int EngineBase::init(const cmdg_desc *d)
         // digest of the face tables: one pass over the reference's arrays, checked as it goes
         const int NFT = 4 * NQ * NQV + 2 * NQ * NQ;
         const int64_t nt = std::max<int64_t>(nreal, 1) * NFT;
-        int *d_bad = nullptr, bad = 0;
-        HIPCHK(hipMalloc(&d_faceP, sizeof(int32_t) * nt));
-        HIPCHK(hipMalloc(&d_faceG, sizeof(double) * 4 * nt));
-        HIPCHK(hipMalloc(&d_bad, sizeof(int)));
-        HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(int), s_comp));  // (stream-ordered before the digest, see alloc0)
+        DevBuf<int> d_bad;
+        int bad = 0;
+        HIPCHK(d_faceP.alloc(nt));
+        HIPCHK(d_faceG.alloc(4 * nt));
+        HIPCHK(d_bad.alloc_zeroed(1, s_comp));  // (stream-ordered before the digest, see below)
         if (nreal > 0)
             hipLaunchKernelGGL(k_face_digest, dim3((unsigned)((nreal * NFT + 255) / 256)), dim3(256), 0,
                                s_comp, g.vgeo, g.nvgeo, g.sgeo, g.vmapM, g.vmapP, g.elemtobndy, NQ,
-                               NQV, nreal, d_faceP, d_faceG, d_bad);
+                               NQV, nreal, d_faceP.get(), d_faceG.get(), d_bad.get());
         hipError_t le = hipGetLastError();
         hipError_t ce = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s_comp);
         hipError_t se = hipStreamSynchronize(s_comp);
-        hipFree(d_bad);
+        d_bad.reset();
         if (le != hipSuccess || ce != hipSuccess || se != hipSuccess)
             return fail(CMDG_ERR_HIP, "cmdg_create: digest of the face tables failed");
         if (bad & 1)
@@ -361,38 +318,32 @@ int EngineBase::init(const cmdg_desc *d)
     // hipMemset of device memory returns before the fill has run, and on the null stream it is not
     // ordered against this engine's non-blocking streams (scripts/probe/memset_null_stream_order.py):
     // every fill is enqueued on the compute stream, which init() drains before it returns
-    auto alloc0 = [&](double **p, size_t n) -> int {
-        if (n == 0) n = 1;
-        HIPCHK(hipMalloc(p, sizeof(double) * n));
-        HIPCHK(hipMemsetAsync(*p, 0, sizeof(double) * n, s_comp));
-        return CMDG_OK;
-    };
     gf = gf_node_major() ? nullptr : d->state_gradient_flux;
     gf_user = gf_node_major() ? d->state_gradient_flux : nullptr;
     if (!gf) {
-        own_gf = true;
-        if (int r = alloc0(&gf, nd * ngf)) return r;
+        HIPCHK(gf_own.alloc_zeroed(std::max<size_t>(nd * ngf, 1), s_comp));
+        gf = gf_own;
     }
     // Qhypervisc_grad is node-major inside the library (cmdg_common.h); a caller's array receives
     // the reference layout only from cmdg_export_hypervisc_grad (export_hypgrad)
     hypgrad_user = ngl > 0 ? d->Qhypervisc_grad : nullptr;
-    if (int r = alloc0(&hypgrad, nd * 3 * ngl)) return r;
+    HIPCHK(hypgrad.alloc_zeroed(std::max<size_t>(nd * 3 * ngl, 1), s_comp));
     hypdiv = d->Qhypervisc_div;
     if (!hypdiv) {
-        own_hd = true;
-        if (int r = alloc0(&hypdiv, nd * nhyp)) return r;
+        HIPCHK(hd_own.alloc_zeroed(std::max<size_t>(nd * nhyp, 1), s_comp));
+        hypdiv = hd_own;
     }
     slot_nvar_max = std::max(std::max(ns, ngf), std::max(3 * ngl, nhyp));
     if (communicate()) {
         for (auto &s : slot) {
-            HIPCHK(hipMalloc(&s.sendbuf, sizeof(double) * slot_nvar_max * std::max<int64_t>(nvmapsend, 1)));
-            HIPCHK(hipMalloc(&s.recvbuf, sizeof(double) * slot_nvar_max * std::max<int64_t>(nvmaprecv, 1)));
-            HIPCHK(hipEventCreateWithFlags(&s.ev_packed, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&s.ev_pulled, hipEventDisableTiming));
+            HIPCHK(s.sendbuf.alloc(slot_nvar_max * std::max<int64_t>(nvmapsend, 1)));
+            HIPCHK(s.recvbuf.alloc(slot_nvar_max * std::max<int64_t>(nvmaprecv, 1)));
+            HIPCHK(s.ev_packed.create(hipEventDisableTiming));
+            HIPCHK(s.ev_done.create(hipEventDisableTiming));
+            HIPCHK(s.ev_pulled.create(hipEventDisableTiming));
         }
     }
-    HIPCHK(hipMalloc(&d_partial, sizeof(double) * 1024));
+    HIPCHK(d_partial.alloc(1024));
     if (communicate())
         if (int r = init_halo_tables()) return r;
     // debugging overrides of the two exchange options (cmdg_set_option still has the last word)
@@ -400,7 +351,7 @@ int EngineBase::init(const cmdg_desc *d)
     if (const char *v = getenv("CMDG_HALO_PIPELINE")) no_pipeline = *v == '0';
     if (const char *v = getenv("CMDG_FUSED_COLUMNS")) fused_columns = atoi(v);
     if (int r = init_derived()) return r;
-    HIPCHK(hipStreamSynchronize(s_comp));  // the fills of alloc0 have run
+    HIPCHK(hipStreamSynchronize(s_comp));  // the fills have run
     return CMDG_OK;
 }
 
@@ -433,8 +384,8 @@ int EngineBase::init_halo_tables()
             const int64_t id = vs[i] - 1, e = id / Np;
             ent[fill[e]++] = SendEnt{(int32_t)(id - e * Np), (int32_t)i};
         }
-        HIPCHK(hipMalloc(&d_sendoff, sizeof(int32_t) * off.size()));
-        HIPCHK(hipMalloc(&d_sendent, sizeof(SendEnt) * ent.size()));
+        HIPCHK(d_sendoff.alloc(off.size()));
+        HIPCHK(d_sendent.alloc(ent.size()));
         HIPCHK(hipMemcpy(d_sendoff, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d_sendent, ent.data(), sizeof(SendEnt) * ent.size(), hipMemcpyHostToDevice));
     }
@@ -455,7 +406,7 @@ int EngineBase::init_halo_tables()
             if (fP[q] >= g0 && (fP[q] - g0 >= ng || gs[fP[q] - g0] < 0)) okr = false;
     }
     if (okr) {
-        HIPCHK(hipMalloc(&d_ghostslot, sizeof(int32_t) * gs.size()));
+        HIPCHK(d_ghostslot.alloc(gs.size()));
         HIPCHK(hipMemcpy(d_ghostslot, gs.data(), sizeof(int32_t) * gs.size(), hipMemcpyHostToDevice));
     }
     direct_recv_ok = okr;
@@ -483,8 +434,7 @@ int EngineBase::ensure_work()
             // streams below, so it could land AFTER the first stages had stored into W and zero
             // them (the "priority stream ordering failure" of round 3: high-priority halo streams
             // merely let the stage kernels overtake the fill; scripts/probe/memset_null_stream_order.py).
-            HIPCHK(hipMalloc(&W[i], sizeof(double) * n));
-            HIPCHK(hipMemsetAsync(W[i], 0, sizeof(double) * n, s_comp));
+            HIPCHK(W[i].alloc_zeroed(n, s_comp));
             HIPCHK(hipStreamSynchronize(s_comp));
         }
     return CMDG_OK;
@@ -496,8 +446,7 @@ int EngineBase::ensure_garg()
 {
     if (!garg) {
         const size_t n = std::max<size_t>((size_t)Np * ngl * nelem, 1);
-        HIPCHK(hipMalloc(&garg, sizeof(double) * n));
-        HIPCHK(hipMemsetAsync(garg, 0, sizeof(double) * n, s_comp));
+        HIPCHK(garg.alloc_zeroed(n, s_comp));
         HIPCHK(hipStreamSynchronize(s_comp));
     }
     return CMDG_OK;
@@ -511,16 +460,18 @@ int EngineBase::synchronize()
 }
 
 // ---- profiling ---------------------------------------------------------------------
+ProfRec &EngineBase::prof_pair(int kernel, bool clamp, Event e1)
+{
+    ProfRec r{kernel, Event(), std::move(e1), clamp};
+    r.e0.create();
+    if (!r.e1) r.e1.create();
+    prof.push_back(std::move(r));
+    return prof.back();
+}
 void EngineBase::prof_begin(int kernel, hipStream_t st)
 {
     if (!profiling) return;
-    ProfRec r;
-    r.kernel = kernel;
-    r.clamp = false;
-    hipEventCreate(&r.e0);
-    hipEventCreate(&r.e1);
-    hipEventRecord(r.e0, st);
-    prof.push_back(r);
+    hipEventRecord(prof_pair(kernel, false).e0, st);
 }
 void EngineBase::prof_end(hipStream_t st)
 {
@@ -563,10 +514,8 @@ void EngineBase::prof_collect()
             prof_ms[r.kernel] += r.clamp && ms < 0 ? 0.0f : ms;
             prof_n[r.kernel] += 1;
         }
-        hipEventDestroy(r.e0);
-        hipEventDestroy(r.e1);
     }
-    prof.clear();
+    prof.clear();  // (destroys the events)
 }
 
 // ---- halo: begin_ghost_exchange! / end_ghost_exchange!  MPIStateArrays.jl:411-483 ----
@@ -693,8 +642,8 @@ int EngineBase::set_stack_height(int nv)
             return std::make_tuple(col / TILE_C, lev / TILE_L, col % TILE_C, lev % TILE_L);
         };
         std::stable_sort(h.begin(), h.end(), [&](int64_t x, int64_t y) { return key(x) < key(y); });
-        int64_t *&own = which ? d_exterior_tiled : d_interior_tiled;
-        if (!own) HIPCHK(hipMalloc(&own, sizeof(int64_t) * n));
+        DevBuf<int64_t> &own = which ? d_exterior_tiled : d_interior_tiled;
+        if (!own) HIPCHK(own.alloc(n));
         HIPCHK(hipMemcpy(own, h.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
         (which ? d_exterior : d_interior) = own;
     }
@@ -713,14 +662,12 @@ int EngineBase::set_stream_priority(int level)
     if (level < -1 || level > 1) return fail(CMDG_ERR_INVALID, "stream priority: 0 (default), 1 (highest) or -1 (lowest)");
     if (int r = synchronize()) return r;
     drop_graph();
-    hipStream_t nc = nullptr, nm = nullptr;
+    Stream nc, nm;
     const int prio = level > 0 ? hi : (level < 0 ? lo : 0);
-    HIPCHK(hipStreamCreateWithPriority(&nc, hipStreamNonBlocking, prio));
-    HIPCHK(hipStreamCreateWithPriority(&nm, hipStreamNonBlocking, prio));
-    hipStreamDestroy(s_comp);
-    hipStreamDestroy(s_comm);
-    s_comp = nc;
-    s_comm = nm;
+    HIPCHK(nc.create(hipStreamNonBlocking, prio));
+    HIPCHK(nm.create(hipStreamNonBlocking, prio));
+    s_comp = std::move(nc);  // (the old streams are drained: synchronize() above)
+    s_comm = std::move(nm);
     stream_priority = level;
     return CMDG_OK;
 }
@@ -774,14 +721,9 @@ int EngineBase::halo_end(int s, double *array, int nvar, bool unpack, bool on_ha
     if (profiling) {
         // exposed time of this exchange: from the moment the compute stream has nothing left to
         // do but wait (its interior launches are done) to the moment the ghosts are in place
-        ProfRec r;
-        r.kernel = CMDG_K_HALO_EXPOSED;
-        r.clamp = true;
-        hipEventCreate(&r.e0);
-        hipEventCreate(&r.e1);
+        ProfRec &r = prof_pair(CMDG_K_HALO_EXPOSED, true);
         hipEventRecord(r.e0, s_comp);
         hipEventRecord(r.e1, s_comm);
-        prof.push_back(r);
     }
     if (dbg_sync() & 16) HIPCHK(hipStreamSynchronize(s_comm));
     HIPCHK(hipStreamWaitEvent(s_comp, h.ev_done, 0));
@@ -812,7 +754,7 @@ int EngineBase::rhs_segment(int seg, const RhsCtx &c)
     // interior launch I_p of a pass (enqueued before its exterior launch): waits for E_(p-1)
     // a capture has events of its own (the eager ones keep their last eager record), and its first
     // launches wait for nothing of the step before: graphs launched on one stream run in order
-    hipEvent_t *const EI = capturing ? gev_int : ev_int, *const EE = capturing ? gev_ext : ev_ext;
+    const Event *const EI = capturing ? gev_int : ev_int, *const EE = capturing ? gev_ext : ev_ext;
     // index of pass q's event: alternating parity when eager, one event per pass in a capture
     auto evi = [&](int64_t q) { return capturing ? (int)((cap_pass + (q - pass_seq)) % NGEV) : (int)(q & 1); };
     auto interior_begin = [&]() -> int {
@@ -822,14 +764,7 @@ int EngineBase::rhs_segment(int seg, const RhsCtx &c)
         if (capturing && cap_interior++ == 0) return CMDG_OK;
         if (profiling && prof_ext_done) {
             // exposed: the compute stream idle until the previous exterior launch is done
-            ProfRec pr;
-            pr.kernel = CMDG_K_HALO_EXPOSED;
-            pr.clamp = true;
-            hipEventCreate(&pr.e0);
-            hipEventRecord(pr.e0, s_comp);
-            pr.e1 = prof_ext_done;
-            prof_ext_done = nullptr;
-            prof.push_back(pr);
+            hipEventRecord(prof_pair(CMDG_K_HALO_EXPOSED, true, std::move(prof_ext_done)).e0, s_comp);
         }
         if (dbg_sync() & 64) HIPCHK(hipStreamSynchronize(s_comm));
         HIPCHK(hipStreamWaitEvent(s_comp, EE[evi(pass_seq - 1)], 0));
@@ -850,8 +785,7 @@ int EngineBase::rhs_segment(int seg, const RhsCtx &c)
     auto exterior_end = [&]() -> int {
         if (pipe) HIPCHK(ev_record(EE[evi(pass_seq)], s_comm));
         if (pipe && profiling) {
-            if (prof_ext_done) hipEventDestroy(prof_ext_done);
-            hipEventCreate(&prof_ext_done);
+            prof_ext_done.create();  // (one that no interior launch took is destroyed)
             hipEventRecord(prof_ext_done, s_comm);
         }
         return CMDG_OK;
@@ -894,7 +828,7 @@ int EngineBase::rhs_segment(int seg, const RhsCtx &c)
             if (gf_node_major()) {  // the filter kernels work on the reference layout
                 const int64_t n = (int64_t)Np * ngf * nelem;
                 const unsigned nb = (unsigned)((n + 255) / 256);
-                if (!gf_scratch) HIPCHK(hipMalloc(&gf_scratch, sizeof(double) * n));
+                if (!gf_scratch) HIPCHK(gf_scratch.alloc(n));
                 hipLaunchKernelGGL(k_export_node_major, dim3(nb), dim3(256), 0, s_comp, gf_scratch, gf, Np, ngf, nelem);
                 TRY(filter_apply(gradient_filter, gf_scratch, ngf));
                 hipLaunchKernelGGL(k_import_node_major, dim3(nb), dim3(256), 0, s_comp, gf, gf_scratch, Np, ngf, nelem);
@@ -1054,588 +988,13 @@ int EngineBase::courant(int mode, int kind, const double *Q, double dt, double t
         *out = mode == 0 ? INFINITY : -INFINITY;
         return CMDG_OK;
     }
-    if (!d_elemred) HIPCHK(hipMalloc(&d_elemred, sizeof(double) * (nreal + 1)));
+    if (!d_elemred) HIPCHK(d_elemred.alloc(nreal + 1));
     if (int r = launch_courant(mode, kind, Q, dt, t, dir, d_elemred)) return r;
     hipLaunchKernelGGL(k_extremum, dim3(1), dim3(1024), 0, s_comp, d_elemred, nreal, mode == 0,
                        d_elemred + nreal);
     HIPCHK(hipMemcpyAsync(out, d_elemred + nreal, sizeof(double), hipMemcpyDeviceToHost, s_comp));
     HIPCHK(hipStreamSynchronize(s_comp));
     return CMDG_OK;
-}
-
-// ---- indefinite_stack_integral! / reverse_indefinite_stack_integral!  DGModel.jl:445-529 ----
-template <int NQ_, int NOUT>
-static void launch_stack(bool reverse, const StackArgs &a, hipStream_t st)
-{
-    constexpr int SPB = 256 / (NQ_ * NQ_);
-    const dim3 grid((unsigned)((a.nhorz + SPB - 1) / SPB)), block(256);
-    if (reverse)
-        hipLaunchKernelGGL((k_reverse_stack_integral<NQ_, NOUT>), grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL((k_stack_integral<NQ_, NOUT>), grid, block, 0, st, a);
-}
-
-int EngineBase::stack_integral(bool reverse, const double *Q, int nstate, double *aux_arr,
-                               int naux_arr, int nvert, const double *Imat_host,
-                               const cmdg_stack_integral_desc *d, int64_t h0, int64_t nh)
-{
-    if (NQ < 2 || NQ > 8 || NQV != NQ)
-        return fail(CMDG_ERR_UNSUPPORTED, "stack integral: polynomial order not compiled in");
-    if (!stacked) return fail(CMDG_ERR_INVALID, "stack integral: the topology is not stacked");
-    if (nvert < 1 || nreal % nvert != 0)
-        return fail(CMDG_ERR_INVALID, "stack integral: nreal is not a multiple of nvertelem");
-    if (d->nout < 1 || d->nout > CMDG_STACK_MAXOUT) return fail(CMDG_ERR_INVALID, "stack integral: nout");
-    if (g.nvgeo < 16) return fail(CMDG_ERR_INVALID, "stack integral: vgeo lacks the JcV column");
-    for (int s = 0; s < d->nout; ++s) {
-        const bool st = !reverse && d->src_is_state[s] != 0;
-        const int src = reverse ? d->rsrc_col[s] : d->src_col[s];
-        const int dst = reverse ? d->rdst_col[s] : d->dst_col[s];
-        if (st && !Q) return fail(CMDG_ERR_INVALID, "stack integral: state integrand without Q");
-        if (src < 0 || src >= (st ? nstate : naux_arr) || dst < 0 || dst >= naux_arr)
-            return fail(CMDG_ERR_INVALID, "stack integral: column out of range");
-    }
-    if (nh < 0) nh = nreal / nvert;
-    if (nh == 0) return CMDG_OK;
-    if (!reverse && Imat_host) {  // (NULL: the matrix uploaded by an earlier call / the hooks)
-        if (!d_Imat) HIPCHK(hipMalloc(&d_Imat, sizeof(double) * NQ * NQ));
-        HIPCHK(hipMemcpyAsync(d_Imat, Imat_host, sizeof(double) * NQ * NQ, hipMemcpyHostToDevice, s_comp));
-        HIPCHK(hipStreamSynchronize(s_comp));  // Imat_host may be a temporary of the caller
-    }
-    if (!reverse && !d_Imat) return fail(CMDG_ERR_INVALID, "stack integral: Imat is NULL");
-    StackArgs a{};
-    a.Q = Q;
-    a.aux = aux_arr;
-    a.vgeo = g.vgeo;
-    a.Imat = d_Imat;
-    a.nstate = nstate;
-    a.naux = naux_arr;
-    a.nvgeo = g.nvgeo;
-    a.nvert = nvert;
-    a.jcv = 15;  // _JcV (Grids.jl:76-92)
-    a.h0 = h0;
-    a.nhorz = nh;
-    // integrals of different variables are independent: four ride in one launch
-    for (int c0 = 0; c0 < d->nout; c0 += 4) {
-        const int n = std::min(4, d->nout - c0);
-        for (int s = 0; s < n; ++s) {
-            a.is_state[s] = reverse ? 0 : d->src_is_state[c0 + s];
-            a.src[s] = reverse ? d->rsrc_col[c0 + s] : d->src_col[c0 + s];
-            a.dst[s] = reverse ? d->rdst_col[c0 + s] : d->dst_col[c0 + s];
-            a.scale[s] = d->scale[c0 + s];
-        }
-        prof_begin(CMDG_K_STACK_INTEGRAL, s_comp);
-#define CMDG_STACK_CASE(Q)                                          \
-    case Q:                                                         \
-        switch (n) {                                                \
-        case 1: launch_stack<Q, 1>(reverse, a, s_comp); break;      \
-        case 2: launch_stack<Q, 2>(reverse, a, s_comp); break;      \
-        case 3: launch_stack<Q, 3>(reverse, a, s_comp); break;      \
-        default: launch_stack<Q, 4>(reverse, a, s_comp); break;     \
-        }                                                           \
-        break;
-        switch (NQ) {
-            CMDG_STACK_CASE(2) CMDG_STACK_CASE(3) CMDG_STACK_CASE(4) CMDG_STACK_CASE(5)
-            CMDG_STACK_CASE(6) CMDG_STACK_CASE(7) CMDG_STACK_CASE(8)
-        default: break;
-        }
-#undef CMDG_STACK_CASE
-        prof_end(s_comp);
-    }
-    return launch_status("stack integral launch");
-}
-
-// ---- law-specific update_auxiliary_state! / update_auxiliary_state_gradient! as hooks ----
-int EngineBase::set_hooks(const cmdg_rhs_hooks *hk)
-{
-    auto forget_child = [&]() {  // this handle no longer evaluates its former nested operator
-        if (has_hooks && hooks.pre_rhs_handle && hooks.pre_rhs_handle->eng) {
-            auto &v = hooks.pre_rhs_handle->eng->nested_in;
-            v.erase(std::remove(v.begin(), v.end(), this), v.end());
-        }
-    };
-    if (!hk) {
-        forget_child();
-        has_hooks = false;
-        hooks_orphaned = false;
-        hooks.pre_rhs_handle = nullptr;
-        return CMDG_OK;
-    }
-    if (hk->npre < 0 || hk->npre > CMDG_MAX_HOOK_OPS || hk->ncopy < 0 || hk->ncopy > CMDG_MAX_HOOK_OPS ||
-        hk->nsurf < 0 || hk->nsurf > CMDG_MAX_HOOK_OPS)
-        return fail(CMDG_ERR_INVALID, "hooks: too many operations");
-    if (gf_node_major() && hk->ncopy > 0)
-        return fail(CMDG_ERR_UNSUPPORTED, "hooks: gradient-flux copies are not built for laws whose state_gradient_flux "
-                                          "is node-major inside the library (the dry atmosphere)");
-    const bool cols = hk->has_integral || hk->has_reverse_integral || hk->nsurf > 0 ||
-                      hk->has_flow_deviation;
-    if (cols && (!stacked || hk->nvertelem < 1 || nreal % hk->nvertelem || nghost % hk->nvertelem))
-        return fail(CMDG_ERR_INVALID, "hooks: column operators need a stacked topology and nvertelem");
-    for (int i = 0; i < hk->ncopy; ++i)
-        if (hk->copy_gf_col[i] < 0 || hk->copy_gf_col[i] >= ngf || hk->copy_aux_col[i] < 0 ||
-            hk->copy_aux_col[i] >= naux)
-            return fail(CMDG_ERR_INVALID, "hooks: copy column out of range");
-    for (int i = 0; i < hk->nsurf; ++i)
-        if (hk->surf_src_col[i] < 0 || hk->surf_src_col[i] >= naux || hk->surf_dst_col[i] < 0 ||
-            hk->surf_dst_col[i] >= naux || hk->surf_src_col[i] == hk->surf_dst_col[i])
-            return fail(CMDG_ERR_INVALID, "hooks: surface column out of range (or source == destination)");
-    for (int i = 0; i < hk->npre; ++i)
-        if (!hk->pre_filter[i]) return fail(CMDG_ERR_INVALID, "hooks: NULL filter");
-    if (hk->has_flow_deviation) {
-        if (hk->flow_u_col < 0 || hk->flow_u_col + 2 > ns || hk->flow_ud_col < 0 ||
-            hk->flow_ud_col + 2 > naux || !(hk->flow_H > 0))
-            return fail(CMDG_ERR_INVALID, "hooks: flow deviation columns / depth");
-        if (!d_flowint) HIPCHK(hipMalloc(&d_flowint, sizeof(double) * 2 * Np * nelem));
-    }
-    if (hk->pre_rhs_handle) {
-        EngineBase *ch = hk->pre_rhs_handle->eng;
-        if (!ch || ch == this || ch->Np != Np || ch->nelem != nelem || ch->ns != ns || ch->dev != dev)
-            return fail(CMDG_ERR_INVALID, "hooks: the nested operator must share grid, state and device");
-        if (ch->nabrtorank != nabrtorank || ch->nreal != nreal)
-            return fail(CMDG_ERR_INVALID, "hooks: the nested operator must live on the same partition (same neighbours)");
-        if (hk->pre_rhs_src_col < 0 || hk->pre_rhs_src_col >= ch->ns || hk->pre_rhs_dst_aux_col < 0 ||
-            hk->pre_rhs_dst_aux_col >= naux)
-            return fail(CMDG_ERR_INVALID, "hooks: nested operator column out of range");
-        if (!d_preT) HIPCHK(hipMalloc(&d_preT, sizeof(double) * (size_t)Np * ch->ns * nelem));
-    }
-    if (hk->has_integral || hk->has_flow_deviation) {
-        if (!hk->Imat) return fail(CMDG_ERR_INVALID, "hooks: Imat is NULL");
-        if (!d_Imat) HIPCHK(hipMalloc(&d_Imat, sizeof(double) * NQ * NQ));
-        HIPCHK(hipMemcpy(d_Imat, hk->Imat, sizeof(double) * NQ * NQ, hipMemcpyHostToDevice));
-    }
-    forget_child();
-    hooks = *hk;
-    hooks.Imat = nullptr;
-    has_hooks = true;
-    hooks_orphaned = false;
-    if (hooks.pre_rhs_handle) hooks.pre_rhs_handle->eng->nested_in.push_back(this);
-    return CMDG_OK;
-}
-
-// update_auxiliary_state!(dg, law, Q, t, realelems) as the recorded composition.  First half: the
-// pre filters, and the context of the nested operator's evaluation (whose stream is made to follow
-// this one); second half: its tendency column into the auxiliary state, the column operators, the
-// flow deviation.  Between the two the nested operator is evaluated -- by run_pre_hooks itself for
-// a single handle (one rank, or one RCCL rank per process: the nested operator exchanges with its
-// own communicator, in the same order on every rank), by group_rhs in lock step for a local group.
-int EngineBase::run_pre_hooks_a(const RhsCtx &c, RhsCtx &cc)
-{
-    if (hooks_orphaned)
-        return fail(CMDG_ERR_INVALID, "hooks: the nested operator of this handle was destroyed; set new hooks");
-    if (!filter_pair(c.Qin))  // (two vertical filters on disjoint states: one launch)
-        for (int i = 0; i < hooks.npre; ++i)
-            if (int r = filter_apply(reinterpret_cast<const FilterObj *>(hooks.pre_filter[i]), c.Qin, ns))
-                return r;
-    if (hooks.pre_rhs_handle) {
-        // conti3d_dg(ct3d_dQ, Q, p, t; increment = false); A.w = dQ.theta  (OceanModel.jl:456-477)
-        EngineBase *ch = hooks.pre_rhs_handle->eng;
-        HIPCHK(ev_record(ev_comp, s_comp));
-        HIPCHK(hipStreamWaitEvent(ch->s_comp, ev_comp, 0));
-        cc = RhsCtx();
-        cc.tendency = d_preT;
-        cc.Qin = c.Qin;
-        cc.t = c.t;
-        cc.alpha = 1.0;
-        cc.beta = 0.0;
-    }
-    return CMDG_OK;
-}
-
-// The two pre filters of the ocean models as one launch (filters.h k_apply_vfilter_pair) when they
-// are vertical spectral FilterIndices filters on disjoint states; false: apply them one by one.
-bool EngineBase::filter_pair(double *Q)
-{
-    if (fused_columns < 2 || hooks.npre != 2 || NQ < 2 || NQ > 8 || NQV != NQ || nreal <= 0) return false;
-    const FilterObj *f1 = reinterpret_cast<const FilterObj *>(hooks.pre_filter[0]);
-    const FilterObj *f2 = reinterpret_cast<const FilterObj *>(hooks.pre_filter[1]);
-    for (const FilterObj *f : {f1, f2})
-        if (f->kind != CMDG_FILTER_SPECTRAL || f->target != CMDG_TARGET_INDICES || f->direction != DIR_VERTICAL)
-            return false;
-    if (f1->nindices + f2->nindices > 8) return false;
-    for (int i = 0; i < f1->nindices; ++i) {
-        if (f1->indices[i] > ns) return false;
-        for (int j = 0; j < f2->nindices; ++j)
-            if (f2->indices[j] > ns || f1->indices[i] == f2->indices[j]) return false;
-    }
-    FilterArgs a{};
-    a.Q = Q;
-    a.aux = aux;
-    a.vgeo = g.vgeo;
-    a.Fh = f1->d_Fh;
-    a.Fv = f1->d_Fv;
-    a.nstate = ns;
-    a.naux = naux;
-    a.nvgeo = g.nvgeo;
-    a.nreal = nreal;
-    a.nfs = f1->nindices + f2->nindices;
-    for (int i = 0; i < f1->nindices; ++i) a.idx[i] = f1->indices[i];
-    for (int j = 0; j < f2->nindices; ++j) a.idx[f1->nindices + j] = f2->indices[j];
-    a.do_h = 0, a.do_v = 1;
-    prof_begin(CMDG_K_FILTER, s_comp);
-#define CMDG_FP_CASE(N)                                                                                    \
-    case N:                                                                                                \
-        hipLaunchKernelGGL((k_apply_vfilter_pair<N>),                                                      \
-                           dim3((unsigned)(((int64_t)N * N * a.nfs * nreal + 255) / 256)), dim3(256), 0,   \
-                           s_comp, a, (const double *)f2->d_Fv, f1->nindices);                             \
-        break;
-    switch (NQ) {
-        CMDG_FP_CASE(2) CMDG_FP_CASE(3) CMDG_FP_CASE(4) CMDG_FP_CASE(5) CMDG_FP_CASE(6) CMDG_FP_CASE(7)
-        CMDG_FP_CASE(8)
-    default: break;
-    }
-#undef CMDG_FP_CASE
-    prof_end(s_comp);
-    return true;
-}
-
-int EngineBase::run_pre_hooks_b(const RhsCtx &c)
-{
-    if (hooks.pre_rhs_handle) {
-        EngineBase *ch = hooks.pre_rhs_handle->eng;
-        HIPCHK(ev_record(ch->ev_comp, ch->s_comp));
-        HIPCHK(hipStreamWaitEvent(s_comp, ch->ev_comp, 0));
-        const int64_t n = nreal * Np;
-        hipLaunchKernelGGL(k_scaled_column_copy, dim3(nblocks(n)), dim3(256), 0, s_comp, aux, naux,
-                           hooks.pre_rhs_dst_aux_col, (const double *)d_preT, ch->ns, hooks.pre_rhs_src_col,
-                           1.0, Np, (int64_t)0, nreal);
-    }
-    if (hooks.ops_before_gradients)
-        if (int r = run_column_ops(c, 0, nreal)) return r;
-    if (hooks.has_flow_deviation)
-        if (int r = flow_deviation(c.Qin, 0, nreal / hooks.nvertelem)) return r;
-    return CMDG_OK;
-}
-
-int EngineBase::run_pre_hooks(const RhsCtx &c)
-{
-    RhsCtx cc;
-    if (int r = run_pre_hooks_a(c, cc)) return r;
-    if (hooks.pre_rhs_handle) {
-        EngineBase *ch = hooks.pre_rhs_handle->eng;
-        if (int r = ch->rhs_async(cc)) return fail(r, "nested operator: " + ch->err);
-    }
-    return run_pre_hooks_b(c);
-}
-
-// compute_flow_deviation!(dg, ::HBModel, ::Coupled, Q, t)
-// (HydrostaticBoussinesqCoupling.jl:43-85): u_d = u - (1/H) int u dz on the stacks
-// [h0, h0 + nh).  For ghost stacks (after the exchange of Q) the integral runs over the received
-// face pencils, which is all the neighbours read.
-int EngineBase::flow_deviation(double *Q, int64_t h0, int64_t nh)
-{
-    if (nh <= 0) return CMDG_OK;
-    if (fused_columns && NQ >= 2 && NQ <= 8 && NQV == NQ && g.nvgeo >= 16 && d_Imat) {
-        // integral and subtraction in one launch (columns.h k_flow_deviation)
-        prof_begin(CMDG_K_STACK_INTEGRAL, s_comp);
-#define CMDG_FD_CASE(N)                                                                                  \
-    case N: {                                                                                            \
-        constexpr int SPB = 256 / (N * N);                                                               \
-        hipLaunchKernelGGL((k_flow_deviation<N>), dim3((unsigned)((nh + SPB - 1) / SPB)), dim3(256), 0,  \
-                           s_comp, (const double *)Q, ns, hooks.flow_u_col, aux, naux, hooks.flow_ud_col, \
-                           g.vgeo, g.nvgeo, 15, (const double *)d_Imat, hooks.flow_H, hooks.nvertelem,   \
-                           h0, nh);                                                                      \
-    } break;
-        switch (NQ) {
-            CMDG_FD_CASE(2) CMDG_FD_CASE(3) CMDG_FD_CASE(4) CMDG_FD_CASE(5) CMDG_FD_CASE(6) CMDG_FD_CASE(7)
-            CMDG_FD_CASE(8)
-        default: break;
-        }
-#undef CMDG_FD_CASE
-        prof_end(s_comp);
-        return CMDG_OK;
-    }
-    if (int r = integrate_velocity(Q, ns, hooks.flow_u_col, hooks.nvertelem, h0, nh)) return r;
-    const int64_t n = nh * hooks.nvertelem * Np;
-    hipLaunchKernelGGL(k_column_minus_top_over_H, dim3(nblocks(n)), dim3(256), 0, s_comp, aux, naux,
-                       hooks.flow_ud_col, (const double *)Q, ns, hooks.flow_u_col, (const double *)d_flowint,
-                       hooks.flow_H, NQ * NQ, NQ, hooks.nvertelem, h0, nh);
-    return CMDG_OK;
-}
-
-// update_auxiliary_state!(integral_model, ...) of VerticalIntegralModel.jl:60-81: the upward
-// column integral of X[:, col..col+1, :] into the scratch d_flowint (Np, 2, nelem)
-int EngineBase::integrate_velocity(const double *X, int nstate, int col, int nvert, int64_t h0,
-                                   int64_t nh)
-{
-    if (nh < 0) nh = nreal / nvert;
-    if (!d_flowint) HIPCHK(hipMalloc(&d_flowint, sizeof(double) * 2 * Np * nelem));
-    cmdg_stack_integral_desc d{};
-    d.nout = 2;
-    for (int c = 0; c < 2; ++c) {
-        d.src_is_state[c] = 1;
-        d.src_col[c] = col + c;
-        d.scale[c] = 1.0;
-        d.dst_col[c] = c;
-    }
-    return stack_integral(false, X, nstate, d_flowint, 2, nvert, nullptr, &d, h0, nh);
-}
-
-int EngineBase::run_gradient_hooks(const RhsCtx &c, int64_t e0, int64_t e1)
-{
-    if (e1 <= e0) return CMDG_OK;
-    if (!hooks.ops_before_gradients && column_chain(c, e0, e1, true)) return CMDG_OK;
-    const int64_t n = (e1 - e0) * Np;
-    const unsigned nb = nblocks(n);
-    for (int i = 0; i < hooks.ncopy; ++i)
-        hipLaunchKernelGGL(k_scaled_column_copy, dim3(nb), dim3(256), 0, s_comp, aux, naux,
-                           hooks.copy_aux_col[i], gf, ngf, hooks.copy_gf_col[i], hooks.copy_scale[i],
-                           Np, e0, e1);
-    if (hooks.ops_before_gradients) return CMDG_OK;  // done in update_auxiliary_state! already
-    return run_column_ops(c, e0, e1);
-}
-
-// The recorded composition copy -> upward integrals -> reverse integral -> surface value as ONE
-// launch (columns.h k_column_chain) when it has the shape the ocean models record: every copied
-// gradient-flux column is the integrand AND the destination of one upward integral, every
-// reverse integral runs in place on an upward integral's result, every surface value is taken from
-// an upward integral that is not reversed.  Anything else: false, and the caller issues the
-// operations one by one.
-bool EngineBase::column_chain(const RhsCtx &c, int64_t e0, int64_t e1, bool with_copies)
-{
-    if (!fused_columns || !hooks.has_integral || NQ < 2 || NQ > 8 || NQV != NQ || g.nvgeo < 16 || !d_Imat)
-        return false;
-    const cmdg_stack_integral_desc &d = hooks.integral;
-    const int nv = hooks.nvertelem;
-    if (d.nout < 1 || d.nout > 4 || !stacked || nv < 1) return false;
-    ChainArgs ch{};
-    StackArgs &a = ch.a;
-    a.Q = c.Qin;
-    a.aux = aux;
-    a.vgeo = g.vgeo;
-    a.Imat = d_Imat;
-    a.nstate = ns;
-    a.naux = naux;
-    a.nvgeo = g.nvgeo;
-    a.nvert = nv;
-    a.jcv = 15;
-    a.h0 = e0 / nv;
-    a.nhorz = (e1 - e0) / nv;
-    ch.gf = gf;
-    ch.ngf = ngf;
-    for (int s = 0; s < STACK_MAXOUT; ++s) ch.gf_col[s] = ch.rev_dst[s] = ch.surf_dst[s] = -1;
-    for (int s = 0; s < d.nout; ++s) {
-        a.is_state[s] = d.src_is_state[s];
-        a.src[s] = d.src_col[s];
-        a.dst[s] = d.dst_col[s];
-        a.scale[s] = d.scale[s];
-        if (d.src_is_state[s] && !c.Qin) return false;
-    }
-    if (with_copies)
-        for (int i = 0; i < hooks.ncopy; ++i) {
-            int hit = -1;
-            for (int s = 0; s < d.nout; ++s)
-                if (!d.src_is_state[s] && d.src_col[s] == hooks.copy_aux_col[i] &&
-                    d.dst_col[s] == hooks.copy_aux_col[i] && ch.gf_col[s] < 0)
-                    hit = s;
-            // the copied column must feed exactly that integral (nobody else reads the copy)
-            for (int s = 0; s < d.nout; ++s)
-                if (s != hit && !d.src_is_state[s] && d.src_col[s] == hooks.copy_aux_col[i]) hit = -1;
-            if (hit < 0) return false;
-            ch.gf_col[hit] = hooks.copy_gf_col[i];
-            ch.gf_scale[hit] = hooks.copy_scale[i];
-        }
-    if (hooks.has_reverse_integral) {
-        const cmdg_stack_integral_desc &r = hooks.reverse_integral;
-        for (int q = 0; q < r.nout; ++q) {
-            int hit = -1;
-            for (int s = 0; s < d.nout; ++s)
-                if (d.dst_col[s] == r.rsrc_col[q] && r.rdst_col[q] == r.rsrc_col[q] && ch.rev_dst[s] < 0) hit = s;
-            if (hit < 0) return false;
-            ch.rev_dst[hit] = r.rdst_col[q];
-        }
-    }
-    for (int i = 0; i < hooks.nsurf; ++i) {
-        int hit = -1;
-        for (int s = 0; s < d.nout; ++s)
-            if (d.dst_col[s] == hooks.surf_src_col[i] && ch.rev_dst[s] < 0 && ch.surf_dst[s] < 0) hit = s;
-        if (hit < 0) return false;
-        for (int s = 0; s < d.nout; ++s)  // the destination is nobody's integrand or result
-            if (hooks.surf_dst_col[i] == d.dst_col[s] || (!d.src_is_state[s] && hooks.surf_dst_col[i] == d.src_col[s]))
-                return false;
-        ch.surf_dst[hit] = hooks.surf_dst_col[i];
-    }
-    // (two upward integrals must not write one column, nor read what another one writes)
-    for (int s = 0; s < d.nout; ++s)
-        for (int q = 0; q < d.nout; ++q)
-            if (q != s && (d.dst_col[s] == d.dst_col[q] || (!d.src_is_state[q] && d.src_col[q] == d.dst_col[s])))
-                return false;
-    if (a.nhorz <= 0) return true;
-    prof_begin(CMDG_K_STACK_INTEGRAL, s_comp);
-#define CMDG_CHAIN_CASE(N)                                                                                   \
-    case N: {                                                                                                \
-        constexpr int SPB = 256 / (N * N);                                                                   \
-        const dim3 grid((unsigned)((a.nhorz + SPB - 1) / SPB)), block(256);                                  \
-        switch (d.nout) {                                                                                    \
-        case 1: hipLaunchKernelGGL((k_column_chain<N, 1>), grid, block, 0, s_comp, ch); break;               \
-        case 2: hipLaunchKernelGGL((k_column_chain<N, 2>), grid, block, 0, s_comp, ch); break;               \
-        case 3: hipLaunchKernelGGL((k_column_chain<N, 3>), grid, block, 0, s_comp, ch); break;               \
-        default: hipLaunchKernelGGL((k_column_chain<N, 4>), grid, block, 0, s_comp, ch); break;              \
-        }                                                                                                    \
-    } break;
-    switch (NQ) {
-        CMDG_CHAIN_CASE(2) CMDG_CHAIN_CASE(3) CMDG_CHAIN_CASE(4) CMDG_CHAIN_CASE(5) CMDG_CHAIN_CASE(6)
-        CMDG_CHAIN_CASE(7) CMDG_CHAIN_CASE(8)
-    default: break;
-    }
-#undef CMDG_CHAIN_CASE
-    prof_end(s_comp);
-    return true;
-}
-
-// upward integral, downward integral, surface value down the column: elements [e0, e1)
-int EngineBase::run_column_ops(const RhsCtx &c, int64_t e0, int64_t e1)
-{
-    if (e1 <= e0) return CMDG_OK;
-    if (column_chain(c, e0, e1, false)) return CMDG_OK;
-    const int64_t n = (e1 - e0) * Np;
-    const unsigned nb = nblocks(n);
-    const int nv = hooks.nvertelem;
-    if (hooks.has_integral)
-        if (int r = stack_integral(false, c.Qin, ns, aux, naux, nv, nullptr, &hooks.integral, e0 / nv,
-                                   (e1 - e0) / nv))
-            return r;
-    if (hooks.has_reverse_integral)
-        if (int r = stack_integral(true, nullptr, 0, aux, naux, nv, nullptr, &hooks.reverse_integral,
-                                   e0 / nv, (e1 - e0) / nv))
-            return r;
-    for (int i = 0; i < hooks.nsurf; ++i)
-        hipLaunchKernelGGL(k_surface_to_column, dim3(nb), dim3(256), 0, s_comp, aux, naux,
-                           hooks.surf_src_col[i], hooks.surf_dst_col[i], NQ * NQ, NQ, nv, e0 / nv,
-                           (e1 - e0) / nv);
-    return CMDG_OK;
-}
-
-// ---- Filters.apply_async!   Filters.jl:440-607 ----------------------------------------
-int EngineBase::filter_create(const cmdg_filter_desc *d, FilterObj **out)
-{
-    if (d->kind < CMDG_FILTER_SPECTRAL || d->kind > CMDG_FILTER_TMAR)
-        return fail(CMDG_ERR_INVALID, "filter: unknown kind");
-    if (d->target < CMDG_TARGET_INDICES || d->target > CMDG_TARGET_ATMOS_SPECIFIC_PERTURBATIONS)
-        return fail(CMDG_ERR_INVALID, "filter: unknown target");
-    if (d->direction < 0 || d->direction > 2) return fail(CMDG_ERR_INVALID, "filter: bad direction");
-    if (d->kind == CMDG_FILTER_TMAR && d->target != CMDG_TARGET_INDICES)
-        return fail(CMDG_ERR_INVALID, "TMAR filter takes FilterIndices targets");
-    if (d->target == CMDG_TARGET_INDICES) {
-        if (d->nindices < 1 || d->nindices > CMDG_MAX_FILTER_STATES)
-            return fail(CMDG_ERR_INVALID, "filter: 1..32 filtered states");
-        for (int i = 0; i < d->nindices; ++i)
-            if (d->indices[i] < 1) return fail(CMDG_ERR_INVALID, "filter: indices are 1-based");
-    } else if (d->aux_ref_rho < 0 || d->aux_ref_rho >= naux || d->aux_ref_rhoe < 0 ||
-               d->aux_ref_rhoe >= naux) {
-        return fail(CMDG_ERR_INVALID, "filter: reference-state columns outside state_auxiliary");
-    }
-    if (d->kind != CMDG_FILTER_TMAR && (!d->filter_h || !d->filter_v))
-        return fail(CMDG_ERR_INVALID, "filter: filter matrices are NULL");
-    FilterObj *f = new (std::nothrow) FilterObj();
-    if (!f) return fail(CMDG_ERR_INVALID, "filter: out of memory");
-    f->kind = d->kind;
-    f->target = d->target;
-    f->direction = d->direction;
-    f->nindices = d->nindices;
-    for (int i = 0; i < CMDG_MAX_FILTER_STATES; ++i) f->indices[i] = d->indices[i];
-    f->aux_ref_rho = d->aux_ref_rho;
-    f->aux_ref_rhoe = d->aux_ref_rhoe;
-    if (d->kind != CMDG_FILTER_TMAR) {
-        const size_t nb = sizeof(double) * NQ * NQ;
-        if (hipMalloc(&f->d_Fh, nb) != hipSuccess || hipMalloc(&f->d_Fv, nb) != hipSuccess ||
-            hipMemcpy(f->d_Fh, d->filter_h, nb, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(f->d_Fv, d->filter_v, nb, hipMemcpyHostToDevice) != hipSuccess) {
-            if (f->d_Fh) hipFree(f->d_Fh);
-            if (f->d_Fv) hipFree(f->d_Fv);
-            delete f;
-            return fail(CMDG_ERR_HIP, "filter: upload of the filter matrices failed");
-        }
-    }
-    *out = f;
-    return CMDG_OK;
-}
-
-template <int NQ_>
-static void launch_filter(const FilterObj *f, const FilterArgs &a, int nfs, int64_t nreal,
-                          hipStream_t st)
-{
-    const dim3 grid((unsigned)nreal), block(FDims<NQ_>::NT);
-    const size_t lds = sizeof(double) * 2 * nfs * FDims<NQ_>::Np;
-    auto spectral = [&](auto K) { hipLaunchKernelGGL(K, grid, block, lds, st, a); };
-    if (f->kind == CMDG_FILTER_TMAR) {
-        hipLaunchKernelGGL((k_apply_tmar_filter<NQ_>), grid, dim3(64), 0, st, a);
-    } else if (f->kind == CMDG_FILTER_SPECTRAL) {
-        if (f->target == CMDG_TARGET_INDICES) spectral(k_apply_filter<NQ_, TGT_INDICES>);
-        else if (f->target == CMDG_TARGET_ATMOS_PERTURBATIONS) spectral(k_apply_filter<NQ_, TGT_ATMOS_PERT>);
-        else spectral(k_apply_filter<NQ_, TGT_ATMOS_SPECIFIC>);
-    } else {
-        if (f->target == CMDG_TARGET_INDICES) spectral(k_apply_mp_filter<NQ_, TGT_INDICES>);
-        else if (f->target == CMDG_TARGET_ATMOS_PERTURBATIONS) spectral(k_apply_mp_filter<NQ_, TGT_ATMOS_PERT>);
-        else spectral(k_apply_mp_filter<NQ_, TGT_ATMOS_SPECIFIC>);
-    }
-}
-
-static void launch_filter_nq(int NQ, const FilterObj *f, const FilterArgs &a, int nfs,
-                             int64_t nreal, hipStream_t st)
-{
-    switch (NQ) {
-    case 2: launch_filter<2>(f, a, nfs, nreal, st); break;
-    case 3: launch_filter<3>(f, a, nfs, nreal, st); break;
-    case 4: launch_filter<4>(f, a, nfs, nreal, st); break;
-    case 5: launch_filter<5>(f, a, nfs, nreal, st); break;
-    case 6: launch_filter<6>(f, a, nfs, nreal, st); break;
-    case 7: launch_filter<7>(f, a, nfs, nreal, st); break;
-    case 8: launch_filter<8>(f, a, nfs, nreal, st); break;
-    default: break;
-    }
-}
-
-int EngineBase::filter_apply(const FilterObj *f, double *Q, int nstate)
-{
-    if (!f || !Q) return fail(CMDG_ERR_INVALID, "filter: NULL argument");
-    if (NQ < 2 || NQ > 8 || NQV != NQ)
-        return fail(CMDG_ERR_UNSUPPORTED, "filter: polynomial order not compiled in");
-    if (nreal <= 0) return CMDG_OK;
-    FilterArgs a{};
-    a.Q = Q;
-    a.aux = aux;
-    a.vgeo = g.vgeo;
-    a.Fh = f->d_Fh;
-    a.Fv = f->d_Fv;
-    a.nstate = nstate;
-    a.naux = naux;
-    a.nvgeo = g.nvgeo;
-    a.aux_rho = f->aux_ref_rho;
-    a.aux_rhoe = f->aux_ref_rhoe;
-    a.nreal = nreal;
-    if (f->target == CMDG_TARGET_INDICES) {
-        for (int i = 0; i < f->nindices; ++i)
-            if (f->indices[i] > nstate) return fail(CMDG_ERR_INVALID, "filter: index beyond nstate");
-    } else if (nstate != ATMOS_NS) {
-        return fail(CMDG_ERR_INVALID, "filter: atmos targets need the 5-variable dry state");
-    }
-    const bool every = f->direction == DIR_EVERY;
-    const bool h = every || f->direction == DIR_HORIZONTAL, v = every || f->direction == DIR_VERTICAL;
-    // FilterIndices states are independent: at most CHUNK of them share the LDS of a launch
-    // (two LDS buffers of nfs * Np doubles, below the 64 KB a work-group may claim by default)
-    const int CHUNK = std::max(1, std::min(16, (56 * 1024) / (16 * Np)));
-    const int ntot = f->target == CMDG_TARGET_INDICES ? f->nindices : ATMOS_NS;
-    for (int c0 = 0; c0 < ntot; c0 += CHUNK) {
-        const int nfs = std::min(CHUNK, ntot - c0);
-        a.nfs = nfs;
-        for (int i = 0; i < nfs; ++i) a.idx[i] = f->indices[c0 + i];
-        prof_begin(CMDG_K_FILTER, s_comp);
-        if (f->kind == CMDG_FILTER_MASS_PRESERVING) {
-            // one launch per direction, each with its own mass correction (Filters.jl:566-605)
-            if (h) {
-                a.do_h = 1, a.do_v = 0;
-                launch_filter_nq(NQ, f, a, nfs, nreal, s_comp);
-            }
-            if (v) {
-                a.do_h = 0, a.do_v = 1;
-                launch_filter_nq(NQ, f, a, nfs, nreal, s_comp);
-            }
-        } else {
-            a.do_h = h, a.do_v = v;
-            launch_filter_nq(NQ, f, a, nfs, nreal, s_comp);
-        }
-        prof_end(s_comp);
-    }
-    return launch_status("filter launch");
 }
 
 int EngineBase::wsum2(const double *A, const double *B, int nvar, int weighted, double *out)
@@ -2083,12 +1442,11 @@ int cmdg_comm_selftest(cmdg_handle h, int64_t count)
     EngineBase *e = h->eng;
     if (e->transport != TRANSPORT_RCCL || !e->nccl_comm)
         return set_err(h, e->fail(CMDG_ERR_COMM, "selftest: RCCL transport not initialised"));
-    double *src = nullptr, *dst = nullptr;
+    DevBuf<double> src, dst;
     std::vector<double> host((size_t)count), back((size_t)count, -1.0);
     for (int64_t i = 0; i < count; ++i) host[i] = 0.5 * (double)i + 1e-3 * e->rank;
     int rc = CMDG_OK;
-    if (hipMalloc(&src, sizeof(double) * count) != hipSuccess ||
-        hipMalloc(&dst, sizeof(double) * count) != hipSuccess)
+    if (src.alloc(count) != hipSuccess || dst.alloc(count) != hipSuccess)
         rc = e->fail(CMDG_ERR_HIP, "selftest: hipMalloc failed");
     if (!rc && hipMemcpy(src, host.data(), sizeof(double) * count, hipMemcpyHostToDevice) != hipSuccess)
         rc = e->fail(CMDG_ERR_HIP, "selftest: upload failed");
@@ -2104,8 +1462,6 @@ int cmdg_comm_selftest(cmdg_handle h, int64_t count)
         rc = e->fail(CMDG_ERR_HIP, "selftest: download failed");
     if (!rc && memcmp(back.data(), host.data(), sizeof(double) * count) != 0)
         rc = e->fail(CMDG_ERR_COMM, "selftest: payload mismatch");
-    if (src) hipFree(src);
-    if (dst) hipFree(dst);
     return set_err(h, rc);
 }
 
@@ -2331,8 +1687,6 @@ int cmdg_filter_destroy(cmdg_handle h, cmdg_filter f)
             if (e->hooks.pre_filter[i] != f) e->hooks.pre_filter[k++] = e->hooks.pre_filter[i];
         e->hooks.npre = k;
     }
-    if (o->d_Fh) hipFree(o->d_Fh);
-    if (o->d_Fv) hipFree(o->d_Fv);
     delete o;
     return CMDG_OK;
 }

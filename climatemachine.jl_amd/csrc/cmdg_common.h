@@ -7,6 +7,7 @@ namespace cmdg {
 
 // vgeo column ids, 0-based (reference ids Grids.jl:76-92 minus one)
 enum { XI1X1 = 0, XI2X1, XI3X1, XI1X2, XI2X2, XI3X2, XI1X3, XI2X3, XI3X3, VM, VMI };
+constexpr int JCV = 15;  // _JcV, the vertical line-integral weight the column operators read
 // sgeo row ids (Grids.jl:129-130)
 enum { SN1 = 0, SN2, SN3, SSM, SVMI };
 enum { DIR_EVERY = 0, DIR_HORIZONTAL = 1, DIR_VERTICAL = 2 };

@@ -155,7 +155,7 @@ struct cmdg_columnlu {
     int64_t ncol = 0, n = 0;
     double alpha = 0;
     int state = 0;  // 0 empty, 1 assembled (I - alpha L), 2 factored
-    double *band = nullptr, *probe = nullptr, *dprobe = nullptr;
+    DevBuf<double> band, probe, dprobe;
 };
 
 namespace {
@@ -287,7 +287,8 @@ int cmdg_columnlu_create(cmdg_handle linear, int32_t nvertelem, double alpha, cm
                                    " has no boundary face at its bottom or top; the band cannot hold the "
                                    "coupling of its top and bottom elements)");
     }
-    auto *lu = new cmdg_columnlu(tmp);
+    auto *lu = new cmdg_columnlu;
+    lu->lin = linear;
     lu->dev = e->dev;
     lu->nvert = nvertelem;
     lu->nqh2 = e->NQ * e->NQ;
@@ -310,9 +311,9 @@ int cmdg_columnlu_create(cmdg_handle linear, int32_t nvertelem, double alpha, cm
                  band / 1e9, (long long)lu->ncol, (long long)lu->n, NS, lu->P, states / 1e9, freeb / 1e9);
         r = lu_fail(lu, CMDG_ERR_INVALID, msg);
     }
-    if (!r) r = hip_ok(lu, hipMalloc(&lu->band, band), "hipMalloc(band)");
-    if (!r) r = hip_ok(lu, hipMalloc(&lu->probe, states / 2), "hipMalloc(probe)");
-    if (!r) r = hip_ok(lu, hipMalloc(&lu->dprobe, states / 2), "hipMalloc(probe)");
+    if (!r) r = hip_ok(lu, lu->band.alloc(band / sizeof(double)), "hipMalloc(band)");
+    if (!r) r = hip_ok(lu, lu->probe.alloc(states / 2 / sizeof(double)), "hipMalloc(probe)");
+    if (!r) r = hip_ok(lu, lu->dprobe.alloc(states / 2 / sizeof(double)), "hipMalloc(probe)");
     if (!r) r = hip_ok(lu, hipMemset(lu->probe, 0, states / 2), "hipMemset");
     if (!r) r = hip_ok(lu, hipMemset(lu->dprobe, 0, states / 2), "hipMemset");
     if (!r) r = update(lu, alpha);
@@ -390,12 +391,9 @@ int cmdg_columnlu_destroy(cmdg_columnlu_handle lu)
         (void)hipGetDevice(&prev);
         (void)hipSetDevice(lu->dev);
         (void)hipDeviceSynchronize();
-        if (lu->band) (void)hipFree(lu->band);
-        if (lu->probe) (void)hipFree(lu->probe);
-        if (lu->dprobe) (void)hipFree(lu->dprobe);
+        delete lu;  // (frees the band and the probe states on their device)
         if (prev >= 0) (void)hipSetDevice(prev);
     }
-    delete lu;
     return CMDG_OK;
 }
 

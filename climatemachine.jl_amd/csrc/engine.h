@@ -19,6 +19,7 @@
 
 #include "../../include/cmdg.h"
 #include "kernels.h"
+#include "owned.h"
 
 namespace cmdg {
 
@@ -26,8 +27,8 @@ enum { SLOT_Q = 0, SLOT_GF = 1, SLOT_HG = 2, SLOT_HD = 3, NSLOT = 4 };
 enum { TRANSPORT_NONE = 0, TRANSPORT_LOCAL = 1, TRANSPORT_RCCL = 2 };
 
 struct HaloSlot {
-    double *sendbuf = nullptr, *recvbuf = nullptr;
-    hipEvent_t ev_packed = nullptr, ev_done = nullptr, ev_pulled = nullptr;
+    DevBuf<double> sendbuf, recvbuf;
+    Event ev_packed, ev_done, ev_pulled;
     bool active = false;  // begin issued, end pending
     int nvar = 0;         // columns per position of the packed buffers
     int ncol = 0;         // columns of the array (>= nvar: the leading nvar travel)
@@ -72,7 +73,7 @@ struct FilterObj {
     int nindices = 0;
     int indices[CMDG_MAX_FILTER_STATES] = {0};
     int aux_ref_rho = 0, aux_ref_rhoe = 0;
-    double *d_Fh = nullptr, *d_Fv = nullptr;
+    DevBuf<double> d_Fh, d_Fv;
 };
 
 // roctx range around the host-side enqueue of a phase (the reference instruments the same five
@@ -88,7 +89,7 @@ void roctx_pop();
 //   64 interior_begin / exterior_begin         128 the join at the end of segment 5
 //   256 device synchronize before every group_rhs   512 device synchronize after every segment
 int dbg_sync();
-hipError_t ev_record(hipEvent_t &e, hipStream_t s);
+hipError_t ev_record(hipEvent_t e, hipStream_t s);
 // work-groups of 256 for a grid-stride launch over n items
 inline unsigned nblocks(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 65535); }
 struct Range {
@@ -100,7 +101,7 @@ struct Range {
 
 struct ProfRec {
     int kernel;
-    hipEvent_t e0, e1;
+    Event e0, e1;
     bool clamp;  // record max(0, elapsed): e1 may precede e0 (exposed halo time)
 };
 
@@ -174,6 +175,8 @@ struct RunWorker {
     } while (0)
 
 struct EngineBase {
+    // declared first, so destroyed last: after every member that was used on them
+    Stream s_comp, s_comm;
     RunWorker *worker = nullptr;  // CMDG_OPT_ASYNC_RUN
     // ---- configuration (copied from cmdg_desc) ---------------------------------------
     int NQ = 0, NQV = 0, Np = 0, Nfp = 0;  // horizontal / vertical points per direction
@@ -184,40 +187,42 @@ struct EngineBase {
     const int64_t *d_interior = nullptr, *d_exterior = nullptr;
     // CMDG_OPT_STACK_HEIGHT: the caller's lists and the engine's own tiled copies of them
     const int64_t *d_interior_user = nullptr, *d_exterior_user = nullptr;
-    int64_t *d_interior_tiled = nullptr, *d_exterior_tiled = nullptr;
+    DevBuf<int64_t> d_interior_tiled, d_exterior_tiled;
     int set_stack_height(int nv);
     int set_stream_priority(int level);  // CMDG_OPT_STREAM_PRIORITY
     int stream_priority = 0;
     int64_t ninterior = 0, nexterior = 0;
     const uint8_t *d_activedofs = nullptr;
-    double *d_D = nullptr;
-    int32_t *d_faceP = nullptr;  // digested face tables (GridDev::faceP / faceG)
-    double *d_faceG = nullptr;
+    DevBuf<double> d_D;
+    DevBuf<int32_t> d_faceP;  // digested face tables (GridDev::faceP / faceG)
+    DevBuf<double> d_faceG;
     const int64_t *d_vmapsend = nullptr, *d_vmaprecv = nullptr;
     int64_t nvmapsend = 0, nvmaprecv = 0;
     std::vector<int> nabrtorank;
     std::vector<int64_t> nabrsend, nabrrecv;  // 2*nnabr (first,last) 1-based
-    double *aux = nullptr, *gf = nullptr, *hypgrad = nullptr, *hypdiv = nullptr;
-    double *derived = nullptr;  // (Np, NDER, nelem), library-owned
-    bool own_gf = false, own_hd = false;  // (hypgrad is always the library's own)
+    // gf and hypdiv may be the caller's arrays: views, with gf_own / hd_own holding the library's own
+    double *aux = nullptr, *gf = nullptr, *hypdiv = nullptr;
+    DevBuf<double> hypgrad;  // (always the library's own)
+    DevBuf<double> derived;  // (Np, NDER, nelem), library-owned
+    DevBuf<double> gf_own, hd_own;
     // the caller's Qhypervisc_grad / state_gradient_flux (reference layout) when the working copy is
     // node-major: written by cmdg_export_* only; gf_scratch: reference-layout copy for a gradient filter
-    double *hypgrad_user = nullptr, *gf_user = nullptr, *gf_scratch = nullptr;
+    double *hypgrad_user = nullptr, *gf_user = nullptr;
+    DevBuf<double> gf_scratch;
     bool node_major(const double *array) const
     {
         return array == hypgrad || (array == gf && gf_node_major());
     }
     // ---- runtime -----------------------------------------------------------------------
     int dev = 0;  // the device this engine was created on (every ABI entry binds to it)
-    hipStream_t s_comp = nullptr, s_comm = nullptr;
-    hipEvent_t ev_comp = nullptr;
+    Event ev_comp;
     HaloSlot slot[NSLOT];
     int slot_nvar_max = 0;
-    double *W[2] = {nullptr, nullptr};  // LSRK work states
+    DevBuf<double> W[2];  // LSRK work states
     // ---- CMDG_OPT_GRADARG_HANDOFF (kernels.h GradArgHandoff) --------------------------------
     // (ngl, Np, nelem) gradient arguments of the next stage's input, written by the fused update
     // and read by the next gradient pass of the same cmdg_lsrk_run; never trusted across calls
-    double *garg = nullptr;
+    DevBuf<double> garg;
     bool gradarg_handoff = true;   // the option
     bool handoff_used = false;     // did the last cmdg_lsrk_run use it (cmdg_query)
     int64_t handoff_refreshes = 0; // hand-off updates of the last run that carried the auxiliary refresh
@@ -231,7 +236,7 @@ struct EngineBase {
                !step_graph && nghost == 0 && !communicate();
     }
     int ensure_garg();
-    double *d_partial = nullptr;        // reduction scratch
+    DevBuf<double> d_partial;           // reduction scratch
     int transport = TRANSPORT_NONE;
     int rank = 0, nranks = 1;
     std::vector<EngineBase *> group;    // local transport: engine of every rank
@@ -256,6 +261,8 @@ struct EngineBase {
     // make stream `later` wait for everything enqueued so far on `earlier` (through ev_comp)
     int order(hipStream_t earlier, hipStream_t later);
     bool communicate() const { return !nabrtorank.empty(); }
+    // the orders the column operators and the filters are compiled for (one order in every direction)
+    bool column_orders() const { return NQ >= 2 && NQ <= 8 && NQV == NQ; }
     // does an evaluation of this handle exchange ghosts (DGModel.jl:104-108: not the vertical
     // operator of a stacked mesh)
     bool exchanges() const { return communicate() && !(stacked && direction == DIR_VERTICAL); }
@@ -293,8 +300,8 @@ struct EngineBase {
     // tables built at create from vmapsend / vmaprecv / the digested face table; *_ok = they
     // could be built (every node of vmapsend in an exterior element, every ghost node received
     // once, every ghost node a face reads received)
-    int32_t *d_sendoff = nullptr, *d_ghostslot = nullptr;
-    SendEnt *d_sendent = nullptr;
+    DevBuf<int32_t> d_sendoff, d_ghostslot;
+    DevBuf<SendEnt> d_sendent;
     bool direct_send_ok = false, direct_recv_ok = false;
     bool reference_halo = false;  // CMDG_OPT_REFERENCE_HALO: pack and unpack as the reference does
     int init_halo_tables();
@@ -337,10 +344,10 @@ struct EngineBase {
     // for I_(p-1) (events of alternating parity): the interior work of a pass hides the exchanges
     // of two, and a step costs max(chain, compute) instead of the sum over passes of
     // max(I_p, X_p) + E_p.
-    hipEvent_t ev_int[2] = {nullptr, nullptr}, ev_ext[2] = {nullptr, nullptr};
+    Event ev_int[2], ev_ext[2];
     int64_t pass_seq = 0;  // passes started on this handle
     int64_t host_post_ns = 0, host_post_n = 0;  // host time inside halo_post (RCCL group calls)
-    hipEvent_t prof_ext_done = nullptr;  // profiling: end of the last exterior launch
+    Event prof_ext_done;  // profiling: end of the last exterior launch
     bool no_pipeline = false;  // CMDG_OPT_HALO_PIPELINE = 0
     bool pipelined() const
     {
@@ -373,7 +380,7 @@ struct EngineBase {
     int cap_interior = 0, cap_exterior = 0;  // launches begun in this capture
     // (every record of a capture gets an event of its own: 4 passes x 16 stages at most)
     static constexpr int NGEV = 64;
-    hipEvent_t gev_int[NGEV] = {nullptr}, gev_ext[NGEV] = {nullptr}, gev_fork = nullptr;
+    Event gev_int[NGEV], gev_ext[NGEV], gev_fork;
     int cap_pass = 0;  // passes begun in this capture
     hipGraphExec_t graph_exec = nullptr;
     struct GraphKey {
@@ -391,7 +398,7 @@ struct EngineBase {
             return true;
         }
     } graph_key;
-    double *d_gtime = nullptr;      // [t_next, dt, times[16], rkc[16]]
+    DevBuf<double> d_gtime;         // [t_next, dt, times[16], rkc[16]]
     int64_t graph_steps = 0;        // steps replayed from the graph (cmdg_query)
     bool graph_failed = false;      // a capture failed: this handle stays eager
     bool graph_eligible() const;
@@ -434,7 +441,7 @@ struct EngineBase {
     int synchronize();
     int wsum2(const double *A, const double *B, int nvar, int weighted, double *out);
     int courant(int mode, int kind, const double *Q, double dt, double t, int dir, double *out);
-    double *d_elemred = nullptr;  // (nreal) per-element extrema
+    DevBuf<double> d_elemred;  // (nreal) per-element extrema
     int stack_integral(bool reverse, const double *Q, int nstate, double *aux_arr, int naux_arr,
                        int nvert, const double *Imat_host, const cmdg_stack_integral_desc *d,
                        int64_t h0 = 0, int64_t nh = -1);
@@ -453,8 +460,8 @@ struct EngineBase {
     int integrate_velocity(const double *X, int nstate, int col, int nvert, int64_t h0 = 0,
                            int64_t nh = -1);
     int flow_deviation(double *Q, int64_t h0, int64_t nh);
-    double *d_flowint = nullptr;  // (Np, 2, nelem) column integral of the horizontal velocity
-    double *d_preT = nullptr;     // tendency of the nested operator of the hooks (pre_rhs_handle)
+    DevBuf<double> d_flowint;  // (Np, 2, nelem) column integral of the horizontal velocity
+    DevBuf<double> d_preT;     // tendency of the nested operator of the hooks (pre_rhs_handle)
     int run_column_ops(const RhsCtx &c, int64_t e0, int64_t e1);
     // the column operators of a recorded composition in one launch (columns.h k_column_chain,
     // k_flow_deviation); CMDG_FUSED_COLUMNS=0 issues them one by one as recorded (A/B, tests)
@@ -464,13 +471,15 @@ struct EngineBase {
     bool column_chain(const RhsCtx &c, int64_t e0, int64_t e1, bool with_copies);
     bool filter_pair(double *Q);
     int run_gradient_hooks(const RhsCtx &c, int64_t e0, int64_t e1);
-    double *d_Imat = nullptr;
+    DevBuf<double> d_Imat;
     int ensure_Imat(const double *host);  // the steppers' Imat (NQ x NQ): uploaded if absent
-    double *d_Dv = nullptr;  // vertical derivative matrix when the vertical order differs
+    DevBuf<double> d_Dv;  // vertical derivative matrix when the vertical order differs
     int filter_create(const cmdg_filter_desc *d, FilterObj **out);
     int filter_apply(const FilterObj *f, double *Q, int nstate);
 
     // profiling brackets
+    // a new record with both events created (e1 may be given instead: an event recorded already)
+    ProfRec &prof_pair(int kernel, bool clamp, Event e1 = Event());
     void prof_begin(int kernel, hipStream_t st);
     void prof_end(hipStream_t st);
     void prof_collect();
@@ -685,7 +694,7 @@ struct EngineT : EngineBase {
     {
         if constexpr (P::NDER > 0) {
             const int64_t n = nelem * KDims<NQ_, NQV_>::Np;
-            if (hipMalloc(&derived, sizeof(double) * n * P::NDER) != hipSuccess)
+            if (derived.alloc((size_t)n * P::NDER) != hipSuccess)
                 return fail(CMDG_ERR_HIP, "hipMalloc(derived) failed");
             hipLaunchKernelGGL((k_init_derived<P, NQ_, NQV_>), dim3((unsigned)((n + 255) / 256)), dim3(256),
                                0, s_comp, prm, aux, derived, nelem);

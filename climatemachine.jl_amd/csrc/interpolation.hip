@@ -21,6 +21,8 @@
 #include <vector>
 
 #include "interpolation.h"
+#include "owned.h"
+#include "with_constant.h"
 
 namespace cmdg {
 
@@ -136,41 +138,22 @@ __global__ void k_scatter(double *__restrict__ fiv, const double *__restrict__ v
 
 using InterpKernel = void (*)(const Work *, const double *, const double *, const double *, const double *, double *,
                               int, int, int64_t, Nodes);
-template <int QH>
-InterpKernel pick_v(int qv)
-{
-    switch (qv) {
-    case 2: return k_interpolate<QH, 2>;
-    case 3: return k_interpolate<QH, 3>;
-    case 4: return k_interpolate<QH, 4>;
-    case 5: return k_interpolate<QH, 5>;
-    case 6: return k_interpolate<QH, 6>;
-    case 7: return k_interpolate<QH, 7>;
-    case 8: return k_interpolate<QH, 8>;
-    }
-    return nullptr;
-}
+// NULL: an order that is not compiled in
 InterpKernel pick(int qh, int qv)
 {
-    switch (qh) {
-    case 2: return pick_v<2>(qv);
-    case 3: return pick_v<3>(qv);
-    case 4: return pick_v<4>(qv);
-    case 5: return pick_v<5>(qv);
-    case 6: return pick_v<6>(qv);
-    case 7: return pick_v<7>(qv);
-    case 8: return pick_v<8>(qv);
-    }
-    return nullptr;
+    InterpKernel k = nullptr;
+    with_constant<QMIN, QMAX>(qh, [&](auto h) {
+        with_constant<QMIN, QMAX>(qv, [&](auto v) { k = k_interpolate<h(), v()>; });
+    });
+    return k;
 }
 
 template <class T>
-bool upload(T **dst, const T *src, size_t n)
+bool upload(DevBuf<T> &dst, const T *src, size_t n)
 {
-    *dst = nullptr;
     if (n == 0) return true;
-    if (hipMalloc((void **)dst, n * sizeof(T)) != hipSuccess) return false;
-    return hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
+    if (dst.alloc(n) != hipSuccess) return false;
+    return hipMemcpy(dst, src, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
 }
 
 int finish(hipStream_t st, bool wait, const char *what, std::string &err)
@@ -191,27 +174,16 @@ struct InterpObj {
     int64_t nelem = 0, npoints = 0, n1 = 0, n2 = 0, n3 = 0;
     Nodes nd{};
     InterpKernel kernel = nullptr;
-    double *xi[3] = {nullptr, nullptr, nullptr};
-    int32_t *idx[3] = {nullptr, nullptr, nullptr};
-    double *lat = nullptr, *lon = nullptr;
-    Work *work = nullptr;
+    DevBuf<double> xi[3];
+    DevBuf<int32_t> idx[3];
+    DevBuf<double> lat, lon;
+    DevBuf<Work> work;
     int64_t nwork = 0;
 };
 
 int interp_device(const InterpObj *o) { return o->dev; }
 
-void interp_destroy(InterpObj *o)
-{
-    if (!o) return;
-    for (int d = 0; d < 3; ++d) {
-        if (o->xi[d]) (void)hipFree(o->xi[d]);
-        if (o->idx[d]) (void)hipFree(o->idx[d]);
-    }
-    if (o->lat) (void)hipFree(o->lat);
-    if (o->lon) (void)hipFree(o->lon);
-    if (o->work) (void)hipFree(o->work);
-    delete o;
-}
+void interp_destroy(InterpObj *o) { delete o; }
 
 int interp_create(const cmdg_interp_desc *d, InterpObj **out, std::string &err)
 {
@@ -275,6 +247,11 @@ int interp_create(const cmdg_interp_desc *d, InterpObj **out, std::string &err)
         o->Np = o->QH * o->QH * o->QV;
         o->nelem = d->nelem;
         o->kernel = pick(o->QH, o->QV);
+        if (!o->kernel) {
+            delete o;
+            err = "cmdg_interp_create: compiled for 2 to 8 points per direction";
+            return CMDG_ERR_UNSUPPORTED;
+        }
         for (int hv = 0; hv < 2; ++hv) {  // baryweights(r): wb_i = 1 / prod_{j != i} (r_i - r_j)
             const double *m = d->xi_nodes[hv ? 2 : 0];
             const int n = hv ? o->QV : o->QH;
@@ -297,10 +274,10 @@ int interp_create(const cmdg_interp_desc *d, InterpObj **out, std::string &err)
                 work.push_back({(int32_t)e, (int32_t)p0, (int32_t)std::min<int64_t>(NT, d->offset[e + 1] - p0), 0});
     }
     o->nwork = (int64_t)work.size();
-    bool ok = upload(&o->work, work.data(), work.size());
+    bool ok = upload(o->work, work.data(), work.size());
     for (int k = 0; k < 3 && ok; ++k)
-        ok = (tables_only || upload(&o->xi[k], xis[k], (size_t)d->npoints)) && upload(&o->idx[k], ids[k], (size_t)d->npoints);
-    if (ok && d->lat_grd) ok = upload(&o->lat, d->lat_grd, (size_t)d->n2) && upload(&o->lon, d->long_grd, (size_t)d->n1);
+        ok = (tables_only || upload(o->xi[k], xis[k], (size_t)d->npoints)) && upload(o->idx[k], ids[k], (size_t)d->npoints);
+    if (ok && d->lat_grd) ok = upload(o->lat, d->lat_grd, (size_t)d->n2) && upload(o->lon, d->long_grd, (size_t)d->n1);
     if (!ok) {
         (void)hipGetLastError();
         interp_destroy(o);

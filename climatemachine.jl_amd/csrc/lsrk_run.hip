@@ -141,13 +141,13 @@ int EngineBase::capture_step(double *Q, double *dQ, double dt, int nstages, cons
         hipGraphExecDestroy(graph_exec);
         graph_exec = nullptr;
     }
-    if (!d_gtime) HIPCHK(hipMalloc(&d_gtime, sizeof(double) * 34));
+    if (!d_gtime) HIPCHK(d_gtime.alloc(34));
     std::vector<EngineBase *> one{this};
     double *Qs[1] = {Q}, *dQs[1] = {dQ};
     if (4 * nstages + 1 > NGEV) return fail(CMDG_ERR_UNSUPPORTED, "step graph: too many stages");
     for (int i = 0; i < NGEV; ++i) {  // (created on first use: most handles never capture)
-        if (!gev_int[i]) HIPCHK(hipEventCreateWithFlags(&gev_int[i], hipEventDisableTiming));
-        if (!gev_ext[i]) HIPCHK(hipEventCreateWithFlags(&gev_ext[i], hipEventDisableTiming));
+        if (!gev_int[i]) HIPCHK(gev_int[i].create(hipEventDisableTiming));
+        if (!gev_ext[i]) HIPCHK(gev_ext[i].create(hipEventDisableTiming));
     }
     capturing = true;
     cap_interior = cap_exterior = cap_pass = 0;

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "stepping.h"
+#include "with_constant.h"
 
 using namespace cmdg;
 
@@ -62,30 +63,21 @@ __global__ void __launch_bounds__(256) k_mri_qhat(const MriArgs a)
     a.out[i] = qh;
 }
 
-void launch_update(const MriArgs &a, int nR, hipStream_t st)
+// the kernels are compiled for 1..MAXR forcing arrays; every caller has checked nR against that
+int launch_update(EngineBase *e, const MriArgs &a, int nR)
 {
     const dim3 g(grid_one_per_thread(a.n)), b(256);
-    switch (nR) {
-        case 1: hipLaunchKernelGGL(k_lsrk_mri_update<1>, g, b, 0, st, a); break;
-        case 2: hipLaunchKernelGGL(k_lsrk_mri_update<2>, g, b, 0, st, a); break;
-        case 3: hipLaunchKernelGGL(k_lsrk_mri_update<3>, g, b, 0, st, a); break;
-        case 4: hipLaunchKernelGGL(k_lsrk_mri_update<4>, g, b, 0, st, a); break;
-        case 5: hipLaunchKernelGGL(k_lsrk_mri_update<5>, g, b, 0, st, a); break;
-        case 6: hipLaunchKernelGGL(k_lsrk_mri_update<6>, g, b, 0, st, a); break;
-    }
+    if (!with_constant<1, MAXR>(nR, [&](auto n) { hipLaunchKernelGGL(k_lsrk_mri_update<n()>, g, b, 0, e->s_comp, a); }))
+        return e->fail(CMDG_ERR_UNSUPPORTED, "mri: update not compiled for " + std::to_string(nR) + " forcing arrays");
+    return CMDG_OK;
 }
 
-void launch_qhat(const MriArgs &a, int nR, hipStream_t st)
+int launch_qhat(EngineBase *e, const MriArgs &a, int nR)
 {
     const dim3 g(grid_one_per_thread(a.n)), b(256);
-    switch (nR) {
-        case 1: hipLaunchKernelGGL(k_mri_qhat<1>, g, b, 0, st, a); break;
-        case 2: hipLaunchKernelGGL(k_mri_qhat<2>, g, b, 0, st, a); break;
-        case 3: hipLaunchKernelGGL(k_mri_qhat<3>, g, b, 0, st, a); break;
-        case 4: hipLaunchKernelGGL(k_mri_qhat<4>, g, b, 0, st, a); break;
-        case 5: hipLaunchKernelGGL(k_mri_qhat<5>, g, b, 0, st, a); break;
-        case 6: hipLaunchKernelGGL(k_mri_qhat<6>, g, b, 0, st, a); break;
-    }
+    if (!with_constant<1, MAXR>(nR, [&](auto n) { hipLaunchKernelGGL(k_mri_qhat<n()>, g, b, 0, e->s_comp, a); }))
+        return e->fail(CMDG_ERR_UNSUPPORTED, "mri: qhat not compiled for " + std::to_string(nR) + " forcing arrays");
+    return CMDG_OK;
 }
 
 // the low-level entries' common checks and argument struct
@@ -159,7 +151,7 @@ int step(const Op &slow, const Op &fast, cmdg_columnlu_handle lu, const cmdg_mri
                 a.rka_next = d->fast_rka[(st + 1) % nf];
                 a.rkb_dt = d->fast_rkb[st] * dtf;
                 if (int r = ch.to(ef->s_comp)) return r;
-                launch_update(a, s + 1, ef->s_comp);
+                if (int r = launch_update(ef, a, s + 1)) return r;
             }
             time = final_step ? stage_end : time + dtf;
         }
@@ -176,7 +168,7 @@ int step(const Op &slow, const Op &fast, cmdg_columnlu_handle lu, const cmdg_mri
                 qa.sc[j] = sc;
             }
             if (int r = ch.to(elu->s_comp)) return r;
-            launch_qhat(qa, s + 1, elu->s_comp);
+            if (int r = launch_qhat(elu, qa, s + 1)) return r;
             const double alpha = dt * G(0, 2 * s + 1, s + 1);
             if (alpha != columnlu_alpha(lu)) {
                 if (!d->lu_adjustable) {
@@ -250,7 +242,7 @@ int cmdg_mri_lsrk_update(cmdg_handle h, double *dQ, double *Q, double rka_next, 
     if (int r = low_level_args(h, dQ, Q, nR, R, sc, &a)) return set_err(h, r);
     a.rka_next = rka_next;
     a.rkb_dt = rkb_dt;
-    launch_update(a, nR, h->eng->s_comp);
+    if (int r = launch_update(h->eng, a, nR)) return set_err(h, r);
     return set_err(h, h->eng->launch_status("k_lsrk_mri_update"));
 }
 
@@ -261,7 +253,7 @@ int cmdg_mri_qhat(cmdg_handle h, double *Qhat, const double *Q, int32_t nR, cons
     DevGuard guard_(h->eng);
     MriArgs a;
     if (int r = low_level_args(h, Qhat, Q, nR, R, sc, &a)) return set_err(h, r);
-    launch_qhat(a, nR, h->eng->s_comp);
+    if (int r = launch_qhat(h->eng, a, nR)) return set_err(h, r);
     return set_err(h, h->eng->launch_status("k_mri_qhat"));
 }
 

@@ -197,21 +197,29 @@ __global__ __launch_bounds__(NT) void k_reduce_final(const double *__restrict__ 
 
 // ---- per-engine scratch, allocated on first use (EngineBase keeps no member for it) ------------
 struct Scratch {
-    double *part = nullptr, *out = nullptr, *gather = nullptr, *host = nullptr;
+    DevBuf<double> part, out, gather;
+    double *host = nullptr;  // pinned
     size_t npart = 0, nout = 0, ngather = 0, nhost = 0;
 };
 std::mutex g_scratch_m;
 std::unordered_map<const EngineBase *, Scratch> g_scratch;
 
-// device buffer *p of at least n doubles (grown, never shrunk)
-hipError_t grow(double *&p, size_t &cap, size_t n, bool host)
+// buffer p of at least n doubles (grown, never shrunk): on the device, or pinned on the host
+hipError_t grow(DevBuf<double> &p, size_t &cap, size_t n)
 {
     if (n <= cap) return hipSuccess;
-    if (p) (void)(host ? hipHostFree(p) : hipFree(p));
+    cap = 0;
+    const hipError_t r = p.alloc(n);
+    if (r == hipSuccess) cap = n;
+    return r;
+}
+hipError_t grow_host(double *&p, size_t &cap, size_t n)
+{
+    if (n <= cap) return hipSuccess;
+    if (p) (void)hipHostFree(p);
     p = nullptr;
     cap = 0;
-    const hipError_t r = host ? hipHostMalloc((void **)&p, sizeof(double) * n, hipHostMallocDefault)
-                              : hipMalloc((void **)&p, sizeof(double) * n);
+    const hipError_t r = hipHostMalloc((void **)&p, sizeof(double) * n, hipHostMallocDefault);
     if (r == hipSuccess) cap = n;
     return r;
 }
@@ -389,8 +397,8 @@ int reduce_device(EngineBase *e, const cmdg_reduce_desc *d, const double *A, con
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(NB_MAX, (nn + NT - 1) / NT));
     Scratch &s = scratch(e);
     const size_t nslots = ps ? (size_t)nsel : (size_t)nchunk;
-    hipError_t r = grow(s.part, s.npart, nslots * nb * 2, false);
-    if (r == hipSuccess) r = grow(s.out, s.nout, (size_t)nout * 2, false);
+    hipError_t r = grow(s.part, s.npart, nslots * nb * 2);
+    if (r == hipSuccess) r = grow(s.out, s.nout, (size_t)nout * 2);
     if (r != hipSuccess) return e->fail(CMDG_ERR_HIP, std::string("reduce: scratch: ") + hipGetErrorString(r));
     Launch L{A, B, e->g.vgeo, (int64_t)e->Np * e->g.nvgeo, (int64_t)e->Np * VM, (int64_t)e->Np * d->nstate,
              (uint32_t)e->Np, (uint32_t)nn, d->p, weighted, nb, s.part, s.out, e->s_comp};
@@ -414,7 +422,7 @@ int reduce_device(EngineBase *e, const cmdg_reduce_desc *d, const double *A, con
 int reduce_gather_buffer(EngineBase *e, size_t n, double **buf)
 {
     Scratch &s = scratch(e);
-    const hipError_t r = grow(s.gather, s.ngather, n, false);
+    const hipError_t r = grow(s.gather, s.ngather, n);
     if (r != hipSuccess) return e->fail(CMDG_ERR_HIP, std::string("reduce: gather buffer: ") + hipGetErrorString(r));
     *buf = s.gather;
     return CMDG_OK;
@@ -423,7 +431,7 @@ int reduce_gather_buffer(EngineBase *e, size_t n, double **buf)
 int reduce_host_buffer(EngineBase *e, size_t n, double **buf)
 {
     Scratch &s = scratch(e);
-    const hipError_t r = grow(s.host, s.nhost, n, true);
+    const hipError_t r = grow_host(s.host, s.nhost, n);
     if (r != hipSuccess) return e->fail(CMDG_ERR_HIP, std::string("reduce: host buffer: ") + hipGetErrorString(r));
     *buf = s.host;
     return CMDG_OK;
@@ -468,12 +476,8 @@ void reduce_release(EngineBase *e)
     std::lock_guard<std::mutex> lk(g_scratch_m);
     auto it = g_scratch.find(e);
     if (it == g_scratch.end()) return;
-    Scratch &s = it->second;
-    if (s.part) (void)hipFree(s.part);
-    if (s.out) (void)hipFree(s.out);
-    if (s.gather) (void)hipFree(s.gather);
-    if (s.host) (void)hipHostFree(s.host);
-    g_scratch.erase(it);
+    if (it->second.host) (void)hipHostFree(it->second.host);
+    g_scratch.erase(it);  // (frees the device buffers)
 }
 
 }  // namespace cmdg

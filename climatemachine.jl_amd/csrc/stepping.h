@@ -45,16 +45,12 @@ inline void lsrk_update(EngineBase *e, double *dQ, double *Q, double rka_next, d
 struct Chain {
     EngineBase *owner;  // takes the messages of ordering failures
     std::string who;    // their prefix: the stepper's name
-    hipEvent_t ev = nullptr;
+    Event ev;
     hipStream_t cur = nullptr;
     Chain(EngineBase *e, const char *stepper) : owner(e), who(stepper) {}
-    ~Chain()
-    {
-        if (ev) (void)hipEventDestroy(ev);
-    }
     int create()
     {
-        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
+        if (ev.create(hipEventDisableTiming) != hipSuccess)
             return owner->fail(CMDG_ERR_HIP, who + ": hipEventCreate failed");
         return CMDG_OK;
     }

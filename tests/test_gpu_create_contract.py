@@ -104,3 +104,27 @@ def test_retired_tendency_options_are_accepted_and_change_nothing(cm, torch):
         dg.close()
     assert np.isfinite(out[0]).all() and np.abs(out[0]).max() > 0
     assert np.array_equal(out[0], out[1])
+
+
+def test_stream_priority_replaces_the_streams_and_not_the_result(cm, torch):
+    """``CMDG_OPT_STREAM_PRIORITY`` gives the handle two new streams and destroys the old ones: at
+    the lowest, the default and the highest priority an evaluation computes, bit for bit, what it
+    computed before the option was touched; a level outside -1..1 is refused and changes nothing.
+    The smallest mesh the path runs on: a 2 x 2 x 2 stacked brick at order 2."""
+    from helpers import pseudo1d_setup
+    law, grid, _ = pseudo1d_setup(Ne=2, N=2)
+    dg = cm.dgmodel.DGModel(law, grid)
+    Q = dg.init_ode_state(0.0)
+    before, after = dg.create_state(), dg.create_state()
+    dg(before, Q, 0.25)
+    assert float(before.abs().max()) > 0
+    for level in (-1, 0, 1):
+        dg.set_option(cm._lib.OPT_STREAM_PRIORITY, level)
+        after.fill_(float("nan"))
+        dg(after, Q, 0.25)
+        assert torch.equal(after, before), level
+    with pytest.raises(cm._lib.CmdgError, match="stream priority"):
+        dg.set_option(cm._lib.OPT_STREAM_PRIORITY, 2)
+    dg(after, Q, 0.25)
+    assert torch.equal(after, before)
+    dg.close()

@@ -10,7 +10,7 @@ LIB_PATH = os.environ.get("CMDG_LIB", os.path.join(_HERE, "libcmdg.so"))   # CMD
 
 CMDG_K = dict(GRADIENTS=0, DIVGRAD=1, GRADLAP=2, TENDENCY=3, PACK=4, UNPACK=5, UPDATE_AUX=6,
               FILTER=7, STACK_INTEGRAL=8, TRANSPORT=9, HALO_EXPOSED=10, GRADIENTS_EXT=11,
-              DIVGRAD_EXT=12, GRADLAP_EXT=13, TENDENCY_EXT=14)
+              DIVGRAD_EXT=12, GRADLAP_EXT=13, TENDENCY_EXT=14, FV_GRADIENTS=15, FV_TENDENCY=16)
 STACK_MAXOUT = 8
 OPT_KEEP_GRADFLUX = 1
 OPT_STACK_HEIGHT = 2
@@ -123,6 +123,16 @@ class CmdgReduceDesc(C.Structure):
                 ("nstates", C.c_int32)]
 
 
+class CmdgFvDesc(C.Structure):
+    """``cmdg_fv_desc`` of include/cmdg.h."""
+    _fields_ = [("reconstruction", C.c_int32), ("width", C.c_int32), ("limiter", C.c_int32),
+                ("nvertelem", C.c_int32), ("periodicstack", C.c_int32)]
+
+
+FV_CONSTANT, FV_LINEAR = 0, 1
+FV_VANLEER, FV_NOLIMITER = 0, 1
+
+
 # every symbol include/cmdg.h declares: (name, restype, argtypes)
 _vp, _i32, _i64, _d = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = [
@@ -130,6 +140,7 @@ SYMBOLS = [
     ("cmdg_status_string", C.c_char_p, [C.c_int]),
     ("cmdg_physics_counts", C.c_int, [_i32, _vp, _vp]),
     ("cmdg_create", C.c_int, [C.POINTER(CmdgDesc), C.POINTER(_vp)]),
+    ("cmdg_create_dgfv", C.c_int, [C.POINTER(CmdgDesc), C.POINTER(CmdgFvDesc), C.POINTER(_vp)]),
     ("cmdg_destroy", C.c_int, [_vp]),
     ("cmdg_last_error", C.c_char_p, [_vp]),
     ("cmdg_rhs", C.c_int, [_vp, _vp, _vp, _d, _d, _d]),

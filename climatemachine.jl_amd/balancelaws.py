@@ -37,7 +37,7 @@ __all__ = [
     "RusanovNumericalFlux", "CentralNumericalFluxFirstOrder", "RoeNumericalFlux",
     "HLLCNumericalFlux", "LMARSNumericalFlux", "RoeNumericalFluxMoist", "RoeNumericalFluxMoistLM",
     "RoeNumericalFluxMoistHH", "RoeNumericalFluxMoistLV", "RoeNumericalFluxMoistLVPP",
-    "InhomogeneousBC", "HomogeneousBC", "AdvectionDiffusion", "Pseudo1D",
+    "InhomogeneousBC", "HomogeneousBC", "AdvectionDiffusion", "Pseudo1D", "SineAdvection",
     "ConstantHyperDiffusion", "DirectionSplitBox",
 ]
 
@@ -202,6 +202,30 @@ class Pseudo1D:
         xn = n[0] * coord[0] + n[1] * coord[1] + n[2] * coord[2]
         a = xn - self.mu - self.alpha * t
         return np.exp(-(a * a) / (4 * self.beta * (self.delta + t))) / np.sqrt(1 + t / self.delta)
+
+
+class SineAdvection:
+    """``Pseudo1D{n, alpha}`` of test/Numerics/DGMethods/advection_diffusion/fvm_advection.jl:33-54:
+    pure advection with velocity ``alpha n`` of the wave ``sin(pi (n . x - alpha t))``, which also
+    supplies the inflow data of ``InhomogeneousBC{0}``."""
+    problem_id = 8
+
+    def __init__(self, n, alpha):
+        self.n, self.alpha = np.asarray(n, dtype=np.float64), float(alpha)
+
+    def dparam(self):
+        d = np.zeros(32)
+        d[0:3] = self.n
+        d[3] = self.alpha
+        return d
+
+    def init_velocity_diffusion(self, law, aux, coord):
+        aux[:, law.off_u:law.off_u + 3, :] = (self.alpha * self.n)[None, :, None]
+
+    def initial_condition(self, coord, t):
+        n = self.n
+        xn = n[0] * coord[0] + n[1] * coord[1] + n[2] * coord[2]
+        return np.sin((xn - self.alpha * t) * np.pi)
 
 
 class ConstantHyperDiffusion:

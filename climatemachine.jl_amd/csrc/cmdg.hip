@@ -627,6 +627,7 @@ int EngineBase::set_stack_height(int nv)
     constexpr int TILE_C = 32, TILE_L = 4, MIN_HEIGHT = 17;
     if (nv < 0 || (nv > 0 && (!stacked || nreal % nv != 0)))
         return fail(CMDG_ERR_INVALID, "stack height: not a stacked topology or nreal is not a multiple of it");
+    if (fv) return CMDG_OK;  // the finite-volume pass walks the caller's lists stack by stack
     HIPCHK(hipStreamSynchronize(s_comp));
     d_interior = d_interior_user;
     d_exterior = d_exterior_user;
@@ -1133,9 +1134,8 @@ int cmdg_physics_counts(int32_t physics_id, const int32_t *iparam, int32_t out[6
     }
 }
 
-int cmdg_create(const cmdg_desc *d, cmdg_handle *out)
+static int create_handle(const cmdg_desc *d, const cmdg_fv_desc *fv, cmdg_handle *out)
 {
-    if (!d || !out) return CMDG_ERR_INVALID;
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
@@ -1160,6 +1160,16 @@ int cmdg_create(const cmdg_desc *d, cmdg_handle *out)
     }
     std::string err;
     EngineBase *e = nullptr;
+    if (fv) {
+        if (d->physics_id == CMDG_PHYSICS_ADVECTION_DIFFUSION)
+            e = make_engine_advdiff_fv(d, fv, err);
+        else
+            err = "cmdg_create_dgfv: the finite-volume passes are compiled for the AdvectionDiffusion law only";
+        if (!e) {
+            g_create_err = err;
+            return CMDG_ERR_UNSUPPORTED;
+        }
+    } else
     switch (d->physics_id) {
     case CMDG_PHYSICS_ADVECTION_DIFFUSION: e = make_engine_advdiff(d, err); break;
     case CMDG_PHYSICS_DRY_ATMOS: e = make_engine_atmos(d, err); break;
@@ -1183,6 +1193,7 @@ int cmdg_create(const cmdg_desc *d, cmdg_handle *out)
         }
     }
     int r = e->init(d);
+    if (r == CMDG_OK && fv) r = e->init_fv();
     if (r != CMDG_OK) {
         g_create_err = e->err;
         delete e;
@@ -1195,6 +1206,72 @@ int cmdg_create(const cmdg_desc *d, cmdg_handle *out)
     }
     c->eng = e;
     *out = c;
+    return CMDG_OK;
+}
+
+int cmdg_create(const cmdg_desc *d, cmdg_handle *out)
+{
+    if (!d || !out) return CMDG_ERR_INVALID;
+    if (d->dim == 3 && d->N[2] == 0) {
+        *out = nullptr;
+        g_create_err = "cmdg_create: N[2] == 0 is a finite-volume vertical: use cmdg_create_dgfv";
+        return CMDG_ERR_INVALID;
+    }
+    return create_handle(d, nullptr, out);
+}
+
+// DGFVModel(balance_law, grid, fv_reconstruction, nf1, nf2, nfgrad; direction)  DGFVModel.jl:22-69
+int cmdg_create_dgfv(const cmdg_desc *d, const cmdg_fv_desc *fv, cmdg_handle *out)
+{
+    if (!d || !fv || !out) return CMDG_ERR_INVALID;
+    *out = nullptr;
+    auto refuse = [&](int code, const char *msg) {
+        g_create_err = msg;
+        return code;
+    };
+    if (d->dim != 3 || d->N[2] != 0)
+        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: the vertical polynomial order N[2] must be 0 (use cmdg_create otherwise)");
+    if (!d->stacked)
+        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: the finite-volume vertical needs a stacked grid");
+    if (fv->nvertelem < 2)
+        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: nvertelem < 2");
+    if (fv->reconstruction != CMDG_FV_CONSTANT && fv->reconstruction != CMDG_FV_LINEAR)
+        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: unknown reconstruction");
+    if (fv->width < 0 || fv->width > 3)
+        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: reconstruction width outside 0..3");
+    if (fv->reconstruction == CMDG_FV_LINEAR && fv->width == 0)
+        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: a linear reconstruction needs width >= 1");
+    if (fv->reconstruction == CMDG_FV_CONSTANT && fv->width != 0)
+        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: the constant reconstruction has width 0");
+    if (fv->limiter != CMDG_FV_VANLEER && fv->limiter != CMDG_FV_NOLIMITER)
+        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: unknown slope limiter");
+    if (d->nreal % fv->nvertelem != 0 || d->nghost % fv->nvertelem != 0)
+        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: element counts are not multiples of nvertelem");
+    return create_handle(d, fv, out);
+}
+
+// what a DGFVModel handle adds to init(): exchanges packed / unpacked as the reference does, and
+// element lists that are whole stacks, bottom element first
+int EngineBase::init_fv()
+{
+    reference_halo = true;
+    const int nv = fv_nvert;
+    // (fv.h fv_lds_bytes: primitives, face fluxes and cell weights of one stack)
+    if (sizeof(double) * NQ * NQ * ((size_t)ns * nv + (size_t)ns * (nv + 1) + nv) > 64 * 1024)
+        return fail(CMDG_ERR_UNSUPPORTED, "cmdg_create_dgfv: a stack of this height does not fit the 64 KiB of LDS "
+                                          "the finite-volume pass stages it in");
+    for (int which = 0; which < 2; ++which) {
+        const int64_t n = which ? nexterior : ninterior;
+        if (n == 0) continue;
+        std::vector<int64_t> h((size_t)n);
+        HIPCHK(hipMemcpy(h.data(), which ? d_exterior_user : d_interior_user, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+        bool ok = n % nv == 0;
+        for (int64_t i = 0; ok && i < n; ++i)
+            ok = h[i] >= 1 && h[i] <= nreal && (h[i] - 1) % nv == i % nv && (i % nv == 0 || h[i] == h[i - 1] + 1);
+        if (!ok)
+            return fail(CMDG_ERR_INVALID, "cmdg_create_dgfv: interiorelems / exteriorelems must list whole stacks, "
+                                          "bottom element first");
+    }
     return CMDG_OK;
 }
 
@@ -1288,7 +1365,7 @@ int cmdg_set_option(cmdg_handle h, int32_t option, int32_t value)
     case CMDG_OPT_REFERENCE_HALO:
         if (int r = e->synchronize()) return set_err(h, r);
         e->drop_graph();
-        e->reference_halo = value != 0;
+        e->reference_halo = value != 0 || e->fv;
         e->invalidate_sends();
         return CMDG_OK;
     case CMDG_OPT_STEP_GRAPH:
@@ -1633,6 +1710,9 @@ int cmdg_courant(cmdg_handle h, int32_t kind, const double *Q, double dt, double
 {
     if (!h || !Q || !out_host) return CMDG_ERR_INVALID;
     DevGuard guard_(h->eng);
+    if (h->eng->fv)
+        return set_err(h, h->eng->fail(CMDG_ERR_UNSUPPORTED, "courant: the device Courant number is not defined "
+                                                             "for a finite-volume vertical (DGFVModel handle)"));
     return set_err(h, h->eng->courant(1, kind, Q, dt, simtime, direction, out_host));
 }
 
@@ -1640,6 +1720,9 @@ int cmdg_min_node_distance(cmdg_handle h, int32_t direction, double *out_host)
 {
     if (!h || !out_host) return CMDG_ERR_INVALID;
     DevGuard guard_(h->eng);
+    if (h->eng->fv)
+        return set_err(h, h->eng->fail(CMDG_ERR_UNSUPPORTED, "min_node_distance: on a DGFVModel handle the vertical "
+                                                             "distance is the cell height 2 JcV; use the host grid's"));
     return set_err(h, h->eng->courant(0, 0, nullptr, 0.0, 0.0, direction, out_host));
 }
 

@@ -424,6 +424,7 @@ int EngineBase::run_column_ops(const RhsCtx &c, int64_t e0, int64_t e1)
 // ---- Filters.apply_async!   Filters.jl:440-607 ----------------------------------------
 int EngineBase::filter_create(const cmdg_filter_desc *d, FilterObj **out)
 {
+    if (fv) return fail(CMDG_ERR_UNSUPPORTED, "filter: element filters are not defined on a DGFVModel handle (vertical order 0)");
     if (d->kind < CMDG_FILTER_SPECTRAL || d->kind > CMDG_FILTER_TMAR)
         return fail(CMDG_ERR_INVALID, "filter: unknown kind");
     if (d->target < CMDG_TARGET_INDICES || d->target > CMDG_TARGET_ATMOS_SPECIFIC_PERTURBATIONS)

@@ -261,6 +261,14 @@ struct EngineBase {
     // make stream `later` wait for everything enqueued so far on `earlier` (through ev_comp)
     int order(hipStream_t earlier, hipStream_t later);
     bool communicate() const { return !nabrtorank.empty(); }
+    // a DGFVModel handle (cmdg_create_dgfv, engine_fv.h): NQV == 1, finite volume in the vertical.
+    // Its exchanges are packed and unpacked as the reference does (the vertical pass increments what
+    // an exterior launch would already have sent), and the LSRK update is the separate kernel after
+    // the finite-volume pass.
+    bool fv = false;
+    int fv_nvert = 0;
+    bool fused_lsrk() const { return tendency_filter == nullptr && !fv; }
+    int init_fv();
     // the orders the column operators and the filters are compiled for (one order in every direction)
     bool column_orders() const { return NQ >= 2 && NQ <= 8 && NQV == NQ; }
     // does an evaluation of this handle exchange ghosts (DGModel.jl:104-108: not the vertical
@@ -732,6 +740,7 @@ EngineBase *make_engine(const cmdg_desc *d)
 // factories implemented per physics family (one translation unit each)
 EngineBase *make_engine_advdiff(const cmdg_desc *d, std::string &err);
 int counts_advdiff(const int32_t *iparam, int32_t out[6]);
+EngineBase *make_engine_advdiff_fv(const cmdg_desc *d, const cmdg_fv_desc *fv, std::string &err);
 EngineBase *make_engine_atmos(const cmdg_desc *d, std::string &err);
 int counts_atmos(const int32_t *iparam, int32_t out[6]);
 EngineBase *make_engine_ocean(const cmdg_desc *d, std::string &err);

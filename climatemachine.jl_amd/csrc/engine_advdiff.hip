@@ -1,5 +1,5 @@
 // Engine instantiations for the AdvectionDiffusion law (physics_advdiff.h).
-#include "engine.h"
+#include "engine_fv.h"
 #include "physics_advdiff.h"
 
 namespace cmdg {
@@ -57,6 +57,36 @@ EngineBase *make_engine_advdiff(const cmdg_desc *d, std::string &err)
     case 7: return pick<8>(d, err);
     default:
         err = "AdvectionDiffusion: polynomial order not compiled in (have N = 1..7)";
+        return nullptr;
+    }
+}
+
+// DGFVModel handles: advection, and advection + diffusion, at N_h = 4 and N_h = 1
+template <int NQ>
+static EngineBase *pick_fv(const cmdg_desc *d, const cmdg_fv_desc *fv, std::string &err)
+{
+    const bool adv = d->iparam[1], diff = d->iparam[2], hyp = d->iparam[3];
+    if (hyp) {
+        err = "DGFVModel: a law with hyperdiffusive states is not supported (DGFVModel.jl:91)";
+        return nullptr;
+    }
+    if (adv && diff) return make_engine_fv<AdvDiff<true, true, false>, NQ>(d, fv);
+    if (adv && !diff) return make_engine_fv<AdvDiff<true, false, false>, NQ>(d, fv);
+    err = "DGFVModel AdvectionDiffusion: advection, or advection + diffusion, are compiled in";
+    return nullptr;
+}
+
+EngineBase *make_engine_advdiff_fv(const cmdg_desc *d, const cmdg_fv_desc *fv, std::string &err)
+{
+    if (d->iparam[0] != 1) {
+        err = "AdvectionDiffusion: num_equations != 1 is not compiled in";
+        return nullptr;
+    }
+    switch (d->N[0]) {
+    case 1: return pick_fv<2>(d, fv, err);
+    case 4: return pick_fv<5>(d, fv, err);
+    default:
+        err = "DGFVModel AdvectionDiffusion: horizontal polynomial orders compiled in are 1 and 4";
         return nullptr;
     }
 }

@@ -1,0 +1,120 @@
+// Engine of a DGFVModel handle (cmdg_create_dgfv): spectral-element DG in the horizontal, a
+// cell-centred finite volume method in the vertical.  The orchestration is EngineBase::rhs_segment
+// unchanged -- (dgfvm::DGFVModel)(tendency, Q, _, t, alpha, beta) (DGFVModel.jl:85-320) cuts an
+// evaluation at the same exchanges as the DGModel's -- with the two passes that have a vertical part
+// launched as the reference launches them for a DGFVModel (SpaceDiscretization.jl:505,604,
+// 1100-1158,1224-1278): the DG kernels at (NQ, NQV = 1) in the horizontal direction (faces 1-4,
+// volume sources added), then the finite-volume kernel of fv.h on the same element list.  The
+// vertical passes read their own stack only, so they need no halo of their own.
+#pragma once
+#include "engine.h"
+#include "fv.h"
+
+namespace cmdg {
+
+template <class P, int NQ_>
+struct EngineFV : EngineT<P, NQ_, 1> {
+    using Base = EngineT<P, NQ_, 1>;
+    cmdg_fv_desc fvd{};
+    using FvKernel = void (*)(FvArgs<P>);
+
+    FvArgs<P> fv_args(const RhsCtx &c, const int64_t *elems, int64_t n) const
+    {
+        FvArgs<P> a;
+        a.prm = this->prm;
+        a.g = this->g;
+        a.elems = elems;
+        a.nelems = n;
+        a.nvert = fvd.nvertelem;
+        a.Q = c.Qin;
+        a.aux = this->aux;
+        a.derived = this->derived;
+        a.gf = this->gf;
+        a.tendency = c.tendency;
+        a.t = c.t;
+        a.alpha = c.alpha;
+        a.beta = c.beta;
+        a.increment = this->direction == DIR_EVERY;
+        a.add_source = this->direction == DIR_VERTICAL;
+        a.model_dir = this->direction;
+        a.nf_first = this->nf_first;
+        a.recon = fvd.reconstruction;
+        a.limiter = fvd.limiter;
+        return a;
+    }
+    template <bool PERIODIC>
+    static FvKernel pick_fv_tendency(int width)
+    {
+        switch (width) {
+        case 0: return k_fv_tendency<P, NQ_, 0, PERIODIC>;
+        case 1: return k_fv_tendency<P, NQ_, 1, PERIODIC>;
+        case 2: return k_fv_tendency<P, NQ_, 2, PERIODIC>;
+        default: return k_fv_tendency<P, NQ_, 3, PERIODIC>;
+        }
+    }
+    void launch_gradients(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
+    {
+        if (n <= 0) return;
+        if (this->diffusion_direction != DIR_VERTICAL) {
+            this->in_pass(Base::GRADIENTS, n, exterior, st, [&] {
+                const PassArgs<P> args = this->make_args(c, elems, n, DIR_HORIZONTAL, exterior, nullptr, nullptr);
+                hipLaunchKernelGGL(Base::pick_gradients(this->gf_live(), false), dim3((unsigned)n),
+                                   dim3(KDims<NQ_, 1>::NT), 0, st, args);
+            });
+        }
+        if (this->diffusion_direction != DIR_HORIZONTAL && P::NGF > 0 && this->gf_live()) {
+            this->prof_begin(CMDG_K_FV_GRADIENTS, st);
+            FvArgs<P> a = fv_args(c, elems, n);
+            // (SpaceDiscretization.jl:717-719: increments after the horizontal values of an
+            // EveryDirection model)
+            a.increment = this->direction == DIR_EVERY;
+            const int64_t nthreads = n * NQ_ * NQ_;
+            FvKernel k = k_fv_gradients<P, NQ_, false>;
+            if (fvd.periodicstack) k = k_fv_gradients<P, NQ_, true>;
+            hipLaunchKernelGGL(k, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, st, a);
+            this->prof_end(st);
+        }
+    }
+    void launch_tendency(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
+    {
+        if (n <= 0) return;
+        if (this->direction != DIR_VERTICAL) {
+            this->in_pass(Base::TENDENCY, n, exterior, st, [&] {
+                using SH = TendencyShape<P, NQ_, 1>;
+                const PassArgs<P> args = this->make_args(c, elems, n, DIR_HORIZONTAL, exterior, nullptr, nullptr);
+                hipLaunchKernelGGL(Base::pick_tendency(false, P::needs_gradflux(this->prm), false, GargOut::none),
+                                   dim3((unsigned)SH::blocks(n)), dim3(SH::NT), 0, st, args);
+            });
+        }
+        if (this->direction != DIR_HORIZONTAL) {
+            this->prof_begin(CMDG_K_FV_TENDENCY, st);
+            const FvArgs<P> a = fv_args(c, elems, n);
+            const int nv = fvd.nvertelem;
+            const FvKernel k = fvd.periodicstack ? pick_fv_tendency<true>(fvd.width) : pick_fv_tendency<false>(fvd.width);
+            hipLaunchKernelGGL(k, dim3((unsigned)(n / nv)), dim3(fv_threads(NQ_ * NQ_, nv)),
+                               fv_lds_bytes(P::NS, NQ_ * NQ_, nv), st, a);
+            this->prof_end(st);
+        }
+    }
+};
+
+template <class P, int NQ_>
+EngineBase *make_engine_fv(const cmdg_desc *d, const cmdg_fv_desc *fv)
+{
+    auto *e = new EngineFV<P, NQ_>();
+    e->NQ = NQ_;
+    e->NQV = 1;
+    e->ns = P::NS;
+    e->naux = P::NAUX;
+    e->ngrad = P::NGRAD;
+    e->ngf = P::NGF;
+    e->ngl = P::NGL;
+    e->nhyp = P::NHYP;
+    e->fv = true;
+    e->fv_nvert = fv->nvertelem;
+    e->fvd = *fv;
+    P::make_params(e->prm, d->iparam, d->dparam);
+    return e;
+}
+
+}  // namespace cmdg

@@ -58,7 +58,7 @@ int group_lsrk_step(std::vector<EngineBase *> &g, double **Q, double **dQ, doubl
         for (size_t i = 0; i < g.size(); ++i) {
             RhsCtx &x = c[i];
             // a tendency filter acts on dQ between rhs! and update!: no fused update then
-            const bool fused = g[i]->tendency_filter == nullptr;
+            const bool fused = g[i]->fused_lsrk();
             if (fused) {
                 lsrk_stage_buffers(g[i], Q[i], s, nstages, &x.Qin, &x.Qout);
             } else {
@@ -83,7 +83,7 @@ int group_lsrk_step(std::vector<EngineBase *> &g, double **Q, double **dQ, doubl
     }
     for (size_t i = 0; i < g.size(); ++i) {
         EngineBase *e = g[i];
-        if (nstages == 1 && e->tendency_filter == nullptr)
+        if (nstages == 1 && e->fused_lsrk())
             if (hipMemcpyAsync(Q[i], e->W[0], sizeof(double) * e->Np * e->ns * e->nreal,
                                hipMemcpyDeviceToDevice, e->s_comp) != hipSuccess)
                 return e->fail(CMDG_ERR_HIP, "lsrk: copy back failed");
@@ -129,7 +129,9 @@ bool EngineBase::graph_eligible() const
     // (scripts/probe/rccl_capture_probe.py, profiles/r04_rccl_capture_probes.txt).  The halo stream
     // is therefore the origin of such a capture and the compute stream the forked one.
     const bool comm_ok = !exchanges() || (transport == TRANSPORT_RCCL && pipelined());
-    return step_graph && !graph_failed && !profiling && !step_filter && !tendency_filter &&
+    // (a DGFVModel handle stays eager: its step has never been recorded and replayed on a device, and
+    // nothing asks for it yet)
+    return step_graph && !fv && !graph_failed && !profiling && !step_filter && !tendency_filter &&
            !gradient_filter && !has_hooks && (!has_update_aux() || fused_update_aux()) && comm_ok;
 }
 

@@ -6,6 +6,7 @@
 //   problem 2  ConstantHyperDiffusion{mu, k} with boundary data  hyperdiffusion_bc.jl:25-112
 //   problem 3  HeatEqn{n, kappa, A}                              pseudo1D_heat_eqn.jl:28-88
 //   problem 7  ReversingDeformationalFlow (velocity refresh)     advection_sphere.jl:56-103
+//   problem 8  Pseudo1D{n, alpha} sine wave                      fvm_advection.jl:33-54
 //
 // Parameter block (cmdg_desc.iparam / dparam):
 //   iparam[0]=num_equations (1)  [1]=advection [2]=diffusion [3]=hyperdiffusion
@@ -109,6 +110,10 @@ struct AdvDiff {
             const double *n = m.d, ka = m.d[3], A = m.d[4];
             const double xn = n[0] * x[0] + n[1] * x[1] + n[2] * x[2];
             return xn + A * cos(ka * xn) * exp(-(ka * ka) * t);
+        } else if (m.problem == 8) {  // d[0..2] = n, d[3] = alpha
+            const double *n = m.d;
+            const double xn = n[0] * x[0] + n[1] * x[1] + n[2] * x[2];
+            return sin((xn - m.d[3] * t) * M_PI);
         }
         return 0.0;
     }

@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from .balancelaws import EveryDirection, RusanovNumericalFlux
 
-__all__ = ["DGModel", "RemainderDGModel", "remainder_DGModel", "connect_local", "group_rhs", "group_lsrk_run", "group_halo",
+__all__ = ["DGModel", "DGFVModel", "RemainderDGModel", "remainder_DGModel", "connect_local", "group_rhs", "group_lsrk_run", "group_halo",
            "reference_pressure_gradient", "rccl_unique_id",
            "ADVECTIVE_COURANT", "NONDIFFUSIVE_COURANT", "DIFFUSIVE_COURANT"]
 
@@ -116,7 +116,7 @@ class DGModel:
         d.Qhypervisc_div = self.Qhypervisc_div.data_ptr()
         torch.cuda.synchronize(dev)          # tables uploaded on torch's stream
         h = C.c_void_p()
-        _lib.check(L.cmdg_create(C.byref(d), C.byref(h)))
+        self._create(d, h)
         self.handle = h
         self._desc = d
         if keep_gradient_flux:
@@ -124,6 +124,9 @@ class DGModel:
         if g.topology.isstacked and g.topology.stacksize:
             # length(topology.stacksize): lets the engine pick the launch order of tall stacks
             self.set_option(_lib.OPT_STACK_HEIGHT, int(g.topology.stacksize))
+
+    def _create(self, d, h):
+        _lib.check(self.L.cmdg_create(C.byref(d), C.byref(h)))
 
     def set_option(self, option, value):
         """``cmdg_set_option``: ``_lib.OPT_KEEP_GRADFLUX`` = refresh ``state_gradient_flux`` in
@@ -389,6 +392,33 @@ class DGModel:
                                            C.cast(C.byref(ms), C.c_void_p),
                                            C.cast(C.byref(n), C.c_void_p)), self.handle)
         return ms.value, n.value
+
+
+class DGFVModel(DGModel):
+    """``DGFVModel(balance_law, grid, fv_reconstruction, numerical_flux_first_order, ...;
+    direction)`` (src/Numerics/DGMethods/DGFVModel.jl:22-69): spectral-element DG in the
+    horizontal, cell-centred finite volumes in the vertical, on a stacked grid built with
+    ``polynomialorder = (N_h, 0)``.  ``fv_reconstruction`` is an ``fvreconstructions.FVConstant()``
+    or ``FVLinear(width, limiter)``.  Same methods as ``DGModel`` (``cmdg_create_dgfv`` handle)."""
+
+    def __init__(self, balance_law, grid, fv_reconstruction, numerical_flux_first_order=RusanovNumericalFlux,
+                 direction=EveryDirection, device="cuda:0", state_auxiliary=None):
+        if grid.dim != 3 or grid.N[2] != 0:
+            raise _lib.CmdgError("DGFVModel needs a grid with polynomialorder = (N_h, 0)")
+        if not grid.topology.isstacked:
+            raise _lib.CmdgError("DGFVModel needs a stacked topology")
+        self.fv_reconstruction = fv_reconstruction
+        super().__init__(balance_law, grid, numerical_flux_first_order=numerical_flux_first_order,
+                         direction=direction, device=device, state_auxiliary=state_auxiliary)
+
+    def _create(self, d, h):
+        r, t = self.fv_reconstruction, self.grid.topology
+        fv = _lib.CmdgFvDesc()
+        fv.reconstruction, fv.width = int(r.reconstruction_id), int(r.width)
+        fv.limiter = int(r.limiter.limiter_id)
+        fv.nvertelem, fv.periodicstack = int(t.stacksize), int(bool(t.periodicstack))
+        self._fv_desc = fv
+        _lib.check(self.L.cmdg_create_dgfv(C.byref(d), C.byref(fv), C.byref(h)))
 
 
 class RemainderDGModel:

@@ -25,7 +25,7 @@ _n1, _n2, _n3, _sM, _vMI = range(5)
 NSGEO = 5
 
 __all__ = ["DiscontinuousSpectralElementGrid", "mappings", "commmapping",
-           "computegeometry", "NVGEO", "NSGEO"]
+           "computegeometry", "computegeometry_fvm", "glpoints", "NVGEO", "NSGEO"]
 
 
 def _fmask(Nq):
@@ -291,6 +291,73 @@ def computegeometry(elemtocoord, D, xi, omega, meshwarp=None):
     return vgeo, sgeo
 
 
+def glpoints(N):
+    """Points and weights of the element in one direction: Legendre-Gauss-Lobatto for N >= 1, the
+    single Gauss point ``xi = [0]``, ``omega = [2]`` for the finite-volume order N = 0
+    (Grids.jl:312,426)."""
+    if N == 0:
+        return np.zeros(1), np.full(1, 2.0)
+    return elements.lglpoints(N)
+
+
+def computegeometry_fvm(elemtocoord, D, xi, omega, meshwarp=None):
+    """Geometry of a grid whose vertical order is 0 (``computegeometry_fvm``, Grids.jl:812-1010):
+    the N = 1 geometry in the collapsed direction, reduced to one cell-centred node.  ``M`` is the
+    sum of the two N = 1 values, ``MI = 1/M``, ``JcV`` their average, the nine metric terms their
+    mass-weighted average times ``MI``, ``MH`` follows ``horizontal_metrics!``.  On the vertical
+    faces ``sgeo`` keeps the N = 1 normals and ``sM``; on the horizontal faces ``sM`` is summed and
+    the normals are ``sM``-weighted; ``vMI`` is ``MI`` at the face node everywhere.  The nine
+    ``dx/dxi`` columns this library adds to vgeo are plain averages."""
+    d = len(D)
+    assert d == 3 and D[2].shape[0] == 1 and D[0].shape[0] > 1 and D[1].shape[0] > 1, \
+        "finite volume order 0 is supported in the vertical of a 3-D grid only"
+    nelem = elemtocoord.shape[0]
+    Nq = [Dj.shape[0] for Dj in D]
+    Np = int(np.prod(Nq))
+    Nfp = [Np // q for q in Nq]
+    xi1, om1 = elements.lglpoints(1)
+    D1 = elements.spectralderivative(xi1)
+    vg1, sg1 = computegeometry(elemtocoord, [D[0], D[1], D1], [xi[0], xi[1], xi1],
+                               [omega[0], omega[1], om1], meshwarp)
+    v1 = vg1.reshape(nelem, NVGEO, 2, Np)                  # the collapsed direction is the slowest
+    vgeo = np.zeros((nelem, NVGEO, Np))
+    x = _creategrid(elemtocoord, xi)
+    x1, x2, x3 = x[:, :, 0], x[:, :, 1], x[:, :, 2]
+    if meshwarp is not None:
+        x1, x2, x3 = meshwarp(x1, x2, x3)
+    vgeo[:, _x1], vgeo[:, _x2], vgeo[:, _x3] = x1, x2, x3
+    M1 = v1[:, _M]
+    vgeo[:, _M] = M1[:, 0] + M1[:, 1]
+    vgeo[:, _MI] = 1.0 / vgeo[:, _M]
+    vgeo[:, _JcV] = (v1[:, _JcV, 0] + v1[:, _JcV, 1]) / 2
+    for c in (_xi1x1, _xi2x1, _xi3x1, _xi1x2, _xi2x2, _xi3x2, _xi1x3, _xi2x3, _xi3x3):
+        vgeo[:, c] = (M1[:, 0] * v1[:, c, 0] + M1[:, 1] * v1[:, c, 1]) * vgeo[:, _MI]
+    for c in (_x1xi1, _x2xi1, _x3xi1, _x1xi2, _x2xi2, _x3xi2, _x1xi3, _x2xi3, _x3xi3):
+        vgeo[:, c] = (v1[:, c, 0] + v1[:, c, 1]) / 2
+    # horizontal_metrics! (Grids.jl:1135-1154) on the collapsed arrays
+    MHw = np.kron(omega[1], omega[0])
+    Mfull = np.kron(omega[2], MHw)
+    Jn = vgeo[:, _M] / Mfull[None, :]
+    vgeo[:, _MH] = MHw[None, :] * np.sqrt((Jn * vgeo[:, _xi3x1]) ** 2 + (Jn * vgeo[:, _xi3x2]) ** 2
+                                          + (Jn * vgeo[:, _xi3x3]) ** 2)
+    fmask = _fmask(Nq)
+    sgeo = np.full((nelem, 2 * d, max(Nfp), NSGEO), np.nan)
+    for f in range(2 * d):
+        dd = f // 2
+        nfp = Nfp[dd]
+        if dd == 2:                                        # the face keeps all of its N = 1 nodes
+            sgeo[:, f, :nfp, :_vMI] = sg1[:, f, :nfp, :_vMI]
+        else:
+            s1 = sg1[:, f, :2 * nfp, :].reshape(nelem, 2, nfp, NSGEO)
+            sM = s1[:, 0, :, _sM] + s1[:, 1, :, _sM]
+            sgeo[:, f, :nfp, _sM] = sM
+            for c in (_n1, _n2, _n3):
+                sgeo[:, f, :nfp, c] = (s1[:, 0, :, _sM] * s1[:, 0, :, c]
+                                       + s1[:, 1, :, _sM] * s1[:, 1, :, c]) / sM
+        sgeo[:, f, :nfp, _vMI] = vgeo[:, _MI][:, fmask[f]]
+    return vgeo, sgeo
+
+
 def indefinite_integral_interpolation_matrix(r, omega):
     """Reference: Grids.jl:1184-1207.  ``I @ f(r)`` is the indefinite integral (from ``r[0]``)
     of the interpolant of ``f``, evaluated at the points ``r``."""
@@ -299,6 +366,8 @@ def indefinite_integral_interpolation_matrix(r, omega):
     Nq = len(r)
     I = np.zeros((Nq, Nq))
     I[0, :] = omega[0] if Nq == 1 else 0.0
+    if Nq == 1:
+        return I
     wbary = elements.baryweights(r)
     for n in range(1, Nq):
         rdst = (1 - r) / 2 * r[0] + (1 + r) / 2 * r[n]
@@ -310,7 +379,9 @@ def indefinite_integral_interpolation_matrix(r, omega):
 
 class DiscontinuousSpectralElementGrid:
     """Reference: Grids.jl:170-413.  ``polynomialorder`` is an int or a tuple
-    (a 2-tuple in 3-D means (horizontal, vertical))."""
+    (a 2-tuple in 3-D means (horizontal, vertical)).  A vertical order of 0 makes the grid of a
+    ``DGFVModel``: one cell-centred node per horizontal node and element in the vertical
+    (``computegeometry_fvm``); it needs a stacked topology."""
 
     def __init__(self, topology, polynomialorder, meshwarp=None):
         dim = topology.dim
@@ -335,14 +406,19 @@ class DiscontinuousSpectralElementGrid:
             N, ghostidx, t.ghostfaces, t.nabrtorecv)
         self.vmapsend, self.nabrtovmapsend = commmapping(
             N, t.sendelems, t.sendfaces, t.nabrtosend)
-        xw = [elements.lglpoints(n) for n in N]
+        fvm = min(N) == 0
+        if fvm and not (dim == 3 and N[2] == 0 and N[0] >= 1 and N[1] >= 1
+                        and getattr(topology, "isstacked", False)):
+            raise ValueError("polynomial order 0 (finite volume) is supported in the vertical of a "
+                             "stacked 3-D topology only")
+        xw = [glpoints(n) for n in N] if fvm else [elements.lglpoints(n) for n in N]
         self.xi = [p[0] for p in xw]
         self.omega = [p[1] for p in xw]
-        self.D = [elements.spectralderivative(x) for x in self.xi]
+        self.D = [elements.spectralderivative(x) if len(x) > 1 else np.zeros((1, 1)) for x in self.xi]
         self.Imat = [indefinite_integral_interpolation_matrix(x, w)
                      for x, w in zip(self.xi, self.omega)]
-        self.vgeo, self.sgeo = computegeometry(t.elemtocoord, self.D, self.xi,
-                                               self.omega, meshwarp)
+        self.vgeo, self.sgeo = (computegeometry_fvm if fvm else computegeometry)(
+            t.elemtocoord, self.D, self.xi, self.omega, meshwarp)
         act = np.zeros(self.Np * t.nelem, dtype=bool)
         act[: self.Np * t.nreal] = True
         if len(self.vmaprecv):
@@ -375,6 +451,9 @@ def min_node_distance(grid, direction=0):
     md = np.inf
     for ax in range(d):
         if not use[ax]:
+            continue
+        if Nq[ax] == 1:       # FV vertical: the cell height 2 JcV (Grids.jl:1295-1317)
+            md = min(md, float(2 * grid.vgeo[:grid.nreal, _JcV, :].min()))
             continue
         npax = d - ax                                   # numpy axis of tensor dim ax
         diff = np.diff(x, axis=npax)

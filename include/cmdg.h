@@ -151,6 +151,32 @@ int cmdg_physics_counts(int32_t physics_id, const int32_t *iparam, int32_t out[6
 int cmdg_create(const cmdg_desc *desc, cmdg_handle *out);
 int cmdg_destroy(cmdg_handle h);
 
+/* Finite-volume reconstruction of a DGFVModel: FVConstant / FVLinear{W}(limiter)
+ * (src/Numerics/DGMethods/FVReconstructions.jl:60-192). */
+enum { CMDG_FV_CONSTANT = 0, CMDG_FV_LINEAR = 1 };
+enum { CMDG_FV_VANLEER = 0, CMDG_FV_NOLIMITER = 1 };
+typedef struct cmdg_fv_desc {
+    int32_t reconstruction; /* CMDG_FV_CONSTANT | CMDG_FV_LINEAR */
+    int32_t width;          /* width(reconstruction): 0 for the constant, 1..3 for the linear one */
+    int32_t limiter;        /* CMDG_FV_VANLEER | CMDG_FV_NOLIMITER */
+    int32_t nvertelem;      /* grid.topology.stacksize */
+    int32_t periodicstack;  /* grid.topology.periodicstack */
+} cmdg_fv_desc;
+/* replaces DGFVModel(balance_law, grid, fv_reconstruction, nf1, nf2, nfgrad; direction)
+ * construction, src/Numerics/DGMethods/DGFVModel.jl:22-69: spectral-element DG in the horizontal, a
+ * cell-centred finite volume method in the vertical, on a grid with polynomialorder = (N_h, 0)
+ * (desc->N[2] == 0, desc->Dv may be NULL).  The handle serves cmdg_rhs, cmdg_lsrk_step / _run /
+ * _update, the reductions, the halo and the group calls like any other; its evaluations follow
+ * (dgfvm::DGFVModel)(tendency, Q, _, t, alpha, beta), DGFVModel.jl:85-320.
+ * Refused with CMDG_ERR_INVALID and a message in cmdg_last_error(NULL): N[2] != 0 (and N[2] == 0
+ * through cmdg_create), an unstacked grid, nvertelem < 2, width outside 0..3 or 0 with a linear
+ * reconstruction, element lists that are not whole stacks.  CMDG_ERR_UNSUPPORTED: a law or order
+ * not compiled in (AdvectionDiffusion, advection or advection + diffusion, N_h = 1 and 4), a law
+ * with hyperdiffusive states (DGFVModel.jl:91), a stack too tall for the LDS staging.  On such a
+ * handle element filters, cmdg_courant, cmdg_min_node_distance and cmdg_columnlu_create are refused
+ * with CMDG_ERR_UNSUPPORTED. */
+int cmdg_create_dgfv(const cmdg_desc *desc, const cmdg_fv_desc *fv, cmdg_handle *out);
+
 /* Balance laws / template combinations outside the compiled set.  In the reference a law's
  * pointwise functions are compiled into the kernels when the model first runs
  * (src/BalanceLaws/interface.jl:37-464, KernelAbstractions); behind a C ABI the equivalent is a
@@ -750,7 +776,9 @@ enum {
     /* the exterior launches of the four passes of a handle with neighbours (their interior
      * launches stay under CMDG_K_GRADIENTS ... CMDG_K_TENDENCY) */
     CMDG_K_GRADIENTS_EXT = 11, CMDG_K_DIVGRAD_EXT = 12, CMDG_K_GRADLAP_EXT = 13,
-    CMDG_K_TENDENCY_EXT = 14, CMDG_K_COUNT = 15
+    CMDG_K_TENDENCY_EXT = 14,
+    /* the vertical finite-volume passes of a DGFVModel handle (interior and exterior launches) */
+    CMDG_K_FV_GRADIENTS = 15, CMDG_K_FV_TENDENCY = 16, CMDG_K_COUNT = 17
 };
 /* bracket every launch with HIP events on the launch stream (off by default) */
 int cmdg_profile_enable(cmdg_handle h, int32_t on);

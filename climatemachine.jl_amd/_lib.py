@@ -139,6 +139,7 @@ SYMBOLS = [
     ("cmdg_version", C.c_char_p, []),
     ("cmdg_status_string", C.c_char_p, [C.c_int]),
     ("cmdg_physics_counts", C.c_int, [_i32, _vp, _vp]),
+    ("cmdg_atmos_host_constants", C.c_int, [_vp, _vp, _vp]),
     ("cmdg_create", C.c_int, [C.POINTER(CmdgDesc), C.POINTER(_vp)]),
     ("cmdg_create_dgfv", C.c_int, [C.POINTER(CmdgDesc), C.POINTER(CmdgFvDesc), C.POINTER(_vp)]),
     ("cmdg_destroy", C.c_int, [_vp]),

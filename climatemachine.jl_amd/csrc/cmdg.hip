@@ -1134,6 +1134,12 @@ int cmdg_physics_counts(int32_t physics_id, const int32_t *iparam, int32_t out[6
     }
 }
 
+int cmdg_atmos_host_constants(const int32_t *iparam, const double *dparam, double out[7])
+{
+    if (!iparam || !dparam || !out) return CMDG_ERR_INVALID;
+    return host_constants_atmos(iparam, dparam, out);
+}
+
 static int create_handle(const cmdg_desc *d, const cmdg_fv_desc *fv, cmdg_handle *out)
 {
     *out = nullptr;

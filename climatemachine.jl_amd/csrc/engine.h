@@ -743,6 +743,7 @@ int counts_advdiff(const int32_t *iparam, int32_t out[6]);
 EngineBase *make_engine_advdiff_fv(const cmdg_desc *d, const cmdg_fv_desc *fv, std::string &err);
 EngineBase *make_engine_atmos(const cmdg_desc *d, std::string &err);
 int counts_atmos(const int32_t *iparam, int32_t out[6]);
+int host_constants_atmos(const int32_t *iparam, const double *dparam, double out[7]);
 EngineBase *make_engine_ocean(const cmdg_desc *d, std::string &err);
 int counts_ocean(const int32_t *iparam, int32_t out[6]);
 EngineBase *make_engine_sw(const cmdg_desc *d, std::string &err);

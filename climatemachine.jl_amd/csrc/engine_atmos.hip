@@ -16,6 +16,17 @@ int counts_atmos(const int32_t *ip, int32_t out[6])
     return CMDG_OK;
 }
 
+// what make_params derives from the parameter block (the same for every variant of the functor)
+int host_constants_atmos(const int32_t *ip, const double *dp, double out[7])
+{
+    static_assert(ATMOS_NHOSTCONST == 7, "cmdg_atmos_host_constants documents seven");
+    using P = DryAtmos<false, false, false>;
+    P::Params prm;
+    P::make_params(prm, ip, dp);
+    P::host_constants(prm, out);
+    return CMDG_OK;
+}
+
 template <int NQ>
 static EngineBase *pick(const cmdg_desc *d, std::string &err)
 {

@@ -499,6 +499,9 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
     // viscosity (Held-Suarez) tau = -2*0*S and D_t = 0: the 9 fields only ever multiply
     // zeros, so the host picks the instantiation that does not read them (identical results).
     constexpr bool use_gf = NGF > 0 && USE_GF;
+    // the hyperdiffusive inviscid instantiation at N <= 4 (Held-Suarez): 126 VGPRs, five work-groups
+    // per CU, and its SIMDs issue fp64 VALU work 60 % of the time
+    constexpr bool HS_SHAPE = NHYP > 0 && !use_gf && Np <= 125 && NS >= 5;
     int32_t f_idP = 0;
     int f_bctag = 0, f_f = 0, f_n = 0;
     KD::face_task(tid, f_f, f_n);
@@ -519,7 +522,7 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
         // residency: the hyperdiffusive inviscid instantiation at N <= 4 (Held-Suarez) sits at 126
         // VGPRs, five work-groups per CU; with nine more doubles live across the flux arithmetic it
         // takes 148 and runs on four (661 us against 636; rising bubble 132 -> 124 us, BOMEX 589 -> 578)
-        constexpr bool METRICS_FIRST = !(NHYP > 0 && !use_gf && Np <= 125 && NS >= 5);
+        constexpr bool METRICS_FIRST = !HS_SHAPE;
         if constexpr (METRICS_FIRST) {
             if (hz) {
                 x11 = vg[XI1X1 * Np], x12 = vg[XI1X2 * Np], x13 = vg[XI1X3 * Np];
@@ -607,6 +610,28 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
 #pragma unroll
             for (int s = 0; s < NS; ++s) Tprev[s] = a.tendency[tid + (int64_t)Np * (s + (int64_t)NS * e)];
         }
+        // MI * D does not depend on the state, but the compiler forms it (and reads D) once per
+        // state: it does not merge across the per-state direction tests.  Where the instruction
+        // stream is a bound (HS_SHAPE) the 15 products are formed once -- (MI * D) * F as before; the
+        // other instantiations keep their code and their registers (30 more VGPRs would move some).
+        double mDi[NQ], mDj[NQ], mDk[NQV];
+#pragma unroll
+        for (int n = 0; n < NQ; ++n) mDi[n] = mDj[n] = 0.0;
+#pragma unroll
+        for (int kk = 0; kk < NQV; ++kk) mDk[kk] = 0.0;
+        if constexpr (HS_SHAPE) {
+            if (hz) {
+#pragma unroll
+                for (int n = 0; n < NQ; ++n) {
+                    mDi[n] = MI * sD[n + NQ * i];
+                    mDj[n] = MI * sD[n + NQ * j];
+                }
+            }
+            if (vt) {
+#pragma unroll
+                for (int kk = 0; kk < NQV; ++kk) mDk[kk] = MI * sDv[kk + NQV * k];
+            }
+        }
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             double T = 0.0;
@@ -616,8 +641,8 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
                 if (a.direction == DIR_HORIZONTAL && P::HAS_SOURCE) lt += S[s];
 #pragma unroll
                 for (int n = 0; n < NQ; ++n) {
-                    lt += MI * sD[n + NQ * i] * sF[(0 * NS + s) * Np + n + NQ * (j + NQ * k)];
-                    lt += MI * sD[n + NQ * j] * sF[(1 * NS + s) * Np + i + NQ * (n + NQ * k)];
+                    lt += (HS_SHAPE ? mDi[n] : MI * sD[n + NQ * i]) * sF[(0 * NS + s) * Np + n + NQ * (j + NQ * k)];
+                    lt += (HS_SHAPE ? mDj[n] : MI * sD[n + NQ * j]) * sF[(1 * NS + s) * Np + i + NQ * (n + NQ * k)];
                 }
                 T = a.beta != 0 ? a.alpha * lt + a.beta * Told : a.alpha * lt;
             }
@@ -626,7 +651,7 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
                 double lt = 0.0;
 #pragma unroll
                 for (int kk = 0; kk < NQV; ++kk) {
-                    lt += MI * sDv[kk + NQV * k] * sF[(2 * NS + s) * Np + i + NQ * (j + NQ * kk)];
+                    lt += (HS_SHAPE ? mDk[kk] : MI * sDv[kk + NQV * k]) * sF[(2 * NS + s) * Np + i + NQ * (j + NQ * kk)];
                     if (kk == k && P::HAS_SOURCE) lt += S[s];
                 }
                 if (hz)

@@ -29,7 +29,16 @@ struct AtmosParams {
     int bc[8];
     double visc, tau, R_d, cp_d, cv_d, T_0, grav, Omega, MSLP, day, invPr, C_smag;
     int withdiv, zero_h;  // WithDivergence stress; total_specific_enthalpy overridden to zero
+    // Quotients and products of the members above that the pointwise functions used to form per
+    // thread -- an fp64 division is ten VALU instructions, spent on a value all lanes share.
+    // make_params evaluates the very expressions the device code had (an IEEE double division or
+    // product gives the same bits on the host); cmdg_atmos_host_constants returns them in this order.
+    double k_a, k_f, k_s;   // Held-Suarez rates 1 / (40 day), 1 / day, 1 / (4 day)
+    double kappa;           // R_d / cp_d (the Exner exponent)
+    double gamma, gamma_R;  // cp_d / cv_d; gamma * R_d (soundspeed)
+    double R_ratio;         // R_m / R_d of a dry phase: R_d / R_d (virtual_pottemp)
 };
+static constexpr int ATMOS_NHOSTCONST = 7;
 
 template <bool ORIENT, bool REF, bool HYPER, bool SMAG = false, bool LAWNF = false>
 struct DryAtmos {
@@ -125,6 +134,23 @@ struct DryAtmos {
         p.C_smag = dp[13];
         p.withdiv = ip[15] & 1;
         p.zero_h = (ip[15] >> 1) & 1;
+        derive_params(p);
+    }
+    static void derive_params(Params &p)
+    {
+        const double day = p.day, R_d = p.R_d, cp_d = p.cp_d, cv_d = p.cv_d;
+        p.k_a = 1 / (40 * day);
+        p.k_f = 1 / day;
+        p.k_s = 1 / (4 * day);
+        p.kappa = R_d / cp_d;
+        p.gamma = cp_d / cv_d;
+        p.gamma_R = p.gamma * R_d;
+        p.R_ratio = R_d / R_d;
+    }
+    static void host_constants(const Params &p, double *out)
+    {
+        const double c[ATMOS_NHOSTCONST] = {p.k_a, p.k_f, p.k_s, p.kappa, p.gamma, p.gamma_R, p.R_ratio};
+        for (int i = 0; i < ATMOS_NHOSTCONST; ++i) out[i] = c[i];
     }
 
     // ---- dry thermodynamics ----------------------------------------------------------
@@ -142,8 +168,7 @@ struct DryAtmos {
     __device__ static double air_p(const Params &m, double T, double rho) { return m.R_d * rho * T; }
     __device__ static double soundspeed(const Params &m, double T)
     {
-        const double gamma = m.cp_d / m.cv_d;
-        return sqrt(gamma * m.R_d * T);
+        return sqrt(m.gamma_R * T);  // gamma = cp_d / cv_d; sqrt(gamma * R_d * T)
     }
 
     // ---- local Courant numbers: src/Atmos/Model/courant.jl:12-83 ------------------------
@@ -232,7 +257,14 @@ struct DryAtmos {
     {
         const double *S = gf + 3;
         if constexpr (!SMAG) {
-            const double v = m.kinematic ? m.visc : m.visc / Q[0];
+            // m.kinematic is uniform: a scalar branch.  (Left to itself the compiler evaluates the
+            // division in every lane and selects per lane; the empty statement keeps it from
+            // hoisting the quotient out of its branch.)
+            double v = m.visc;
+            if (!m.kinematic) {
+                __asm__ volatile("");
+                v = m.visc / Q[0];
+            }
             nu[0] = nu[1] = nu[2] = v;
         } else {
             const double norm2 = S[0] * S[0] + 2 * (S[1] * S[1]) + 2 * (S[2] * S[2]) + S[3] * S[3] +
@@ -308,12 +340,11 @@ struct DryAtmos {
     __device__ static void hs_coeffs(const Params &m, const double *Q, const double *der,
                                      double T, double &k_v, double &k_T, double &T_equil)
     {
-        const double day = m.day;
-        const double k_a = 1 / (40 * day), k_f = 1 / day, k_s = 1 / (4 * day);
+        const double k_a = m.k_a, k_f = m.k_f, k_s = m.k_s;  // 1 / (40 day), 1 / day, 1 / (4 day)
         const double dTy = 60, dthz = 10, T_eq = 315, T_min = 200, sig_b = 7.0 / 10;
         const double p = air_p(m, T, Q[0]);
         const double sig = p / m.MSLP;
-        const double exner = pow(sig, m.R_d / m.cp_d);
+        const double exner = pow(sig, m.kappa);
         const double dsig = (sig - sig_b) / (1 - sig_b);
         const double hf = dsig > 0 ? dsig : 0;
         const double s = der[0], c = der[1];
@@ -500,8 +531,8 @@ struct DryAtmos {
     }
     __device__ static double theta_v(const Params &m, double T, double rho)
     {  // virtual_pottemp of a dry phase (moisture.jl:53-62)
-        const double exner = pow(air_p(m, T, rho) / m.MSLP, m.R_d / m.cp_d);
-        return m.R_d / m.R_d * (T / exner);
+        const double exner = pow(air_p(m, T, rho) / m.MSLP, m.kappa);
+        return m.R_ratio * (T / exner);
     }
     __device__ static void gradient_flux(const Params &m, double *gf, const double *g,
                                          const double *Q, const double *aux, double t)

@@ -135,6 +135,10 @@ const char *cmdg_status_string(int status);
 /* number_states(balance_law, st) for st = Prognostic, Auxiliary, Gradient, GradientFlux,
  * GradientLaplacian, Hyperdiffusive (src/BalanceLaws/state_types.jl:40-108) -> out[6] */
 int cmdg_physics_counts(int32_t physics_id, const int32_t *iparam, int32_t out[6]);
+/* CMDG_PHYSICS_DRY_ATMOS: the constants the library derives on the host from the parameter block
+ * and hands to its kernels (no device needed) -> out[7]: 1 / (40 day), 1 / day, 1 / (4 day),
+ * R_d / cp_d, cp_d / cv_d, (cp_d / cv_d) R_d, R_d / R_d */
+int cmdg_atmos_host_constants(const int32_t *iparam, const double *dparam, double out[7]);
 
 /* ---- lifetime ----------------------------------------------------------------- */
 /* replaces DGModel(...) construction, DGModel.jl:22-65.

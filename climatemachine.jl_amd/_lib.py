@@ -10,7 +10,8 @@ LIB_PATH = os.environ.get("CMDG_LIB", os.path.join(_HERE, "libcmdg.so"))   # CMD
 
 CMDG_K = dict(GRADIENTS=0, DIVGRAD=1, GRADLAP=2, TENDENCY=3, PACK=4, UNPACK=5, UPDATE_AUX=6,
               FILTER=7, STACK_INTEGRAL=8, TRANSPORT=9, HALO_EXPOSED=10, GRADIENTS_EXT=11,
-              DIVGRAD_EXT=12, GRADLAP_EXT=13, TENDENCY_EXT=14, FV_GRADIENTS=15, FV_TENDENCY=16)
+              DIVGRAD_EXT=12, GRADLAP_EXT=13, TENDENCY_EXT=14, FV_GRADIENTS=15, FV_TENDENCY=16,
+              ESDG_TENDENCY=17)
 STACK_MAXOUT = 8
 OPT_KEEP_GRADFLUX = 1
 OPT_STACK_HEIGHT = 2
@@ -130,6 +131,16 @@ class CmdgFvDesc(C.Structure):
 
 
 FV_CONSTANT, FV_LINEAR = 0, 1
+
+
+class CmdgEsdgDesc(C.Structure):
+    """``cmdg_esdg_desc`` of include/cmdg.h."""
+    _fields_ = [("volume_flux", C.c_int32), ("surface_flux", C.c_int32), ("Mcut", C.c_double),
+                ("low_mach", C.c_int32), ("kinetic_energy_preserving", C.c_int32)]
+
+
+(ESDG_FLUX_NONE, ESDG_FLUX_ENTROPY_CONSERVATIVE, ESDG_FLUX_CENTRAL, ESDG_FLUX_KG, ESDG_FLUX_RUSANOV,
+ ESDG_FLUX_ENTROPY_CONSERVATIVE_PENALTY, ESDG_FLUX_MATRIX) = range(7)
 FV_VANLEER, FV_NOLIMITER = 0, 1
 
 
@@ -142,6 +153,8 @@ SYMBOLS = [
     ("cmdg_atmos_host_constants", C.c_int, [_vp, _vp, _vp]),
     ("cmdg_create", C.c_int, [C.POINTER(CmdgDesc), C.POINTER(_vp)]),
     ("cmdg_create_dgfv", C.c_int, [C.POINTER(CmdgDesc), C.POINTER(CmdgFvDesc), C.POINTER(_vp)]),
+    ("cmdg_create_esdg", C.c_int, [C.POINTER(CmdgDesc), C.POINTER(CmdgEsdgDesc), C.POINTER(_vp)]),
+    ("cmdg_esdg_entropy", C.c_int, [_vp, _vp, _vp, _vp]),
     ("cmdg_destroy", C.c_int, [_vp]),
     ("cmdg_last_error", C.c_char_p, [_vp]),
     ("cmdg_rhs", C.c_int, [_vp, _vp, _vp, _d, _d, _d]),

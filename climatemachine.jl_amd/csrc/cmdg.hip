@@ -1130,6 +1130,7 @@ int cmdg_physics_counts(int32_t physics_id, const int32_t *iparam, int32_t out[6
     case CMDG_PHYSICS_OCEAN_SE01:
     case CMDG_PHYSICS_CONTINUITY3D_SE01:
     case CMDG_PHYSICS_BAROTROPIC_SE01: return counts_se01(physics_id, out);
+    case CMDG_PHYSICS_ESDG_DRY_ATMOS: return counts_esdg_dryatmos(iparam, out);
     default: return CMDG_ERR_UNSUPPORTED;
     }
 }
@@ -1140,7 +1141,7 @@ int cmdg_atmos_host_constants(const int32_t *iparam, const double *dparam, doubl
     return host_constants_atmos(iparam, dparam, out);
 }
 
-static int create_handle(const cmdg_desc *d, const cmdg_fv_desc *fv, cmdg_handle *out)
+static int create_handle(const cmdg_desc *d, const cmdg_fv_desc *fv, cmdg_handle *out, const cmdg_esdg_desc *esdg = nullptr)
 {
     *out = nullptr;
     int ndev = 0;
@@ -1166,7 +1167,13 @@ static int create_handle(const cmdg_desc *d, const cmdg_fv_desc *fv, cmdg_handle
     }
     std::string err;
     EngineBase *e = nullptr;
-    if (fv) {
+    if (esdg) {
+        e = make_engine_esdg(d, esdg, err);
+        if (!e) {
+            g_create_err = err;
+            return CMDG_ERR_UNSUPPORTED;
+        }
+    } else if (fv) {
         if (d->physics_id == CMDG_PHYSICS_ADVECTION_DIFFUSION)
             e = make_engine_advdiff_fv(d, fv, err);
         else
@@ -1200,6 +1207,7 @@ static int create_handle(const cmdg_desc *d, const cmdg_fv_desc *fv, cmdg_handle
     }
     int r = e->init(d);
     if (r == CMDG_OK && fv) r = e->init_fv();
+    if (esdg) e->reference_halo = true;  // the face phase reads ghost neighbours from the ghost elements
     if (r != CMDG_OK) {
         g_create_err = e->err;
         delete e;
@@ -1221,6 +1229,12 @@ int cmdg_create(const cmdg_desc *d, cmdg_handle *out)
     if (d->dim == 3 && d->N[2] == 0) {
         *out = nullptr;
         g_create_err = "cmdg_create: N[2] == 0 is a finite-volume vertical: use cmdg_create_dgfv";
+        return CMDG_ERR_INVALID;
+    }
+    if (d->physics_id == CMDG_PHYSICS_ESDG_DRY_ATMOS) {
+        *out = nullptr;
+        g_create_err = "cmdg_create: the DryAtmosModel of the entropy-stable discretisation has no DGModel passes: "
+                       "use cmdg_create_esdg";
         return CMDG_ERR_INVALID;
     }
     return create_handle(d, nullptr, out);
@@ -1254,6 +1268,44 @@ int cmdg_create_dgfv(const cmdg_desc *d, const cmdg_fv_desc *fv, cmdg_handle *ou
     if (d->nreal % fv->nvertelem != 0 || d->nghost % fv->nvertelem != 0)
         return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: element counts are not multiples of nvertelem");
     return create_handle(d, fv, out);
+}
+
+// ESDGModel(balance_law, grid; volume_numerical_flux_first_order, surface_numerical_flux_first_order)
+// ESDGModel.jl:75-94
+int cmdg_create_esdg(const cmdg_desc *d, const cmdg_esdg_desc *ed, cmdg_handle *out)
+{
+    if (!d || !ed || !out) return CMDG_ERR_INVALID;
+    *out = nullptr;
+    auto refuse = [&](int code, const char *msg) {
+        g_create_err = msg;
+        return code;
+    };
+    if (d->physics_id != CMDG_PHYSICS_ESDG_DRY_ATMOS)
+        return refuse(CMDG_ERR_UNSUPPORTED, "cmdg_create_esdg: the two-point fluxes are defined for CMDG_PHYSICS_ESDG_DRY_ATMOS only");
+    if (d->dim != 3)
+        return refuse(CMDG_ERR_UNSUPPORTED, "cmdg_create_esdg: only dim == 3 is compiled in");
+    if (d->N[0] != d->N[1] || d->N[0] != d->N[2])
+        return refuse(CMDG_ERR_UNSUPPORTED, "cmdg_create_esdg: mixed polynomial orders are not compiled in (one order in every direction)");
+    if (d->N[0] != 3 && d->N[0] != 4)
+        return refuse(CMDG_ERR_UNSUPPORTED, "cmdg_create_esdg: the flux-differencing kernel is compiled for polynomial orders 3 and 4");
+    const int vf = ed->volume_flux, sf = ed->surface_flux;
+    if (vf != CMDG_ESDG_FLUX_NONE && vf != CMDG_ESDG_FLUX_ENTROPY_CONSERVATIVE && vf != CMDG_ESDG_FLUX_CENTRAL &&
+        vf != CMDG_ESDG_FLUX_KG)
+        return refuse(CMDG_ERR_INVALID, "cmdg_create_esdg: unknown volume flux");
+    if (sf != CMDG_ESDG_FLUX_NONE && sf != CMDG_ESDG_FLUX_ENTROPY_CONSERVATIVE && sf != CMDG_ESDG_FLUX_RUSANOV &&
+        sf != CMDG_ESDG_FLUX_ENTROPY_CONSERVATIVE_PENALTY && sf != CMDG_ESDG_FLUX_MATRIX)
+        return refuse(CMDG_ERR_INVALID, "cmdg_create_esdg: unknown surface flux");
+    cmdg_desc dd = *d;  // (nf_first, direction: not read by an ESDG handle)
+    dd.nf_first = CMDG_RUSANOV;
+    dd.direction = dd.diffusion_direction = CMDG_EVERY_DIRECTION;
+    return create_handle(&dd, nullptr, out, ed);
+}
+
+int cmdg_esdg_entropy(cmdg_handle h, const double *Q, double *beta, double *eta)
+{
+    if (!h || !Q) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    return set_err(h, h->eng->launch_entropy(Q, beta, eta));
 }
 
 // what a DGFVModel handle adds to init(): exchanges packed / unpacked as the reference does, and
@@ -1371,7 +1423,7 @@ int cmdg_set_option(cmdg_handle h, int32_t option, int32_t value)
     case CMDG_OPT_REFERENCE_HALO:
         if (int r = e->synchronize()) return set_err(h, r);
         e->drop_graph();
-        e->reference_halo = value != 0 || e->fv;
+        e->reference_halo = value != 0 || e->fv || e->esdg;
         e->invalidate_sends();
         return CMDG_OK;
     case CMDG_OPT_STEP_GRAPH:

@@ -64,6 +64,7 @@ int EngineBase::stack_integral(bool reverse, const double *Q, int nstate, double
                                const cmdg_stack_integral_desc *d, int64_t h0, int64_t nh)
 {
     const char *const no_order = "stack integral: polynomial order not compiled in";
+    if (esdg) return fail(CMDG_ERR_UNSUPPORTED, "stack integral: an ESDGModel handle serves no column operators");
     if (!column_orders()) return fail(CMDG_ERR_UNSUPPORTED, no_order);
     if (!stacked) return fail(CMDG_ERR_INVALID, "stack integral: the topology is not stacked");
     if (nvert < 1 || nreal % nvert != 0)
@@ -115,6 +116,8 @@ int EngineBase::set_hooks(const cmdg_rhs_hooks *hk)
             v.erase(std::remove(v.begin(), v.end(), this), v.end());
         }
     };
+    if (hk && esdg)
+        return fail(CMDG_ERR_UNSUPPORTED, "rhs hooks: an ESDGModel handle runs no update_auxiliary_state! composition");
     if (!hk) {
         forget_child();
         has_hooks = false;
@@ -425,6 +428,7 @@ int EngineBase::run_column_ops(const RhsCtx &c, int64_t e0, int64_t e1)
 int EngineBase::filter_create(const cmdg_filter_desc *d, FilterObj **out)
 {
     if (fv) return fail(CMDG_ERR_UNSUPPORTED, "filter: element filters are not defined on a DGFVModel handle (vertical order 0)");
+    if (esdg) return fail(CMDG_ERR_UNSUPPORTED, "filter: an ESDGModel handle applies no element filters");
     if (d->kind < CMDG_FILTER_SPECTRAL || d->kind > CMDG_FILTER_TMAR)
         return fail(CMDG_ERR_INVALID, "filter: unknown kind");
     if (d->target < CMDG_TARGET_INDICES || d->target > CMDG_TARGET_ATMOS_SPECIFIC_PERTURBATIONS)

@@ -266,6 +266,8 @@ int cmdg_columnlu_create(cmdg_handle linear, int32_t nvertelem, double alpha, cm
     tmp.lin = linear;
     if (e->fv)
         return lu_fail(&tmp, CMDG_ERR_UNSUPPORTED, "column LU is not available on a DGFVModel handle (finite-volume vertical)");
+    if (e->esdg)
+        return lu_fail(&tmp, CMDG_ERR_UNSUPPORTED, "column LU is not available on an ESDGModel handle");
     if (e->direction != DIR_VERTICAL || !e->stacked)
         return lu_fail(&tmp, CMDG_ERR_INVALID, "the operator must be a VerticalDirection DG model on a stacked grid");
     if ((e->ns != 5 && e->ns != 6) || e->ngf != 0)

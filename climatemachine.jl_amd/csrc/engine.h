@@ -267,7 +267,11 @@ struct EngineBase {
     // the finite-volume pass.
     bool fv = false;
     int fv_nvert = 0;
-    bool fused_lsrk() const { return tendency_filter == nullptr && !fv; }
+    // an ESDGModel handle (cmdg_create_esdg, engine_esdg.hip): one flux-differencing launch per element
+    // list; like a DGFVModel handle it unpacks its exchange, uses the separate LSRK update and stays
+    // eager
+    bool esdg = false;
+    bool fused_lsrk() const { return tendency_filter == nullptr && !fv && !esdg; }
     int init_fv();
     // the orders the column operators and the filters are compiled for (one order in every direction)
     bool column_orders() const { return NQ >= 2 && NQ <= 8 && NQV == NQ; }
@@ -303,6 +307,11 @@ struct EngineBase {
     // mode 0: per-element minimum node distance, mode 1: per-element maximum Courant number
     virtual int launch_courant(int mode, int kind, const double *Q, double dt, double t, int dir,
                                double *out_elem) = 0;
+    // cmdg_esdg_entropy: entropy variables and entropy of the real elements (ESDG handles)
+    virtual int launch_entropy(const double *, double *, double *)
+    {
+        return fail(CMDG_ERR_UNSUPPORTED, "cmdg_esdg_entropy: not an ESDGModel handle (cmdg_create_esdg)");
+    }
 
     // ---- ghost exchange without pack / unpack launches (HaloDev, cmdg_common.h) -------------
     // tables built at create from vmapsend / vmaprecv / the digested face table; *_ok = they
@@ -757,6 +766,8 @@ int counts_pgrad(const int32_t *iparam, int32_t out[6]);
 EngineBase *make_engine_atmos_linear(const cmdg_desc *d, std::string &err);
 int counts_atmos_linear(const int32_t *iparam, int32_t out[6]);
 EngineBase *make_engine_moist_linear(const cmdg_desc *d, std::string &err);
+EngineBase *make_engine_esdg(const cmdg_desc *d, const cmdg_esdg_desc *ed, std::string &err);
+int counts_esdg_dryatmos(const int32_t *iparam, int32_t out[6]);
 int counts_moist_linear(const int32_t *iparam, int32_t out[6]);
 
 }  // namespace cmdg

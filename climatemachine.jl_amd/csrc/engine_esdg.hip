@@ -1,0 +1,107 @@
+// Engine of an ESDGModel handle (cmdg_create_esdg) and its instantiations for the dry atmosphere of
+// the entropy-stable tests (physics_esdg_dryatmos.h).  The orchestration is EngineBase::rhs_segment
+// unchanged: the law has no gradient, gradient-flux or hyperdiffusive states, so an evaluation is
+// one exchange of Q with the interior element list launched before the ghosts arrive and the
+// exterior list after -- (esdg::ESDGModel)(tendency, Q, _, t, alpha, beta), ESDGModel.jl:110-316,
+// whose volume launches read no ghost and commute with the end of the exchange.  The tendency of
+// either list is the one launch of esdg.h.
+#include "engine.h"
+#include "esdg.h"
+
+namespace cmdg {
+
+template <class P, int NQ_>
+struct EngineESDG : EngineT<P, NQ_, NQ_> {
+    using Base = EngineT<P, NQ_, NQ_>;
+    using Kernel = void (*)(EsdgArgs<P>);
+    cmdg_esdg_desc ed{};
+
+    template <int VF>
+    static Kernel pick_surface(int sf)
+    {
+        switch (sf) {
+        case ESDG_NONE: return k_esdg_tendency<P, NQ_, VF, ESDG_NONE>;
+        case ESDG_EC: return k_esdg_tendency<P, NQ_, VF, ESDG_EC>;
+        case ESDG_RUSANOV: return k_esdg_tendency<P, NQ_, VF, ESDG_RUSANOV>;
+        case ESDG_EC_PENALTY: return k_esdg_tendency<P, NQ_, VF, ESDG_EC_PENALTY>;
+        default: return k_esdg_tendency<P, NQ_, VF, ESDG_MATRIX>;
+        }
+    }
+    Kernel pick() const
+    {
+        switch (ed.volume_flux) {
+        case ESDG_NONE: return pick_surface<ESDG_NONE>(ed.surface_flux);
+        case ESDG_EC: return pick_surface<ESDG_EC>(ed.surface_flux);
+        case ESDG_CENTRAL: return pick_surface<ESDG_CENTRAL>(ed.surface_flux);
+        default: return pick_surface<ESDG_KG>(ed.surface_flux);
+        }
+    }
+    void launch_tendency(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
+    {
+        if (n <= 0) return;
+        Range range_(exterior ? "cmdg:esdg_tendency:exterior" : "cmdg:esdg_tendency");
+        this->prof_begin(CMDG_K_ESDG_TENDENCY, st);
+        EsdgArgs<P> a;
+        a.prm = this->prm;
+        a.g = this->g;
+        a.elems = elems;
+        a.nelems = n;
+        a.Q = c.Qin;
+        a.aux = this->aux;
+        a.naux = this->naux;
+        a.tendency = c.tendency;
+        a.t = c.t;
+        a.alpha = c.alpha;
+        a.beta = c.beta;
+        hipLaunchKernelGGL(pick(), dim3((unsigned)n), dim3(KDims<NQ_, NQ_>::NT), 0, st, a);
+        this->prof_end(st);
+    }
+    int launch_entropy(const double *Q, double *beta, double *eta) override
+    {
+        constexpr int Np = KDims<NQ_, NQ_>::Np;
+        const int64_t n = this->nreal * Np;
+        if (n > 0)
+            hipLaunchKernelGGL((k_esdg_entropy<P, Np>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, this->s_comp,
+                               this->prm, Q, this->aux, this->naux, beta, eta, this->nreal);
+        return this->launch_status("k_esdg_entropy");
+    }
+};
+
+template <class P, int NQ_>
+static EngineBase *make_engine_esdg_t(const cmdg_desc *d, const cmdg_esdg_desc *ed)
+{
+    auto *e = new EngineESDG<P, NQ_>();
+    e->NQ = NQ_;
+    e->NQV = NQ_;
+    e->ns = P::NS;
+    e->naux = P::NAUX + (d->iparam[1] != 0 ? 4 : 0);
+    e->ngrad = e->ngf = e->ngl = e->nhyp = 0;
+    e->esdg = true;
+    e->ed = *ed;
+    P::make_params(e->prm, d->iparam, d->dparam);
+    e->prm.Mcut = ed->Mcut;
+    e->prm.low_mach = ed->low_mach != 0;
+    e->prm.kep = ed->kinetic_energy_preserving != 0;
+    return e;
+}
+
+int counts_esdg_dryatmos(const int32_t *ip, int32_t out[6])
+{
+    out[0] = 5;
+    out[1] = 4 + (ip[1] != 0 ? 4 : 0);
+    out[2] = out[3] = out[4] = out[5] = 0;
+    return CMDG_OK;
+}
+
+EngineBase *make_engine_esdg(const cmdg_desc *d, const cmdg_esdg_desc *ed, std::string &err)
+{
+    switch (d->N[0]) {
+    case 3: return make_engine_esdg_t<EsdgDryAtmos, 4>(d, ed);
+    case 4: return make_engine_esdg_t<EsdgDryAtmos, 5>(d, ed);
+    default:
+        err = "cmdg_create_esdg: the flux-differencing kernel is compiled for polynomial orders 3 and 4";
+        return nullptr;
+    }
+}
+
+}  // namespace cmdg

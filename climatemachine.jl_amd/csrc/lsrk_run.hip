@@ -131,7 +131,7 @@ bool EngineBase::graph_eligible() const
     const bool comm_ok = !exchanges() || (transport == TRANSPORT_RCCL && pipelined());
     // (a DGFVModel handle stays eager: its step has never been recorded and replayed on a device, and
     // nothing asks for it yet)
-    return step_graph && !fv && !graph_failed && !profiling && !step_filter && !tendency_filter &&
+    return step_graph && !fv && !esdg && !graph_failed && !profiling && !step_filter && !tendency_filter &&
            !gradient_filter && !has_hooks && (!has_update_aux() || fused_update_aux()) && comm_ok;
 }
 

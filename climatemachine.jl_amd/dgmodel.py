@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from .balancelaws import EveryDirection, RusanovNumericalFlux
 
-__all__ = ["DGModel", "DGFVModel", "RemainderDGModel", "remainder_DGModel", "connect_local", "group_rhs", "group_lsrk_run", "group_halo",
+__all__ = ["DGModel", "DGFVModel", "ESDGModel", "RemainderDGModel", "remainder_DGModel", "connect_local", "group_rhs", "group_lsrk_run", "group_halo",
            "reference_pressure_gradient", "rccl_unique_id",
            "ADVECTIVE_COURANT", "NONDIFFUSIVE_COURANT", "DIFFUSIVE_COURANT"]
 
@@ -419,6 +419,64 @@ class DGFVModel(DGModel):
         fv.nvertelem, fv.periodicstack = int(t.stacksize), int(bool(t.periodicstack))
         self._fv_desc = fv
         _lib.check(self.L.cmdg_create_dgfv(C.byref(d), C.byref(fv), C.byref(h)))
+
+
+_DEFAULT_FLUX = object()
+
+
+class ESDGModel(DGModel):
+    """``ESDGModel(balance_law, grid; state_auxiliary, volume_numerical_flux_first_order,
+    surface_numerical_flux_first_order)`` (src/Numerics/DGMethods/ESDGModel.jl:47-94): entropy-stable
+    flux-differencing DG for ``esdg.DryAtmosModel``.  The fluxes are objects of ``esdg``
+    (``EntropyConservative()`` by default, ``None`` for the reference's ``nothing``).  Same methods as
+    ``DGModel`` where they apply (``cmdg_create_esdg`` handle), plus ``entropy_variables`` and
+    ``entropy``."""
+
+    def __init__(self, balance_law, grid, volume_numerical_flux_first_order=_DEFAULT_FLUX,
+                 surface_numerical_flux_first_order=_DEFAULT_FLUX, state_auxiliary=None, device="cuda:0"):
+        from . import esdg
+        vf, sf = volume_numerical_flux_first_order, surface_numerical_flux_first_order
+        vf = esdg.EntropyConservative() if vf is _DEFAULT_FLUX else vf
+        sf = esdg.EntropyConservative() if sf is _DEFAULT_FLUX else sf
+        if vf is not None and not getattr(vf, "volume", False):
+            raise _lib.CmdgError("ESDGModel: %s is not a two-point volume flux" % type(vf).__name__)
+        if sf is not None and not getattr(sf, "surface", False):
+            raise _lib.CmdgError("ESDGModel: %s is not a surface flux" % type(sf).__name__)
+        if int(np.max(grid.elemtobndy, initial=0)) > 2:
+            raise _lib.CmdgError("ESDGModel: the DryAtmosModel defines boundary conditions 1 and 2 only")
+        self.volume_numerical_flux_first_order, self.surface_numerical_flux_first_order = vf, sf
+        super().__init__(balance_law, grid, numerical_flux_first_order=RusanovNumericalFlux,
+                         direction=EveryDirection, device=device, state_auxiliary=state_auxiliary)
+
+    def _create(self, d, h):
+        vf, sf = self.volume_numerical_flux_first_order, self.surface_numerical_flux_first_order
+        ed = _lib.CmdgEsdgDesc()
+        ed.volume_flux = int(vf.flux_id) if vf is not None else _lib.ESDG_FLUX_NONE
+        ed.surface_flux = int(sf.flux_id) if sf is not None else _lib.ESDG_FLUX_NONE
+        if sf is not None:
+            ed.Mcut, ed.low_mach = float(sf.Mcut), int(sf.low_mach)
+            ed.kinetic_energy_preserving = int(sf.kinetic_energy_preserving)
+        self._esdg_desc = ed
+        _lib.check(self.L.cmdg_create_esdg(C.byref(d), C.byref(ed), C.byref(h)))
+
+    def _entropy(self, Q, want_beta, want_eta):
+        g = self.grid
+        beta = torch.zeros((g.nelem, self.balance_law.nentropy, g.Np), dtype=torch.float64,
+                           device=self.device) if want_beta else None
+        eta = torch.zeros((g.nelem, 1, g.Np), dtype=torch.float64, device=self.device) if want_eta else None
+        self._torch_ready()
+        _lib.check(self.L.cmdg_esdg_entropy(self.handle, Q.data_ptr(), beta.data_ptr() if want_beta else None,
+                                            eta.data_ptr() if want_eta else None), self.handle)
+        self.synchronize()
+        return beta, eta
+
+    def entropy_variables(self, Q):
+        """``state_to_entropy_variables!`` at every node of the real elements: ``(nelem, 6, Np)``."""
+        return self._entropy(Q, True, False)[0]
+
+    def entropy(self, Q):
+        """``state_to_entropy`` at every node of the real elements: ``(nelem, 1, Np)``."""
+        return self._entropy(Q, False, True)[1]
 
 
 class RemainderDGModel:

@@ -77,7 +77,10 @@ enum {
     /* AtmosAcousticGravityLinearModel of the moist AtmosModel (EquilMoist, linear.jl:57-72): six
      * states, on the full CMDG_PHYSICS_MOIST_ATMOS model's parameter block and 19-column
      * auxiliary array; N = 4, 6; Rusanov or central first-order flux */
-    CMDG_PHYSICS_MOIST_LINEAR_AG = 11
+    CMDG_PHYSICS_MOIST_LINEAR_AG = 11,
+    /* DryAtmosModel of the entropy-stable discretisation (test/Numerics/ESDGMethods/DryAtmos/
+     * DryAtmos.jl, total_energy = false, fluctuation_gravity = false): cmdg_create_esdg only */
+    CMDG_PHYSICS_ESDG_DRY_ATMOS = 12
 };
 
 /* Construction record: the fields of `DGModel(balance_law, grid, nf1, nf2, nfgrad;
@@ -180,6 +183,42 @@ typedef struct cmdg_fv_desc {
  * handle element filters, cmdg_courant, cmdg_min_node_distance and cmdg_columnlu_create are refused
  * with CMDG_ERR_UNSUPPORTED. */
 int cmdg_create_dgfv(const cmdg_desc *desc, const cmdg_fv_desc *fv, cmdg_handle *out);
+
+/* Two-point fluxes of an ESDGModel (DryAtmos.jl:411-539, :564-745; NumericalFluxes.jl:540-581).
+ * Volume: NONE, ENTROPY_CONSERVATIVE, CENTRAL, KG.  Surface: NONE, ENTROPY_CONSERVATIVE, RUSANOV,
+ * ENTROPY_CONSERVATIVE_PENALTY, MATRIX. */
+enum {
+    CMDG_ESDG_FLUX_NONE = 0, CMDG_ESDG_FLUX_ENTROPY_CONSERVATIVE = 1, CMDG_ESDG_FLUX_CENTRAL = 2,
+    CMDG_ESDG_FLUX_KG = 3, CMDG_ESDG_FLUX_RUSANOV = 4, CMDG_ESDG_FLUX_ENTROPY_CONSERVATIVE_PENALTY = 5,
+    CMDG_ESDG_FLUX_MATRIX = 6
+};
+typedef struct cmdg_esdg_desc {
+    int32_t volume_flux;  /* CMDG_ESDG_FLUX_* */
+    int32_t surface_flux; /* CMDG_ESDG_FLUX_* */
+    double Mcut;          /* MatrixFlux(Mcut, low_mach, kinetic_energy_preserving) */
+    int32_t low_mach;
+    int32_t kinetic_energy_preserving;
+} cmdg_esdg_desc;
+/* replaces ESDGModel(balance_law, grid; state_auxiliary, volume_numerical_flux_first_order,
+ * surface_numerical_flux_first_order) construction, src/Numerics/DGMethods/ESDGModel.jl:75-94:
+ * entropy-stable flux-differencing DG.  The handle serves cmdg_rhs, cmdg_lsrk_step / _run / _update,
+ * cmdg_ssprk_step, cmdg_ls3n_step, the reductions, the halo and the group calls like any other;
+ * its evaluations follow (esdg::ESDGModel)(tendency, Q, _, t, alpha, beta), ESDGModel.jl:110-316:
+ * one exchange of Q, no gradient passes.  desc->nf_first, direction and diffusion_direction are
+ * not read; CMDG_OPT_STEP_GRAPH is accepted and has no effect (the handle stays eager), exchanges
+ * are always unpacked (CMDG_OPT_REFERENCE_HALO).
+ * Refused with a message in cmdg_last_error(NULL) -- CMDG_ERR_UNSUPPORTED: a law other than
+ * CMDG_PHYSICS_ESDG_DRY_ATMOS, an order outside {3, 4} or mixed orders, dim == 2;
+ * CMDG_ERR_INVALID: an unknown flux id (and cmdg_create with this physics id).  On such a handle
+ * element filters, cmdg_set_rhs_hooks, the stack integrals and cmdg_columnlu_create are refused
+ * with CMDG_ERR_UNSUPPORTED. */
+int cmdg_create_esdg(const cmdg_desc *desc, const cmdg_esdg_desc *esdg, cmdg_handle *out);
+/* state_to_entropy_variables! and state_to_entropy (DryAtmos.jl:339-363, :401-409) of every node of
+ * the real elements of Q, on the handle's compute stream (follow with cmdg_synchronize, or with a
+ * reduction of the same handle): beta (Np, 6, nelem) and eta (Np, 1, nelem) device arrays, either
+ * may be NULL; ghost elements are not written.  CMDG_ERR_UNSUPPORTED on a handle that is not an
+ * ESDGModel's. */
+int cmdg_esdg_entropy(cmdg_handle h, const double *Q, double *beta, double *eta);
 
 /* Balance laws / template combinations outside the compiled set.  In the reference a law's
  * pointwise functions are compiled into the kernels when the model first runs
@@ -782,7 +821,9 @@ enum {
     CMDG_K_GRADIENTS_EXT = 11, CMDG_K_DIVGRAD_EXT = 12, CMDG_K_GRADLAP_EXT = 13,
     CMDG_K_TENDENCY_EXT = 14,
     /* the vertical finite-volume passes of a DGFVModel handle (interior and exterior launches) */
-    CMDG_K_FV_GRADIENTS = 15, CMDG_K_FV_TENDENCY = 16, CMDG_K_COUNT = 17
+    CMDG_K_FV_GRADIENTS = 15, CMDG_K_FV_TENDENCY = 16,
+    /* the flux-differencing launch of an ESDGModel handle (interior and exterior launches) */
+    CMDG_K_ESDG_TENDENCY = 17, CMDG_K_COUNT = 18
 };
 /* bracket every launch with HIP events on the launch stream (off by default) */
 int cmdg_profile_enable(cmdg_handle h, int32_t on);

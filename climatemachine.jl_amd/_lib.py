@@ -114,6 +114,15 @@ class CmdgMrigarkDesc(C.Structure):
                 ("fast_dt", C.c_double), ("lu_adjustable", C.c_int32)]
 
 
+GMRES_MAX_M = 64
+
+
+class CmdgGmresInfo(C.Structure):
+    """``cmdg_gmres_info`` of include/cmdg.h."""
+    _fields_ = [("iterations", C.c_int64), ("converged", C.c_int32), ("residual_norm", C.c_double),
+                ("threshold", C.c_double)]
+
+
 RED_WEIGHTEDSUM, RED_SUM, RED_DOT, RED_DISTANCE, RED_NORM, RED_MAX, RED_MIN = range(7)
 
 
@@ -222,6 +231,14 @@ SYMBOLS = [
     ("cmdg_mri_lsrk_update", C.c_int, [_vp, _vp, _vp, _d, _d, _i32, _vp, _vp]),
     ("cmdg_mri_qhat", C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp]),
     ("cmdg_mrigark_step", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d]),
+    ("cmdg_gmres_create", C.c_int, [_vp, _i32, _d, _d, C.POINTER(_vp)]),
+    ("cmdg_gmres_fits", C.c_int, [_vp, _i32, _i64, _vp]),
+    ("cmdg_gmres_prepare", C.c_int, [_vp, _d]),
+    ("cmdg_gmres_solve", C.c_int, [_vp, _d, _vp, _vp, _d, _i64, C.POINTER(CmdgGmresInfo)]),
+    ("cmdg_gmres_step_info", C.c_int, [_vp, _i32, _vp, _vp]),
+    ("cmdg_gmres_destroy", C.c_int, [_vp]),
+    ("cmdg_ark_step_gmres", C.c_int, [_vp, _vp, _vp, _vp, _d, _d, _i32, _vp, _vp, _vp, _vp, _i32]),
+    ("cmdg_mrigark_step_gmres", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d]),
     ("cmdg_interp_create", C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     ("cmdg_interp_destroy", C.c_int, [_vp, _vp]),
     ("cmdg_interp_apply", C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp]),

@@ -25,12 +25,14 @@ grad^3 h_tot (3)``.
 """
 import numpy as np
 
-from .balancelaws import PHYSICS_ATMOS_LINEAR_AG, PHYSICS_DRY_ATMOS, PHYSICS_MOIST_ATMOS, PHYSICS_MOIST_LINEAR_AG
+from .balancelaws import (PHYSICS_ATMOS_LINEAR_ACOUSTIC, PHYSICS_ATMOS_LINEAR_AG, PHYSICS_DRY_ATMOS,
+                          PHYSICS_MOIST_ATMOS, PHYSICS_MOIST_LINEAR_AG)
 from .mesh import grids as G
 
 __all__ = ["PlanetParameters", "DryAtmosModel", "IsentropicVortexSetup", "HeldSuarezSetup",
            "DecayingTemperatureProfile", "DryAdiabaticProfile", "RisingBubbleSetup",
-           "CourantTestSetup", "MMSSetup", "IsothermalProfile", "AtmosAcousticGravityLinearModel"]
+           "CourantTestSetup", "MMSSetup", "IsothermalProfile", "AtmosAcousticGravityLinearModel",
+           "IsentropicVortexReferenceState", "AtmosAcousticLinearModel"]
 
 
 class PlanetParameters:
@@ -170,6 +172,24 @@ class IsentropicVortexSetup:
         return rho, [rho * u[0], rho * u[1], rho * u[2]], rhoe
 
 
+class IsentropicVortexReferenceState:
+    """``IsentropicVortexReferenceState(setup)`` (isentropicvortex_setup.jl:64-100): the constant
+    far field ``rho_inf, p_inf, T_inf, rho_inf cv_d (T_inf - T_0)`` in the reference-state columns.
+    It is not a ``HydrostaticState``: the full law carries it and subtracts nothing
+    (tendencies_momentum.jl), so ``DryAtmosModel`` turns ``subtract_off`` off for it; its user is the
+    linear model (``AtmosAcousticLinearModel``)."""
+
+    def __init__(self, setup):
+        self.setup = setup
+
+    def fill(self, ps, aux, off_ref):
+        s = self.setup
+        aux[:, off_ref + 0, :] = s.rho_inf
+        aux[:, off_ref + 1, :] = s.p_inf
+        aux[:, off_ref + 2, :] = s.T_inf
+        aux[:, off_ref + 3, :] = s.rho_inf * (ps.cv_d * (s.T_inf - ps.T_0))   # internal_energy(T_inf)
+
+
 class MMSSetup:
     """``mms3_init_state!`` of test/Numerics/DGMethods/compressible_Navier_Stokes/
     mms_bc_atmos.jl:88-97: the manufactured solution (generating script mms_solution.jl:10-25)
@@ -279,7 +299,10 @@ class DryAtmosModel:
         self.init_state = init_state
         self.orientation = orientation
         self.ref_state = ref_state
-        self.subtract_off = bool(subtract_off)
+        # only a HydrostaticState is subtracted (tendencies_momentum.jl)
+        self.subtract_off = bool(subtract_off) and not isinstance(ref_state, IsentropicVortexReferenceState)
+        if orientation == ORIENT_NONE and ref_state is not None and self.subtract_off:
+            raise ValueError("DryAtmosModel: a hydrostatic reference state needs an orientation")
         self.viscosity, self.dynamic_viscosity = float(viscosity), bool(dynamic_viscosity)
         self.tau_hyper = hyperdiffusion_timescale
         self.sources = int(sources)
@@ -347,7 +370,9 @@ class DryAtmosModel:
             # auxiliary_field_gradient!: element-local strong gradient
             # (dgsem_auxiliary_field_gradient!, DGModel_kernels.jl:3097-3232)
             aux[:, self.off_phi + 1:self.off_phi + 4, :] = G.auxiliary_field_gradient(grid, phi)
-        if self.ref_state is not None:
+        if isinstance(self.ref_state, IsentropicVortexReferenceState):
+            self.ref_state.fill(ps, aux, self.off_ref)
+        elif self.ref_state is not None:
             # ref_state_init_p_rho! and ref_state_finalize_init! (ref_state.jl:70-140).  The
             # reference additionally re-derives rho from a DG gradient of p (discrete
             # hydrostatic balance, :150-175); the synthetic state here keeps the analytic
@@ -465,3 +490,32 @@ class AtmosAcousticGravityLinearModel:
 
     def init_state_prognostic(self, grid, aux, t):
         return np.zeros((grid.nelem, self.ns, grid.Np))
+
+
+class AtmosAcousticLinearModel(AtmosAcousticGravityLinearModel):
+    """``AtmosAcousticLinearModel(atmos)`` (src/Atmos/Model/linear.jl:214-245,
+    linear_tendencies.jl:55-60) of a dry ``DryAtmosModel`` with ``ORIENT_NONE`` and a reference state
+    (the isentropic vortex's): the acoustic-gravity model's fluxes with ``e_pot = 0`` -- ``rho u``,
+    ``p_lin I`` with ``p_lin = rho R_d T_0 + R_d / cv_d rho e`` and ``((rho e_ref + p_ref) / rho_ref)
+    rho u`` -- and no source.  It reads the full model's auxiliary state (reference state at
+    ``off_ref = 3``) and works in any direction.  Device functor: csrc/physics_atmos_linear.h with
+    ``ORIENT = false``, N = 4."""
+    physics_id = PHYSICS_ATMOS_LINEAR_ACOUSTIC
+
+    def __init__(self, atmos):
+        if atmos.physics_id != PHYSICS_DRY_ATMOS:
+            raise ValueError("AtmosAcousticLinearModel: only the dry model is implemented (the moist "
+                             "acoustic law is not)")
+        if atmos.ref_state is None:
+            raise ValueError("AtmosAcousticLinearModel needs a model with a reference state")
+        if atmos.orientation != ORIENT_NONE:
+            raise ValueError("AtmosAcousticLinearModel is implemented for ORIENT_NONE (e_pot = 0); with an "
+                             "orientation use AtmosAcousticGravityLinearModel")
+        if atmos.tau_hyper is not None or atmos.C_smag is not None:
+            raise ValueError("AtmosAcousticLinearModel: the full model's auxiliary layout must be "
+                             "coordinates, reference state, moisture (no hyperdiffusion, no Smagorinsky)")
+        self.atmos = atmos
+        self.ps = atmos.ps
+        self.off_phi, self.off_ref = atmos.off_phi, atmos.off_ref
+        self.ns, self.naux = 5, atmos.naux
+        self.ngrad = self.ngradflux = self.ngradlap = self.nhyper = 0

@@ -31,6 +31,7 @@ PHYSICS_SHALLOW_WATER = 5
 PHYSICS_MOIST_ATMOS = 6
 PHYSICS_ATMOS_LINEAR_AG = 10
 PHYSICS_MOIST_LINEAR_AG = 11
+PHYSICS_ATMOS_LINEAR_ACOUSTIC = 13
 
 __all__ = [
     "EveryDirection", "HorizontalDirection", "VerticalDirection",

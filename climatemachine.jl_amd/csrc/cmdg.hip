@@ -1127,6 +1127,7 @@ int cmdg_physics_counts(int32_t physics_id, const int32_t *iparam, int32_t out[6
     case CMDG_PHYSICS_MOIST_ATMOS: return counts_moist(iparam, out);
     case CMDG_PHYSICS_ATMOS_LINEAR_AG: return counts_atmos_linear(iparam, out);
     case CMDG_PHYSICS_MOIST_LINEAR_AG: return counts_moist_linear(iparam, out);
+    case CMDG_PHYSICS_ATMOS_LINEAR_ACOUSTIC: return counts_atmos_acoustic(iparam, out);
     case CMDG_PHYSICS_OCEAN_SE01:
     case CMDG_PHYSICS_CONTINUITY3D_SE01:
     case CMDG_PHYSICS_BAROTROPIC_SE01: return counts_se01(physics_id, out);
@@ -1192,6 +1193,7 @@ static int create_handle(const cmdg_desc *d, const cmdg_fv_desc *fv, cmdg_handle
     case CMDG_PHYSICS_MOIST_ATMOS: e = make_engine_moist(d, err); break;
     case CMDG_PHYSICS_ATMOS_LINEAR_AG: e = make_engine_atmos_linear(d, err); break;
     case CMDG_PHYSICS_MOIST_LINEAR_AG: e = make_engine_moist_linear(d, err); break;
+    case CMDG_PHYSICS_ATMOS_LINEAR_ACOUSTIC: e = make_engine_atmos_acoustic(d, err); break;
     case CMDG_PHYSICS_OCEAN_SE01:
     case CMDG_PHYSICS_CONTINUITY3D_SE01:
     case CMDG_PHYSICS_BAROTROPIC_SE01: e = make_engine_se01(d, err); break;

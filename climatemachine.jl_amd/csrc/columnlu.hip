@@ -148,14 +148,17 @@ __global__ void __launch_bounds__(64) k_band_solve(double *X, const double *B, c
 
 using namespace cmdg;
 
-struct cmdg_columnlu {
-    cmdg_handle lin = nullptr;
+struct cmdg_columnlu : cmdg::BackwardEuler {
     int dev = 0;  // the linear handle's device (destroy does not need the handle any more)
     int nvert = 0, nqh2 = 0, nqv = 0, ns = 0, p = 0, q = 0, P = 0;
     int64_t ncol = 0, n = 0;
-    double alpha = 0;
+    double alpha_lu = 0;
     int state = 0;  // 0 empty, 1 assembled (I - alpha L), 2 factored
     DevBuf<double> band, probe, dprobe;
+    // stepping.h: enqueued on the linear handle's stream, errors also on its engine
+    double alpha() const override { return state == 2 ? alpha_lu : NAN; }  // NaN while the band is not factored
+    int ready(double a) override;
+    int solve(double *X, const double *B, double t) override;
 };
 
 namespace {
@@ -196,7 +199,7 @@ int assemble(cmdg_columnlu *lu, double alpha)
                                    lu->probe, lu->dprobe, e->nreal, e->Np, NS, lu->nqh2, lu->nqv, lu->nvert,
                                    k, s, ev0, lu->p, lu->q, lu->ncol, -alpha);
             }
-    lu->alpha = alpha;
+    lu->alpha_lu = alpha;
     lu->state = 1;
     return hip_ok(lu, hipGetLastError(), "assembly kernels");
 }
@@ -236,22 +239,21 @@ int solve(cmdg_columnlu *lu, double *X, const double *B)
 
 }  // namespace
 
+int cmdg_columnlu::ready(double a)
+{
+    const int r = update(this, a);
+    if (r) lin->eng->err = lin->err;
+    return r;
+}
+int cmdg_columnlu::solve(double *X, const double *B, double)
+{
+    const int r = ::solve(this, X, B);
+    if (r) lin->eng->err = lin->err;
+    return r;
+}
+
 namespace cmdg {
-// stepping.h: enqueued on the linear handle's stream, errors also on its engine
-cmdg_handle columnlu_linear(cmdg_columnlu_handle lu) { return lu->lin; }
-double columnlu_alpha(cmdg_columnlu_handle lu) { return lu->state == 2 ? lu->alpha : NAN; }
-int columnlu_refactor_async(cmdg_columnlu_handle lu, double alpha)
-{
-    const int r = update(lu, alpha);
-    if (r) lu->lin->eng->err = lu->lin->err;
-    return r;
-}
-int columnlu_solve_async(cmdg_columnlu_handle lu, double *X, const double *B)
-{
-    const int r = solve(lu, X, B);
-    if (r) lu->lin->eng->err = lu->lin->err;
-    return r;
-}
+BackwardEuler *columnlu_solver(cmdg_columnlu_handle lu) { return lu; }
 }  // namespace cmdg
 
 extern "C" {
@@ -371,7 +373,7 @@ int cmdg_columnlu_info(cmdg_columnlu_handle lu, int64_t out[8])
 int cmdg_columnlu_alpha(cmdg_columnlu_handle lu, double *alpha)
 {
     if (!lu || !alpha) return CMDG_ERR_INVALID;
-    *alpha = lu->alpha;
+    *alpha = lu->alpha_lu;
     return CMDG_OK;
 }
 

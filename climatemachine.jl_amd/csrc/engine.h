@@ -766,6 +766,8 @@ int counts_pgrad(const int32_t *iparam, int32_t out[6]);
 EngineBase *make_engine_atmos_linear(const cmdg_desc *d, std::string &err);
 int counts_atmos_linear(const int32_t *iparam, int32_t out[6]);
 EngineBase *make_engine_moist_linear(const cmdg_desc *d, std::string &err);
+EngineBase *make_engine_atmos_acoustic(const cmdg_desc *d, std::string &err);
+int counts_atmos_acoustic(const int32_t *iparam, int32_t out[6]);
 EngineBase *make_engine_esdg(const cmdg_desc *d, const cmdg_esdg_desc *ed, std::string &err);
 int counts_esdg_dryatmos(const int32_t *iparam, int32_t out[6]);
 int counts_moist_linear(const int32_t *iparam, int32_t out[6]);

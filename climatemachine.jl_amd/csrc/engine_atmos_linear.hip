@@ -55,6 +55,26 @@ EngineBase *make_engine_atmos_linear(const cmdg_desc *d, std::string &err)
     }
 }
 
+int counts_atmos_acoustic(const int32_t *ip, int32_t out[6]) { return counts_atmos_linear(ip, out); }
+
+EngineBase *make_engine_atmos_acoustic(const cmdg_desc *d, std::string &err)
+{
+    if (d->iparam[0] != 0 || d->iparam[1] == 0 || d->iparam[4] != 0 || d->iparam[14] != 0) {
+        err = "AtmosAcousticLinearModel is compiled for a dry model with NoOrientation and a reference state "
+              "(no hyperdiffusion, constant viscosity)";
+        return nullptr;
+    }
+    if (d->nf_first != CMDG_RUSANOV && d->nf_first != CMDG_CENTRAL_FIRST_ORDER) {
+        err = "AtmosAcousticLinearModel: Rusanov or central first-order flux only";
+        return nullptr;
+    }
+    if (d->N[0] != 4) {
+        err = "AtmosAcousticLinearModel: polynomial order not compiled in (have N = 4)";
+        return nullptr;
+    }
+    return make_engine<AtmosLinearAG<12, false, false>, 5>(d);
+}
+
 int counts_moist_linear(const int32_t *, int32_t out[6])
 {
     out[0] = 6;

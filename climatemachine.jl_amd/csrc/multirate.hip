@@ -99,7 +99,7 @@ int low_level_args(cmdg_handle h, double *out, const double *Q, int nR, const do
     return CMDG_OK;
 }
 
-int step(const Op &slow, const Op &fast, cmdg_columnlu_handle lu, const cmdg_mrigark_desc *d, double *Q,
+int step(const Op &slow, const Op &fast, BackwardEuler *be, const cmdg_mrigark_desc *d, double *Q,
          double *const *work, double t, double dt)
 {
     EngineBase *es = slow.h->eng, *ef = fast.h->eng;
@@ -112,7 +112,7 @@ int step(const Op &slow, const Op &fast, cmdg_columnlu_handle lu, const cmdg_mri
     double *dQ = work[ns], *Qhat = work[ns + 1];
     Chain ch(es, "mrigark");
     if (int r = ch.create()) return r;
-    EngineBase *elu = implicit ? columnlu_linear(lu)->eng : nullptr;
+    EngineBase *elu = implicit ? be->lin->eng : nullptr;
     MriArgs a{};
     a.out = dQ;
     a.Q = Q;
@@ -170,18 +170,19 @@ int step(const Op &slow, const Op &fast, cmdg_columnlu_handle lu, const cmdg_mri
             if (int r = ch.to(elu->s_comp)) return r;
             if (int r = launch_qhat(elu, qa, s + 1)) return r;
             const double alpha = dt * G(0, 2 * s + 1, s + 1);
-            if (alpha != columnlu_alpha(lu)) {
+            if (alpha != be->alpha()) {
                 if (!d->lu_adjustable) {
                     char msg[224];
                     snprintf(msg, sizeof msg,
                              "mrigark: the column solver is not adjustable (isadjustable = false) and was "
                              "factored for alpha = %.17g; stage %d needs alpha = dt Gamma = %.17g",
-                             columnlu_alpha(lu), s + 1, alpha);
+                             be->alpha(), s + 1, alpha);
                     return elu->fail(CMDG_ERR_INVALID, msg);
                 }
-                if (int r = columnlu_refactor_async(lu, alpha)) return r;
+                if (int r = be->ready(alpha)) return r;
             }
-            if (int r = columnlu_solve_async(lu, Q, Qhat)) return r;
+            // besolver!(Q, Qhat, alpha, param, stage_end_time): Q is an iterative solver's initial guess
+            if (int r = be->solve(Q, Qhat, stage_end)) return r;
         }
         if (int r = ef->launch_status("mrigark kernels")) return r;
         ts += dts;
@@ -190,7 +191,7 @@ int step(const Op &slow, const Op &fast, cmdg_columnlu_handle lu, const cmdg_mri
     return CMDG_OK;
 }
 
-int check_desc(cmdg_handle slow, cmdg_handle fast, cmdg_columnlu_handle lu, const cmdg_mrigark_desc *d,
+int check_desc(cmdg_handle slow, cmdg_handle fast, BackwardEuler *lu, const cmdg_mrigark_desc *d,
                double *const *work, double dt)
 {
     EngineBase *es = slow->eng, *ef = fast->eng;
@@ -220,13 +221,37 @@ int check_desc(cmdg_handle slow, cmdg_handle fast, cmdg_columnlu_handle lu, cons
     if (implicit) {
         if (!lu) return es->fail(CMDG_ERR_INVALID, "mrigark: the decoupled-implicit kind needs the column solver");
         if (!work[d->nstages + 1]) return es->fail(CMDG_ERR_INVALID, "mrigark: work array Qhat is NULL");
-        if (columnlu_linear(lu) != slow)
+        if (lu->lin != slow)
             return es->fail(CMDG_ERR_INVALID,
                             "mrigark: the decoupled-implicit slow operator must be the column solver's linear model");
     } else if (lu) {
         return es->fail(CMDG_ERR_INVALID, "mrigark: the explicit kind takes no column solver");
     }
     return CMDG_OK;
+}
+
+// the step behind cmdg_mrigark_step and cmdg_mrigark_step_gmres
+int mrigark_step(cmdg_handle slow, cmdg_handle slow_minus, cmdg_handle fast, cmdg_handle fast_minus,
+                 BackwardEuler *be, const cmdg_mrigark_desc *d, double *Q, double *const *work, double t, double dt)
+{
+    if (!slow || !fast || !d || !Q) return CMDG_ERR_INVALID;
+    std::vector<std::pair<cmdg_handle, std::string>> named{{slow, "slow"}};
+    if (slow_minus) named.push_back({slow_minus, "slow minus"});
+    named.push_back({fast, "fast"});
+    if (fast_minus) named.push_back({fast_minus, "fast minus"});
+    GroupCall gc(named);
+    if (!gc.ok()) return CMDG_ERR_INVALID;
+    EngineBase *es = slow->eng;
+    if (slow_minus)
+        if (int r = check_same_grid("mrigark", es, slow_minus->eng, "subtracted slow")) return gc.finish(r);
+    if (int r = check_same_grid("mrigark", es, fast->eng, "fast")) return gc.finish(r);
+    if (fast_minus)
+        if (int r = check_same_grid("mrigark", es, fast_minus->eng, "subtracted fast")) return gc.finish(r);
+    if (int r = check_desc(slow, fast, be, d, work, dt)) return gc.finish(r);
+    if (be && slow_minus)
+        return gc.finish(es->fail(CMDG_ERR_INVALID,
+                                  "mrigark: the decoupled-implicit slow operator cannot be a remainder"));
+    return gc.finish(step(Op{slow, slow_minus}, Op{fast, fast_minus}, be, d, Q, work, t, dt));
 }
 
 }  // namespace
@@ -261,24 +286,15 @@ int cmdg_mrigark_step(cmdg_handle slow, cmdg_handle slow_minus, cmdg_handle fast
                       cmdg_columnlu_handle lu, const cmdg_mrigark_desc *d, double *Q, double *const *work,
                       double t, double dt)
 {
-    if (!slow || !fast || !d || !Q) return CMDG_ERR_INVALID;
-    std::vector<std::pair<cmdg_handle, std::string>> named{{slow, "slow"}};
-    if (slow_minus) named.push_back({slow_minus, "slow minus"});
-    named.push_back({fast, "fast"});
-    if (fast_minus) named.push_back({fast_minus, "fast minus"});
-    GroupCall gc(named);
-    if (!gc.ok()) return CMDG_ERR_INVALID;
-    EngineBase *es = slow->eng;
-    if (slow_minus)
-        if (int r = check_same_grid("mrigark", es, slow_minus->eng, "subtracted slow")) return gc.finish(r);
-    if (int r = check_same_grid("mrigark", es, fast->eng, "fast")) return gc.finish(r);
-    if (fast_minus)
-        if (int r = check_same_grid("mrigark", es, fast_minus->eng, "subtracted fast")) return gc.finish(r);
-    if (int r = check_desc(slow, fast, lu, d, work, dt)) return gc.finish(r);
-    if (lu && slow_minus)
-        return gc.finish(es->fail(CMDG_ERR_INVALID,
-                                  "mrigark: the decoupled-implicit slow operator cannot be a remainder"));
-    return gc.finish(step(Op{slow, slow_minus}, Op{fast, fast_minus}, lu, d, Q, work, t, dt));
+    return mrigark_step(slow, slow_minus, fast, fast_minus, lu ? columnlu_solver(lu) : nullptr, d, Q, work, t, dt);
+}
+
+int cmdg_mrigark_step_gmres(cmdg_handle slow, cmdg_handle slow_minus, cmdg_handle fast, cmdg_handle fast_minus,
+                            cmdg_gmres_handle gmres, const cmdg_mrigark_desc *d, double *Q, double *const *work,
+                            double t, double dt)
+{
+    if (!gmres) return CMDG_ERR_INVALID;
+    return mrigark_step(slow, slow_minus, fast, fast_minus, gmres_solver(gmres), d, Q, work, t, dt);
 }
 
 }  // extern "C"

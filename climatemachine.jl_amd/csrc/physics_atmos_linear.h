@@ -17,6 +17,10 @@
 // 34) and enters only p_lin.  Boundaries: every tag is AtmosBC() (Impenetrable FreeSlip,
 // Insulating; the plus side's rho q_tot is the minus side's), boundary_conditions(
 // ::AtmosLinearModel) at linear.jl:215-216.
+//
+// ORIENT = false: AtmosAcousticLinearModel (linear.jl:214-245, linear_tendencies.jl:55-60) of a dry
+// model with NoOrientation(): no Phi columns (the reference state follows the coordinates), e_pot = 0
+// in p_lin and in the energy flux ((ref.rho e + ref.p) / ref.rho - e_pot) rho u, no source.
 #pragma once
 #include "cmdg_common.h"
 
@@ -27,19 +31,23 @@ struct AtmosLinearParams {
     double e_int_v0, e_int_i0;  // EquilMoist only
 };
 
-template <int NAUX_FULL, bool MOIST = false>
+template <int NAUX_FULL, bool MOIST = false, bool ORIENT = true>
 struct AtmosLinearAG {
+    static_assert(ORIENT || !MOIST, "the moist acoustic law is not laid out");
     using Params = AtmosLinearParams;
     // auxiliary layout of DryAtmos with orientation and reference state (physics_atmos.h), which
     // MoistAtmos keeps in its first 15 columns (physics_moist.h)
-    static constexpr int OPHI = 3, OREF = 7;
+    static constexpr int OPHI = 3, OREF = ORIENT ? 7 : 3;
     static constexpr int NS = MOIST ? 6 : 5, NAUX = NAUX_FULL, NGRAD = 0, NGF = 0, NGL = 0, NHYP = 0;
-    static constexpr bool HAS_UPDATE_AUX = false, FUSE_UPDATE_AUX = false, HAS_SOURCE = true;
+    static constexpr bool HAS_UPDATE_AUX = false, FUSE_UPDATE_AUX = false, HAS_SOURCE = ORIENT;
     static constexpr bool HAS_COURANT = false, HAS_PENALTY = false;
     static constexpr int NUPD = 0, NDER = 0;
     // faces read Phi and the reference rho, p, T, rho e
-    static constexpr int NFAUX = 5;
-    __host__ __device__ static constexpr int face_aux(int i) { return i == 0 ? OPHI : OREF + (i - 1); }
+    static constexpr int NFAUX = ORIENT ? 5 : 4;
+    __host__ __device__ static constexpr int face_aux(int i)
+    {
+        return ORIENT ? (i == 0 ? OPHI : OREF + (i - 1)) : OREF + i;
+    }
     __host__ __device__ static constexpr int upd_aux(int) { return 0; }
     __host__ __device__ static constexpr int hv_indexmap(int) { return 0; }
     __host__ __device__ static bool needs_gradflux(const Params &) { return false; }
@@ -57,6 +65,7 @@ struct AtmosLinearAG {
     // (:57-72) passes rho q_tot, with rho q_liq = rho q_ice = 0 kept in the reference's order
     __device__ static double p_lin(const Params &m, const double *Q, const double *aux)
     {
+        if constexpr (!ORIENT) return Q[0] * m.R_d * m.T_0 + m.R_d / m.cv_d * Q[4];
         const double rhoe_pot = Q[0] * aux[OPHI];
         if constexpr (MOIST)
             return Q[0] * m.R_d * m.T_0 +
@@ -96,7 +105,8 @@ struct AtmosLinearAG {
         S[4] = 0;
         if constexpr (MOIST) S[5] = 0;
 #pragma unroll
-        for (int d = 0; d < 3; ++d) S[1 + d] = direction == DIR_HORIZONTAL ? 0.0 : -Q[0] * aux[OPHI + 1 + d];
+        for (int d = 0; d < 3; ++d)
+            S[1 + d] = !ORIENT || direction == DIR_HORIZONTAL ? 0.0 : -Q[0] * aux[OPHI + 1 + d];
     }
     __device__ static void init_derived(const Params &, double *, const double *) {}
     __device__ static void gradient_argument(const Params &, double *, const double *,

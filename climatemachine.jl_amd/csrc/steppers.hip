@@ -49,8 +49,9 @@ struct ArkArgs {
     int64_t len;
 };
 
-// stage_update! (LowStorageVariant, AdditiveRungeKuttaMethod.jl:565-605) over the real elements
-__global__ void __launch_bounds__(256) k_ark_stage(const ArkArgs a, double *Qhat, int is)
+// stage_update! (LowStorageVariant, AdditiveRungeKuttaMethod.jl:565-605) over the real elements; Qtt
+// (when given) is initialised for an iterative solver, which starts from it (:603)
+__global__ void __launch_bounds__(256) k_ark_stage(const ArkArgs a, double *Qhat, double *Qtt, int is)
 {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= a.len) return;
@@ -65,6 +66,7 @@ __global__ void __launch_bounds__(256) k_ark_stage(const ArkArgs a, double *Qhat
     }
     a.Qs[is][i] = Qst;
     Qhat[i] = Qhat_i;
+    if (Qtt) Qtt[i] = Qhat_i;
 }
 
 __global__ void k_add(double *a, const double *b, int64_t len)
@@ -85,6 +87,74 @@ __global__ void __launch_bounds__(256) k_ark_solution(const ArkArgs a, int nstag
         q += a.bdt[is] * a.R[is][i];
     }
     a.Qs[0][i] = q;
+}
+
+// The full operator runs on its handle's stream, as do the stage and solution kernels; the linear
+// operator, the backward-Euler solve and k_add run on the linear handle's.
+int ark_step(cmdg_handle full, BackwardEuler *be, double *Q, double *const *work, double t, double dt,
+             int32_t nstages, const double *rka_explicit, const double *rka_implicit, const double *rkb,
+             const double *rkc, int32_t split_explicit_implicit)
+{
+    if (!full || !be || !Q || !work || !rka_explicit || !rka_implicit || !rkb || !rkc) return CMDG_ERR_INVALID;
+    const cmdg_handle lin = be->lin;
+    GroupCall gc({{full, "full"}, {lin, "linear"}});
+    if (!gc.ok()) return CMDG_ERR_INVALID;
+    EngineBase *ef = full->eng, *el = lin->eng;
+    if (nstages < 2 || nstages > 4) return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: 2 to 4 stages"));
+    if (ef->ns != el->ns)
+        return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: the full model has " + std::to_string(ef->ns) +
+                                                        " states, the linear model " + std::to_string(el->ns) +
+                                                        "; they must be the same"));
+    if (ef->nreal != el->nreal || ef->Np != el->Np || ef->dev != el->dev)
+        return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: the full and the linear model live on different grids"));
+    const int ns = nstages;
+    for (int i = 0; i < 2 * ns + 1; ++i)
+        if (!work[i]) return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: work array " + std::to_string(i) + " is NULL"));
+    auto A = [&](const double *m, int i, int j) { return m[i * ns + j]; };  // row-major (stage, stage)
+    // work: Qstages[1..ns-1], Rstages[0..ns-1], Qhat, Qtt
+    ArkArgs a{};
+    a.Qs[0] = Q;
+    for (int i = 1; i < ns; ++i) a.Qs[i] = work[i - 1];
+    for (int i = 0; i < ns; ++i) a.R[i] = work[ns - 1 + i];
+    double *const *Qs = a.Qs, *const *R = work + ns - 1;
+    double *Qhat = work[2 * ns - 1], *Qtt = work[2 * ns];
+    a.len = real_len(ef);
+    for (int is = 0; is < ns; ++is) a.bdt[is] = rkb[is] * dt;
+    const dim3 g(grid_one_per_thread(a.len)), b(256);
+    hipStream_t sf = ef->s_comp, sl = el->s_comp;
+    Chain ch(ef, "ark");
+    if (int r = ch.create()) return gc.finish(r);
+    // the explicit tendency: the full operator, or "full minus linear" as two evaluations (not the
+    // reference's fused RemBL kernel)
+    const Op expl{full, split_explicit_implicit ? lin : nullptr}, impl{lin};
+    if (int r = expl.eval(ch, R[0], Qs[0], t + rkc[0] * dt, 0.0)) return gc.finish(r);
+    for (int is = 1; is < ns; ++is) {
+        for (int js = 0; js < is; ++js) {
+            a.rkcoeff[js] = split_explicit_implicit
+                                ? A(rka_implicit, is, js) / A(rka_implicit, is, is)
+                                : (A(rka_implicit, is, js) - A(rka_explicit, is, js)) / A(rka_implicit, is, is);
+            a.dtA[js] = dt * A(rka_explicit, is, js);
+        }
+        if (int r = ch.to(sf)) return gc.finish(r);
+        hipLaunchKernelGGL(k_ark_stage, g, b, 0, sf, a, Qhat, be->iterative ? Qtt : (double *)nullptr, is);
+        // Q_tt = Qhat + alpha L(Q_tt), alpha = dt a_ii; the solver is made ready again when alpha changes
+        if (int r = ch.to(sl)) return gc.finish(r);
+        const double alpha = dt * A(rka_implicit, is, is);
+        if (alpha != be->alpha())
+            if (int r = be->ready(alpha)) return gc.finish(r);
+        if (int r = be->solve(Qtt, Qhat, t + rkc[is] * dt)) return gc.finish(r);
+        hipLaunchKernelGGL(k_add, g, b, 0, sl, Qs[is], Qtt, a.len);
+        if (int r = expl.eval(ch, R[is], Qs[is], t + rkc[is] * dt, 0.0)) return gc.finish(r);
+    }
+    if (split_explicit_implicit)
+        // rhs_implicit!(Rstages[is], Qstages[is], p, stagetime, increment = true)
+        for (int is = 0; is < ns; ++is)
+            if (int r = impl.eval(ch, R[is], Qs[is], t + rkc[is] * dt, 1.0)) return gc.finish(r);
+    if (int r = ch.to(sf)) return gc.finish(r);
+    hipLaunchKernelGGL(k_ark_solution, g, b, 0, sf, a, ns);
+    if (int r = ef->launch_status("ark kernels")) return gc.finish(r);
+    if (hipStreamSynchronize(sf) != hipSuccess) return gc.finish(ef->fail(CMDG_ERR_HIP, "ark: hipStreamSynchronize"));
+    return CMDG_OK;
 }
 
 }  // namespace
@@ -138,72 +208,22 @@ int cmdg_ssprk_step(cmdg_handle h, double *Q, double *Rstage, double *Qstage, do
     return set_err(h, e->launch_status(LAUNCH));
 }
 
-// The full operator runs on its handle's stream, as do the stage and solution kernels; the linear
-// operator, the band solve and k_add run on the linear handle's.
 int cmdg_ark_step(cmdg_handle full, cmdg_columnlu_handle lu, double *Q, double *const *work, double t,
                   double dt, int32_t nstages, const double *rka_explicit, const double *rka_implicit,
                   const double *rkb, const double *rkc, int32_t split_explicit_implicit)
 {
-    if (!full || !lu || !Q || !work || !rka_explicit || !rka_implicit || !rkb || !rkc) return CMDG_ERR_INVALID;
-    const cmdg_handle lin = columnlu_linear(lu);
-    GroupCall gc({{full, "full"}, {lin, "linear"}});
-    if (!gc.ok()) return CMDG_ERR_INVALID;
-    EngineBase *ef = full->eng, *el = lin->eng;
-    if (nstages < 2 || nstages > 4) return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: 2 to 4 stages"));
-    if (ef->ns != el->ns)
-        return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: the full model has " + std::to_string(ef->ns) +
-                                                        " states, the linear model " + std::to_string(el->ns) +
-                                                        "; they must be the same"));
-    if (ef->nreal != el->nreal || ef->Np != el->Np || ef->dev != el->dev)
-        return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: the full and the linear model live on different grids"));
-    const int ns = nstages;
-    for (int i = 0; i < 2 * ns + 1; ++i)
-        if (!work[i]) return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: work array " + std::to_string(i) + " is NULL"));
-    auto A = [&](const double *m, int i, int j) { return m[i * ns + j]; };  // row-major (stage, stage)
-    // work: Qstages[1..ns-1], Rstages[0..ns-1], Qhat, Qtt
-    ArkArgs a{};
-    a.Qs[0] = Q;
-    for (int i = 1; i < ns; ++i) a.Qs[i] = work[i - 1];
-    for (int i = 0; i < ns; ++i) a.R[i] = work[ns - 1 + i];
-    double *const *Qs = a.Qs, *const *R = work + ns - 1;
-    double *Qhat = work[2 * ns - 1], *Qtt = work[2 * ns];
-    a.len = real_len(ef);
-    for (int is = 0; is < ns; ++is) a.bdt[is] = rkb[is] * dt;
-    const dim3 g(grid_one_per_thread(a.len)), b(256);
-    hipStream_t sf = ef->s_comp, sl = el->s_comp;
-    Chain ch(ef, "ark");
-    if (int r = ch.create()) return gc.finish(r);
-    // the explicit tendency: the full operator, or "full minus linear" as two evaluations (not the
-    // reference's fused RemBL kernel)
-    const Op expl{full, split_explicit_implicit ? lin : nullptr}, impl{lin};
-    if (int r = expl.eval(ch, R[0], Qs[0], t + rkc[0] * dt, 0.0)) return gc.finish(r);
-    for (int is = 1; is < ns; ++is) {
-        for (int js = 0; js < is; ++js) {
-            a.rkcoeff[js] = split_explicit_implicit
-                                ? A(rka_implicit, is, js) / A(rka_implicit, is, is)
-                                : (A(rka_implicit, is, js) - A(rka_explicit, is, js)) / A(rka_implicit, is, is);
-            a.dtA[js] = dt * A(rka_explicit, is, js);
-        }
-        if (int r = ch.to(sf)) return gc.finish(r);
-        hipLaunchKernelGGL(k_ark_stage, g, b, 0, sf, a, Qhat, is);
-        // Q_tt = Qhat + alpha L(Q_tt), alpha = dt a_ii; refactored when alpha changes
-        if (int r = ch.to(sl)) return gc.finish(r);
-        const double alpha = dt * A(rka_implicit, is, is);
-        if (alpha != columnlu_alpha(lu))
-            if (int r = columnlu_refactor_async(lu, alpha)) return gc.finish(r);
-        if (int r = columnlu_solve_async(lu, Qtt, Qhat)) return gc.finish(r);
-        hipLaunchKernelGGL(k_add, g, b, 0, sl, Qs[is], Qtt, a.len);
-        if (int r = expl.eval(ch, R[is], Qs[is], t + rkc[is] * dt, 0.0)) return gc.finish(r);
-    }
-    if (split_explicit_implicit)
-        // rhs_implicit!(Rstages[is], Qstages[is], p, stagetime, increment = true)
-        for (int is = 0; is < ns; ++is)
-            if (int r = impl.eval(ch, R[is], Qs[is], t + rkc[is] * dt, 1.0)) return gc.finish(r);
-    if (int r = ch.to(sf)) return gc.finish(r);
-    hipLaunchKernelGGL(k_ark_solution, g, b, 0, sf, a, ns);
-    if (int r = ef->launch_status("ark kernels")) return gc.finish(r);
-    if (hipStreamSynchronize(sf) != hipSuccess) return gc.finish(ef->fail(CMDG_ERR_HIP, "ark: hipStreamSynchronize"));
-    return CMDG_OK;
+    if (!lu) return CMDG_ERR_INVALID;
+    return ark_step(full, columnlu_solver(lu), Q, work, t, dt, nstages, rka_explicit, rka_implicit, rkb, rkc,
+                    split_explicit_implicit);
+}
+
+int cmdg_ark_step_gmres(cmdg_handle full, cmdg_gmres_handle gmres, double *Q, double *const *work, double t,
+                        double dt, int32_t nstages, const double *rka_explicit, const double *rka_implicit,
+                        const double *rkb, const double *rkc, int32_t split_explicit_implicit)
+{
+    if (!gmres) return CMDG_ERR_INVALID;
+    return ark_step(full, gmres_solver(gmres), Q, work, t, dt, nstages, rka_explicit, rka_implicit, rkb, rkc,
+                    split_explicit_implicit);
 }
 
 }  // extern "C"

@@ -19,12 +19,22 @@ int group_lsrk_step(std::vector<EngineBase *> &g, double **Q, double **dQ, doubl
                     bool continued = false, const double *stage_times_dev = nullptr,
                     const StepInRun *handoff = nullptr);
 
-// columnlu.hip: the column solver's pieces that a step drives on the linear handle's stream;
-// errors land on that handle's engine (where GroupCall::finish looks)
-cmdg_handle columnlu_linear(cmdg_columnlu_handle lu);
-double columnlu_alpha(cmdg_columnlu_handle lu);  // NaN while the band is not factored
-int columnlu_refactor_async(cmdg_columnlu_handle lu, double alpha);
-int columnlu_solve_async(cmdg_columnlu_handle lu, double *X, const double *B);
+// What a step drives as "a backward-Euler solver" (LinBESolver, BackwardEulerSolvers.jl:112-196) for
+// Q = Qhat + alpha L(Q): the linear handle, "make ready for alpha" and "solve into X from B at time
+// t", all on the linear handle's stream; errors land on that handle's engine (where
+// GroupCall::finish looks).  The column LU (columnlu.hip) and GMRES (gmres.hip) implement it.
+struct BackwardEuler {
+    cmdg_handle lin = nullptr;
+    // X on entry is the solver's initial guess: a step has to fill it (the direct solver ignores it)
+    bool iterative = false;
+    virtual ~BackwardEuler() = default;
+    virtual double alpha() const = 0;     // the alpha it is ready for; NaN: none yet
+    virtual int ready(double alpha) = 0;  // update_backward_Euler_solver!
+    virtual int solve(double *X, const double *B, double t) = 0;
+};
+BackwardEuler *columnlu_solver(cmdg_columnlu_handle lu);
+// (a step entry's call: also starts the record of the step's solves, cmdg_gmres_step_info)
+BackwardEuler *gmres_solver(cmdg_gmres_handle g);
 
 // Work-groups of 256 for a kernel that handles one item per thread and returns past n: every
 // item needs its own thread, so the count is not capped (nblocks, engine.h, is for grid-stride

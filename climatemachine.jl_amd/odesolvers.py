@@ -9,9 +9,10 @@ Explicit low-storage 2N: ``LowStorageRungeKutta2N`` / ``dostep!`` / ``update!``
 ``StrongStabilityPreservingRungeKutta`` and its four tableaus
 ``StrongStabilityPreservingRungeKuttaMethod.jl:27-285`` (``cmdg_ssprk_step``);
 ``LowStorageRungeKutta3N`` ``LowStorageRungeKutta3NMethod.jl`` (``cmdg_ls3n_step``);
-``AdditiveRungeKutta``, LowStorageVariant, ``AdditiveRungeKuttaMethod.jl`` (``cmdg_ark_step``);
+``AdditiveRungeKutta``, LowStorageVariant, ``AdditiveRungeKuttaMethod.jl`` (``cmdg_ark_step``,
+``cmdg_ark_step_gmres``);
 ``MRIGARKExplicit`` / ``MRIGARKDecoupledImplicit`` ``MultirateInfinitesimalGARK*.jl``
-(``cmdg_mrigark_step``).
+(``cmdg_mrigark_step``, ``cmdg_mrigark_step_gmres``).
 
 The 2N stage loop is ``cmdg_lsrk_run``: five fused RHS+update passes per step, enqueued without
 host synchronisation.
@@ -23,14 +24,15 @@ from fractions import Fraction
 import numpy as np
 
 from . import _lib
-from .systemsolvers import ColumnLU, ManyColumnLU
+from .systemsolvers import ColumnLU, GeneralizedMinimalResidual, GmresSolver, ManyColumnLU
 
 __all__ = ["LSRK54CarpenterKennedy", "LSRK144NiegemannDiehlBusch", "solve",
            "LowStorageRungeKutta2N", "LSRK144_COEFFICIENTS", "StrongStabilityPreservingRungeKutta",
            "SSPRK22Heuns", "SSPRK22Ralstons", "SSPRK33ShuOsher", "SSPRK34SpiteriRuuth",
            "SSPRK_COEFFICIENTS", "LowStorageRungeKutta3N", "LS3NRK44Classic", "LS3NRK33Heuns",
            "LS3N_COEFFICIENTS", "AdditiveRungeKutta", "ARK2GiraldoKellyConstantinescu",
-           "ark2gkc_tableau", "LinearBackwardEulerSolver", "ManyColumnLU", "MRIGARKExplicit",
+           "ark2gkc_tableau", "LinearBackwardEulerSolver", "ManyColumnLU", "GeneralizedMinimalResidual",
+           "MRIGARKExplicit",
            "MRIGARKDecoupledImplicit", "MRIGARKERK33aSandu", "MRIGARKERK45aSandu",
            "MRIGARKIRK21aSandu", "MRIGARKESDIRK23LSA", "MRIGARKESDIRK24LSA", "MRIGARKESDIRK34aSandu",
            "MRIGARKESDIRK46aSandu", "MRIGARK_TABLEAUS", "mrigark_explicit_coefficients",
@@ -197,15 +199,28 @@ LS3NRK44Classic, LS3NRK33Heuns = _ls3n("LS3NRK44Classic"), _ls3n("LS3NRK33Heuns"
 
 class LinearBackwardEulerSolver:
     """``LinearBackwardEulerSolver(solver; isadjustable = true)`` (BackwardEulerSolvers.jl:108-190):
-    solves ``Q = Qhat + alpha L(Q)`` with a direct column solver, refactored whenever alpha
-    changes.  With ``isadjustable = False`` the solver keeps the alpha it was first factored
+    solves ``Q = Qhat + alpha L(Q)`` with ``ManyColumnLU()``, a direct column solver refactored
+    whenever alpha changes (vertical linear models on stacked grids), or with
+    ``GeneralizedMinimalResidual(...)`` (a linear model of any direction on any grid, one rank).
+    With ``isadjustable = False`` the solver keeps the alpha it was first set up
     for: a solve or ``updatedt`` that needs another alpha is refused (the reference's
-    ``@assert lin.isadjustable``)."""
+    ``@assert lin.isadjustable``).  ``preconditioner_update_freq > 0`` (ColumnwiseLUPreconditioner)
+    is not implemented."""
 
-    def __init__(self, solver, isadjustable=True):
-        if not isinstance(solver, ManyColumnLU):
-            raise TypeError("LinearBackwardEulerSolver: only ManyColumnLU() is implemented")
+    def __init__(self, solver, isadjustable=True, preconditioner_update_freq=-1):
+        if not isinstance(solver, (ManyColumnLU, GeneralizedMinimalResidual)):
+            raise TypeError("LinearBackwardEulerSolver: ManyColumnLU() and GeneralizedMinimalResidual() "
+                            "are implemented")
+        if preconditioner_update_freq > 0:
+            raise ValueError("LinearBackwardEulerSolver: preconditioner_update_freq > 0 "
+                             "(ColumnwiseLUPreconditioner) is not implemented")
         self.solver, self.isadjustable = solver, bool(isadjustable)
+
+    def setup(self, linear_dg, alpha):
+        """``setup_backward_Euler_solver``: the device solver for ``linear_dg`` and ``alpha``."""
+        if isinstance(self.solver, GeneralizedMinimalResidual):
+            return GmresSolver(linear_dg, alpha, self.solver)
+        return ColumnLU(linear_dg, alpha)
 
 
 def _refuse_alpha(lu, alpha):
@@ -230,16 +245,20 @@ def ark2gkc_tableau(paperversion=False):
 class AdditiveRungeKutta:
     """``AdditiveRungeKutta(F, L, backward_euler_solver, RKA_explicit, RKA_implicit, RKB, RKC,
     split_explicit_implicit, LowStorageVariant(), Q; dt, t0)`` (AdditiveRungeKuttaMethod.jl:95-200)
-    with ``LinearBackwardEulerSolver(ManyColumnLU())``.  ``dg`` is the full model (every
-    direction), ``linear_dg`` the vertical linear model on the same auxiliary state.  One step is
-    one ``cmdg_ark_step``; the column solver is built once for ``dt a_ii`` and refactored when
-    ``dt`` changes (``updatedt``)."""
+    with ``LinearBackwardEulerSolver(ManyColumnLU())`` or ``LinearBackwardEulerSolver(
+    GeneralizedMinimalResidual(...))``.  ``dg`` is the full model (every direction), ``linear_dg``
+    the linear model on the same auxiliary state: vertical on a stacked grid for the column solver,
+    of any direction on any grid for GMRES.  One step is one ``cmdg_ark_step`` /
+    ``cmdg_ark_step_gmres``; the solver is built once for ``dt a_ii`` and refactored when ``dt``
+    changes (``updatedt``).  With GMRES ``solve_info`` holds the ``GmresInfo`` of the last step's
+    solves; a solve that stops unconverged at its iteration limit warns once."""
 
     def __init__(self, dg, linear_dg, backward_euler_solver, RKA_explicit, RKA_implicit, RKB, RKC,
                  Q, dt=None, t0=0.0, split_explicit_implicit=False):
         assert dt is not None
         if not isinstance(backward_euler_solver, LinearBackwardEulerSolver):
-            raise TypeError("AdditiveRungeKutta: a LinearBackwardEulerSolver(ManyColumnLU()) is needed")
+            raise TypeError("AdditiveRungeKutta: a LinearBackwardEulerSolver(ManyColumnLU() or "
+                            "GeneralizedMinimalResidual()) is needed")
         A_e, A_i = _tableau(RKA_explicit), _tableau(RKA_implicit)
         ns = A_e.shape[0]
         diag = [A_i[i, i] for i in range(ns)]
@@ -255,7 +274,9 @@ class AdditiveRungeKutta:
         self._ptrs = (C.c_void_p * len(self.work))(*[w.data_ptr() for w in self.work])
         self.isadjustable = backward_euler_solver.isadjustable
         self._diag = diag[1]
-        self.lu = ColumnLU(linear_dg, self.dt * diag[1])
+        self.lu = backward_euler_solver.setup(linear_dg, self.dt * diag[1])
+        self._gmres = isinstance(self.lu, GmresSolver)
+        self.solve_info = []
 
     def updatedt(self, dt):
         """``updatedt!``: the next stage refactors the column matrices for ``dt a_ii`` (refused
@@ -268,10 +289,14 @@ class AdditiveRungeKutta:
         dt = self.dt if dt is None else dt
         if not self.isadjustable and dt * self._diag != self.lu.alpha:
             _refuse_alpha(self.lu, dt * self._diag)
-        _run(self, nsteps, dt, lambda t, dt: self.dg.L.cmdg_ark_step(
+        step = self.dg.L.cmdg_ark_step_gmres if self._gmres else self.dg.L.cmdg_ark_step
+        _run(self, nsteps, dt, lambda t, dt: step(
             self.dg.handle, self.lu.handle, Q.data_ptr(), C.cast(self._ptrs, C.c_void_p), t, dt,
             len(self.RKB), _ptr(self.RKA_explicit), _ptr(self.RKA_implicit), _ptr(self.RKB),
             _ptr(self.RKC), int(self.split_explicit_implicit)), self.linear_dg.handle)
+        if self._gmres:
+            self.lu.alpha = dt * self._diag
+            self.solve_info = self.lu.step_info()
 
     def close(self):
         self.lu.close()
@@ -548,9 +573,11 @@ class _MRIGARK:
     def dostep(self, Q, nsteps=1, dt=None):
         self._desc.fast_dt = float(self.fastsolver.dt)
         lu = self.lu.handle if self.lu is not None else None
+        gmres = isinstance(self.lu, GmresSolver)
+        entry = self.dg.L.cmdg_mrigark_step_gmres if gmres else self.dg.L.cmdg_mrigark_step
 
         def step(t, dt):
-            rc = self.dg.L.cmdg_mrigark_step(
+            rc = entry(
                 self._slow[0], self._slow[1], self._fast[0], self._fast[1], lu, C.byref(self._desc),
                 Q.data_ptr(), C.cast(self._work, C.c_void_p), t, dt)
             if rc == 0:
@@ -560,6 +587,9 @@ class _MRIGARK:
                 self.fastsolver.t = t
             return rc
         _run(self, nsteps, self.dt if dt is None else dt, step)
+        if gmres:
+            self.lu.alpha = (self.dt if dt is None else dt) * self.Gammas[0][2 * len(self.dc) - 1][len(self.dc)]
+            self.solve_info = self.lu.step_info()
 
     def close(self):
         if self.lu is not None:
@@ -582,10 +612,12 @@ class MRIGARKExplicit(_MRIGARK):
 
 class MRIGARKDecoupledImplicit(_MRIGARK):
     """``MRIGARKDecoupledImplicit(slowrhs!, backward_euler_solver, fastsolver, Γs, γ̂s, Q, dt, t0)``
-    (MultirateInfinitesimalGARKDecoupledImplicit.jl:60-200): the slow operator is the vertical
-    linear model, solved by ``LinearBackwardEulerSolver(ManyColumnLU())``, factored for
-    ``dt Γ_0[2, 2]``.  ``updatedt`` with another alpha is refused when the solver is not
-    adjustable."""
+    (MultirateInfinitesimalGARKDecoupledImplicit.jl:60-200): the slow operator is the linear
+    model itself (not a remainder), solved by ``LinearBackwardEulerSolver(ManyColumnLU())``
+    (vertical, stacked grid; factored for ``dt Γ_0[2, 2]``) or by
+    ``LinearBackwardEulerSolver(GeneralizedMinimalResidual(...))`` (any direction, any grid;
+    ``solve_info`` then holds the ``GmresInfo`` of the last step's solves).  ``updatedt`` with
+    another alpha is refused when the solver is not adjustable."""
 
     KIND = 1
 
@@ -593,13 +625,15 @@ class MRIGARKDecoupledImplicit(_MRIGARK):
         from .dgmodel import RemainderDGModel
         _fast_solver(fastsolver, "MRIGARKDecoupledImplicit")
         if not isinstance(backward_euler_solver, LinearBackwardEulerSolver):
-            raise TypeError("MRIGARKDecoupledImplicit: a LinearBackwardEulerSolver(ManyColumnLU()) is needed")
+            raise TypeError("MRIGARKDecoupledImplicit: a LinearBackwardEulerSolver(ManyColumnLU() or "
+                            "GeneralizedMinimalResidual()) is needed")
         if isinstance(slow_rhs, RemainderDGModel):
             raise TypeError("MRIGARKDecoupledImplicit: the implicit slow operator must be the vertical "
                             "linear model itself, not a remainder")
         G, gh, dc = mrigark_implicit_coefficients(Gammas, gammahats)
         self.isadjustable = backward_euler_solver.isadjustable
-        lu = ColumnLU(slow_rhs, float(dt) * G[0][1][1])
+        lu = backward_euler_solver.setup(slow_rhs, float(dt) * G[0][1][1])
+        self.solve_info = []
         self._setup(slow_rhs, fastsolver, G, gh, dc, Q, dt, t0, lu=lu, adjustable=self.isadjustable)
 
     def updatedt(self, dt):

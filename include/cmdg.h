@@ -80,7 +80,11 @@ enum {
     CMDG_PHYSICS_MOIST_LINEAR_AG = 11,
     /* DryAtmosModel of the entropy-stable discretisation (test/Numerics/ESDGMethods/DryAtmos/
      * DryAtmos.jl, total_energy = false, fluctuation_gravity = false): cmdg_create_esdg only */
-    CMDG_PHYSICS_ESDG_DRY_ATMOS = 12
+    CMDG_PHYSICS_ESDG_DRY_ATMOS = 12,
+    /* AtmosAcousticLinearModel (linear.jl:214-245) of a dry AtmosModel with NoOrientation() and a
+     * reference state: no gravity source, e_pot = 0; on the full model's parameter block and
+     * 12-column auxiliary array; N = 4; Rusanov or central first-order flux */
+    CMDG_PHYSICS_ATMOS_LINEAR_ACOUSTIC = 13
 };
 
 /* Construction record: the fields of `DGModel(balance_law, grid, nf1, nf2, nfgrad;
@@ -874,6 +878,53 @@ int cmdg_ark_step(cmdg_handle full, cmdg_columnlu_handle lu, double *Q, double *
                   double dt, int32_t nstages, const double *rka_explicit, const double *rka_implicit,
                   const double *rkb, const double *rkc, int32_t split_explicit_implicit);
 
+/* ---- GeneralizedMinimalResidual (generalized_minimal_residual_solver.jl, linearsolve!) ----------
+ * Restarted GMRES for (I - alpha L) Q = Qrhs, L any handle cmdg_rhs serves, in any direction, on a
+ * stacked or unstacked grid, single rank.  initialize!: r0 = Qrhs - A Q from the caller's Q,
+ * threshold = rtol |r0|; threshold < atol returns converged after 0 iterations with Q untouched,
+ * otherwise the working threshold is max(threshold, atol).  Cycles of at most M Arnoldi steps
+ * (modified Gram-Schmidt, one Givens rotation per column) break when |g0[j+1]| < threshold; after a
+ * cycle Q += sum y_i v_i and, when not converged, the solver restarts from the new residual.  At
+ * most max_iters inner iterations in total.  Dots and norms are plain sums over the real elements
+ * (weighted_norm = false), accumulated in fp64 in a fixed order: a repeated solve repeats its bits.
+ * The solver owns M + 1 device arrays shaped like Q and its small matrices; one host wait per inner
+ * iteration reads the residual norm.  Refused at create, message in cmdg_last_error(linear):
+ * CMDG_ERR_INVALID for M outside 1 .. CMDG_GMRES_MAX_M, rtol or atol negative or NaN, or a basis
+ * that does not fit in free device memory (the message names its size); CMDG_ERR_UNSUPPORTED for a
+ * handle with halo neighbours (a multi-rank solve needs an all-reduce per dot and one convergence
+ * decision for every rank: a follow-up). */
+#define CMDG_GMRES_MAX_M 64
+typedef struct cmdg_gmres *cmdg_gmres_handle;
+typedef struct cmdg_gmres_info {
+    int64_t iterations;    /* inner iterations done */
+    int32_t converged;
+    double residual_norm;  /* |g0[j+1]| of the last iteration; |r0| after 0 iterations */
+    double threshold;      /* the working threshold */
+} cmdg_gmres_info;
+int cmdg_gmres_create(cmdg_handle linear, int32_t M, double rtol, double atol, cmdg_gmres_handle *out);
+/* the size check of cmdg_gmres_create against free_bytes of device memory (CMDG_ERR_INVALID and the
+ * message when the basis does not fit); basis_bytes (may be NULL) receives (M + 1) state arrays */
+int cmdg_gmres_fits(cmdg_handle linear, int32_t M, int64_t free_bytes, int64_t *basis_bytes);
+/* setup_backward_Euler_solver / update_backward_Euler_solver!: the alpha the step entries compare
+ * with dt a_ii (prefactorize does nothing for an iterative solver) */
+int cmdg_gmres_prepare(cmdg_gmres_handle g, double alpha);
+/* Q: initial guess in, solution out; Q and Qrhs are distinct device arrays shaped like the linear
+ * handle's state; t is passed to L; max_iters < 0: the reference's default, the length of Q.  A
+ * solve that stops at max_iters returns CMDG_OK with info->converged = 0.  A residual norm that is
+ * not finite is CMDG_ERR_INVALID with a message. */
+int cmdg_gmres_solve(cmdg_gmres_handle g, double alpha, double *Q, const double *Qrhs, double t,
+                     int64_t max_iters, cmdg_gmres_info *info);
+/* the solves of the last cmdg_ark_step_gmres / cmdg_mrigark_step_gmres, in order: *nsolves of them,
+ * the first min(capacity, *nsolves) copied to out */
+int cmdg_gmres_step_info(cmdg_gmres_handle g, int32_t capacity, cmdg_gmres_info *out, int32_t *nsolves);
+int cmdg_gmres_destroy(cmdg_gmres_handle g);
+/* cmdg_ark_step with GMRES as the backward-Euler solver: `linear` is the solver's handle, of any
+ * direction; Qtt is initialised to Qhat by the stage update (the solver's initial guess,
+ * AdditiveRungeKuttaMethod.jl:603); every solve runs with max_iters = the length of Q */
+int cmdg_ark_step_gmres(cmdg_handle full, cmdg_gmres_handle gmres, double *Q, double *const *work, double t,
+                        double dt, int32_t nstages, const double *rka_explicit, const double *rka_implicit,
+                        const double *rkb, const double *rkc, int32_t split_explicit_implicit);
+
 /* One slow step of a multirate infinitesimal GARK scheme (Sandu 2019) whose fast method is a
  * low-storage 2N Runge-Kutta method: dostep! of MultirateInfinitesimalGARKExplicit.jl (kind
  * CMDG_MRIGARK_EXPLICIT) or of MultirateInfinitesimalGARKDecoupledImplicit.jl (kind
@@ -912,6 +963,11 @@ typedef struct cmdg_mrigark_desc {
 int cmdg_mrigark_step(cmdg_handle slow, cmdg_handle slow_minus, cmdg_handle fast, cmdg_handle fast_minus,
                       cmdg_columnlu_handle lu, const cmdg_mrigark_desc *d, double *Q, double *const *work,
                       double t, double dt);
+/* the decoupled-implicit kind with GMRES in place of the column solver (required): the slow
+ * operator is the solver's linear handle, in any direction; Q is each solve's initial guess */
+int cmdg_mrigark_step_gmres(cmdg_handle slow, cmdg_handle slow_minus, cmdg_handle fast, cmdg_handle fast_minus,
+                            cmdg_gmres_handle gmres, const cmdg_mrigark_desc *d, double *Q,
+                            double *const *work, double t, double dt);
 
 #ifdef __cplusplus
 }

@@ -1,68 +1,15 @@
-// libcmdg: engine orchestration + the C ABI declared in include/cmdg.h.
+// libcmdg: the engine's construction and its evaluation (rhs_segment), and the C entries of
+// include/cmdg.h for them; the exchange is in halo.hip, the create path in create.hip.
 #include <dlfcn.h>
 
 #include <algorithm>
-#include <chrono>
-#include <cstdio>
-#include <cstring>
 #include <new>
 #include <tuple>
 
+#include "rccl.h"
 #include "stepping.h"
-#include "reductions.h"
-#include "interpolation.h"
 
 namespace cmdg {
-
-// ---- RCCL, resolved lazily so that single-GPU use has no link-time dependency -------
-namespace rccl {
-typedef struct { char internal[128]; } uid_t;
-typedef int (*GetUniqueId_t)(uid_t *);
-typedef int (*CommInitRank_t)(void **, int, uid_t, int);
-typedef int (*CommDestroy_t)(void *);
-typedef int (*GroupStart_t)();
-typedef int (*GroupEnd_t)();
-typedef int (*Send_t)(const void *, size_t, int, int, void *, hipStream_t);
-typedef int (*Recv_t)(void *, size_t, int, int, void *, hipStream_t);
-typedef const char *(*GetErrorString_t)(int);
-typedef int (*AllGather_t)(const void *, void *, size_t, int, void *, hipStream_t);
-static void *lib = nullptr;
-static GetUniqueId_t GetUniqueId;
-static CommInitRank_t CommInitRank;
-static CommDestroy_t CommDestroy;
-static GroupStart_t GroupStart;
-static GroupEnd_t GroupEnd;
-static Send_t Send;
-static Recv_t Recv;
-static GetErrorString_t GetErrorString;
-static AllGather_t AllGather;
-constexpr int kDouble = 8;  // ncclFloat64 / ncclDouble
-static bool load(std::string &err)
-{
-    if (lib) return true;
-    // one RCCL instance per process: the path the caller names (CMDG_RCCL_LIB, e.g. the copy
-    // torch ships and has loaded already), else whatever is loaded, else the system library
-    const char *names[] = {"librccl.so.1", "librccl.so", nullptr};
-    if (const char *p = getenv("CMDG_RCCL_LIB"))
-        if (*p) lib = dlopen(p, RTLD_NOW | RTLD_GLOBAL);
-    for (int i = 0; names[i] && !lib; ++i) lib = dlopen(names[i], RTLD_NOW | RTLD_GLOBAL | RTLD_NOLOAD);
-    for (int i = 0; names[i] && !lib; ++i) lib = dlopen(names[i], RTLD_NOW | RTLD_GLOBAL);
-    if (!lib) {
-        err = std::string("cannot load librccl: ") + dlerror();
-        return false;
-    }
-#define SYM(n)                                                \
-    n = (n##_t)dlsym(lib, "nccl" #n);                         \
-    if (!n) {                                                 \
-        err = "librccl lacks nccl" #n;                        \
-        return false;                                         \
-    }
-    SYM(GetUniqueId) SYM(CommInitRank) SYM(CommDestroy) SYM(GroupStart) SYM(GroupEnd) SYM(Send)
-        SYM(Recv) SYM(GetErrorString) SYM(AllGather)
-#undef SYM
-    return true;
-}
-}  // namespace rccl
 
 // ---- roctx, resolved lazily: ranges cost nothing when nobody listens ----------------------
 namespace {
@@ -202,6 +149,57 @@ EngineBase::~EngineBase()
     prof_collect();
     if (graph_exec) hipGraphExecDestroy(graph_exec);
     if (nccl_comm && rccl::CommDestroy) rccl::CommDestroy(nccl_comm);
+}
+
+// One-time digest of the reference face tables (see GridDev); bad[0] collects what does not
+// hold: bit 0 vmap- is not the canonical face numbering, bit 1 sgeo's vMI is not vgeo's MI at
+// the face node, bit 2 a plus-side id does not fit 32 bits.
+static __global__ void k_face_digest(const double *__restrict__ vgeo, int nvgeo,
+                                     const double *__restrict__ sgeo,
+                                     const int64_t *__restrict__ vmapM,
+                                     const int64_t *__restrict__ vmapP,
+                                     const int64_t *__restrict__ elemtobndy, int NQ, int NQV,
+                                     int64_t nreal, int32_t *__restrict__ faceP,
+                                     double *__restrict__ faceG, int *__restrict__ bad)
+{
+    const int Np = NQ * NQ * NQV, Nfph = NQ * NQV, Nfpv = NQ * NQ;
+    const int Nfp = Nfph > Nfpv ? Nfph : Nfpv, NFT = 4 * Nfph + 2 * Nfpv;
+    const int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (I >= nreal * NFT) return;
+    const int64_t e = I / NFT;
+    const int t = (int)(I % NFT);
+    int f, n;
+    if (t < 4 * Nfph) {
+        f = t / Nfph;
+        n = t % Nfph;
+    } else {
+        f = 4 + (t - 4 * Nfph) / Nfpv;
+        n = (t - 4 * Nfph) % Nfpv;
+    }
+    const int64_t o = n + (int64_t)Nfp * (f + 6 * e);
+    const int a = n % NQ, b = n / NQ;
+    int vid;
+    switch (f) {
+    case 0: vid = NQ * (a + NQ * b); break;
+    case 1: vid = (NQ - 1) + NQ * (a + NQ * b); break;
+    case 2: vid = a + NQ * NQ * b; break;
+    case 3: vid = a + NQ * ((NQ - 1) + NQ * b); break;
+    case 4: vid = n; break;
+    default: vid = n + NQ * NQ * (NQV - 1); break;
+    }
+    int flags = 0;
+    const int64_t idM = vmapM[o] - 1;
+    if (idM != e * Np + vid) flags |= 1;
+    int64_t idP = vmapP[o] - 1;
+    if (elemtobndy[f + 6 * e] != 0) idP = e * Np + vid;  // DGModel_kernels.jl:686-692
+    if (idP < 0 || idP > 2147483647LL) flags |= 4;
+    faceP[I] = (int32_t)idP;
+    const double *sg = sgeo + 5 * o;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) faceG[((int64_t)4 * e + c) * NFT + t] = sg[c];
+    const double mi = vgeo[vid + (int64_t)Np * (VMI + (int64_t)nvgeo * e)];
+    if (!(sg[SVMI] == mi)) flags |= 2;
+    if (flags) atomicOr(bad, flags);
 }
 
 int EngineBase::init(const cmdg_desc *d)
@@ -355,74 +353,6 @@ int EngineBase::init(const cmdg_desc *d)
     return CMDG_OK;
 }
 
-// Tables of the exchange without pack / unpack launches (HaloDev).  Whatever cannot be built
-// leaves the corresponding half on the reference's pack / unpack kernels; nothing here fails
-// a create that the reference's tables allow.
-int EngineBase::init_halo_tables()
-{
-    const int64_t NFT = 4 * NQ * NQV + 2 * NQ * NQ;
-    std::vector<int64_t> vs((size_t)nvmapsend), vr((size_t)nvmaprecv), ext((size_t)nexterior);
-    if (nvmapsend) HIPCHK(hipMemcpy(vs.data(), d_vmapsend, sizeof(int64_t) * nvmapsend, hipMemcpyDeviceToHost));
-    if (nvmaprecv) HIPCHK(hipMemcpy(vr.data(), d_vmaprecv, sizeof(int64_t) * nvmaprecv, hipMemcpyDeviceToHost));
-    if (nexterior) HIPCHK(hipMemcpy(ext.data(), d_exterior_user, sizeof(int64_t) * nexterior, hipMemcpyDeviceToHost));
-    // ---- sender: per-element lists of (node, position in vmapsend)
-    bool oks = nvmapsend < 2147483647LL;
-    std::vector<uint8_t> is_ext((size_t)std::max<int64_t>(nreal, 1), 0);
-    for (int64_t e1 : ext)
-        if (e1 >= 1 && e1 <= nreal) is_ext[e1 - 1] = 1;
-    std::vector<int32_t> off((size_t)nreal + 1, 0);
-    for (int64_t i = 0; i < nvmapsend && oks; ++i) {
-        const int64_t id = vs[i] - 1, e = id / Np;
-        if (id < 0 || e >= nreal || !is_ext[e]) oks = false;
-        else off[e + 1] += 1;
-    }
-    if (oks) {
-        for (int64_t e = 0; e < nreal; ++e) off[e + 1] += off[e];
-        std::vector<SendEnt> ent((size_t)std::max<int64_t>(nvmapsend, 1));
-        std::vector<int32_t> fill(off.begin(), off.end() - 1);
-        for (int64_t i = 0; i < nvmapsend; ++i) {
-            const int64_t id = vs[i] - 1, e = id / Np;
-            ent[fill[e]++] = SendEnt{(int32_t)(id - e * Np), (int32_t)i};
-        }
-        HIPCHK(d_sendoff.alloc(off.size()));
-        HIPCHK(d_sendent.alloc(ent.size()));
-        HIPCHK(hipMemcpy(d_sendoff, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_sendent, ent.data(), sizeof(SendEnt) * ent.size(), hipMemcpyHostToDevice));
-    }
-    direct_send_ok = oks;
-    // ---- receiver: position in vmaprecv of every ghost node
-    const int64_t ng = nghost * Np, g0 = nreal * Np;
-    bool okr = nvmaprecv < 2147483647LL;
-    std::vector<int32_t> gs((size_t)std::max<int64_t>(ng, 1), -1);
-    for (int64_t i = 0; i < nvmaprecv && okr; ++i) {
-        const int64_t id = vr[i] - 1 - g0;
-        if (id < 0 || id >= ng || gs[id] >= 0) okr = false;
-        else gs[id] = (int32_t)i;
-    }
-    if (okr && nreal > 0) {  // every ghost node a face of a real element reads is received
-        std::vector<int32_t> fP((size_t)(nreal * NFT));
-        HIPCHK(hipMemcpy(fP.data(), d_faceP, sizeof(int32_t) * fP.size(), hipMemcpyDeviceToHost));
-        for (size_t q = 0; q < fP.size() && okr; ++q)
-            if (fP[q] >= g0 && (fP[q] - g0 >= ng || gs[fP[q] - g0] < 0)) okr = false;
-    }
-    if (okr) {
-        HIPCHK(d_ghostslot.alloc(gs.size()));
-        HIPCHK(hipMemcpy(d_ghostslot, gs.data(), sizeof(int32_t) * gs.size(), hipMemcpyHostToDevice));
-    }
-    direct_recv_ok = okr;
-    return CMDG_OK;
-}
-
-int EngineBase::before_direct_send(int s, hipStream_t st)
-{
-    if (transport == TRANSPORT_LOCAL && communicate() && direct_send())
-        for (int r : nabrtorank) {
-            if (dbg_sync() & 32) HIPCHK(hipStreamSynchronize(group[r]->s_comm));
-            HIPCHK(hipStreamWaitEvent(st, group[r]->slot[s].ev_pulled, 0));
-        }
-    return CMDG_OK;
-}
-
 int EngineBase::ensure_work()
 {
     for (int i = 0; i < 2; ++i)
@@ -478,6 +408,28 @@ void EngineBase::prof_end(hipStream_t st)
     if (!profiling) return;
     hipEventRecord(prof.back().e1, st);
 }
+// ---------------------------------------------------------------------------------
+// A node-major array of the library (ncol, Np, nelem) into the reference layout (Np, ncol, nelem) of
+// a caller that asked for it (create_states.jl:17-26), and back.
+static __global__ void k_export_node_major(double *__restrict__ dst, const double *__restrict__ src, int Np,
+                                           int ncol, int64_t nelem)
+{
+    const int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (I >= (int64_t)Np * ncol * nelem) return;
+    const int64_t e = I / ((int64_t)Np * ncol);
+    const int r = (int)(I - e * Np * ncol), s = r / Np, n = r - s * Np;
+    dst[I] = src[s + (int64_t)ncol * (n + (int64_t)Np * e)];
+}
+static __global__ void k_import_node_major(double *__restrict__ dst, const double *__restrict__ src, int Np,
+                                           int ncol, int64_t nelem)
+{
+    const int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (I >= (int64_t)Np * ncol * nelem) return;
+    const int64_t e = I / ((int64_t)Np * ncol);
+    const int r = (int)(I - e * Np * ncol), n = r / ncol, s = r - n * ncol;
+    dst[I] = src[n + (int64_t)Np * (s + (int64_t)ncol * e)];
+}
+
 // the library's Qhypervisc_grad / state_gradient_flux in the reference layout (Np, ncol, nelem), on demand
 int EngineBase::export_hypgrad(double *dst)
 {
@@ -516,104 +468,6 @@ void EngineBase::prof_collect()
         }
     }
     prof.clear();  // (destroys the events)
-}
-
-// ---- halo: begin_ghost_exchange! / end_ghost_exchange!  MPIStateArrays.jl:411-483 ----
-int EngineBase::halo_begin(int s, double *array, int nvar, int ncol, bool on_halo_stream)
-{
-    if (int r = halo_pack(s, array, nvar, ncol, on_halo_stream)) return r;
-    return halo_post(&s, 1);
-}
-
-int EngineBase::halo_pack(int s, double *array, int nvar, int ncol, bool on_halo_stream)
-{
-    if (!communicate()) return CMDG_OK;
-    if (transport == TRANSPORT_NONE)
-        return fail(CMDG_ERR_COMM, "halo exchange needs cmdg_comm_init_rccl or cmdg_comm_connect_local");
-    Range range_("cmdg:halo:pack");
-    HaloSlot &h = slot[s];
-    if (h.active) return fail(CMDG_ERR_INVALID, "The current ghost exchange must end before another begins.");
-    if (nvar > slot_nvar_max) return fail(CMDG_ERR_INVALID, "halo: nstate too large for the buffers");
-    if (ncol == 0) ncol = nvar;
-    if (ncol < nvar) return fail(CMDG_ERR_INVALID, "halo: more packed columns than the array has");
-    h.nvar = nvar;
-    h.ncol = ncol;
-    h.array = array;
-    // an exterior launch of this evaluation wrote the nodes of vmapsend already
-    const bool fresh = h.fresh_for == array && h.fresh_nvar == nvar && direct_send();
-    h.fresh_for = nullptr;
-    // the data to send is produced on the compute stream -- unless an exterior launch of the
-    // halo stream's own pipeline wrote it (pipelined())
-    if (capturing && !(fresh && on_halo_stream))
-        return fail(CMDG_ERR_UNSUPPORTED, "step graph: an exchange of this step would have to be packed");
-    if (!(fresh && on_halo_stream)) {
-        if (dbg_sync() & 2) HIPCHK(hipStreamSynchronize(s_comp));
-        HIPCHK(ev_record(ev_comp, s_comp));
-        HIPCHK(hipStreamWaitEvent(s_comm, ev_comp, 0));
-    }
-    if (transport == TRANSPORT_LOCAL) {
-        // neighbours must have pulled the previous payload of this slot
-        for (int r : nabrtorank) {
-            if (dbg_sync() & 4) HIPCHK(hipStreamSynchronize(group[r]->s_comm));
-            HIPCHK(hipStreamWaitEvent(s_comm, group[r]->slot[s].ev_pulled, 0));
-        }
-    }
-    if (nvmapsend > 0 && !fresh) {
-        const int64_t n = nvmapsend * nvar;
-        prof_begin(CMDG_K_PACK, s_comm);
-        hipLaunchKernelGGL(k_fillsendbuf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s_comm,
-                           h.sendbuf, array, d_vmapsend, nvmapsend, Np, nvar, ncol,
-                           (int)node_major(array));
-        prof_end(s_comm);
-    }
-    if (!capturing) HIPCHK(ev_record(h.ev_packed, s_comm));  // (read by the local transport only)
-    return CMDG_OK;
-}
-
-int EngineBase::halo_post(const int *slots, int nslots)
-{
-    if (!communicate()) return CMDG_OK;
-    Range range_("cmdg:halo:transport");
-    const auto host_t0 = std::chrono::steady_clock::now();
-    struct HostTimer {  // host time spent posting exchanges (cmdg_query CMDG_Q_HOST_POST_NS)
-        EngineBase *e;
-        std::chrono::steady_clock::time_point t0;
-        ~HostTimer()
-        {
-            e->host_post_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(
-                                   std::chrono::steady_clock::now() - t0).count();
-            e->host_post_n += 1;
-        }
-    } host_timer_{this, host_t0};
-    if (transport == TRANSPORT_RCCL) {
-        // one group for everything that begins here: every neighbour pair has its own xGMI
-        // link, and one group costs one RCCL launch however many arrays travel
-        prof_begin(CMDG_K_TRANSPORT, s_comm);
-        if (rccl::GroupStart()) return fail(CMDG_ERR_COMM, "ncclGroupStart failed");
-        for (int q = 0; q < nslots; ++q) {
-            HaloSlot &h = slot[slots[q]];
-            const int nvar = h.nvar;
-            for (size_t n = 0; n < nabrtorank.size(); ++n) {
-                const int64_t r0 = nabrrecv[2 * n] - 1, rn = nabrrecv[2 * n + 1] - r0;
-                const int64_t s0 = nabrsend[2 * n] - 1, sn = nabrsend[2 * n + 1] - s0;
-                int rc = rccl::Recv(h.recvbuf + r0 * nvar, (size_t)(rn * nvar), rccl::kDouble,
-                                    nabrtorank[n], nccl_comm, s_comm);
-                if (!rc)
-                    rc = rccl::Send(h.sendbuf + s0 * nvar, (size_t)(sn * nvar), rccl::kDouble,
-                                    nabrtorank[n], nccl_comm, s_comm);
-                if (rc) {
-                    rccl::GroupEnd();
-                    return fail(CMDG_ERR_COMM, std::string("ncclSend/Recv: ") + rccl::GetErrorString(rc));
-                }
-            }
-        }
-        if (int rc = rccl::GroupEnd())
-            return fail(CMDG_ERR_COMM, std::string("ncclGroupEnd: ") + rccl::GetErrorString(rc));
-        prof_end(s_comm);
-    }
-    // only now: a failure above leaves the slots free for the next call
-    for (int q = 0; q < nslots; ++q) slot[slots[q]].active = true;
-    return CMDG_OK;
 }
 
 // Launch order of the element lists (results do not depend on it).  Column by column, a tall
@@ -670,64 +524,6 @@ int EngineBase::set_stream_priority(int level)
     s_comp = std::move(nc);  // (the old streams are drained: synchronize() above)
     s_comm = std::move(nm);
     stream_priority = level;
-    return CMDG_OK;
-}
-
-void EngineBase::abort_exchanges()
-{
-    for (auto &h : slot) {
-        h.active = false;
-        h.fresh_for = nullptr;
-    }
-}
-
-int EngineBase::halo_end(int s, double *array, int nvar, bool unpack, bool on_halo_stream)
-{
-    if (!communicate()) return CMDG_OK;
-    Range range_(unpack ? "cmdg:halo:end+unpack" : "cmdg:halo:end");
-    HaloSlot &h = slot[s];
-    if (!h.active) return fail(CMDG_ERR_INVALID, "A ghost exchange must begin before it ends.");
-    if (h.array != array || h.nvar != nvar)
-        return fail(CMDG_ERR_INVALID, "halo_end does not match the pending halo_begin");
-    h.active = false;
-    if (transport == TRANSPORT_LOCAL) {
-        for (size_t n = 0; n < nabrtorank.size(); ++n) {
-            EngineBase *peer = group[nabrtorank[n]];
-            int m = -1;
-            for (size_t q = 0; q < peer->nabrtorank.size(); ++q)
-                if (peer->nabrtorank[q] == rank) m = (int)q;
-            if (m < 0) return fail(CMDG_ERR_COMM, "local transport: neighbour lists are not symmetric");
-            const int64_t r0 = nabrrecv[2 * n] - 1, rn = nabrrecv[2 * n + 1] - r0;
-            const int64_t s0 = peer->nabrsend[2 * m] - 1, sn = peer->nabrsend[2 * m + 1] - s0;
-            if (rn != sn) return fail(CMDG_ERR_COMM, "local transport: send/recv sizes differ");
-            if (dbg_sync() & 8) HIPCHK(hipStreamSynchronize(peer->s_comm));
-            HIPCHK(hipStreamWaitEvent(s_comm, peer->slot[s].ev_packed, 0));
-            if (n == 0) prof_begin(CMDG_K_TRANSPORT, s_comm);
-            HIPCHK(hipMemcpyAsync(h.recvbuf + r0 * nvar, peer->slot[s].sendbuf + s0 * nvar,
-                                  sizeof(double) * rn * nvar, hipMemcpyDeviceToDevice, s_comm));
-        }
-        if (!nabrtorank.empty()) prof_end(s_comm);
-        HIPCHK(ev_record(h.ev_pulled, s_comm));
-    }
-    if (nvmaprecv > 0 && unpack) {
-        const int64_t n = nvmaprecv * nvar;
-        prof_begin(CMDG_K_UNPACK, s_comm);
-        hipLaunchKernelGGL(k_transferrecvbuf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                           s_comm, array, h.recvbuf, d_vmaprecv, nvmaprecv, Np, nvar, h.ncol,
-                           (int)node_major(array));
-        prof_end(s_comm);
-    }
-    if (on_halo_stream) return CMDG_OK;  // the consumer is the next launch of the halo stream
-    HIPCHK(ev_record(h.ev_done, s_comm));
-    if (profiling) {
-        // exposed time of this exchange: from the moment the compute stream has nothing left to
-        // do but wait (its interior launches are done) to the moment the ghosts are in place
-        ProfRec &r = prof_pair(CMDG_K_HALO_EXPOSED, true);
-        hipEventRecord(r.e0, s_comp);
-        hipEventRecord(r.e1, s_comm);
-    }
-    if (dbg_sync() & 16) HIPCHK(hipStreamSynchronize(s_comm));
-    HIPCHK(hipStreamWaitEvent(s_comp, h.ev_done, 0));
     return CMDG_OK;
 }
 
@@ -913,8 +709,7 @@ int EngineBase::rhs_segment(int seg, const RhsCtx &c)
         if (tendency_filter) TRY(filter_apply(tendency_filter, c.tendency, ns));  // (:417-425)
         if (c.update_after) {
             const int64_t n = (int64_t)Np * ns * nreal;
-            hipLaunchKernelGGL(k_lsrk_update, dim3(nblocks(n)), dim3(256), 0, s_comp, c.tendency, c.Qin,
-                               c.rka_next, c.rkb_dt, n);
+            lsrk_update(s_comp, c.tendency, c.Qin, c.rka_next, c.rkb_dt, n);
         }
         break;
     default: break;
@@ -979,6 +774,24 @@ int group_rhs(std::vector<EngineBase *> &g, std::vector<RhsCtx> &c, bool keep_fr
     return CMDG_OK;
 }
 
+// extremum of n values into out[0] (one block)
+static __global__ void k_extremum(const double *__restrict__ v, int64_t n, int is_min,
+                                  double *__restrict__ out)
+{
+    __shared__ double s[1024];
+    double a = is_min ? INFINITY : -INFINITY;
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) a = is_min ? fmin(a, v[i]) : fmax(a, v[i]);
+    s[threadIdx.x] = a;
+    __syncthreads();
+    for (int h = blockDim.x / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h)
+            s[threadIdx.x] = is_min ? fmin(s[threadIdx.x], s[threadIdx.x + h])
+                                    : fmax(s[threadIdx.x], s[threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = s[0];
+}
+
 // ---- courant / min_node_distance: rank-local extremum, the caller Allreduces ------------
 int EngineBase::courant(int mode, int kind, const double *Q, double dt, double t, int dir,
                         double *out)
@@ -996,6 +809,34 @@ int EngineBase::courant(int mode, int kind, const double *Q, double dt, double t
     HIPCHK(hipMemcpyAsync(out, d_elemred + nreal, sizeof(double), hipMemcpyDeviceToHost, s_comp));
     HIPCHK(hipStreamSynchronize(s_comp));
     return CMDG_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// local part of norm / euclidean_distance (MPIStateArrays.jl:583-644): per-block
+// partial sums in a fixed order (deterministic), finished on the host.
+static __global__ void k_wsum2(const double *__restrict__ A, const double *__restrict__ B,
+                        const double *__restrict__ vgeo, int nvgeo, int Np, int nvar,
+                        int64_t nreal, int weighted, double *__restrict__ partial)
+{
+    __shared__ double sh[256];
+    const int64_t total = (int64_t)Np * nvar * nreal;
+    double acc = 0.0;
+    for (int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; I < total;
+         I += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t e = I / ((int64_t)Np * nvar);
+        const int n = (int)(I % Np);
+        double d = A[I];
+        if (B) d -= B[I];
+        const double w = weighted ? vgeo[n + (int64_t)Np * (VM + (int64_t)nvgeo * e)] : 1.0;
+        acc += w * d * d;
+    }
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
 }
 
 int EngineBase::wsum2(const double *A, const double *B, int nvar, int weighted, double *out)
@@ -1019,88 +860,9 @@ int EngineBase::wsum2(const double *A, const double *B, int nvar, int weighted, 
 // =====================================================================================
 using namespace cmdg;
 
-static thread_local std::string g_create_err;
-
-// ---- engine plug-ins: balance-law functors / template combinations outside the compiled set ----
-// A plug-in is a shared object built from this library's own headers (csrc/engine.h + a
-// physics_*.h, one translation unit instantiating make_engine<Law, Nq>) that exports
-//   cmdg::EngineBase *cmdg_plugin_make_engine(const cmdg_desc *, char *err, int errlen)
-// returning NULL for a descriptor it does not serve.  climatemachine.jl_amd/plugins.py writes and
-// builds them with hipcc (the reference compiles a law's pointwise functions into its kernels when
-// the model is first run; this is the ahead-of-time equivalent for a C ABI).
-namespace {
-typedef EngineBase *(*plugin_make_t)(const cmdg_desc *, char *, int);
-std::vector<plugin_make_t> g_plugin_make;
-std::vector<std::string> g_plugin_path;
-bool g_plugins_env_read = false;
-int load_plugin(const char *path, std::string &err)
-{
-    for (const auto &p : g_plugin_path)
-        if (p == path) return CMDG_OK;
-    void *lib = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    if (!lib) {
-        err = std::string("cannot load plug-in: ") + dlerror();
-        return CMDG_ERR_INVALID;
-    }
-    plugin_make_t f = (plugin_make_t)dlsym(lib, "cmdg_plugin_make_engine");
-    if (!f) {
-        err = std::string(path) + " does not export cmdg_plugin_make_engine";
-        dlclose(lib);
-        return CMDG_ERR_INVALID;
-    }
-    // a plug-in shares the C++ layout of EngineBase with the library: one built against other
-    // headers is refused here instead of corrupting a handle later
-    typedef unsigned long (*plugin_abi_t)();
-    plugin_abi_t abi = (plugin_abi_t)dlsym(lib, "cmdg_plugin_abi");
-    if (!abi || abi() != engine_abi_stamp()) {
-        err = std::string(path) + (abi ? " was built against another libcmdg (engine layout differs): rebuild it"
-                                       : " does not export cmdg_plugin_abi");
-        dlclose(lib);
-        return CMDG_ERR_INVALID;
-    }
-    g_plugin_make.push_back(f);
-    g_plugin_path.push_back(path);
-    return CMDG_OK;
-}
-EngineBase *plugin_engine(const cmdg_desc *d, std::string &err)
-{
-    if (!g_plugins_env_read) {
-        g_plugins_env_read = true;
-        if (const char *env = getenv("CMDG_PLUGINS")) {
-            std::string all(env), e2;
-            size_t a = 0;
-            while (a <= all.size()) {
-                const size_t b = all.find(':', a);
-                const std::string one = all.substr(a, b == std::string::npos ? std::string::npos : b - a);
-                if (!one.empty() && load_plugin(one.c_str(), e2) != CMDG_OK) err += e2 + "; ";
-                if (b == std::string::npos) break;
-                a = b + 1;
-            }
-        }
-    }
-    for (plugin_make_t f : g_plugin_make) {
-        char buf[512] = {0};
-        if (EngineBase *e = f(d, buf, (int)sizeof(buf))) return e;
-        if (buf[0]) err += std::string(buf) + "; ";
-    }
-    if (g_plugin_make.empty() && err.empty()) err = "none loaded";
-    return nullptr;
-}
-}  // namespace
-
-
 extern "C" {
 
 const char *cmdg_version(void) { return "cmdg 0.1 (gfx950)"; }
-
-int cmdg_load_plugin(const char *path)
-{
-    if (!path) return CMDG_ERR_INVALID;
-    std::string err;
-    const int r = load_plugin(path, err);
-    if (r) g_create_err = err;
-    return r;
-}
 
 const char *cmdg_status_string(int status)
 {
@@ -1115,261 +877,11 @@ const char *cmdg_status_string(int status)
     }
 }
 
-int cmdg_physics_counts(int32_t physics_id, const int32_t *iparam, int32_t out[6])
-{
-    if (!iparam || !out) return CMDG_ERR_INVALID;
-    switch (physics_id) {
-    case CMDG_PHYSICS_ADVECTION_DIFFUSION: return counts_advdiff(iparam, out);
-    case CMDG_PHYSICS_DRY_ATMOS: return counts_atmos(iparam, out);
-    case CMDG_PHYSICS_HYDROSTATIC_BOUSSINESQ: return counts_ocean(iparam, out);
-    case CMDG_PHYSICS_PRESSURE_GRADIENT: return counts_pgrad(iparam, out);
-    case CMDG_PHYSICS_SHALLOW_WATER: return counts_sw(iparam, out);
-    case CMDG_PHYSICS_MOIST_ATMOS: return counts_moist(iparam, out);
-    case CMDG_PHYSICS_ATMOS_LINEAR_AG: return counts_atmos_linear(iparam, out);
-    case CMDG_PHYSICS_MOIST_LINEAR_AG: return counts_moist_linear(iparam, out);
-    case CMDG_PHYSICS_ATMOS_LINEAR_ACOUSTIC: return counts_atmos_acoustic(iparam, out);
-    case CMDG_PHYSICS_OCEAN_SE01:
-    case CMDG_PHYSICS_CONTINUITY3D_SE01:
-    case CMDG_PHYSICS_BAROTROPIC_SE01: return counts_se01(physics_id, out);
-    case CMDG_PHYSICS_ESDG_DRY_ATMOS: return counts_esdg_dryatmos(iparam, out);
-    default: return CMDG_ERR_UNSUPPORTED;
-    }
-}
-
-int cmdg_atmos_host_constants(const int32_t *iparam, const double *dparam, double out[7])
-{
-    if (!iparam || !dparam || !out) return CMDG_ERR_INVALID;
-    return host_constants_atmos(iparam, dparam, out);
-}
-
-static int create_handle(const cmdg_desc *d, const cmdg_fv_desc *fv, cmdg_handle *out, const cmdg_esdg_desc *esdg = nullptr)
-{
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        g_create_err = "no HIP device visible";
-        return CMDG_ERR_NO_DEVICE;
-    }
-    if (d->dim != 3 || d->N[0] != d->N[1]) {
-        g_create_err = "only dim == 3 with one horizontal polynomial order is compiled in";
-        return CMDG_ERR_UNSUPPORTED;
-    }
-    if (d->nf_first < CMDG_RUSANOV || d->nf_first > CMDG_ROE_MOIST_LVPP) {
-        g_create_err = "unknown first-order numerical flux";
-        return CMDG_ERR_INVALID;
-    }
-    if (d->nf_first >= CMDG_ROE && d->nf_first <= CMDG_LMARS && d->physics_id != CMDG_PHYSICS_DRY_ATMOS) {
-        g_create_err = "Roe / HLLC / LMARS numerical fluxes are methods of the dry atmosphere law only";
-        return CMDG_ERR_UNSUPPORTED;
-    }
-    if (d->nf_first >= CMDG_ROE_MOIST && d->physics_id != CMDG_PHYSICS_MOIST_ATMOS) {
-        g_create_err = "RoeNumericalFluxMoist is a method of the moist atmosphere law (EquilMoist) only";
-        return CMDG_ERR_UNSUPPORTED;
-    }
-    std::string err;
-    EngineBase *e = nullptr;
-    if (esdg) {
-        e = make_engine_esdg(d, esdg, err);
-        if (!e) {
-            g_create_err = err;
-            return CMDG_ERR_UNSUPPORTED;
-        }
-    } else if (fv) {
-        if (d->physics_id == CMDG_PHYSICS_ADVECTION_DIFFUSION)
-            e = make_engine_advdiff_fv(d, fv, err);
-        else
-            err = "cmdg_create_dgfv: the finite-volume passes are compiled for the AdvectionDiffusion law only";
-        if (!e) {
-            g_create_err = err;
-            return CMDG_ERR_UNSUPPORTED;
-        }
-    } else
-    switch (d->physics_id) {
-    case CMDG_PHYSICS_ADVECTION_DIFFUSION: e = make_engine_advdiff(d, err); break;
-    case CMDG_PHYSICS_DRY_ATMOS: e = make_engine_atmos(d, err); break;
-    case CMDG_PHYSICS_HYDROSTATIC_BOUSSINESQ: e = make_engine_ocean(d, err); break;
-    case CMDG_PHYSICS_PRESSURE_GRADIENT: e = make_engine_pgrad(d, err); break;
-    case CMDG_PHYSICS_SHALLOW_WATER: e = make_engine_sw(d, err); break;
-    case CMDG_PHYSICS_MOIST_ATMOS: e = make_engine_moist(d, err); break;
-    case CMDG_PHYSICS_ATMOS_LINEAR_AG: e = make_engine_atmos_linear(d, err); break;
-    case CMDG_PHYSICS_MOIST_LINEAR_AG: e = make_engine_moist_linear(d, err); break;
-    case CMDG_PHYSICS_ATMOS_LINEAR_ACOUSTIC: e = make_engine_atmos_acoustic(d, err); break;
-    case CMDG_PHYSICS_OCEAN_SE01:
-    case CMDG_PHYSICS_CONTINUITY3D_SE01:
-    case CMDG_PHYSICS_BAROTROPIC_SE01: e = make_engine_se01(d, err); break;
-    default: err = "unknown physics_id"; break;
-    }
-    if (!e) {  // not compiled in: ask the plug-ins (cmdg_load_plugin / CMDG_PLUGINS)
-        std::string perr;
-        e = plugin_engine(d, perr);
-        if (!e) {
-            g_create_err = perr.empty() ? err : err + "; plug-ins: " + perr;
-            return CMDG_ERR_UNSUPPORTED;
-        }
-    }
-    int r = e->init(d);
-    if (r == CMDG_OK && fv) r = e->init_fv();
-    if (esdg) e->reference_halo = true;  // the face phase reads ghost neighbours from the ghost elements
-    if (r != CMDG_OK) {
-        g_create_err = e->err;
-        delete e;
-        return r;
-    }
-    cmdg_context *c = new (std::nothrow) cmdg_context();
-    if (!c) {
-        delete e;
-        return CMDG_ERR_INVALID;
-    }
-    c->eng = e;
-    *out = c;
-    return CMDG_OK;
-}
-
-int cmdg_create(const cmdg_desc *d, cmdg_handle *out)
-{
-    if (!d || !out) return CMDG_ERR_INVALID;
-    if (d->dim == 3 && d->N[2] == 0) {
-        *out = nullptr;
-        g_create_err = "cmdg_create: N[2] == 0 is a finite-volume vertical: use cmdg_create_dgfv";
-        return CMDG_ERR_INVALID;
-    }
-    if (d->physics_id == CMDG_PHYSICS_ESDG_DRY_ATMOS) {
-        *out = nullptr;
-        g_create_err = "cmdg_create: the DryAtmosModel of the entropy-stable discretisation has no DGModel passes: "
-                       "use cmdg_create_esdg";
-        return CMDG_ERR_INVALID;
-    }
-    return create_handle(d, nullptr, out);
-}
-
-// DGFVModel(balance_law, grid, fv_reconstruction, nf1, nf2, nfgrad; direction)  DGFVModel.jl:22-69
-int cmdg_create_dgfv(const cmdg_desc *d, const cmdg_fv_desc *fv, cmdg_handle *out)
-{
-    if (!d || !fv || !out) return CMDG_ERR_INVALID;
-    *out = nullptr;
-    auto refuse = [&](int code, const char *msg) {
-        g_create_err = msg;
-        return code;
-    };
-    if (d->dim != 3 || d->N[2] != 0)
-        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: the vertical polynomial order N[2] must be 0 (use cmdg_create otherwise)");
-    if (!d->stacked)
-        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: the finite-volume vertical needs a stacked grid");
-    if (fv->nvertelem < 2)
-        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: nvertelem < 2");
-    if (fv->reconstruction != CMDG_FV_CONSTANT && fv->reconstruction != CMDG_FV_LINEAR)
-        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: unknown reconstruction");
-    if (fv->width < 0 || fv->width > 3)
-        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: reconstruction width outside 0..3");
-    if (fv->reconstruction == CMDG_FV_LINEAR && fv->width == 0)
-        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: a linear reconstruction needs width >= 1");
-    if (fv->reconstruction == CMDG_FV_CONSTANT && fv->width != 0)
-        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: the constant reconstruction has width 0");
-    if (fv->limiter != CMDG_FV_VANLEER && fv->limiter != CMDG_FV_NOLIMITER)
-        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: unknown slope limiter");
-    if (d->nreal % fv->nvertelem != 0 || d->nghost % fv->nvertelem != 0)
-        return refuse(CMDG_ERR_INVALID, "cmdg_create_dgfv: element counts are not multiples of nvertelem");
-    return create_handle(d, fv, out);
-}
-
-// ESDGModel(balance_law, grid; volume_numerical_flux_first_order, surface_numerical_flux_first_order)
-// ESDGModel.jl:75-94
-int cmdg_create_esdg(const cmdg_desc *d, const cmdg_esdg_desc *ed, cmdg_handle *out)
-{
-    if (!d || !ed || !out) return CMDG_ERR_INVALID;
-    *out = nullptr;
-    auto refuse = [&](int code, const char *msg) {
-        g_create_err = msg;
-        return code;
-    };
-    if (d->physics_id != CMDG_PHYSICS_ESDG_DRY_ATMOS)
-        return refuse(CMDG_ERR_UNSUPPORTED, "cmdg_create_esdg: the two-point fluxes are defined for CMDG_PHYSICS_ESDG_DRY_ATMOS only");
-    if (d->dim != 3)
-        return refuse(CMDG_ERR_UNSUPPORTED, "cmdg_create_esdg: only dim == 3 is compiled in");
-    if (d->N[0] != d->N[1] || d->N[0] != d->N[2])
-        return refuse(CMDG_ERR_UNSUPPORTED, "cmdg_create_esdg: mixed polynomial orders are not compiled in (one order in every direction)");
-    if (d->N[0] != 3 && d->N[0] != 4)
-        return refuse(CMDG_ERR_UNSUPPORTED, "cmdg_create_esdg: the flux-differencing kernel is compiled for polynomial orders 3 and 4");
-    const int vf = ed->volume_flux, sf = ed->surface_flux;
-    if (vf != CMDG_ESDG_FLUX_NONE && vf != CMDG_ESDG_FLUX_ENTROPY_CONSERVATIVE && vf != CMDG_ESDG_FLUX_CENTRAL &&
-        vf != CMDG_ESDG_FLUX_KG)
-        return refuse(CMDG_ERR_INVALID, "cmdg_create_esdg: unknown volume flux");
-    if (sf != CMDG_ESDG_FLUX_NONE && sf != CMDG_ESDG_FLUX_ENTROPY_CONSERVATIVE && sf != CMDG_ESDG_FLUX_RUSANOV &&
-        sf != CMDG_ESDG_FLUX_ENTROPY_CONSERVATIVE_PENALTY && sf != CMDG_ESDG_FLUX_MATRIX)
-        return refuse(CMDG_ERR_INVALID, "cmdg_create_esdg: unknown surface flux");
-    cmdg_desc dd = *d;  // (nf_first, direction: not read by an ESDG handle)
-    dd.nf_first = CMDG_RUSANOV;
-    dd.direction = dd.diffusion_direction = CMDG_EVERY_DIRECTION;
-    return create_handle(&dd, nullptr, out, ed);
-}
-
 int cmdg_esdg_entropy(cmdg_handle h, const double *Q, double *beta, double *eta)
 {
     if (!h || !Q) return CMDG_ERR_INVALID;
     DevGuard guard_(h->eng);
     return set_err(h, h->eng->launch_entropy(Q, beta, eta));
-}
-
-// what a DGFVModel handle adds to init(): exchanges packed / unpacked as the reference does, and
-// element lists that are whole stacks, bottom element first
-int EngineBase::init_fv()
-{
-    reference_halo = true;
-    const int nv = fv_nvert;
-    // (fv.h fv_lds_bytes: primitives, face fluxes and cell weights of one stack)
-    if (sizeof(double) * NQ * NQ * ((size_t)ns * nv + (size_t)ns * (nv + 1) + nv) > 64 * 1024)
-        return fail(CMDG_ERR_UNSUPPORTED, "cmdg_create_dgfv: a stack of this height does not fit the 64 KiB of LDS "
-                                          "the finite-volume pass stages it in");
-    for (int which = 0; which < 2; ++which) {
-        const int64_t n = which ? nexterior : ninterior;
-        if (n == 0) continue;
-        std::vector<int64_t> h((size_t)n);
-        HIPCHK(hipMemcpy(h.data(), which ? d_exterior_user : d_interior_user, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
-        bool ok = n % nv == 0;
-        for (int64_t i = 0; ok && i < n; ++i)
-            ok = h[i] >= 1 && h[i] <= nreal && (h[i] - 1) % nv == i % nv && (i % nv == 0 || h[i] == h[i - 1] + 1);
-        if (!ok)
-            return fail(CMDG_ERR_INVALID, "cmdg_create_dgfv: interiorelems / exteriorelems must list whole stacks, "
-                                          "bottom element first");
-    }
-    return CMDG_OK;
-}
-
-int cmdg_destroy(cmdg_handle h)
-{
-    if (!h) return CMDG_ERR_INVALID;
-    {
-        DevGuard guard_(h->eng);
-        // handles whose hooks evaluate this one as their nested operator cannot evaluate any more
-        // (they would compute something else than the law they were given): their next evaluation
-        // fails until cmdg_set_rhs_hooks gives them new hooks; the nested operator of this handle
-        // forgets its parent
-        for (EngineBase *parent : h->eng->nested_in) {
-            parent->synchronize();
-            parent->hooks.pre_rhs_handle = nullptr;
-            parent->hooks_orphaned = true;
-        }
-        if (h->eng->has_hooks && h->eng->hooks.pre_rhs_handle && h->eng->hooks.pre_rhs_handle->eng) {
-            auto &v = h->eng->hooks.pre_rhs_handle->eng->nested_in;
-            v.erase(std::remove(v.begin(), v.end(), h->eng), v.end());
-        }
-        // members of a local group keep pointers to each other: detach the survivors
-        for (EngineBase *peer : h->eng->group)
-            if (peer && peer != h->eng) {
-                peer->group.clear();
-                peer->transport = TRANSPORT_NONE;
-            }
-        reduce_release(h->eng);
-        delete h->eng;
-    }
-    delete h;
-    return CMDG_OK;
-}
-
-const char *cmdg_last_error(cmdg_handle h)
-{
-    if (!h) return g_create_err.c_str();
-    return h->err.c_str();
 }
 
 int cmdg_rhs_async(cmdg_handle h, double *tendency, double *Q, double t, double alpha, double beta)
@@ -1505,124 +1017,6 @@ int cmdg_export_gradient_flux(cmdg_handle h, double *dst)
     return set_err(h, h->eng->export_gradflux(dst));
 }
 
-int cmdg_halo_begin(cmdg_handle h, double *array, int32_t nstate)
-{
-    if (!h || !array) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    h->eng->invalidate_sends();  // the caller's array: always packed
-    return set_err(h, h->eng->halo_begin(SLOT_Q, array, nstate));
-}
-int cmdg_halo_end(cmdg_handle h, double *array, int32_t nstate)
-{
-    if (!h || !array) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    return set_err(h, h->eng->halo_end(SLOT_Q, array, nstate));
-}
-
-int cmdg_fillsendbuf(double *sendbuf, const double *buf, const int64_t *vmapsend, int64_t nvmap,
-                     int32_t Np, int32_t nstate)
-{
-    if (!sendbuf || !buf || !vmapsend || nvmap < 0 || Np < 1 || nstate < 1) return CMDG_ERR_INVALID;
-    if (nvmap == 0) return CMDG_OK;
-    const int64_t n = nvmap * nstate;
-    hipLaunchKernelGGL(k_fillsendbuf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, sendbuf, buf,
-                       vmapsend, nvmap, Np, nstate, nstate);
-    return hipGetLastError() == hipSuccess && hipStreamSynchronize(0) == hipSuccess ? CMDG_OK : CMDG_ERR_HIP;
-}
-
-int cmdg_transferrecvbuf(double *buf, const double *recvbuf, const int64_t *vmaprecv,
-                         int64_t nvmap, int32_t Np, int32_t nstate)
-{
-    if (!buf || !recvbuf || !vmaprecv || nvmap < 0 || Np < 1 || nstate < 1) return CMDG_ERR_INVALID;
-    if (nvmap == 0) return CMDG_OK;
-    const int64_t n = nvmap * nstate;
-    hipLaunchKernelGGL(k_transferrecvbuf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, buf,
-                       recvbuf, vmaprecv, nvmap, Np, nstate, nstate);
-    return hipGetLastError() == hipSuccess && hipStreamSynchronize(0) == hipSuccess ? CMDG_OK : CMDG_ERR_HIP;
-}
-
-int cmdg_comm_unique_id(void *out128)
-{
-    std::string err;
-    if (!out128) return CMDG_ERR_INVALID;
-    if (!rccl::load(err)) {
-        g_create_err = err;
-        return CMDG_ERR_COMM;
-    }
-    rccl::uid_t id;
-    if (rccl::GetUniqueId(&id)) return CMDG_ERR_COMM;
-    memcpy(out128, &id, sizeof(id));
-    return CMDG_OK;
-}
-
-int cmdg_comm_init_rccl(cmdg_handle h, const void *unique_id128, int32_t rank, int32_t nranks)
-{
-    if (!h || !unique_id128 || rank < 0 || rank >= nranks) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    EngineBase *e = h->eng;
-    if (!rccl::load(e->err)) return set_err(h, CMDG_ERR_COMM);
-    rccl::uid_t id;
-    memcpy(&id, unique_id128, sizeof(id));
-    if (int rc = rccl::CommInitRank(&e->nccl_comm, nranks, id, rank))
-        return set_err(h, e->fail(CMDG_ERR_COMM, std::string("ncclCommInitRank: ") +
-                                                   rccl::GetErrorString(rc)));
-    e->transport = TRANSPORT_RCCL;
-    e->rank = rank;
-    e->nranks = nranks;
-    return CMDG_OK;
-}
-
-int cmdg_comm_selftest(cmdg_handle h, int64_t count)
-{
-    if (!h || count < 1) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    EngineBase *e = h->eng;
-    if (e->transport != TRANSPORT_RCCL || !e->nccl_comm)
-        return set_err(h, e->fail(CMDG_ERR_COMM, "selftest: RCCL transport not initialised"));
-    DevBuf<double> src, dst;
-    std::vector<double> host((size_t)count), back((size_t)count, -1.0);
-    for (int64_t i = 0; i < count; ++i) host[i] = 0.5 * (double)i + 1e-3 * e->rank;
-    int rc = CMDG_OK;
-    if (src.alloc(count) != hipSuccess || dst.alloc(count) != hipSuccess)
-        rc = e->fail(CMDG_ERR_HIP, "selftest: hipMalloc failed");
-    if (!rc && hipMemcpy(src, host.data(), sizeof(double) * count, hipMemcpyHostToDevice) != hipSuccess)
-        rc = e->fail(CMDG_ERR_HIP, "selftest: upload failed");
-    if (!rc) {
-        int n = rccl::GroupStart();
-        if (!n) n = rccl::Recv(dst, (size_t)count, rccl::kDouble, e->rank, e->nccl_comm, e->s_comm);
-        if (!n) n = rccl::Send(src, (size_t)count, rccl::kDouble, e->rank, e->nccl_comm, e->s_comm);
-        int g = rccl::GroupEnd();
-        if (n || g) rc = e->fail(CMDG_ERR_COMM, std::string("selftest: ") + rccl::GetErrorString(n ? n : g));
-    }
-    if (!rc && hipStreamSynchronize(e->s_comm) != hipSuccess) rc = e->fail(CMDG_ERR_HIP, "selftest: sync failed");
-    if (!rc && hipMemcpy(back.data(), dst, sizeof(double) * count, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = e->fail(CMDG_ERR_HIP, "selftest: download failed");
-    if (!rc && memcmp(back.data(), host.data(), sizeof(double) * count) != 0)
-        rc = e->fail(CMDG_ERR_COMM, "selftest: payload mismatch");
-    return set_err(h, rc);
-}
-
-int cmdg_comm_connect_local(cmdg_handle *handles, int32_t n)
-{
-    GroupCall gc(handles, n);
-    if (!gc.ok()) return CMDG_ERR_INVALID;
-    std::vector<EngineBase *> g;
-    for (int i = 0; i < n; ++i) {
-        g.push_back(handles[i]->eng);
-        if (g[i]->dev != g[0]->dev)
-            return gc.finish(g[i]->fail(CMDG_ERR_INVALID, "local transport: the handles of a group live on one device"));
-    }
-    for (int i = 0; i < n; ++i) {
-        g[i]->group = g;
-        g[i]->rank = i;
-        g[i]->nranks = n;
-        g[i]->transport = TRANSPORT_LOCAL;
-        for (int r : g[i]->nabrtorank)
-            if (r < 0 || r >= n) return gc.finish(g[i]->fail(CMDG_ERR_COMM, "neighbour rank outside the local group"));
-    }
-    return CMDG_OK;
-}
-
 int cmdg_group_rhs(cmdg_handle *handles, int32_t n, double **tendency, double **Q, double t,
                    double alpha, double beta)
 {
@@ -1644,23 +1038,6 @@ int cmdg_group_rhs(cmdg_handle *handles, int32_t n, double **tendency, double **
     return gc.finish(group_rhs(g, c));
 }
 
-int cmdg_group_halo(cmdg_handle *handles, int32_t n, double **arrays, int32_t nstate)
-{
-    if (!arrays) return CMDG_ERR_INVALID;
-    for (int i = 0; i < n; ++i)
-        if (!arrays[i]) return CMDG_ERR_INVALID;
-    GroupCall gc(handles, n);
-    if (!gc.ok()) return CMDG_ERR_INVALID;
-    for (int i = 0; i < n; ++i) handles[i]->eng->invalidate_sends();
-    for (int i = 0; i < n; ++i)
-        if (int r = handles[i]->eng->halo_begin(SLOT_Q, arrays[i], nstate)) return gc.finish(r);
-    for (int i = 0; i < n; ++i)
-        if (int r = handles[i]->eng->halo_end(SLOT_Q, arrays[i], nstate)) return gc.finish(r);
-    for (int i = 0; i < n; ++i)
-        if (int r = handles[i]->eng->synchronize()) return gc.finish(r);
-    return CMDG_OK;
-}
-
 int cmdg_norm2_local(cmdg_handle h, const double *A, int32_t nstate, int32_t weighted,
                      double *out_host)
 {
@@ -1674,95 +1051,6 @@ int cmdg_distance2_local(cmdg_handle h, const double *A, const double *B, int32_
     if (!h || !A || !B || !out_host) return CMDG_ERR_INVALID;
     DevGuard guard_(h->eng);
     return set_err(h, h->eng->wsum2(A, B, nstate, 1, out_host));
-}
-
-// this rank's nout (hi, lo) pairs into host (the engine's device current)
-static int reduce_to_host(EngineBase *e, const cmdg_reduce_desc *d, const double *A, const double *B,
-                          double *host)
-{
-    const double *r = nullptr;
-    double *stage = nullptr;
-    const size_t n = 2 * (size_t)reduce_nout(d);
-    if (int rc = reduce_device(e, d, A, B, &r)) return rc;
-    if (int rc = reduce_host_buffer(e, n, &stage)) return rc;
-    if (hipMemcpyAsync(stage, r, sizeof(double) * n, hipMemcpyDeviceToHost, e->s_comp) != hipSuccess ||
-        hipStreamSynchronize(e->s_comp) != hipSuccess)
-        return e->fail(CMDG_ERR_HIP, "reduce: copy of the partials failed");
-    memcpy(host, stage, sizeof(double) * n);
-    return CMDG_OK;
-}
-
-int cmdg_reduce_local(cmdg_handle h, const cmdg_reduce_desc *d, const double *A, const double *B,
-                      double *partials_host)
-{
-    if (!h || !partials_host) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    return set_err(h, reduce_to_host(h->eng, d, A, B, partials_host));
-}
-
-int cmdg_reduce_combine(const cmdg_reduce_desc *d, const double *partials, int32_t nranks, double *out)
-{
-    std::string err;
-    const int r = reduce_combine(d, partials, nranks, out, err);
-    if (r) g_create_err = "cmdg_reduce_combine: " + err;
-    return r;
-}
-
-int cmdg_reduce(cmdg_handle h, const cmdg_reduce_desc *d, const double *A, const double *B,
-                double *out_host)
-{
-    if (!h || !out_host) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    EngineBase *e = h->eng;
-    if (e->transport == TRANSPORT_LOCAL && e->nranks > 1)
-        return set_err(h, e->fail(CMDG_ERR_INVALID, "cmdg_reduce: the handle is one rank of a local-transport "
-                                                    "group; reduce the group with cmdg_group_reduce"));
-    std::string err;
-    if (reduce_check(d, err)) return set_err(h, e->fail(CMDG_ERR_INVALID, err));
-    const int nout = reduce_nout(d);
-    const int nranks = e->transport == TRANSPORT_RCCL && e->nccl_comm ? e->nranks : 1;
-    std::vector<double> parts(2 * (size_t)nout * nranks);
-    if (nranks == 1 && e->transport != TRANSPORT_RCCL) {
-        if (int r = reduce_to_host(e, d, A, B, parts.data())) return set_err(h, r);
-    } else {  // every rank's partials, in rank order, on every rank
-        const double *r = nullptr;
-        double *gath = nullptr, *stage = nullptr;
-        if (int rc = reduce_device(e, d, A, B, &r)) return set_err(h, rc);
-        if (int rc = reduce_gather_buffer(e, parts.size(), &gath)) return set_err(h, rc);
-        if (int rc = reduce_host_buffer(e, parts.size(), &stage)) return set_err(h, rc);
-        if (int rc = rccl::AllGather(r, gath, 2 * (size_t)nout, rccl::kDouble, e->nccl_comm, e->s_comp))
-            return set_err(h, e->fail(CMDG_ERR_COMM, std::string("reduce: ncclAllGather: ") + rccl::GetErrorString(rc)));
-        if (hipMemcpyAsync(stage, gath, sizeof(double) * parts.size(), hipMemcpyDeviceToHost, e->s_comp) != hipSuccess ||
-            hipStreamSynchronize(e->s_comp) != hipSuccess)
-            return set_err(h, e->fail(CMDG_ERR_HIP, "reduce: copy of the gathered partials failed"));
-        memcpy(parts.data(), stage, sizeof(double) * parts.size());
-    }
-    if (reduce_combine(d, parts.data(), nranks, out_host, err)) return set_err(h, e->fail(CMDG_ERR_INVALID, err));
-    return CMDG_OK;
-}
-
-int cmdg_group_reduce(cmdg_handle *handles, int32_t n, const cmdg_reduce_desc *d, const double **A,
-                      const double **B, double *out_host)
-{
-    if (!A || !out_host) return CMDG_ERR_INVALID;
-    GroupCall gc(handles, n);
-    if (!gc.ok()) return CMDG_ERR_INVALID;
-    EngineBase *e0 = handles[0]->eng;
-    for (int i = 0; i < n; ++i) {
-        EngineBase *e = handles[i]->eng;
-        if (n > 1 && (e->transport != TRANSPORT_LOCAL || e->nranks != n || e->rank != i))
-            return gc.finish(e->fail(CMDG_ERR_INVALID, "cmdg_group_reduce: handle i must be rank i of "
-                                                       "one group of n connected with cmdg_comm_connect_local"));
-    }
-    std::string err;
-    if (reduce_check(d, err)) return gc.finish(e0->fail(CMDG_ERR_INVALID, err));
-    const size_t per = 2 * (size_t)reduce_nout(d);
-    std::vector<double> parts(per * n);
-    for (int i = 0; i < n; ++i)
-        if (int r = reduce_to_host(handles[i]->eng, d, A[i], B ? B[i] : nullptr, parts.data() + per * i))
-            return gc.finish(r);
-    if (reduce_combine(d, parts.data(), n, out_host, err)) return gc.finish(e0->fail(CMDG_ERR_INVALID, err));
-    return CMDG_OK;
 }
 
 int cmdg_courant(cmdg_handle h, int32_t kind, const double *Q, double dt, double simtime,
@@ -1784,186 +1072,6 @@ int cmdg_min_node_distance(cmdg_handle h, int32_t direction, double *out_host)
         return set_err(h, h->eng->fail(CMDG_ERR_UNSUPPORTED, "min_node_distance: on a DGFVModel handle the vertical "
                                                              "distance is the cell height 2 JcV; use the host grid's"));
     return set_err(h, h->eng->courant(0, 0, nullptr, 0.0, 0.0, direction, out_host));
-}
-
-int cmdg_indefinite_stack_integral(cmdg_handle h, const double *Q, int32_t nstate, double *aux,
-                                   int32_t naux, int32_t nvertelem, const double *Imat,
-                                   const cmdg_stack_integral_desc *d)
-{
-    if (!h || !aux || !d || naux < 1) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    return set_err(h, h->eng->stack_integral(false, Q, nstate, aux, naux, nvertelem, Imat, d));
-}
-
-int cmdg_reverse_indefinite_stack_integral(cmdg_handle h, double *aux, int32_t naux,
-                                           int32_t nvertelem, const cmdg_stack_integral_desc *d)
-{
-    if (!h || !aux || !d || naux < 1) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    return set_err(h, h->eng->stack_integral(true, nullptr, 0, aux, naux, nvertelem, nullptr, d));
-}
-
-int cmdg_filter_create(cmdg_handle h, const cmdg_filter_desc *d, cmdg_filter *out)
-{
-    if (!h || !d || !out) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    FilterObj *f = nullptr;
-    int r = h->eng->filter_create(d, &f);
-    *out = reinterpret_cast<cmdg_filter>(f);
-    return set_err(h, r);
-}
-
-int cmdg_filter_destroy(cmdg_handle h, cmdg_filter f)
-{
-    if (!h || !f) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    EngineBase *e = h->eng;
-    FilterObj *o = reinterpret_cast<FilterObj *>(f);
-    e->synchronize();
-    if (e->gradient_filter == o) e->gradient_filter = nullptr;
-    if (e->tendency_filter == o) e->tendency_filter = nullptr;
-    if (e->step_filter == o) e->step_filter = nullptr;
-    // a recorded update_auxiliary_state! composition may name this filter: drop it from there
-    {
-        int k = 0;
-        for (int i = 0; i < e->hooks.npre; ++i)
-            if (e->hooks.pre_filter[i] != f) e->hooks.pre_filter[k++] = e->hooks.pre_filter[i];
-        e->hooks.npre = k;
-    }
-    delete o;
-    return CMDG_OK;
-}
-
-int cmdg_filter_apply(cmdg_handle h, cmdg_filter f, double *Q, int32_t nstate)
-{
-    if (!h || !f || !Q || nstate < 1) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    return set_err(h, h->eng->filter_apply(reinterpret_cast<FilterObj *>(f), Q, nstate));
-}
-
-// ---- interpolation (interpolation.hip) ------------------------------------------------------
-namespace {
-// the device of an interpolation object made current for a call without a handle
-struct InterpDevice {
-    int prev = -1;
-    bool changed = false;
-    explicit InterpDevice(int dev)
-    {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = hipSetDevice(dev) == hipSuccess;
-    }
-    ~InterpDevice()
-    {
-        if (changed) (void)hipSetDevice(prev);
-    }
-};
-// one epilogue: the message goes to the handle, or to cmdg_last_error(NULL) without one
-int interp_done(cmdg_handle h, int r, const std::string &err)
-{
-    if (r == CMDG_OK) return r;
-    if (h) return set_err(h, h->eng->fail(r, err));
-    g_create_err = err;
-    return r;
-}
-}  // namespace
-
-int cmdg_interp_create(cmdg_handle h, const cmdg_interp_desc *d, cmdg_interp *out)
-{
-    if (!d || !out) return CMDG_ERR_INVALID;
-    std::optional<DevGuard> guard_;
-    if (h) guard_.emplace(h->eng);
-    InterpObj *o = nullptr;
-    std::string err;
-    const int r = interp_create(d, &o, err);
-    *out = reinterpret_cast<cmdg_interp>(o);
-    return interp_done(h, r, err);
-}
-
-int cmdg_interp_destroy(cmdg_handle h, cmdg_interp it)
-{
-    if (!it) return CMDG_ERR_INVALID;
-    InterpObj *o = reinterpret_cast<InterpObj *>(it);
-    std::optional<DevGuard> guard_;
-    if (h) {
-        guard_.emplace(h->eng);
-        h->eng->synchronize();
-    }
-    InterpDevice dev_(interp_device(o));
-    (void)hipStreamSynchronize(nullptr);  // (calls without a handle have returned; see include/cmdg.h)
-    interp_destroy(o);
-    return CMDG_OK;
-}
-
-int cmdg_interp_apply(cmdg_handle h, cmdg_interp it, const double *Q, int32_t nstate, int64_t nelemQ, double *v)
-{
-    if (!it || !Q || !v || nstate < 1) return CMDG_ERR_INVALID;
-    const InterpObj *o = reinterpret_cast<const InterpObj *>(it);
-    std::optional<DevGuard> guard_;
-    if (h) guard_.emplace(h->eng);
-    std::string err;
-    if (h && h->eng->dev != interp_device(o))
-        return interp_done(h, CMDG_ERR_INVALID, "cmdg_interp_apply: the object lives on another device than the handle");
-    InterpDevice dev_(interp_device(o));
-    return interp_done(h, interp_apply(o, Q, nstate, nelemQ, v, h ? h->eng->s_comp : nullptr, !h, err), err);
-}
-
-int cmdg_interp_project(cmdg_handle h, cmdg_interp it, double *v, int32_t nstate, const int32_t uvwi[3])
-{
-    if (!it || !v || !uvwi || nstate < 1) return CMDG_ERR_INVALID;
-    const InterpObj *o = reinterpret_cast<const InterpObj *>(it);
-    std::optional<DevGuard> guard_;
-    if (h) guard_.emplace(h->eng);
-    std::string err;
-    if (h && h->eng->dev != interp_device(o))
-        return interp_done(h, CMDG_ERR_INVALID, "cmdg_interp_project: the object lives on another device than the handle");
-    InterpDevice dev_(interp_device(o));
-    return interp_done(h, interp_project(o, v, nstate, uvwi, h ? h->eng->s_comp : nullptr, !h, err), err);
-}
-
-int cmdg_interp_scatter(cmdg_handle h, const cmdg_interp *its, int32_t n, const double *const *v, int32_t nstate,
-                        double *fiv)
-{
-    if (!its || !v || !fiv || n < 1 || nstate < 1) return CMDG_ERR_INVALID;
-    for (int i = 0; i < n; ++i)
-        if (!its[i]) return CMDG_ERR_INVALID;
-    const InterpObj *const *o = reinterpret_cast<const InterpObj *const *>(its);
-    std::optional<DevGuard> guard_;
-    if (h) guard_.emplace(h->eng);
-    std::string err;
-    if (h && h->eng->dev != interp_device(o[0]))
-        return interp_done(h, CMDG_ERR_INVALID, "cmdg_interp_scatter: the objects live on another device than the handle");
-    InterpDevice dev_(interp_device(o[0]));
-    return interp_done(h, interp_scatter(o, n, v, nstate, fiv, h ? h->eng->s_comp : nullptr, !h, err), err);
-}
-
-int cmdg_set_filters(cmdg_handle h, cmdg_filter gradient_filter, cmdg_filter tendency_filter,
-                     cmdg_filter step_filter)
-{
-    if (!h) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    EngineBase *e = h->eng;
-    auto *gfl = reinterpret_cast<FilterObj *>(gradient_filter);
-    auto *tfl = reinterpret_cast<FilterObj *>(tendency_filter);
-    for (FilterObj *o : {gfl, tfl})
-        if (o && o->target != CMDG_TARGET_INDICES)
-            return set_err(h, e->fail(CMDG_ERR_INVALID, "gradient/tendency filters take FilterIndices targets"));
-    // filters decide which streams the next evaluation's launches go to: start it from a clean slate
-    if (int r = e->synchronize()) return set_err(h, r);
-    e->invalidate_sends();
-    e->drop_graph();
-    e->gradient_filter = gfl;
-    e->tendency_filter = tfl;
-    e->step_filter = reinterpret_cast<FilterObj *>(step_filter);
-    return CMDG_OK;
-}
-
-int cmdg_set_rhs_hooks(cmdg_handle h, const cmdg_rhs_hooks *hooks)
-{
-    if (!h) return CMDG_ERR_INVALID;
-    DevGuard guard_(h->eng);
-    if (int r = h->eng->synchronize()) return set_err(h, r);  // (hooks change the stream layout too)
-    h->eng->invalidate_sends();
-    h->eng->drop_graph();
-    return set_err(h, h->eng->set_hooks(hooks));
 }
 
 int cmdg_profile_enable(cmdg_handle h, int32_t on)

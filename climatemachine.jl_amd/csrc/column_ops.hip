@@ -6,6 +6,7 @@
 
 #include "stepping.h"
 #include "columns.h"
+#include "filters.h"
 #include "with_constant.h"
 
 namespace cmdg {
@@ -538,3 +539,95 @@ int EngineBase::filter_apply(const FilterObj *f, double *Q, int nstate)
 }
 
 }  // namespace cmdg
+
+using namespace cmdg;
+
+extern "C" {
+
+int cmdg_indefinite_stack_integral(cmdg_handle h, const double *Q, int32_t nstate, double *aux,
+                                   int32_t naux, int32_t nvertelem, const double *Imat,
+                                   const cmdg_stack_integral_desc *d)
+{
+    if (!h || !aux || !d || naux < 1) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    return set_err(h, h->eng->stack_integral(false, Q, nstate, aux, naux, nvertelem, Imat, d));
+}
+
+int cmdg_reverse_indefinite_stack_integral(cmdg_handle h, double *aux, int32_t naux,
+                                           int32_t nvertelem, const cmdg_stack_integral_desc *d)
+{
+    if (!h || !aux || !d || naux < 1) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    return set_err(h, h->eng->stack_integral(true, nullptr, 0, aux, naux, nvertelem, nullptr, d));
+}
+
+int cmdg_filter_create(cmdg_handle h, const cmdg_filter_desc *d, cmdg_filter *out)
+{
+    if (!h || !d || !out) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    FilterObj *f = nullptr;
+    int r = h->eng->filter_create(d, &f);
+    *out = reinterpret_cast<cmdg_filter>(f);
+    return set_err(h, r);
+}
+
+int cmdg_filter_destroy(cmdg_handle h, cmdg_filter f)
+{
+    if (!h || !f) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    EngineBase *e = h->eng;
+    FilterObj *o = reinterpret_cast<FilterObj *>(f);
+    e->synchronize();
+    if (e->gradient_filter == o) e->gradient_filter = nullptr;
+    if (e->tendency_filter == o) e->tendency_filter = nullptr;
+    if (e->step_filter == o) e->step_filter = nullptr;
+    // a recorded update_auxiliary_state! composition may name this filter: drop it from there
+    {
+        int k = 0;
+        for (int i = 0; i < e->hooks.npre; ++i)
+            if (e->hooks.pre_filter[i] != f) e->hooks.pre_filter[k++] = e->hooks.pre_filter[i];
+        e->hooks.npre = k;
+    }
+    delete o;
+    return CMDG_OK;
+}
+
+int cmdg_filter_apply(cmdg_handle h, cmdg_filter f, double *Q, int32_t nstate)
+{
+    if (!h || !f || !Q || nstate < 1) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    return set_err(h, h->eng->filter_apply(reinterpret_cast<FilterObj *>(f), Q, nstate));
+}
+
+int cmdg_set_filters(cmdg_handle h, cmdg_filter gradient_filter, cmdg_filter tendency_filter,
+                     cmdg_filter step_filter)
+{
+    if (!h) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    EngineBase *e = h->eng;
+    auto *gfl = reinterpret_cast<FilterObj *>(gradient_filter);
+    auto *tfl = reinterpret_cast<FilterObj *>(tendency_filter);
+    for (FilterObj *o : {gfl, tfl})
+        if (o && o->target != CMDG_TARGET_INDICES)
+            return set_err(h, e->fail(CMDG_ERR_INVALID, "gradient/tendency filters take FilterIndices targets"));
+    // filters decide which streams the next evaluation's launches go to: start it from a clean slate
+    if (int r = e->synchronize()) return set_err(h, r);
+    e->invalidate_sends();
+    e->drop_graph();
+    e->gradient_filter = gfl;
+    e->tendency_filter = tfl;
+    e->step_filter = reinterpret_cast<FilterObj *>(step_filter);
+    return CMDG_OK;
+}
+
+int cmdg_set_rhs_hooks(cmdg_handle h, const cmdg_rhs_hooks *hooks)
+{
+    if (!h) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    if (int r = h->eng->synchronize()) return set_err(h, r);  // (hooks change the stream layout too)
+    h->eng->invalidate_sends();
+    h->eng->drop_graph();
+    return set_err(h, h->eng->set_hooks(hooks));
+}
+
+}  // extern "C"

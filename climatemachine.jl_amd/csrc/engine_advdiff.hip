@@ -1,6 +1,8 @@
 // Engine instantiations for the AdvectionDiffusion law (physics_advdiff.h).
 #include "engine_fv.h"
+#include "laws.h"
 #include "physics_advdiff.h"
+#include "with_constant.h"
 
 namespace cmdg {
 
@@ -47,18 +49,10 @@ EngineBase *make_engine_advdiff(const cmdg_desc *d, std::string &err)
               "advection + diffusion";
         return nullptr;
     }
-    switch (d->N[0]) {  // NQ = N + 1 is a template parameter of every kernel
-    case 1: return pick<2>(d, err);
-    case 2: return pick<3>(d, err);
-    case 3: return pick<4>(d, err);
-    case 4: return pick<5>(d, err);
-    case 5: return pick<6>(d, err);
-    case 6: return pick<7>(d, err);
-    case 7: return pick<8>(d, err);
-    default:
+    EngineBase *e = nullptr;  // NQ = N + 1 is a template parameter of every kernel
+    if (!with_constant<1, 7>(d->N[0], [&](auto n) { e = pick<n() + 1>(d, err); }))
         err = "AdvectionDiffusion: polynomial order not compiled in (have N = 1..7)";
-        return nullptr;
-    }
+    return e;
 }
 
 // DGFVModel handles: advection, and advection + diffusion, at N_h = 4 and N_h = 1

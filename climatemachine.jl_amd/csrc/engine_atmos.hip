@@ -1,6 +1,8 @@
 // Engine instantiations for the dry atmosphere law (physics_atmos.h).
 #include "engine.h"
+#include "laws.h"
 #include "physics_atmos.h"
+#include "with_constant.h"
 
 namespace cmdg {
 
@@ -82,17 +84,12 @@ EngineBase *make_engine_atmos(const cmdg_desc *d, std::string &err)
         err = "DryAtmos: hyperdiffusion needs an orientation";
         return nullptr;
     }
-    switch (d->N[0]) {  // element-per-workgroup kernels: one element's working set lives in LDS
-                        // (N = 6 with hyperdiffusion: 90 KB of the CU's 160 KB)
-    case 2: return pick<3>(d, err);
-    case 3: return pick<4>(d, err);
-    case 4: return pick<5>(d, err);
-    case 5: return pick<6>(d, err);
-    case 6: return pick<7>(d, err);
-    default:
+    // element-per-workgroup kernels: one element's working set lives in LDS (N = 6 with
+    // hyperdiffusion: 90 KB of the CU's 160 KB)
+    EngineBase *e = nullptr;
+    if (!with_constant<2, 6>(d->N[0], [&](auto n) { e = pick<n() + 1>(d, err); }))
         err = "DryAtmos: polynomial order not compiled in (have N = 2..6)";
-        return nullptr;
-    }
+    return e;
 }
 
 }  // namespace cmdg

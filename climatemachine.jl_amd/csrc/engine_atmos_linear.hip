@@ -4,6 +4,7 @@
 // SmagorinskyLilly add one column each.  Of the moist LES law (CMDG_PHYSICS_MOIST_LINEAR_AG) it is
 // always MoistAtmos's 19, at the orders the moist law is compiled for.
 #include "engine.h"
+#include "laws.h"
 #include "physics_atmos_linear.h"
 
 namespace cmdg {

@@ -6,6 +6,7 @@
 // whose volume launches read no ghost and commute with the end of the exchange.  The tendency of
 // either list is the one launch of esdg.h.
 #include "engine.h"
+#include "laws.h"
 #include "esdg.h"
 
 namespace cmdg {

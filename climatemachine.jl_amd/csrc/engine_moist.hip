@@ -1,5 +1,6 @@
 // Engine instantiations for the moist LES law (physics_moist.h).
 #include "engine.h"
+#include "laws.h"
 #include "physics_moist.h"
 
 namespace cmdg {

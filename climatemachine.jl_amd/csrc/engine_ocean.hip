@@ -1,35 +1,42 @@
 // Engine instantiations for the hydrostatic Boussinesq ocean law (physics_ocean.h) and the
 // PressureGradientModel used by the reference-state initialisation (physics_pgrad.h).
 #include "engine.h"
+#include "laws.h"
 #include "physics_ocean.h"
 #include "physics_ocean01.h"
 #include "physics_pgrad.h"
 #include "physics_sw.h"
+#include "with_constant.h"
 
 namespace cmdg {
 
-int counts_ocean(const int32_t *, int32_t out[6])
+// a law whose functor fixes its counts (no gradient-Laplacian or hyperdiffusive states)
+template <class P>
+static int law_counts(int32_t out[6])
 {
-    out[0] = HydroBoussinesq::NS;
-    out[1] = HydroBoussinesq::NAUX;
-    out[2] = HydroBoussinesq::NGRAD;
-    out[3] = HydroBoussinesq::NGF;
-    out[4] = 0;
-    out[5] = 0;
+    out[0] = P::NS;
+    out[1] = P::NAUX;
+    out[2] = P::NGRAD;
+    out[3] = P::NGF;
+    out[4] = out[5] = 0;
     return CMDG_OK;
 }
 
+// make_engine<P, N + 1> for LO <= N <= HI (NQ = N + 1 is a template parameter of every kernel)
+template <class P, int LO, int HI>
+static EngineBase *make_for_order(const cmdg_desc *d, std::string &err, const char *refusal)
+{
+    EngineBase *e = nullptr;
+    if (!with_constant<LO, HI>(d->N[0], [&](auto n) { e = make_engine<P, n() + 1>(d); })) err = refusal;
+    return e;
+}
+
+int counts_ocean(const int32_t *, int32_t out[6]) { return law_counts<HydroBoussinesq>(out); }
+
 EngineBase *make_engine_ocean(const cmdg_desc *d, std::string &err)
 {
-    switch (d->N[0]) {
-    case 2: return make_engine<HydroBoussinesq, 3>(d);
-    case 3: return make_engine<HydroBoussinesq, 4>(d);
-    case 4: return make_engine<HydroBoussinesq, 5>(d);
-    case 5: return make_engine<HydroBoussinesq, 6>(d);
-    default:
-        err = "HydrostaticBoussinesq: polynomial order not compiled in (have N = 2..5)";
-        return nullptr;
-    }
+    return make_for_order<HydroBoussinesq, 2, 5>(
+        d, err, "HydrostaticBoussinesq: polynomial order not compiled in (have N = 2..5)");
 }
 
 int counts_sw(const int32_t *ip, int32_t out[6])
@@ -56,37 +63,15 @@ EngineBase *make_engine_sw(const cmdg_desc *d, std::string &err)
         err = "ShallowWaterModel: mixed polynomial orders compiled in: (4, 1)";
         return nullptr;
     }
-    switch (d->N[0]) {
-    case 2: return make_engine<ShallowWater, 3>(d);
-    case 3: return make_engine<ShallowWater, 4>(d);
-    case 4: return make_engine<ShallowWater, 5>(d);
-    case 5: return make_engine<ShallowWater, 6>(d);
-    default:
-        err = "ShallowWaterModel: polynomial order not compiled in (have N = 2..5)";
-        return nullptr;
-    }
+    return make_for_order<ShallowWater, 2, 5>(
+        d, err, "ShallowWaterModel: polynomial order not compiled in (have N = 2..5)");
 }
 
 // src/Ocean/SplitExplicit01: OceanModel, Continuity3dModel, BarotropicModel (N = 4, the order
 // of its reference tests; the barotropic model also with two nodes along the extrusion)
-template <class P>
-static void se01_counts(int32_t out[6])
-{
-    out[0] = P::NS;
-    out[1] = P::NAUX;
-    out[2] = P::NGRAD;
-    out[3] = P::NGF;
-    out[4] = out[5] = 0;
-}
-int counts_se01(int32_t physics_id, int32_t out[6])
-{
-    switch (physics_id) {
-    case CMDG_PHYSICS_OCEAN_SE01: se01_counts<OceanSE01>(out); return CMDG_OK;
-    case CMDG_PHYSICS_CONTINUITY3D_SE01: se01_counts<Continuity3dSE01>(out); return CMDG_OK;
-    case CMDG_PHYSICS_BAROTROPIC_SE01: se01_counts<BarotropicSE01>(out); return CMDG_OK;
-    default: return CMDG_ERR_UNSUPPORTED;
-    }
-}
+int counts_ocean_se01(const int32_t *, int32_t out[6]) { return law_counts<OceanSE01>(out); }
+int counts_continuity3d_se01(const int32_t *, int32_t out[6]) { return law_counts<Continuity3dSE01>(out); }
+int counts_barotropic_se01(const int32_t *, int32_t out[6]) { return law_counts<BarotropicSE01>(out); }
 
 EngineBase *make_engine_se01(const cmdg_desc *d, std::string &err)
 {
@@ -118,18 +103,8 @@ int counts_pgrad(const int32_t *, int32_t out[6])
 
 EngineBase *make_engine_pgrad(const cmdg_desc *d, std::string &err)
 {
-    switch (d->N[0]) {
-    case 1: return make_engine<PressureGradient, 2>(d);
-    case 2: return make_engine<PressureGradient, 3>(d);
-    case 3: return make_engine<PressureGradient, 4>(d);
-    case 4: return make_engine<PressureGradient, 5>(d);
-    case 5: return make_engine<PressureGradient, 6>(d);
-    case 6: return make_engine<PressureGradient, 7>(d);
-    case 7: return make_engine<PressureGradient, 8>(d);
-    default:
-        err = "PressureGradientModel: polynomial order not compiled in (have N = 1..7)";
-        return nullptr;
-    }
+    return make_for_order<PressureGradient, 1, 7>(
+        d, err, "PressureGradientModel: polynomial order not compiled in (have N = 1..7)");
 }
 
 }  // namespace cmdg

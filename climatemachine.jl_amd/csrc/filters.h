@@ -363,16 +363,4 @@ __global__ __launch_bounds__(64) void k_apply_tmar_filter(FilterArgs a)
     }
 }
 
-// update!  LowStorageRungeKuttaMethod.jl:146-158 (used when a tendency filter sits between
-// the right-hand side and the update, so the update cannot be fused into k_tendency)
-static __global__ void k_lsrk_update(double *__restrict__ dQ, double *__restrict__ Q, double rka,
-                                     double rkb_dt, int64_t n)
-{
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        Q[i] += rkb_dt * dQ[i];
-        dQ[i] *= rka;
-    }
-}
-
 }  // namespace cmdg

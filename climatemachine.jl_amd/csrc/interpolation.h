@@ -1,5 +1,5 @@
 // Interpolation of DG states onto box and latitude-longitude grids (cmdg_interp_* of
-// include/cmdg.h); implemented in interpolation.hip, entered from cmdg.hip.
+// include/cmdg.h); implemented in interpolation.hip, which also holds those entries.
 #pragma once
 #include <hip/hip_runtime.h>
 

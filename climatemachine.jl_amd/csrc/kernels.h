@@ -131,57 +131,6 @@ __device__ __forceinline__ void face_setup(const GridDev &g, int64_t e, int t, i
     face_geometry<NQ, NQV>(g, e, t, f, n, idP, bctag, fp);
 }
 
-// One-time digest of the reference face tables (see GridDev); bad[0] collects what does not
-// hold: bit 0 vmap- is not the canonical face numbering, bit 1 sgeo's vMI is not vgeo's MI at
-// the face node, bit 2 a plus-side id does not fit 32 bits.
-static __global__ void k_face_digest(const double *__restrict__ vgeo, int nvgeo,
-                                     const double *__restrict__ sgeo,
-                                     const int64_t *__restrict__ vmapM,
-                                     const int64_t *__restrict__ vmapP,
-                                     const int64_t *__restrict__ elemtobndy, int NQ, int NQV,
-                                     int64_t nreal, int32_t *__restrict__ faceP,
-                                     double *__restrict__ faceG, int *__restrict__ bad)
-{
-    const int Np = NQ * NQ * NQV, Nfph = NQ * NQV, Nfpv = NQ * NQ;
-    const int Nfp = Nfph > Nfpv ? Nfph : Nfpv, NFT = 4 * Nfph + 2 * Nfpv;
-    const int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (I >= nreal * NFT) return;
-    const int64_t e = I / NFT;
-    const int t = (int)(I % NFT);
-    int f, n;
-    if (t < 4 * Nfph) {
-        f = t / Nfph;
-        n = t % Nfph;
-    } else {
-        f = 4 + (t - 4 * Nfph) / Nfpv;
-        n = (t - 4 * Nfph) % Nfpv;
-    }
-    const int64_t o = n + (int64_t)Nfp * (f + 6 * e);
-    const int a = n % NQ, b = n / NQ;
-    int vid;
-    switch (f) {
-    case 0: vid = NQ * (a + NQ * b); break;
-    case 1: vid = (NQ - 1) + NQ * (a + NQ * b); break;
-    case 2: vid = a + NQ * NQ * b; break;
-    case 3: vid = a + NQ * ((NQ - 1) + NQ * b); break;
-    case 4: vid = n; break;
-    default: vid = n + NQ * NQ * (NQV - 1); break;
-    }
-    int flags = 0;
-    const int64_t idM = vmapM[o] - 1;
-    if (idM != e * Np + vid) flags |= 1;
-    int64_t idP = vmapP[o] - 1;
-    if (elemtobndy[f + 6 * e] != 0) idP = e * Np + vid;  // DGModel_kernels.jl:686-692
-    if (idP < 0 || idP > 2147483647LL) flags |= 4;
-    faceP[I] = (int32_t)idP;
-    const double *sg = sgeo + 5 * o;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) faceG[((int64_t)4 * e + c) * NFT + t] = sg[c];
-    const double mi = vgeo[vid + (int64_t)Np * (VMI + (int64_t)nvgeo * e)];
-    if (!(sg[SVMI] == mi)) flags |= 2;
-    if (flags) atomicOr(bad, flags);
-}
-
 // A law may offer flux_first_order and wavespeed of one state in one call (both need the same
 // thermodynamic state; the moist law's costs a saturation adjustment): detected by the member
 // HAS_FLUX_WAVESPEED, absent from the other laws, whose code is unchanged.
@@ -1385,87 +1334,6 @@ __global__ void k_init_derived(typename P::Params prm, const double *aux, double
     for (int s = 0; s < NDER; ++s) derived[n + (int64_t)Np * (s + (int64_t)NDER * e)] = d[s];
 }
 
-// ---------------------------------------------------------------------------------
-// kernel_fillsendbuf! / kernel_transferrecvbuf!  MPIStateArrays.jl:837-871
-// (nvar = columns per position of the packed buffer = the leading columns of the ncol-column array;
-// the reference packs whole arrays, nvar == ncol)
-static __global__ void k_fillsendbuf(double *__restrict__ sendbuf, const double *__restrict__ buf,
-                              const int64_t *__restrict__ vmapsend, int64_t nvmap, int Np,
-                              int nvar, int ncol, int node_major = 0)
-{
-    const int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (I >= nvmap * nvar) return;
-    const int64_t i = I / nvar;
-    const int s = (int)(I % nvar);
-    const int64_t id = vmapsend[i] - 1;
-    const int64_t e = id / Np, n = id % Np;
-    sendbuf[s + (int64_t)nvar * i] = node_major ? buf[s + (int64_t)ncol * (n + (int64_t)Np * e)]
-                                                : buf[n + (int64_t)Np * (s + (int64_t)ncol * e)];
-}
-static __global__ void k_transferrecvbuf(double *__restrict__ buf, const double *__restrict__ recvbuf,
-                                  const int64_t *__restrict__ vmaprecv, int64_t nvmap, int Np,
-                                  int nvar, int ncol, int node_major = 0)
-{
-    const int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (I >= nvmap * nvar) return;
-    const int64_t i = I / nvar;
-    const int s = (int)(I % nvar);
-    const int64_t id = vmaprecv[i] - 1;
-    const int64_t e = id / Np, n = id % Np;
-    buf[node_major ? s + (int64_t)ncol * (n + (int64_t)Np * e) : n + (int64_t)Np * (s + (int64_t)ncol * e)] =
-        recvbuf[s + (int64_t)nvar * i];
-}
-
-// ---------------------------------------------------------------------------------
-// A node-major array of the library (ncol, Np, nelem) into the reference layout (Np, ncol, nelem) of
-// a caller that asked for it (create_states.jl:17-26), and back.
-static __global__ void k_export_node_major(double *__restrict__ dst, const double *__restrict__ src, int Np,
-                                           int ncol, int64_t nelem)
-{
-    const int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (I >= (int64_t)Np * ncol * nelem) return;
-    const int64_t e = I / ((int64_t)Np * ncol);
-    const int r = (int)(I - e * Np * ncol), s = r / Np, n = r - s * Np;
-    dst[I] = src[s + (int64_t)ncol * (n + (int64_t)Np * e)];
-}
-static __global__ void k_import_node_major(double *__restrict__ dst, const double *__restrict__ src, int Np,
-                                           int ncol, int64_t nelem)
-{
-    const int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (I >= (int64_t)Np * ncol * nelem) return;
-    const int64_t e = I / ((int64_t)Np * ncol);
-    const int r = (int)(I - e * Np * ncol), n = r / ncol, s = r - n * ncol;
-    dst[I] = src[n + (int64_t)Np * (s + (int64_t)ncol * e)];
-}
-
-// ---------------------------------------------------------------------------------
-// local part of norm / euclidean_distance (MPIStateArrays.jl:583-644): per-block
-// partial sums in a fixed order (deterministic), finished on the host.
-static __global__ void k_wsum2(const double *__restrict__ A, const double *__restrict__ B,
-                        const double *__restrict__ vgeo, int nvgeo, int Np, int nvar,
-                        int64_t nreal, int weighted, double *__restrict__ partial)
-{
-    __shared__ double sh[256];
-    const int64_t total = (int64_t)Np * nvar * nreal;
-    double acc = 0.0;
-    for (int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; I < total;
-         I += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t e = I / ((int64_t)Np * nvar);
-        const int n = (int)(I % Np);
-        double d = A[I];
-        if (B) d -= B[I];
-        const double w = weighted ? vgeo[n + (int64_t)Np * (VM + (int64_t)nvgeo * e)] : 1.0;
-        acc += w * d * d;
-    }
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
-}
-
 // ---- courant(local_courant, dg, m, Q, dt, t, direction)  SpaceDiscretization.jl:307-365 ----
 // One block per real element: node coordinates staged in LDS, the minimum neighbour distance
 // (kernel_min_neighbor_distance!, Grids.jl:1228-1333) and the law's local Courant number
@@ -1523,24 +1391,6 @@ __global__ __launch_bounds__((KDims<NQ, NQV>::Np <= 128 ? 128 : 256)) void k_cou
         __syncthreads();
     }
     if (tid == 0) out[e] = sred[0];
-}
-
-// extremum of n values into out[0] (one block)
-static __global__ void k_extremum(const double *__restrict__ v, int64_t n, int is_min,
-                                  double *__restrict__ out)
-{
-    __shared__ double s[1024];
-    double a = is_min ? INFINITY : -INFINITY;
-    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) a = is_min ? fmin(a, v[i]) : fmax(a, v[i]);
-    s[threadIdx.x] = a;
-    __syncthreads();
-    for (int h = blockDim.x / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h)
-            s[threadIdx.x] = is_min ? fmin(s[threadIdx.x], s[threadIdx.x + h])
-                                    : fmax(s[threadIdx.x], s[threadIdx.x + h]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = s[0];
 }
 
 }  // namespace cmdg

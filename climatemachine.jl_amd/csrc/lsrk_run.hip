@@ -6,6 +6,26 @@
 
 namespace cmdg {
 
+// update!  LowStorageRungeKuttaMethod.jl:146-158 (used when a tendency filter sits between
+// the right-hand side and the update, so the update cannot be fused into k_tendency)
+static __global__ void k_lsrk_update(double *__restrict__ dQ, double *__restrict__ Q, double rka,
+                                     double rkb_dt, int64_t n)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        Q[i] += rkb_dt * dQ[i];
+        dQ[i] *= rka;
+    }
+}
+void lsrk_update(hipStream_t st, double *dQ, double *Q, double rka_next, double rkb_dt, int64_t n)
+{
+    hipLaunchKernelGGL(k_lsrk_update, dim3(nblocks(n)), dim3(256), 0, st, dQ, Q, rka_next, rkb_dt, n);
+}
+void lsrk_update(EngineBase *e, double *dQ, double *Q, double rka_next, double rkb_dt)
+{
+    lsrk_update(e->s_comp, dQ, Q, rka_next, rkb_dt, real_len(e));
+}
+
 // The state rotates Q -> W0 -> W1 -> ... -> Q so that the fused update never writes the array its
 // neighbours still read; a one-stage tableau ends in W0 and is copied back.
 static void lsrk_stage_buffers(EngineBase *e, double *Q, int s, int nstages, double **in, double **out)

@@ -1,5 +1,5 @@
 // Reductions of state arrays (cmdg_reduce_*): the device part lives in reductions.hip, the ABI
-// entries and the RCCL all-gather in cmdg.hip.  Free functions that take the engine: nothing here
+// entries and the RCCL all-gather follow it there.  Free functions that take the engine: nothing here
 // changes the layout of EngineBase (the scratch of a handle is kept in a table of reductions.hip).
 #pragma once
 #include <string>

@@ -19,7 +19,8 @@
 #include <unordered_map>
 #include <vector>
 
-#include "engine.h"
+#include "engine_base.h"
+#include "rccl.h"
 #include "reductions.h"
 
 namespace cmdg {
@@ -481,3 +482,98 @@ void reduce_release(EngineBase *e)
 }
 
 }  // namespace cmdg
+
+using namespace cmdg;
+
+extern "C" {
+
+// this rank's nout (hi, lo) pairs into host (the engine's device current)
+static int reduce_to_host(EngineBase *e, const cmdg_reduce_desc *d, const double *A, const double *B,
+                          double *host)
+{
+    const double *r = nullptr;
+    double *stage = nullptr;
+    const size_t n = 2 * (size_t)reduce_nout(d);
+    if (int rc = reduce_device(e, d, A, B, &r)) return rc;
+    if (int rc = reduce_host_buffer(e, n, &stage)) return rc;
+    if (hipMemcpyAsync(stage, r, sizeof(double) * n, hipMemcpyDeviceToHost, e->s_comp) != hipSuccess ||
+        hipStreamSynchronize(e->s_comp) != hipSuccess)
+        return e->fail(CMDG_ERR_HIP, "reduce: copy of the partials failed");
+    memcpy(host, stage, sizeof(double) * n);
+    return CMDG_OK;
+}
+
+int cmdg_reduce_local(cmdg_handle h, const cmdg_reduce_desc *d, const double *A, const double *B,
+                      double *partials_host)
+{
+    if (!h || !partials_host) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    return set_err(h, reduce_to_host(h->eng, d, A, B, partials_host));
+}
+
+int cmdg_reduce_combine(const cmdg_reduce_desc *d, const double *partials, int32_t nranks, double *out)
+{
+    std::string err;
+    const int r = reduce_combine(d, partials, nranks, out, err);
+    if (r) set_create_err("cmdg_reduce_combine: " + err);
+    return r;
+}
+
+int cmdg_reduce(cmdg_handle h, const cmdg_reduce_desc *d, const double *A, const double *B,
+                double *out_host)
+{
+    if (!h || !out_host) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    EngineBase *e = h->eng;
+    if (e->transport == TRANSPORT_LOCAL && e->nranks > 1)
+        return set_err(h, e->fail(CMDG_ERR_INVALID, "cmdg_reduce: the handle is one rank of a local-transport "
+                                                    "group; reduce the group with cmdg_group_reduce"));
+    std::string err;
+    if (reduce_check(d, err)) return set_err(h, e->fail(CMDG_ERR_INVALID, err));
+    const int nout = reduce_nout(d);
+    const int nranks = e->transport == TRANSPORT_RCCL && e->nccl_comm ? e->nranks : 1;
+    std::vector<double> parts(2 * (size_t)nout * nranks);
+    if (nranks == 1 && e->transport != TRANSPORT_RCCL) {
+        if (int r = reduce_to_host(e, d, A, B, parts.data())) return set_err(h, r);
+    } else {  // every rank's partials, in rank order, on every rank
+        const double *r = nullptr;
+        double *gath = nullptr, *stage = nullptr;
+        if (int rc = reduce_device(e, d, A, B, &r)) return set_err(h, rc);
+        if (int rc = reduce_gather_buffer(e, parts.size(), &gath)) return set_err(h, rc);
+        if (int rc = reduce_host_buffer(e, parts.size(), &stage)) return set_err(h, rc);
+        if (int rc = rccl::AllGather(r, gath, 2 * (size_t)nout, rccl::kDouble, e->nccl_comm, e->s_comp))
+            return set_err(h, e->fail(CMDG_ERR_COMM, std::string("reduce: ncclAllGather: ") + rccl::GetErrorString(rc)));
+        if (hipMemcpyAsync(stage, gath, sizeof(double) * parts.size(), hipMemcpyDeviceToHost, e->s_comp) != hipSuccess ||
+            hipStreamSynchronize(e->s_comp) != hipSuccess)
+            return set_err(h, e->fail(CMDG_ERR_HIP, "reduce: copy of the gathered partials failed"));
+        memcpy(parts.data(), stage, sizeof(double) * parts.size());
+    }
+    if (reduce_combine(d, parts.data(), nranks, out_host, err)) return set_err(h, e->fail(CMDG_ERR_INVALID, err));
+    return CMDG_OK;
+}
+
+int cmdg_group_reduce(cmdg_handle *handles, int32_t n, const cmdg_reduce_desc *d, const double **A,
+                      const double **B, double *out_host)
+{
+    if (!A || !out_host) return CMDG_ERR_INVALID;
+    GroupCall gc(handles, n);
+    if (!gc.ok()) return CMDG_ERR_INVALID;
+    EngineBase *e0 = handles[0]->eng;
+    for (int i = 0; i < n; ++i) {
+        EngineBase *e = handles[i]->eng;
+        if (n > 1 && (e->transport != TRANSPORT_LOCAL || e->nranks != n || e->rank != i))
+            return gc.finish(e->fail(CMDG_ERR_INVALID, "cmdg_group_reduce: handle i must be rank i of "
+                                                       "one group of n connected with cmdg_comm_connect_local"));
+    }
+    std::string err;
+    if (reduce_check(d, err)) return gc.finish(e0->fail(CMDG_ERR_INVALID, err));
+    const size_t per = 2 * (size_t)reduce_nout(d);
+    std::vector<double> parts(per * n);
+    for (int i = 0; i < n; ++i)
+        if (int r = reduce_to_host(handles[i]->eng, d, A[i], B ? B[i] : nullptr, parts.data() + per * i))
+            return gc.finish(r);
+    if (reduce_combine(d, parts.data(), n, out_host, err)) return gc.finish(e0->fail(CMDG_ERR_INVALID, err));
+    return CMDG_OK;
+}
+
+}  // extern "C"

@@ -210,9 +210,7 @@ static int group_split_explicit01_step(int n, cmdg_handle *slow, cmdg_handle *fa
         if (int r = group_rhs(S, c)) return r;
         for (int i = 0; i < n; ++i) {  // ... and update!
             const int64_t nn = (int64_t)Np3 * O::NS * S[i]->nreal;
-            if (nn > 0)
-                hipLaunchKernelGGL(k_lsrk_update, dim3(nblocks(nn)), dim3(256), 0, S[i]->s_comp, dQ3[i], Q3[i],
-                                   rka[(s + 1) % nstages], rkb[s] * dt, nn);
+            if (nn > 0) lsrk_update(S[i]->s_comp, dQ3[i], Q3[i], rka[(s + 1) % nstages], rkb[s] * dt, nn);
         }
         // ---- barotropic sub-steps with cummulate_fast_solution! (Communication.jl:226-252)
         for (int sub = 1; sub <= fs3; ++sub) {

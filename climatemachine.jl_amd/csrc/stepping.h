@@ -5,12 +5,11 @@
 #pragma once
 #include <string>
 
-#include "engine.h"
-#include "filters.h"
+#include "engine_base.h"
 
 namespace cmdg {
 
-// cmdg.hip: one evaluation over the handles of a local group, in lock step
+// cmdg.hip (next to rhs_segment): one evaluation over the handles of a local group, in lock step
 int group_rhs(std::vector<EngineBase *> &g, std::vector<RhsCtx> &c, bool keep_fresh = false);
 // lsrk_run.hip: one fused LSRK step over them.  continued: this step follows the previous step of
 // the same run with nothing in between; handoff: see EngineBase::lsrk_step
@@ -37,18 +36,16 @@ BackwardEuler *columnlu_solver(cmdg_columnlu_handle lu);
 BackwardEuler *gmres_solver(cmdg_gmres_handle g);
 
 // Work-groups of 256 for a kernel that handles one item per thread and returns past n: every
-// item needs its own thread, so the count is not capped (nblocks, engine.h, is for grid-stride
+// item needs its own thread, so the count is not capped (nblocks, engine_base.h, is for grid-stride
 // kernels only).
 inline unsigned grid_one_per_thread(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 inline int64_t real_len(const EngineBase *e) { return e->nreal * (int64_t)e->ns * e->Np; }
 
-// update! of the 2N scheme over the real elements, on the engine's compute stream
-inline void lsrk_update(EngineBase *e, double *dQ, double *Q, double rka_next, double rkb_dt)
-{
-    const int64_t n = real_len(e);
-    hipLaunchKernelGGL(k_lsrk_update, dim3(nblocks(n)), dim3(256), 0, e->s_comp, dQ, Q, rka_next, rkb_dt, n);
-}
+// lsrk_run.hip: update! of the 2N scheme over the first n values of dQ and Q on stream st, and over the
+// real elements on the engine's compute stream
+void lsrk_update(hipStream_t st, double *dQ, double *Q, double rka_next, double rkb_dt, int64_t n);
+void lsrk_update(EngineBase *e, double *dQ, double *Q, double rka_next, double rkb_dt);
 
 // Consecutive operations of one step on different streams: the later stream waits for
 // everything enqueued so far on the earlier one.  A step that stays on one stream needs no create().

@@ -227,7 +227,7 @@ def test_step_graph_equals_eager_steps(cm, torch):
     memory, advanced as updatetime! does) for every step but the first of a run.  Same bits as
     eager steps; two runs reuse the graph; the time really advances (the advection-diffusion
     law's boundary data depend on it).  A handle that exchanges through RCCL is recorded with the
-    halo stream as the origin of the capture (csrc/cmdg.hip, graph_eligible): same bits again."""
+    halo stream as the origin of the capture (csrc/lsrk_run.hip, graph_eligible): same bits again."""
     from helpers import pseudo1d_setup
     from test_gpu_halo import _self_neighbour_grid
     out, counts = [], []

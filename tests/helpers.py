@@ -22,7 +22,7 @@ def pseudo1d_setup(Ne=4, N=4, direction=0, flux_bc=False, rank=0, size=1, dim=3)
     return law, grid, dt
 
 
-def variable_degree_setup(level=1, orders=(4, 2), field="horizontal"):
+def variable_degree_setup(level=1, orders=(4, 2), field="horizontal", rank=0, size=1):
     """variable_degree_advection_diffusion.jl:77-150 (dim = 3): polynomialorder = (N_h, N_v); its
     two equations are uncoupled (per-equation wave speed and diffusion tensor), so each is run
     as the one-equation Pseudo1D problem along n_hd = (1, 1, 0)/sqrt(2) or n_vd = (0, 0, 1);
@@ -31,7 +31,7 @@ def variable_degree_setup(level=1, orders=(4, 2), field="horizontal"):
     n = np.array([1, 1, 0]) / np.sqrt(2) if field == "horizontal" else np.array([0, 0, 1.0])
     rng = [np.linspace(-1, 1, Ne + 1)] * 3
     topl = M.StackedBrickTopology(rng, boundary=((1, 2),) * 3, periodicity=(False,) * 3,
-                                  connectivity="full")
+                                  connectivity="full", rank=rank, size=size)
     grid = M.DiscontinuousSpectralElementGrid(topl, (orders[0], orders[0], orders[1]))
     law = BL.AdvectionDiffusion(3, BL.Pseudo1D(n, 1.0, 1 / 100, -1 / 2, 1 / 10),
                                 (BL.InhomogeneousBC(0), BL.InhomogeneousBC(1)))

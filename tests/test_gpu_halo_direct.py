@@ -13,16 +13,17 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _run_group(cm, torch, make, size, nsteps, dt, reference, nan_ghosts=True):
+def _run_group(cm, torch, make, size, nsteps, dt, reference, nan_ghosts=True, init=None):
     """``nsteps`` fused LSRK54 steps of a ``size``-rank partition on one GPU (local transport).
     Returns the per-rank real-element states, the handles' answers to DIRECT_SEND / DIRECT_RECV
-    and the pack / unpack launch counts of rank 0."""
+    and the pack / unpack launch counts of rank 0.  ``init(grid, dg)`` gives a rank's initial state
+    (default: ``dg.init_ode_state(0.0)``)."""
     dgs, Qs, grids = [], [], []
     for r in range(size):
         law, grid, dg = make(r, size)
         if reference:
             dg.set_option(cm._lib.OPT_REFERENCE_HALO, 1)
-        q = dg.init_ode_state(0.0)
+        q = dg.init_ode_state(0.0) if init is None else init(grid, dg)
         if nan_ghosts:
             q[grid.nreal:] = float("nan")      # whatever is read of a ghost comes from the exchange
         dgs.append(dg), Qs.append(q), grids.append(grid)

@@ -1,7 +1,9 @@
 """Polynomial orders other than N = 4 (every kernel is templated on Nq = N + 1): the HIP path
 against the oracle for N = 1..7 (advection-diffusion), N = 2, 3, 5, 6 (dry atmosphere, with
 hyperdiffusion and with SmagorinskyLilly -- N = 6 is the order of BASELINE configs[3]), and the
-reference's filter / integral tests at their own orders (N = 3).  ``-m gpu``."""
+reference's filter / integral tests at their own orders (N = 3).  These are single-rank
+evaluations; N != 4 on a partition, under the fused LSRK update and with mixed-order ghosts lives
+in test_gpu_orders_partitioned.py.  ``-m gpu``."""
 import numpy as np
 import pytest
 

@@ -186,9 +186,17 @@ def test_partitioned_split_explicit_matches_single_rank(cm, torch, size, priorit
     failure with CMDG_HALO_PRIORITY=1 was a fill of the lazily allocated LSRK work states that
     was not ordered before the first stage; test_priority_halo_streams_first_use_in_a_process)."""
     monkeypatch.setenv("CMDG_HALO_PRIORITY", str(priority))
+    _partitioned_pair_against_single_rank(cm, torch, size)
+
+
+def _partitioned_pair_against_single_rank(cm, torch, size, N_extrusion=None, before_launch=None):
+    """Two coupled slow steps of the one-rank pair and of the ``size``-rank pairs from the same
+    perturbed state, compared element by element (u, eta, u_d of the 3-D model; eta, U of the
+    barotropic one).  ``before_launch(rank, slow, fast)`` sees every per-rank pair once it is
+    connected and before anything runs (test_gpu_orders_partitioned.py)."""
     O = cm.ocean
     central = cm.balancelaws.CentralNumericalFluxFirstOrder
-    law3, g3, law2, g2 = split_explicit_setup(True, Nx=4, Ny=3, Nz=3)
+    law3, g3, law2, g2 = split_explicit_setup(True, Nx=4, Ny=3, Nz=3, N_extrusion=N_extrusion)
     dg3 = cm.dgmodel.DGModel(law3, g3)
     keep1 = O.install_hydrostatic_boussinesq_hooks(dg3)
     dg2 = cm.dgmodel.DGModel(law2, g2, numerical_flux_first_order=central)
@@ -207,7 +215,8 @@ def test_partitioned_split_explicit_matches_single_rank(cm, torch, size, priorit
              for i, g in enumerate(g3.topology.globalelems[:g3.nreal])}
     slows, fasts, Q3s, Q2s, grids, keeps = [], [], [], [], [], []
     for r in range(size):
-        l3, gr3, l2, gr2 = split_explicit_setup(True, Nx=4, Ny=3, Nz=3, rank=r, size=size)
+        l3, gr3, l2, gr2 = split_explicit_setup(True, Nx=4, Ny=3, Nz=3, N_extrusion=N_extrusion,
+                                                rank=r, size=size)
         assert gr2.nreal * 3 == gr3.nreal and (gr3.nelem - gr3.nreal) == 3 * (gr2.nelem - gr2.nreal)
         d3 = cm.dgmodel.DGModel(l3, gr3)
         keeps.append(O.install_hydrostatic_boussinesq_hooks(d3))
@@ -225,6 +234,9 @@ def test_partitioned_split_explicit_matches_single_rank(cm, torch, size, priorit
         Q2s.append(_gpu(torch, q2))
     cm.dgmodel.connect_local(slows)
     cm.dgmodel.connect_local(fasts)
+    if before_launch is not None:
+        for r in range(size):
+            before_launch(r, slows[r], fasts[r])
     solvers = [O.SplitExplicitSolver(d3, d2, q3, q2, 1800.0, 300.0)
                for d3, d2, q3, q2 in zip(slows, fasts, Q3s, Q2s)]
     torch.cuda.synchronize()

@@ -78,6 +78,8 @@ def lib():
         if hasattr(_LIB, "orc_atmos_new"):
             _LIB.orc_atmos_new.restype = C.POINTER(_Physics)
             _LIB.orc_atmos_new.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        _LIB.orc_atmos_nf_pointwise.restype = C.c_int
+        _LIB.orc_atmos_nf_pointwise.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6
         for name in ("orc_ocean_se01_new", "orc_conti3d_se01_new", "orc_baro_se01_new",
                      "orc_atmos_linear_new"):
             getattr(_LIB, name).restype = C.POINTER(_Physics)
@@ -185,6 +187,26 @@ class OraclePhysics:
             lib().orc_physics_free(self.c)
         except Exception:
             pass
+
+
+def atmos_nf_pointwise(law, nf, n, QM, auxM, QP, auxP):
+    """The dry atmosphere law's own ``numerical_flux_first_order!`` (``nf`` = 2 Roe, 3 HLLC,
+    4 LMARS) at a batch of face-node pairs, one ``orc_atmos_nf_pointwise`` call each: ``n``
+    ``(k, 3)``, ``QM, QP`` ``(k, 5)``, ``auxM, auxP`` ``(k, law.naux)``; returns ``(k, 5)``."""
+    ip, dp = law.descriptor()
+    ip = np.ascontiguousarray(ip, dtype=np.int32)
+    dp = np.ascontiguousarray(dp, dtype=np.float64)
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (n, QM, auxM, QP, auxP)]
+    k = arrs[0].shape[0]
+    assert [a.shape for a in arrs] == [(k, 3), (k, 5), (k, law.naux), (k, 5), (k, law.naux)]
+    out = np.zeros((k, 5))
+    f, pi, pd = lib().orc_atmos_nf_pointwise, _p(ip), _p(dp)
+    base = [a.ctypes.data for a in arrs + [out]]
+    step = [a.strides[0] for a in arrs + [out]]
+    for i in range(k):
+        naux = f(pi, pd, int(nf), *[b + i * s for b, s in zip(base, step)])
+        assert naux == law.naux
+    return out
 
 
 class NoExchange:

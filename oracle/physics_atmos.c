@@ -562,10 +562,9 @@ static void at_nf_law(const void *p_, int nf, double *fluxn, const double *n, co
     }
 }
 
-orc_physics *orc_atmos_new(const int *ip, const double *dp, int nf_first)
+/* the model's parameters and auxiliary layout from the parameter block; returns naux */
+static int atmos_fill(atmos_t *m, const int *ip, const double *dp)
 {
-    orc_physics *ph = (orc_physics *)calloc(1, sizeof(orc_physics));
-    atmos_t *m = (atmos_t *)calloc(1, sizeof(atmos_t));
     m->orient = ip[0]; m->ref = ip[1]; m->subtract = ip[2]; m->kinematic = ip[3];
     m->hyper = ip[4]; m->src = ip[5]; m->nbc = ip[6];
     for (int i = 0; i < 7; ++i) m->bc[i] = ip[7 + i];
@@ -583,6 +582,28 @@ orc_physics *orc_atmos_new(const int *ip, const double *dp, int nf_first)
     m->oTurb = o;  o += m->smag ? 1 : 0;
     m->oDelta = o; o += m->hyper ? 1 : 0;
     m->oMoist = o; o += 2;
+    return o;
+}
+
+/* One face-node pair through the law's own numerical flux (nf = ORC_NF_ROE, ORC_NF_HLLC or
+ * ORC_NF_LMARS), for pointwise tests: the model is built as orc_atmos_new builds it, the normal
+ * flux is added to fluxn[0..4].  Returns naux. */
+int orc_atmos_nf_pointwise(const int *ip, const double *dp, int nf, const double *n,
+                           const double *QM, const double *auxM, const double *QP,
+                           const double *auxP, double *fluxn)
+{
+    atmos_t m;
+    memset(&m, 0, sizeof m);
+    const int naux = atmos_fill(&m, ip, dp);
+    at_nf_law(&m, nf, fluxn, n, QM, auxM, QP, auxP, 0.0, 0);
+    return naux;
+}
+
+orc_physics *orc_atmos_new(const int *ip, const double *dp, int nf_first)
+{
+    orc_physics *ph = (orc_physics *)calloc(1, sizeof(orc_physics));
+    atmos_t *m = (atmos_t *)calloc(1, sizeof(atmos_t));
+    const int o = atmos_fill(m, ip, dp);
     ph->ns = 5;
     ph->naux = o;
     ph->ngrad = 4 + (m->smag ? 1 : 0) + (m->hyper ? 4 : 0);

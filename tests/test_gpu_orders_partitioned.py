@@ -59,14 +59,17 @@ class _Case:
     grid and are scattered to the ranks by global element number, ghosts included."""
 
     def __init__(self, cm, oracle, torch, tag, setup, size, lists, epb, modes=(1, 1),
-                 gradflux=True, model_kw=None, perturb=None, t_rhs=0.2, theta_v=False):
+                 gradflux=True, model_kw=None, perturb=None, t_rhs=0.2, theta_v=False, flux=None):
         self.cm, self.oracle, self.torch, self.tag = cm, oracle, torch, tag
         self.setup, self.size, self.lists, self.epb, self.modes = setup, size, lists, epb, modes
         self.gradflux, self.kw, self.t_rhs = gradflux, dict(model_kw or {}), t_rhs
         self.theta_v = theta_v        # the gradient pass differentiates aux.moisture.theta_v
+        # the first-order numerical flux, where it is not the default: the two models name it differently
+        self.okw = dict(self.kw, **({} if flux is None else {"nf_first": flux}))
+        self.dkw = dict(self.kw, **({} if flux is None else {"numerical_flux_first_order": flux}))
         self.law, self.grid = setup(0, 1)
         assert self.grid.nreal == self.grid.nelem
-        self.odg = oracle.OracleDGModel(self.law, self.grid, **self.kw)
+        self.odg = oracle.OracleDGModel(self.law, self.grid, **self.okw)
         rng = np.random.default_rng(self.grid.N[0] + 10 * self.grid.N[-1])
         self.Q0 = self.law.init_state_prognostic(self.grid, self.odg.state_auxiliary, 0.0)
         if perturb is not None:
@@ -84,7 +87,7 @@ class _Case:
         """The rank's handle, its preconditions asserted on the host."""
         law, grid = self.setup(rank, size)
         assert (len(grid.interiorelems), len(grid.exteriorelems)) == self.lists[rank], self.tag
-        dg = self.cm.dgmodel.DGModel(law, grid, **self.kw)
+        dg = self.cm.dgmodel.DGModel(law, grid, **self.dkw)
         assert dg.query("TENDENCY_ELEMS_PER_GROUP") == self.epb, self.tag
         return law, grid, dg
 

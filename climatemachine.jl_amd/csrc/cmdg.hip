@@ -160,7 +160,8 @@ static __global__ void k_face_digest(const double *__restrict__ vgeo, int nvgeo,
                                      const int64_t *__restrict__ vmapP,
                                      const int64_t *__restrict__ elemtobndy, int NQ, int NQV,
                                      int64_t nreal, int32_t *__restrict__ faceP,
-                                     double *__restrict__ faceG, int *__restrict__ bad)
+                                     double *__restrict__ faceG, double *__restrict__ faceW,
+                                     int32_t *__restrict__ facePr, int *__restrict__ bad)
 {
     const int Np = NQ * NQ * NQV, Nfph = NQ * NQV, Nfpv = NQ * NQ;
     const int Nfp = Nfph > Nfpv ? Nfph : Nfpv, NFT = 4 * Nfph + 2 * Nfpv;
@@ -194,11 +195,14 @@ static __global__ void k_face_digest(const double *__restrict__ vgeo, int nvgeo,
     if (elemtobndy[f + 6 * e] != 0) idP = e * Np + vid;  // DGModel_kernels.jl:686-692
     if (idP < 0 || idP > 2147483647LL) flags |= 4;
     faceP[I] = (int32_t)idP;
+    const int64_t eP = idP >= 0 ? idP / Np : 0;
+    facePr[I] = (int32_t)(eP * Np + ring_slot_of(NQ, NQV, (int)(idP - eP * Np)));
     const double *sg = sgeo + 5 * o;
 #pragma unroll
     for (int c = 0; c < 4; ++c) faceG[((int64_t)4 * e + c) * NFT + t] = sg[c];
     const double mi = vgeo[vid + (int64_t)Np * (VMI + (int64_t)nvgeo * e)];
     if (!(sg[SVMI] == mi)) flags |= 2;
+    faceW[I] = mi * sg[SSM];  // fp.vMI * fp.sM as the passes formed it
     if (flags) atomicOr(bad, flags);
 }
 
@@ -291,11 +295,14 @@ int EngineBase::init(const cmdg_desc *d)
         int bad = 0;
         HIPCHK(d_faceP.alloc(nt));
         HIPCHK(d_faceG.alloc(4 * nt));
+        HIPCHK(d_faceW.alloc(nt));
+        HIPCHK(d_facePr.alloc(nt));
         HIPCHK(d_bad.alloc_zeroed(1, s_comp));  // (stream-ordered before the digest, see below)
         if (nreal > 0)
             hipLaunchKernelGGL(k_face_digest, dim3((unsigned)((nreal * NFT + 255) / 256)), dim3(256), 0,
                                s_comp, g.vgeo, g.nvgeo, g.sgeo, g.vmapM, g.vmapP, g.elemtobndy, NQ,
-                               NQV, nreal, d_faceP.get(), d_faceG.get(), d_bad.get());
+                               NQV, nreal, d_faceP.get(), d_faceG.get(), d_faceW.get(), d_facePr.get(),
+                               d_bad.get());
         hipError_t le = hipGetLastError();
         hipError_t ce = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s_comp);
         hipError_t se = hipStreamSynchronize(s_comp);
@@ -310,6 +317,8 @@ int EngineBase::init(const cmdg_desc *d)
             return fail(CMDG_ERR_INVALID, "cmdg_create: too many elements for 32-bit face indices");
         g.faceP = d_faceP;
         g.faceG = d_faceG;
+        g.faceW = d_faceW;
+        g.facePr = d_facePr;
     }
     aux = d->state_auxiliary;
     const size_t nd = (size_t)Np * nelem;
@@ -370,13 +379,15 @@ int EngineBase::ensure_work()
     return CMDG_OK;
 }
 
-// the records of CMDG_OPT_GRADARG_HANDOFF, allocated by the first run that uses them: the fill is
-// stream-ordered before the run's launches like that of the work states
+// the records of CMDG_OPT_GRADARG_HANDOFF (gradient arguments, and the Laplacians of the run's
+// ring-ordered evaluations), allocated by the first run that uses them: the fill is stream-ordered
+// before the run's launches like that of the work states
 int EngineBase::ensure_garg()
 {
     if (!garg) {
         const size_t n = std::max<size_t>((size_t)Np * ngl * nelem, 1);
         HIPCHK(garg.alloc_zeroed(n, s_comp));
+        HIPCHK(lapr.alloc_zeroed(n, s_comp));
         HIPCHK(hipStreamSynchronize(s_comp));
     }
     return CMDG_OK;

@@ -33,11 +33,19 @@ struct GridDev {
     //   faceP[e][t]     int32, 0-based global node id of the plus side (eP * Np + vidP; the
     //                   minus node itself on boundary faces, DGModel_kernels.jl:686-692)
     //   faceG[e][c][t]  n1, n2, n3, sM (c = 0..3), one coalesced load per component
+    //   faceW[e][t]     vMI * sM, the lift weight of the face node: the one product the gradient,
+    //                   Laplacian and gradient-of-Laplacian passes need either factor for, so
+    //                   they read neither the MI column at the face nodes nor the sM row
+    //   facePr[e][t]    faceP with the plus-side node in the ring order below (eP * Np +
+    //                   ring_slot(vidP)): what k_gradlap<..., RING> of a hand-off run is handed as
+    //                   faceP, so that its gather needs no arithmetic of its own
     // vmap- is a pure function of (f, n) (checked at create) and vMI is MI of that node
-    // (Grids.jl:1097-1101, checked at create): neither is stored.  36 B per face node
-    // instead of the 56 B of the reference tables.
+    // (Grids.jl:1097-1101, checked at create): neither is stored.  48 B per face node
+    // instead of the 56 B of the reference tables; a pass reads 36 of them.
     const int32_t *faceP;
     const double *faceG;
+    const double *faceW;
+    const int32_t *facePr;
 };
 
 // Ghost exchange without pack / unpack launches (handles with neighbours; every pointer is NULL
@@ -88,6 +96,82 @@ struct KDims {
         }
     }
 };
+
+// Face-contiguous ("ring") node order of the Laplacian records of a hand-off run (PassArgs::lapr;
+// kernels.h GradArgHandoff).  Slot of node n = (i, j, k): the 4 (NQ - 1)
+// perimeter columns (i, j) first, in the order one walks round the square -- along j = 0, up
+// i = NQ - 1, back along j = NQ - 1, down i = 0 --, the interior columns after them, the NQV levels
+// of a column consecutive.  The NQ * NQV nodes of a lateral face then fill one run of consecutive
+// slots (the face i = 0 closes the ring: its run wraps from the last perimeter column to the first),
+// so a plus-side gather of node-major records touches the lines of one contiguous piece of the
+// neighbour instead of records NQ apart (xi1 faces) or runs of NQ records (xi2 faces).
+__host__ __device__ __forceinline__ constexpr int ring_slot_of(int NQ, int NQV, int n)
+{
+    const int i = n % NQ, j = (n / NQ) % NQ, k = n / (NQ * NQ), E = NQ - 1;
+    const int c = j == 0 ? i
+                  : i == E ? E + j
+                  : j == E ? 2 * E + (E - i)
+                  : i == 0 ? 3 * E + (E - j)
+                           : 4 * E + (i - 1) + (NQ - 2) * (j - 1);
+    return c * NQV + k;
+}
+// ... and the node that sits in a slot
+__host__ __device__ __forceinline__ constexpr int ring_node_of(int NQ, int NQV, int slot)
+{
+    const int c = slot / NQV, k = slot - c * NQV, E = NQ - 1, NI = NQ > 2 ? NQ - 2 : 1;
+    const int q = c - 4 * E;
+    const int i = c <= E ? c : c <= 2 * E ? E : c <= 3 * E ? 3 * E - c : c < 4 * E ? 0 : 1 + q % NI;
+    const int j = c <= E ? 0 : c <= 2 * E ? c - E : c <= 3 * E ? E : c < 4 * E ? 4 * E - c : 1 + q / NI;
+    return i + NQ * (j + NQ * k);
+}
+template <int NQ, int NQV = NQ>
+__host__ __device__ __forceinline__ constexpr int ring_slot(int n)
+{
+    return ring_slot_of(NQ, NQV, n);
+}
+template <int NQ, int NQV = NQ>
+__host__ __device__ __forceinline__ constexpr int ring_node(int slot)
+{
+    return ring_node_of(NQ, NQV, slot);
+}
+// what every build proves of the map: it is a bijection of the element's nodes, and the nodes of
+// each lateral face (faces 0..3: i = 0, i = NQ - 1, j = 0, j = NQ - 1) are one cyclic run of the
+// perimeter's slots
+template <int NQ, int NQV>
+constexpr bool ring_order_ok()
+{
+    constexpr int Np = NQ * NQ * NQV, R = 4 * (NQ - 1) * NQV, Nfph = NQ * NQV;
+    for (int n = 0; n < Np; ++n) {
+        const int s = ring_slot<NQ, NQV>(n);
+        if (s < 0 || s >= Np || ring_node<NQ, NQV>(s) != n) return false;
+    }
+    for (int s = 0; s < Np; ++s)
+        if (ring_slot<NQ, NQV>(ring_node<NQ, NQV>(s)) != s) return false;
+    for (int f = 0; f < 4; ++f) {
+        bool on[R] = {};
+        int count = 0;
+        for (int n = 0; n < Np; ++n) {
+            const int i = n % NQ, j = (n / NQ) % NQ;
+            if (f == 0 ? i == 0 : f == 1 ? i == NQ - 1 : f == 2 ? j == 0 : j == NQ - 1) {
+                const int s = ring_slot<NQ, NQV>(n);
+                if (s >= R || on[s]) return false;
+                on[s] = true;
+                ++count;
+            }
+        }
+        if (count != Nfph) return false;
+        int starts = 0;  // slots of the face whose cyclic predecessor is not of the face: one per run
+        for (int s = 0; s < R; ++s)
+            if (on[s] && !on[(s + R - 1) % R]) ++starts;
+        if (starts != 1) return false;
+    }
+    return true;
+}
+// the orders the library instantiates with a hand-off (DryAtmos with hyperdiffusion, one element
+// per work-group: N = 2..4), and the neighbouring ones
+static_assert(ring_order_ok<3, 3>() && ring_order_ok<4, 4>() && ring_order_ok<5, 5>(), "ring order");
+static_assert(ring_order_ok<2, 2>() && ring_order_ok<6, 6>() && ring_order_ok<7, 7>(), "ring order");
+static_assert(ring_order_ok<5, 3>() && ring_order_ok<3, 5>() && ring_order_ok<5, 2>(), "ring order");
 
 // Blocks b and b+8 share an XCD (and its L2); hand each XCD a contiguous run of the
 // element list so face neighbours (adjacent in the stacked/Hilbert order) hit one L2.
@@ -188,6 +272,18 @@ __device__ __forceinline__ void store_node_major(double *__restrict__ arr, int64
     for (int m = tid; m < NHG * Np; m += nthreads) {
         const int n = m / NHG, s = m - n * NHG;
         if (NW == NHG || s < NW) dst[m] = src[s * Np + n];
+    }
+}
+// all NHG columns of element e out of LDS in memory order, the records in the ring order
+template <int NHG, int NQ, int NQV>
+__device__ __forceinline__ void store_ring_major(double *__restrict__ arr, int64_t e, int tid, int nthreads,
+                                                 const double *src)
+{
+    constexpr int Np = KDims<NQ, NQV>::Np;
+    double *dst = arr + (int64_t)NHG * Np * e;
+    for (int m = tid; m < NHG * Np; m += nthreads) {
+        const int r = m / NHG, s = m - r * NHG;
+        dst[m] = src[s * Np + ring_node<NQ, NQV>(r)];
     }
 }
 // exterior launches: the element's nodes of vmapsend into send buffer `which` (NVAR columns per

@@ -30,6 +30,8 @@ struct EngineT : EngineBase {
         a.tendency = c.tendency;
         a.Qout = c.Qout;
         a.garg = garg;
+        a.lapr = lapr;
+        a.hypdiv_out = c.hypdiv_out;
         a.t = c.t;
         a.tptr = c.tptr;
         a.alpha = c.alpha;
@@ -89,6 +91,21 @@ struct EngineT : EngineBase {
         if (lsrk) return gf ? tendency_recv<true, true>(recv) : tendency_recv<true, false>(recv);
         return gf ? tendency_recv<false, true>(recv) : tendency_recv<false, false>(recv);
     }
+    // The Laplacian and gradient-of-Laplacian passes of an evaluation that reads the records (c.garg_in)
+    // hand the Laplacians on as ring-ordered records (cmdg_common.h ring_slot); the second gathers
+    // them through facePr.
+    static Kernel pick_divgrad(bool ring)
+    {
+        if constexpr (HO)
+            if (ring) return k_divgrad<P, NQ_, NQV_, true>;
+        return k_divgrad<P, NQ_, NQV_>;
+    }
+    static Kernel pick_gradlap(bool ring)
+    {
+        if constexpr (HO)
+            if (ring) return k_gradlap<P, NQ_, NQV_, true>;
+        return k_gradlap<P, NQ_, NQV_>;
+    }
     void launch_gradients(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
     {
         in_pass(GRADIENTS, n, exterior, st, [&] {
@@ -103,14 +120,15 @@ struct EngineT : EngineBase {
     {
         in_pass(DIVGRAD, n, exterior, st, [&] {
             const PassArgs<P> args = make_args(c, elems, n, diffusion_direction, exterior, slot[SLOT_HD].sendbuf, nullptr);
-            hipLaunchKernelGGL((k_divgrad<P, NQ_, NQV_>), dim3((unsigned)n), dim3(KDims<NQ_, NQV_>::NT), 0, st, args);
+            hipLaunchKernelGGL(pick_divgrad(c.garg_in), dim3((unsigned)n), dim3(KDims<NQ_, NQV_>::NT), 0, st, args);
         });
     }
     void launch_gradlap(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
     {
         in_pass(GRADLAP, n, exterior, st, [&] {
-            const PassArgs<P> args = make_args(c, elems, n, diffusion_direction, exterior, slot[SLOT_HG].sendbuf, nullptr);
-            hipLaunchKernelGGL((k_gradlap<P, NQ_, NQV_>), dim3((unsigned)n), dim3(KDims<NQ_, NQV_>::NT), 0, st, args);
+            PassArgs<P> args = make_args(c, elems, n, diffusion_direction, exterior, slot[SLOT_HG].sendbuf, nullptr);
+            if (c.garg_in) args.g.faceP = g.facePr;
+            hipLaunchKernelGGL(pick_gradlap(c.garg_in), dim3((unsigned)n), dim3(KDims<NQ_, NQV_>::NT), 0, st, args);
         });
     }
     void launch_tendency(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override

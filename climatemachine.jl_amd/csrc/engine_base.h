@@ -60,7 +60,11 @@ struct RhsCtx {
     bool update_after = false; // separate update!() after the (filtered) tendency
     // CMDG_OPT_GRADARG_HANDOFF, set by cmdg_lsrk_run alone (handoff_stage, lsrk_run.hip): the gradient
     // pass reads the records the previous stage's update left / what the fused update leaves
+    // An evaluation that reads the records hands its Laplacians on as ring-ordered records
+    // (cmdg_common.h ring_slot); hypdiv_out: its Laplacian pass also writes the caller's
+    // Qhypervisc_div (the run's last evaluation: the array ends a run as the ordinary kernels leave it).
     bool garg_in = false;
+    bool hypdiv_out = true;
     GargOut garg_out = GargOut::none;
     double rkb_dt = 0, rka_next = 0;
     // the law's update_auxiliary_state!(realelems) composition has run already (group_rhs runs the
@@ -195,8 +199,10 @@ struct EngineBase {
     int64_t ninterior = 0, nexterior = 0;
     const uint8_t *d_activedofs = nullptr;
     DevBuf<double> d_D;
-    DevBuf<int32_t> d_faceP;  // digested face tables (GridDev::faceP / faceG)
+    DevBuf<int32_t> d_faceP;  // digested face tables (GridDev::faceP / faceG / faceW)
     DevBuf<double> d_faceG;
+    DevBuf<double> d_faceW;
+    DevBuf<int32_t> d_facePr;
     const int64_t *d_vmapsend = nullptr, *d_vmaprecv = nullptr;
     int64_t nvmapsend = 0, nvmaprecv = 0;
     std::vector<int> nabrtorank;
@@ -224,6 +230,9 @@ struct EngineBase {
     // (ngl, Np, nelem) gradient arguments of the next stage's input, written by the fused update
     // and read by the next gradient pass of the same cmdg_lsrk_run; never trusted across calls
     DevBuf<double> garg;
+    // (ngl, Np, nelem) Laplacians of the run's ring-ordered evaluations (the ones whose gradient pass
+    // reads garg): k_divgrad<RING> writes them, k_gradlap<RING> reads and gathers them
+    DevBuf<double> lapr;
     bool gradarg_handoff = true;   // the option
     bool handoff_used = false;     // did the last cmdg_lsrk_run use it (cmdg_query)
     int64_t handoff_refreshes = 0; // hand-off updates of the last run that carried the auxiliary refresh

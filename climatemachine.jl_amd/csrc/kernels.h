@@ -63,6 +63,8 @@ struct PassArgs {
     double *tendency;  // tendency (== dQ when the LSRK update is fused)
     double *Qout;      // LSRK: updated state
     double *garg;      // gradient arguments handed from a fused update to the next stage (GradArgHandoff)
+    double *lapr;      // Laplacian records of a ring-ordered evaluation (k_divgrad / k_gradlap RING)
+    int hypdiv_out;    // k_divgrad<RING>: write the caller's Qhypervisc_div as well (uniform)
     double t, alpha, beta;
     const double *tptr;  // time of the evaluation in device memory (a captured step is replayed
                          // with the time a one-thread kernel of the graph advances); NULL: t
@@ -75,6 +77,7 @@ struct PassArgs {
 
 struct FacePt {
     double n[3], sM, vMI;
+    double w;  // vMI * sM out of the digest (LIFTW passes, which then load neither factor)
     int64_t eP;
     int vidM, vidP, bctag;
 };
@@ -105,7 +108,9 @@ __device__ __forceinline__ void face_index(const GridDev &g, int64_t e, int t, i
     idP = g.faceP[(int64_t)KDims<NQ, NQV>::NFT * e + t];
     bctag = (int)g.elemtobndy[f + 6 * e];
 }
-template <int NQ, int NQV = NQ>
+// LIFTW: the lift weight vMI * sM comes from GridDev::faceW (the gradient, Laplacian and
+// gradient-of-Laplacian passes, whose face phase uses the two factors only in that product)
+template <int NQ, int NQV = NQ, bool LIFTW = false>
 __device__ __forceinline__ void face_geometry(const GridDev &g, int64_t e, int t, int f, int n,
                                               int32_t idP, int bctag, FacePt &fp)
 {
@@ -114,21 +119,25 @@ __device__ __forceinline__ void face_geometry(const GridDev &g, int64_t e, int t
     fp.n[0] = sg[0];
     fp.n[1] = sg[NFT];
     fp.n[2] = sg[2 * NFT];
-    fp.sM = sg[3 * NFT];
     fp.vidM = face_vid<NQ, NQV>(f, n);
-    fp.vMI = g.vgeo[fp.vidM + (int64_t)Np * (VMI + (int64_t)g.nvgeo * e)];
+    if constexpr (LIFTW) {
+        fp.w = g.faceW[(int64_t)NFT * e + t];
+    } else {
+        fp.sM = sg[3 * NFT];
+        fp.vMI = g.vgeo[fp.vidM + (int64_t)Np * (VMI + (int64_t)g.nvgeo * e)];
+    }
     fp.bctag = bctag;
     fp.eP = idP / Np;
     fp.vidP = idP - (int)fp.eP * Np;
 }
-template <int NQ, int NQV = NQ>
+template <int NQ, int NQV = NQ, bool LIFTW = false>
 __device__ __forceinline__ void face_setup(const GridDev &g, int64_t e, int t, int f, int n,
                                            FacePt &fp)
 {
     int32_t idP;
     int bctag;
     face_index<NQ, NQV>(g, e, t, f, idP, bctag);
-    face_geometry<NQ, NQV>(g, e, t, f, n, idP, bctag, fp);
+    face_geometry<NQ, NQV, LIFTW>(g, e, t, f, n, idP, bctag, fp);
 }
 
 // A law may offer flux_first_order and wavespeed of one state in one call (both need the same
@@ -353,6 +362,13 @@ struct TendencyShape {
 // auxiliary refresh for Q+; k_gradients<..., GARG_IN> of the next stage reads and gathers those
 // records instead of 9 columns of Q / aux per node and per interior face node.  Same expressions on
 // the same operands: every bit downstream is unchanged.  One element per work-group only.
+// An evaluation that reads the records also keeps its Laplacians as records of NGL doubles in the
+// face-contiguous order (cmdg_common.h ring_slot; PassArgs::lapr): k_divgrad<..., RING> writes them,
+// k_gradlap<..., RING> reads its own and gathers the plus side from them -- one 32-byte record out
+// of one contiguous run per face instead of four columns of Qhypervisc_div.  That launch is handed
+// GridDev::facePr as faceP, so its FacePt's vidP is the ring slot of the plus-side node.  The
+// records themselves and grad G stay in the natural node order: ring-ordered they measured no
+// faster in any pass (profiles/ab_face_contiguous.txt).
 // A run's hand-off launches follow one another with no hook, filter, exchange or caller in between,
 // so the columns the refresh writes are seen by somebody only after the last of them (it leaves the
 // auxiliary state of the final evaluation's input, as every run promises).  A law whose refreshed
@@ -920,7 +936,7 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
         const bool on = f < 4 ? hz : vt;
         if (on) {
             FacePt fp;
-            face_setup<NQ, NQV>(a.g, e, tid, f, n, fp);
+            face_setup<NQ, NQV, true>(a.g, e, tid, f, n, fp);
             Vec<NS> QM, QP;
             Vec<NAUX> auxM, auxP;
             Vec<NGRAD> GM, GP;
@@ -989,14 +1005,14 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
 #pragma unroll
                 for (int d = 0; d < 3; ++d) {
                     const int q = d + 3 * P::hv_indexmap(s);
-                    corr[NGF + 3 * s + d] = fp.vMI * fp.sM * (tg[q] - nGM[q]);
+                    corr[NGF + 3 * s + d] = fp.w * (tg[q] - nGM[q]);
                 }
             if constexpr (NGF > 0) {
                 Vec<NGF> visc;
                 for (int s = 0; s < NGF; ++s) visc[s] = 0;
                 law_gradient_flux<P>(a.prm, visc, nGM, QM, auxM, a_t, GM);
 #pragma unroll
-                for (int s = 0; s < NGF; ++s) corr[s] = fp.vMI * fp.sM * (lgf[s] - visc[s]);
+                for (int s = 0; s < NGF; ++s) corr[s] = fp.w * (lgf[s] - visc[s]);
             }
             vidM = fp.vidM;
             fpair = f / 2;
@@ -1031,7 +1047,10 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
 // ---------------------------------------------------------------------------------
 // Laplacian pass: volume_divergence_of_gradients! (:2132-2329) +
 // interface_divergence_of_gradients! (:2360-2494)
-template <class P, int NQ, int NQV = NQ>
+// RING (an evaluation of a hand-off run that reads the records, GradArgHandoff): the Laplacians are
+// left as ring-ordered records in PassArgs::lapr for k_gradlap<..., RING>; the caller's
+// Qhypervisc_div is written only where PassArgs::hypdiv_out says so.
+template <class P, int NQ, int NQV = NQ, bool RING = false>
 __global__ void __launch_bounds__((KDims<NQ, NQV>::NT)) k_divgrad(const PassArgs<P> a)
 {
     using KD = KDims<NQ, NQV>;
@@ -1113,7 +1132,7 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT)) k_divgrad(const PassArgs
         const bool on = f < 4 ? hz : vt;
         if (on) {
             FacePt fp;
-            face_setup<NQ, NQV>(a.g, e, tid, f, n, fp);
+            face_setup<NQ, NQV, true>(a.g, e, tid, f, n, fp);
             Vec<NHG> gM, gP;
             const int sidx = surf_index<NQ, NQV>(fp.vidM);
 #pragma unroll
@@ -1133,7 +1152,7 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT)) k_divgrad(const PassArgs
                 const double ldiv = (gP[3 * s] + gM[3 * s]) * nh0 +
                                     (gP[3 * s + 1] + gM[3 * s + 1]) * nh1 +
                                     (gP[3 * s + 2] + gM[3 * s + 2]) * nh2;
-                corr[s] = fp.vMI * fp.sM * ldiv;
+                corr[s] = fp.w * ldiv;
             }
             vidM = fp.vidM;
             fpair = f / 2;
@@ -1147,10 +1166,15 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT)) k_divgrad(const PassArgs
         }
         __syncthreads();
     }
+    // (the records go out of LDS in memory order: one record per lane at its ring slot measured
+    // 13 us per launch slower, profiles/ab_face_contiguous.txt)
+    if constexpr (RING) store_ring_major<NG, NQ, NQV>(a.lapr, e, tid, (int)blockDim.x, sA);
     if (tid < Np) {
+        if (!RING || a.hypdiv_out) {
 #pragma unroll
-        for (int s = 0; s < NGL; ++s)
-            a.hypdiv[tid + (int64_t)Np * (s + (int64_t)NHYP * e)] = sA[s * Np + tid];
+            for (int s = 0; s < NGL; ++s)
+                a.hypdiv[tid + (int64_t)Np * (s + (int64_t)NHYP * e)] = sA[s * Np + tid];
+        }
     }
     // (the NGL columns this pass writes are all the next one reads of Qhypervisc_div)
     if constexpr (NGL > 0)
@@ -1160,7 +1184,8 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT)) k_divgrad(const PassArgs
 // ---------------------------------------------------------------------------------
 // Gradient-of-Laplacian pass: volume_gradients_of_laplacians! (:2525-2824) +
 // interface_gradients_of_laplacians! (:2859-3026)
-template <class P, int NQ, int NQV = NQ>
+// RING: the Laplacians are read and gathered as the ring-ordered records k_divgrad<..., RING> left.
+template <class P, int NQ, int NQV = NQ, bool RING = false>
 __global__ void __launch_bounds__((KDims<NQ, NQV>::NT), CMDG_LAP_MINW) k_gradlap(const PassArgs<P> a)
 {
     using KD = KDims<NQ, NQV>;
@@ -1181,8 +1206,14 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT), CMDG_LAP_MINW) k_gradlap
     const bool hz = a.direction != DIR_VERTICAL, vt = a.direction != DIR_HORIZONTAL;
     if (tid < Np) {
         Vec<NGL> l;  // (all loads in flight before the first LDS store, as in k_divgrad)
+        if constexpr (RING) {
+            const double *rec = a.lapr + garg_at<NG, Np>(ring_slot<NQ, NQV>(tid), e);
 #pragma unroll
-        for (int s = 0; s < NGL; ++s) l[s] = a.hypdiv[tid + (int64_t)Np * (s + (int64_t)NHYP * e)];
+            for (int s = 0; s < NGL; ++s) l[s] = rec[s];
+        } else {
+#pragma unroll
+            for (int s = 0; s < NGL; ++s) l[s] = a.hypdiv[tid + (int64_t)Np * (s + (int64_t)NHYP * e)];
+        }
 #pragma unroll
         for (int s = 0; s < NGL; ++s) sL[s * Np + tid] = l[s];
     }
@@ -1246,18 +1277,32 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT), CMDG_LAP_MINW) k_gradlap
         const bool on = f < 4 ? hz : vt;
         if (on) {
             FacePt fp;
-            face_setup<NQ, NQV>(a.g, e, tid, f, n, fp);
+            face_setup<NQ, NQV, true>(a.g, e, tid, f, n, fp);
             Vec<NS> QM, QP;
             Vec<NAUX> auxM, auxP;
             Vec<NGL> lapM, lapP;
             load_state<NS, Np>(QM, a.Q, fp.vidM, e);
             load_state<NAUX, Np>(auxM, a.aux, fp.vidM, e);
-            const int gslot = ghost_slot<Np>(a.h, fp.eP, fp.vidP);
-            load_plus<NS, Np, NS>(QP, a.Q, a.h.recvQ, gslot, fp.vidP, fp.eP);
-            load_state<NAUX, Np>(auxP, a.aux, fp.vidP, fp.eP);
+            if constexpr (RING) {
+                // fp.vidP is the ring slot of the plus-side node (facePr).  Q+ / aux+ are read by the
+                // boundary state alone, where e+ = e-, vid+ = vid-: copies of the minus side
 #pragma unroll
-            for (int s = 0; s < NGL; ++s) lapM[s] = sL[s * Np + fp.vidM];
-            load_plus<NHYP, Np, NGL, NGL>(lapP, a.hypdiv, a.h.recvHD, gslot, fp.vidP, fp.eP);
+                for (int s = 0; s < NS; ++s) QP[s] = QM[s];
+#pragma unroll
+                for (int s = 0; s < NAUX; ++s) auxP[s] = auxM[s];
+#pragma unroll
+                for (int s = 0; s < NGL; ++s) lapM[s] = sL[s * Np + fp.vidM];
+                const double *rec = a.lapr + garg_at<NG, Np>(fp.vidP, fp.eP);
+#pragma unroll
+                for (int s = 0; s < NGL; ++s) lapP[s] = rec[s];
+            } else {
+                const int gslot = ghost_slot<Np>(a.h, fp.eP, fp.vidP);
+                load_plus<NS, Np, NS>(QP, a.Q, a.h.recvQ, gslot, fp.vidP, fp.eP);
+                load_state<NAUX, Np>(auxP, a.aux, fp.vidP, fp.eP);
+#pragma unroll
+                for (int s = 0; s < NGL; ++s) lapM[s] = sL[s * Np + fp.vidM];
+                load_plus<NHYP, Np, NGL, NGL>(lapP, a.hypdiv, a.h.recvHD, gslot, fp.vidP, fp.eP);
+            }
             if (fp.bctag != 0)  // numerical_boundary_flux_higher_order!  :792-832
                 P::boundary_state_higher_order(a.prm, fp.bctag, QP, auxP, lapP, fp.n, QM, auxM,
                                                lapM, a_t);
@@ -1271,7 +1316,7 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT), CMDG_LAP_MINW) k_gradlap
             for (int s = 0; s < NHYP; ++s) lh[s] = 0;
             P::post_gradient_laplacian(a.prm, lh, G, QM, auxM, a_t);
 #pragma unroll
-            for (int s = 0; s < NHYP; ++s) corr[s] = fp.vMI * fp.sM * lh[s];
+            for (int s = 0; s < NHYP; ++s) corr[s] = fp.w * lh[s];
             vidM = fp.vidM;
             fpair = f / 2;
         }

@@ -38,6 +38,7 @@ static void lsrk_stage_buffers(EngineBase *e, double *Q, int s, int nstages, dou
 struct StageHandoff {
     bool garg_in;  // the gradient pass reads the records the update before it left
     GargOut out;
+    bool last_eval;  // the run's last evaluation: the caller's Qhypervisc_div is written
 };
 // The hand-off lives inside one run, so that nothing is carried over from or into another call:
 //  - every evaluation but the run's first reads the records; that one reads Q;
@@ -46,14 +47,17 @@ struct StageHandoff {
 //    nstages - 2 of the last step: where the law lets the unread ones go (refresh_elidable) the
 //    others leave the records alone.  (A one-stage tableau has that update in the step before the
 //    last; it refreshes in every update.)
+//  - an evaluation that reads the records hands its Laplacians from k_divgrad to k_gradlap as
+//    ring-ordered records (RhsCtx::garg_in); only the run's last one writes the caller's
+//    Qhypervisc_div as well.
 // run == NULL: a step outside cmdg_lsrk_run, or a run that does not hand off.
 static StageHandoff handoff_stage(const StepInRun *run, int s, int nstages, bool refresh_elidable)
 {
-    if (!run) return {false, GargOut::none};
+    if (!run) return {false, GargOut::none, true};
     const bool in = !(run->first_step && s == 0);
-    if (run->last_step && s == nstages - 1) return {in, GargOut::none};
+    if (run->last_step && s == nstages - 1) return {in, GargOut::none, true};
     const bool refresh = !refresh_elidable || nstages == 1 || (run->last_step && s == nstages - 2);
-    return {in, refresh ? GargOut::records_refresh : GargOut::records};
+    return {in, refresh ? GargOut::records_refresh : GargOut::records, false};
 }
 
 int EngineBase::lsrk_step(double *Q, double *dQ, double t, double dt, int nstages, const double *rka,
@@ -97,6 +101,7 @@ int group_lsrk_step(std::vector<EngineBase *> &g, double **Q, double **dQ, doubl
             const StageHandoff h = handoff_stage(handoff, s, nstages, g[i]->refresh_elidable());
             x.garg_in = h.garg_in;
             x.garg_out = h.out;
+            x.hypdiv_out = !h.garg_in || h.last_eval;
             if (h.out == GargOut::records_refresh) g[i]->handoff_refreshes += 1;
         }
         if (int r = group_rhs(g, c, s > 0 || continued)) return r;

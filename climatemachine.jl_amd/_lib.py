@@ -244,6 +244,12 @@ SYMBOLS = [
     ("cmdg_interp_apply", C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp]),
     ("cmdg_interp_project", C.c_int, [_vp, _vp, _vp, _i32, _vp]),
     ("cmdg_interp_scatter", C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp]),
+    ("cmdg_dss_create", C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    ("cmdg_dss_destroy", C.c_int, [_vp, _vp]),
+    ("cmdg_dss_info", C.c_int, [_vp, _vp]),
+    ("cmdg_dss_apply", C.c_int, [_vp, _vp, _vp, _i32]),
+    ("cmdg_dss", C.c_int, [_vp, _vp, _vp, _i32]),
+    ("cmdg_group_dss", C.c_int, [_vp, _i32, _vp, _vp, _i32]),
 ]
 
 _LIB = None

@@ -566,6 +566,32 @@ int set_err(cmdg_handle h, int code);
 // the message of cmdg_last_error(NULL), one per thread (create.hip): calls that fail without a handle
 void set_create_err(const std::string &msg);
 
+// Objects that are not bound to a handle (interpolation, direct stiffness summation) live on the
+// device they were created on: it is made current for a call and the caller's restored on return.
+struct ObjectDevice {
+    int prev = -1;
+    bool changed = false;
+    explicit ObjectDevice(int dev)
+    {
+        if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = hipSetDevice(dev) == hipSuccess;
+    }
+    ~ObjectDevice()
+    {
+        if (changed) (void)hipSetDevice(prev);
+    }
+    ObjectDevice(const ObjectDevice &) = delete;
+    ObjectDevice &operator=(const ObjectDevice &) = delete;
+};
+// the one epilogue of their entries, which take a handle or NULL: the message goes to the handle, or
+// to cmdg_last_error(NULL) without one
+inline int object_call_done(cmdg_handle h, int r, const std::string &err)
+{
+    if (r == CMDG_OK) return r;
+    if (h) return set_err(h, h->eng->fail(r, err));
+    set_create_err(err);
+    return r;
+}
+
 // what a plug-in and the library must agree on (cmdg_load_plugin): the layout of the engine base
 // class and of the descriptor, folded into one number
 inline unsigned long engine_abi_stamp()

@@ -356,30 +356,6 @@ int interp_scatter(const InterpObj *const *o, int n, const double *const *v, int
 // ---- the C entries ------------------------------------------------------------------------------
 using namespace cmdg;
 
-namespace {
-// the device of an interpolation object made current for a call without a handle
-struct InterpDevice {
-    int prev = -1;
-    bool changed = false;
-    explicit InterpDevice(int dev)
-    {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = hipSetDevice(dev) == hipSuccess;
-    }
-    ~InterpDevice()
-    {
-        if (changed) (void)hipSetDevice(prev);
-    }
-};
-// one epilogue: the message goes to the handle, or to cmdg_last_error(NULL) without one
-int interp_done(cmdg_handle h, int r, const std::string &err)
-{
-    if (r == CMDG_OK) return r;
-    if (h) return set_err(h, h->eng->fail(r, err));
-    set_create_err(err);
-    return r;
-}
-}  // namespace
-
 extern "C" {
 
 int cmdg_interp_create(cmdg_handle h, const cmdg_interp_desc *d, cmdg_interp *out)
@@ -391,7 +367,7 @@ int cmdg_interp_create(cmdg_handle h, const cmdg_interp_desc *d, cmdg_interp *ou
     std::string err;
     const int r = interp_create(d, &o, err);
     *out = reinterpret_cast<cmdg_interp>(o);
-    return interp_done(h, r, err);
+    return object_call_done(h, r, err);
 }
 
 int cmdg_interp_destroy(cmdg_handle h, cmdg_interp it)
@@ -403,7 +379,7 @@ int cmdg_interp_destroy(cmdg_handle h, cmdg_interp it)
         guard_.emplace(h->eng);
         h->eng->synchronize();
     }
-    InterpDevice dev_(interp_device(o));
+    ObjectDevice dev_(interp_device(o));
     (void)hipStreamSynchronize(nullptr);  // (calls without a handle have returned; see include/cmdg.h)
     interp_destroy(o);
     return CMDG_OK;
@@ -417,9 +393,9 @@ int cmdg_interp_apply(cmdg_handle h, cmdg_interp it, const double *Q, int32_t ns
     if (h) guard_.emplace(h->eng);
     std::string err;
     if (h && h->eng->dev != interp_device(o))
-        return interp_done(h, CMDG_ERR_INVALID, "cmdg_interp_apply: the object lives on another device than the handle");
-    InterpDevice dev_(interp_device(o));
-    return interp_done(h, interp_apply(o, Q, nstate, nelemQ, v, h ? h->eng->s_comp : nullptr, !h, err), err);
+        return object_call_done(h, CMDG_ERR_INVALID, "cmdg_interp_apply: the object lives on another device than the handle");
+    ObjectDevice dev_(interp_device(o));
+    return object_call_done(h, interp_apply(o, Q, nstate, nelemQ, v, h ? h->eng->s_comp : nullptr, !h, err), err);
 }
 
 int cmdg_interp_project(cmdg_handle h, cmdg_interp it, double *v, int32_t nstate, const int32_t uvwi[3])
@@ -430,9 +406,9 @@ int cmdg_interp_project(cmdg_handle h, cmdg_interp it, double *v, int32_t nstate
     if (h) guard_.emplace(h->eng);
     std::string err;
     if (h && h->eng->dev != interp_device(o))
-        return interp_done(h, CMDG_ERR_INVALID, "cmdg_interp_project: the object lives on another device than the handle");
-    InterpDevice dev_(interp_device(o));
-    return interp_done(h, interp_project(o, v, nstate, uvwi, h ? h->eng->s_comp : nullptr, !h, err), err);
+        return object_call_done(h, CMDG_ERR_INVALID, "cmdg_interp_project: the object lives on another device than the handle");
+    ObjectDevice dev_(interp_device(o));
+    return object_call_done(h, interp_project(o, v, nstate, uvwi, h ? h->eng->s_comp : nullptr, !h, err), err);
 }
 
 int cmdg_interp_scatter(cmdg_handle h, const cmdg_interp *its, int32_t n, const double *const *v, int32_t nstate,
@@ -446,9 +422,9 @@ int cmdg_interp_scatter(cmdg_handle h, const cmdg_interp *its, int32_t n, const 
     if (h) guard_.emplace(h->eng);
     std::string err;
     if (h && h->eng->dev != interp_device(o[0]))
-        return interp_done(h, CMDG_ERR_INVALID, "cmdg_interp_scatter: the objects live on another device than the handle");
-    InterpDevice dev_(interp_device(o[0]));
-    return interp_done(h, interp_scatter(o, n, v, nstate, fiv, h ? h->eng->s_comp : nullptr, !h, err), err);
+        return object_call_done(h, CMDG_ERR_INVALID, "cmdg_interp_scatter: the objects live on another device than the handle");
+    ObjectDevice dev_(interp_device(o[0]));
+    return object_call_done(h, interp_scatter(o, n, v, nstate, fiv, h ? h->eng->s_comp : nullptr, !h, err), err);
 }
 
 }  // extern "C"

@@ -8,6 +8,8 @@ from .topologies import (BrickTopology, CubedShellTopology, StackedBrickTopology
 from .interpolation import (InterpolationBrick, InterpolationCubedSphere,
                             accumulate_interpolated_data, dimensions,
                             interpolate_local, project_cubed_sphere)
+# (``mesh.dss`` is the function, the reference's ``dss!``; the module's other names are re-exported here)
+from .dss import DSS, CmdgDssDesc, dss, dss_apply, group_dss
 
 __all__ = [
     "brickmesh", "elements", "filters", "grids", "interpolation", "topologies",
@@ -16,4 +18,5 @@ __all__ = [
     "equiangular_cubed_sphere_warp", "equiangular_cubed_sphere_unwarp",
     "InterpolationBrick", "InterpolationCubedSphere", "interpolate_local",
     "project_cubed_sphere", "accumulate_interpolated_data", "dimensions",
+    "DSS", "dss", "dss_apply", "group_dss", "CmdgDssDesc",
 ]

@@ -545,7 +545,8 @@ def connectmeshfull(mesh, rank=0, size=1, dim=2, part=None, partcoord=None):
                 j += 2
             else:
                 j += 1
-    # locally unique vertex numbers (for completeness; DSS is out of scope)
+    # locally unique vertex numbers: what the stacked topologies build their DSS tables from
+    # (BrickMesh.jl:1441-1456)
     ev = gldofv[elemtovert[allg]]
     uniq = np.unique(ev)
     remap = {int(v): i + 1 for i, v in enumerate(uniq)}

@@ -25,6 +25,7 @@ _n1, _n2, _n3, _sM, _vMI = range(5)
 NSGEO = 5
 
 __all__ = ["DiscontinuousSpectralElementGrid", "mappings", "commmapping",
+           "init_vertex_edge_face_mappings",
            "computegeometry", "computegeometry_fvm", "glpoints", "NVGEO", "NSGEO"]
 
 
@@ -82,6 +83,49 @@ def mappings(N, elemtoelem, elemtoface, elemtoordr):
             raise NotImplementedError(
                 "Orientation '%d' with dim '%d' not supported yet" % (o2[bad][0], d))
     return vmapM, vmapP
+
+
+def init_vertex_edge_face_mappings(N):
+    """``(vertmap, edgemap, facemap)`` of direct stiffness summation: the 1-based element node of
+    every corner ``vertmap (8,)``, of the ``i``-th interior node of every edge under both
+    orientations ``edgemap (2, 12, Nemax)`` and of the ``ij``-th interior node of every face
+    ``facemap (2, 6, Nfmax)``, padded with -1 where the orders differ; ``None`` where the reference
+    has ``nothing`` (not 3-D, fewer than three points in the vertical, no interior face node).
+    Reference: Grids.jl:640-745."""
+    Np = tuple(n + 1 for n in N)
+    if not (len(N) == 3 and Np[2] > 2):
+        return None, None, None
+    nodes = np.arange(1, int(np.prod(Np)) + 1, dtype=np.int64).reshape(Np, order="F")
+    ends = [(0, Np[d] - 1) for d in range(3)]
+    vertmap = np.array([nodes[ends[0][v & 1], ends[1][(v >> 1) & 1], ends[2][v >> 2]]
+                        for v in range(8)], dtype=np.int64)
+    inner = [slice(1, Np[d] - 1) for d in range(3)]
+    Ne = [q - 2 for q in Np]
+    edgemap = -np.ones((2, 12, max(Ne)), dtype=np.int64)     # (Np[2] > 2: Nemax >= 1)
+    for d in range(3):                      # edges 4 d + 1 .. 4 d + 4 run along direction d
+        if Ne[d] < 1:
+            continue
+        o1, o2 = [x for x in range(3) if x != d]
+        for q in range(4):
+            idx = [None] * 3
+            idx[d], idx[o1], idx[o2] = inner[d], ends[o1][q & 1], ends[o2][q >> 1]
+            line = nodes[tuple(idx)]
+            edgemap[0, 4 * d + q, :Ne[d]] = line
+            edgemap[1, 4 * d + q, :Ne[d]] = line[::-1]
+    Nf = [Ne[1] * Ne[2], Ne[0] * Ne[2], Ne[0] * Ne[1]]
+    facemap = None
+    if max(Nf) >= 1:
+        facemap = -np.ones((2, 6, max(Nf)), dtype=np.int64)
+        for d in range(3):                  # faces 2 d + 1, 2 d + 2 are normal to direction d
+            if Nf[d] < 1:
+                continue
+            for side in range(2):
+                idx = list(inner)
+                idx[d] = ends[d][side]
+                face = nodes[tuple(idx)]    # (first, second) remaining direction
+                facemap[0, 2 * d + side, :Nf[d]] = face.flatten(order="F")
+                facemap[1, 2 * d + side, :Nf[d]] = face[::-1, :].flatten(order="F")
+    return vertmap, edgemap, facemap
 
 
 def commmapping(N, commelems, commfaces, nabrtocomm):
@@ -432,6 +476,23 @@ class DiscontinuousSpectralElementGrid:
     @property
     def nelem(self):
         return self.topology.nelem
+
+    def _dss_maps(self):
+        if getattr(self, "_vefmaps", None) is None:       # built at first access
+            self._vefmaps = init_vertex_edge_face_mappings(self.N)
+        return self._vefmaps
+
+    @property
+    def vertmap(self):
+        return self._dss_maps()[0]
+
+    @property
+    def edgemap(self):
+        return self._dss_maps()[1]
+
+    @property
+    def facemap(self):
+        return self._dss_maps()[2]
 
     @property
     def nreal(self):

@@ -57,10 +57,59 @@ class Topology:
         self.exteriorelems = ext.astype(np.int64)
         self.interiorelems = np.setdiff1d(
             np.arange(1, self.nreal + 1, dtype=np.int64), ext)
+        # locally unique vertex numbers of connectivity = "full" (BrickMesh.jl:1441-1456); a stacked
+        # topology carries its base (2-D) topology's.  The DSS tables below are built from them
+        # at first access.
+        self.elemtovert = conn.get("elemtovert")
+        self._dss = None
 
     @property
     def isstacked(self):
         return self.stacksize is not None
+
+    # -- direct stiffness summation tables (Topologies.jl:810-988, :1687-1850) -------------
+    def _dss_tables(self):
+        if self._dss is None:
+            if not self.isstacked:
+                # BrickTopology / CubedShellTopology: elemtouvert only (Topologies.jl:530, :1136)
+                self._dss = dict(elemtouvert=self.elemtovert, vtconn=None, vtconnoff=None,
+                                 fcconn=None, edgconn=None, edgconnoff=None)
+            else:
+                self._dss = _dss_tables(self)
+        return self._dss
+
+    @property
+    def elemtouvert(self):
+        """``(nelem, nvert)`` locally unique vertex numbers, 1-based; ``None`` without
+        ``connectivity = "full"``."""
+        return self._dss_tables()["elemtouvert"]
+
+    @property
+    def vtconn(self):
+        """Pairs ``(local vertex, element)`` of every vertex more than one element meets at, in
+        ``(el, lvt)`` loop order."""
+        return self._dss_tables()["vtconn"]
+
+    @property
+    def vtconnoff(self):
+        """1-based offsets into ``vtconn``, one more than there are unique vertex numbers."""
+        return self._dss_tables()["vtconnoff"]
+
+    @property
+    def fcconn(self):
+        """``(5, nfc)``: rows ``fc, el, nabrfc, nabrel, ordr`` of every interior face of a real
+        element (Julia ``(nfc, 5)``)."""
+        return self._dss_tables()["fcconn"]
+
+    @property
+    def edgconn(self):
+        """Triples ``(local edge, orientation, element)`` of every shared edge."""
+        return self._dss_tables()["edgconn"]
+
+    @property
+    def edgconnoff(self):
+        """1-based offsets into ``edgconn``."""
+        return self._dss_tables()["edgconnoff"]
 
     @property
     def realelems(self):
@@ -133,14 +182,99 @@ def _stack(base, stacksize, dim, elemtocoord, elemtoordr_map, vert_nbr, vert_bnd
                 elemtoelem=elemtoelem, elemtoface=elemtoface, elemtoordr=elemtoordr,
                 elemtobndy=elemtobndy, nabrtorank=base.nabrtorank,
                 nabrtorecv=nabrtorecv, nabrtosend=nabrtosend,
-                globalelems=gl, origsendorder=base.origsendorder)
+                globalelems=gl, origsendorder=base.origsendorder,
+                elemtovert=base.elemtovert)
     return Topology(dim, conn, stacksize=stacksize, periodicstack=periodicstack,
                     bndytoelem=b2e, bndytoface=b2f, rank=rank, size=size)
 
 
+_EDGEMASK = np.array([[1, 3, 5, 7, 1, 2, 5, 6, 1, 2, 3, 4],
+                      [2, 4, 6, 8, 3, 4, 7, 8, 5, 6, 7, 8]]) - 1
+
+
+def _dss_tables(t):
+    """The direct-stiffness-summation tables of a stacked topology, as Topologies.jl:810-988 (brick)
+    and :1687-1850 (cubed sphere) build them; everything ``None`` where the reference has
+    ``nothing`` (a base topology without ``connectivity = "full"``).  The quirks that fix the
+    summation order and the group set are kept: vertex lists in ``(el, lvt)`` loop order and only
+    where more than one element meets, the top level of a periodic stack wrapping to the bottom
+    numbers, faces numbered by the ``fcmarker`` walk over the real elements, edges keyed by the
+    sorted pair of unique vertex numbers in first-encounter order with orientation 2 where the
+    pair was swapped, edges of one element or of ghost elements only dropped."""
+    none = dict(elemtouvert=None, vtconn=None, vtconnoff=None, fcconn=None, edgconn=None,
+                edgconnoff=None)
+    if t.elemtovert is None:
+        return none
+    dim, S = t.dim, t.stacksize
+    base = np.asarray(t.elemtovert, dtype=np.int64)          # (nelem_base, 2^(dim-1))
+    nvb = base.shape[1]
+    nvert, nface, nelem, nreal = 2 * nvb, 2 * dim, t.nelem, t.nreal
+    # ---- vertices: (b - 1)(S + 1) + level, the top of a periodic stack being the bottom again
+    lvl = np.arange(1, S + 1, dtype=np.int64)
+    bot = (base[:, None, :] - 1) * (S + 1) + lvl[None, :, None]      # (nbase, S, nvb)
+    top = bot + 1
+    if t.periodicstack:
+        top[:, S - 1, :] = bot[:, 0, :]
+    euv = np.concatenate([bot, top], axis=2).reshape(nelem, nvert)
+    flat = euv.reshape(-1)                                   # (el, lvt) loop order
+    order = np.argsort(flat, kind="stable")
+    vtmax = int(flat.max())
+    cnt = np.bincount(flat, minlength=vtmax + 1)[1:]         # elements per unique vertex number
+    keep = cnt > 1
+    vtconnoff = np.ones(vtmax + 1, dtype=np.int64)
+    np.cumsum(np.where(keep, 2 * cnt, 0), out=vtconnoff[1:])
+    vtconnoff[1:] += 1
+    sel = order[keep[flat[order] - 1]]
+    vtconn = np.stack([sel % nvert + 1, sel // nvert + 1], axis=1).reshape(-1)
+    # ---- faces: the reference's two walks over the real elements
+    e2e, e2f = t.elemtoelem.tolist(), t.elemtoface.tolist()
+    e2b, e2o = t.elemtobndy.tolist(), t.elemtoordr.tolist()
+    marker = {}
+    fcno = 0
+    for el in range(nreal):
+        for fc in range(nface):
+            if e2b[el][fc] == 0:
+                nabr = (e2e[el][fc] - 1, e2f[el][fc] - 1)
+                if marker.get((el, fc), -1) == -1 and marker.get(nabr, -1) == -1:
+                    fcno += 1
+                    marker[(el, fc)] = marker[nabr] = fcno
+    rows = [(-1,) * 5] * fcno
+    for el in range(nreal):
+        for fc in range(nface):
+            no = marker.get((el, fc), -1)
+            if no != -1:
+                nabr = (e2e[el][fc] - 1, e2f[el][fc] - 1)
+                rows[no - 1] = (fc + 1, el + 1, nabr[1] + 1, nabr[0] + 1, e2o[el][fc])
+                marker[(el, fc)] = marker[nabr] = -1
+    fcconn = np.ascontiguousarray(np.array(rows, dtype=np.int64).reshape(-1, 5).T)
+    # ---- edges
+    edgconn = edgconnoff = None
+    if dim == 3:
+        a, b = euv[:, _EDGEMASK[0]], euv[:, _EDGEMASK[1]]    # (nelem, 12), (el, edg) loop order
+        orient = (1 + (a > b)).reshape(-1)
+        key = (np.minimum(a, b) * (vtmax + 1) + np.maximum(a, b)).reshape(-1)
+        _, first, inv = np.unique(key, return_index=True, return_inverse=True)
+        rank = np.empty(len(first), dtype=np.int64)
+        rank[np.argsort(first, kind="stable")] = np.arange(len(first))
+        uedg = rank[inv.reshape(-1)]                         # 0-based first-encounter number
+        order = np.argsort(uedg, kind="stable")
+        el = np.arange(nelem * 12) // 12
+        cnt = np.bincount(uedg, minlength=len(first))
+        real = np.bincount(uedg, weights=(el < nreal), minlength=len(first)) > 0
+        keep = (cnt > 1) & real
+        edgconnoff = np.ones(int(keep.sum()) + 1, dtype=np.int64)
+        np.cumsum(3 * cnt[keep], out=edgconnoff[1:])
+        edgconnoff[1:] += 1
+        sel = order[keep[uedg[order]]]
+        edgconn = np.stack([sel % 12 + 1, orient[sel], sel // 12 + 1], axis=1).reshape(-1)
+    return dict(elemtouvert=euv, vtconn=vtconn, vtconnoff=vtconnoff, fcconn=fcconn,
+                edgconn=edgconn, edgconnoff=edgconnoff)
+
+
 def StackedBrickTopology(elemrange, boundary=None, periodicity=None,
                          connectivity="full", rank=0, size=1):
-    """Reference: Topologies.jl:631-1020 (DSS tables omitted: out of scope)."""
+    """Reference: Topologies.jl:631-1020.  The DSS tables (:810-988) are built at first access
+    of ``vtconn``, ``fcconn``, ``edgconn`` and their offsets (:func:`_dss_tables`)."""
     dim = len(elemrange)
     assert dim > 1, "Stacked brick topology works for 2D and 3D"
     boundary = boundary or tuple((1, 1) for _ in range(dim))
@@ -246,7 +380,8 @@ def CubedShellTopology(Neside, T=np.float64, connectivity="full", rank=0, size=1
 
 def StackedCubedSphereTopology(Nhorz, Rrange, boundary=(1, 1), connectivity="full",
                                rank=0, size=1):
-    """Reference: Topologies.jl:1522-1700 (DSS tables omitted: out of scope)."""
+    """Reference: Topologies.jl:1522-1700.  The DSS tables (:1687-1850) are built at first access
+    of ``vtconn``, ``fcconn``, ``edgconn`` and their offsets (:func:`_dss_tables`)."""
     Rrange = np.asarray(Rrange)
     T = Rrange.dtype
     base = CubedShellTopology(Nhorz, T, connectivity, rank, size)

@@ -635,6 +635,68 @@ int cmdg_interp_project(cmdg_handle h, cmdg_interp it, double *v, int32_t nstate
 int cmdg_interp_scatter(cmdg_handle h, const cmdg_interp *its, int32_t n, const double *const *v,
                         int32_t nstate, double *fiv);
 
+/* ---- direct stiffness summation (src/Numerics/Mesh/DSS.jl) --------------------------------------
+ * dss!(Q, grid) makes a DG field single-valued at the nodes elements share: every copy of a shared
+ * vertex, edge node or face node is replaced by the sum over the copies.  The descriptor carries
+ * the reference's own tables unchanged (Int64, 1-based, Julia's column-major layouts): of
+ * grid.topology (Topologies.jl:810-988, :1687-1850) and of the grid (Grids.jl:640-745).  Every
+ * pointer is a HOST pointer and need not outlive cmdg_dss_create, which checks the tables and
+ * flattens them into groups of (element, node) members, one group per shared node.
+ *
+ * The kernel gathers a group's members in the reference's order, adds them starting from -0.0 and
+ * writes the sum to every member: additions only (the library is built without contraction), no
+ * atomics, so the result equals the reference's loops (dss3d_CPU!, DSS.jl:128-165) bit for bit and is
+ * the same in every run.  That is race-free because no node is in two groups, which create checks.
+ *
+ * Refused at create (CMDG_ERR_INVALID, message in cmdg_last_error(h)): fewer than 3 points in the
+ * vertical or 2 in the horizontal; Np nelem beyond 2^31 - 1; offsets that do not start at 1, decrease
+ * or cut a record; an element, node, local vertex (1..8), local edge (1..12), local face (1..6), edge
+ * orientation (1..2) or face orientation (1 or 3) out of range; a node that appears in two groups.
+ *
+ * cmdg_dss_create, cmdg_dss_destroy and cmdg_dss_apply take a handle or NULL under the rules written
+ * at the interpolation entries above: with a handle the summation is enqueued on that handle's
+ * compute stream, after any deferred CMDG_OPT_ASYNC_RUN run, and the call returns without waiting
+ * (follow with cmdg_synchronize), as cmdg_filter_apply does; with NULL it runs on the default stream
+ * of the device the object was created on and the call returns when it is done, which serves
+ * polynomial orders no engine is compiled for, such as (4, 4, 5). */
+/* (the object type is cmdg_dss_t: cmdg_dss is the call that is the reference's dss!) */
+typedef struct cmdg_dss_s *cmdg_dss_t;
+typedef struct cmdg_dss_desc {
+    int32_t Nq[3];             /* polynomialorders(grid) .+ 1 */
+    int64_t nelem;             /* length(topology.elems): real and ghost elements */
+    int64_t nreal;             /* length(topology.realelems) */
+    int64_t nvt;               /* length(vtconnoff) - 1 */
+    const int64_t *vtconn;     /* pairs (local vertex, element) */
+    const int64_t *vtconnoff;  /* nvt + 1 offsets into vtconn, 1-based */
+    int64_t nedg;              /* length(edgconnoff) - 1 */
+    const int64_t *edgconn;    /* triples (local edge, orientation, element) */
+    const int64_t *edgconnoff; /* nedg + 1 offsets into edgconn, 1-based */
+    int64_t nfc;               /* size(fcconn, 1) */
+    const int64_t *fcconn;     /* (nfc, 5) column-major: face, element, neighbour's face, neighbour, orientation */
+    const int64_t *vertmap;    /* 8 */
+    const int64_t *edgemap;    /* (Nemax, 12, 2) column-major, -1 where an edge has fewer nodes */
+    int64_t Nemax;             /* size(edgemap, 1) */
+    const int64_t *facemap;    /* (Nfmax, 6, 2) column-major, -1 where a face has fewer nodes */
+    int64_t Nfmax;             /* size(facemap, 1) */
+} cmdg_dss_desc;
+int cmdg_dss_create(cmdg_handle h, const cmdg_dss_desc *d, cmdg_dss_t *out);
+/* waits for the handle h (if given) and for the device's default stream, then frees the tables; work
+ * that used the object through ANOTHER handle must have been synchronised by the caller */
+int cmdg_dss_destroy(cmdg_handle h, cmdg_dss_t dss);
+/* out[0..3]: groups, members, the most members of one group, nodes touched */
+int cmdg_dss_info(cmdg_dss_t dss, int64_t out[4]);
+/* the summation alone, in place, on Q (Np, nstate, nelem) with nelem as at create (ghost elements
+ * take part: they must hold their owners' values, as after a ghost exchange) */
+int cmdg_dss_apply(cmdg_handle h, cmdg_dss_t dss, double *Q, int32_t nstate);
+/* dss!(Q, grid) (DSS.jl:21-76): begin_ghost_exchange!, end_ghost_exchange! with unpacking into the
+ * ghost elements -- the path of cmdg_halo_begin / cmdg_halo_end, so nstate beyond the handle's
+ * exchange buffers is refused as there -- then the summation, ordered after the exchange.  Needs a
+ * handle whose grid is the object's (same Np and element count); returns when the work is done. */
+int cmdg_dss(cmdg_handle h, cmdg_dss_t dss, double *Q, int32_t nstate);
+/* the same for handles connected with cmdg_comm_connect_local: begin on all, end on all, sum on all,
+ * synchronise all.  dss and Q are HOST arrays of n objects / device arrays. */
+int cmdg_group_dss(cmdg_handle *handles, int32_t n, const cmdg_dss_t *dss, double **Q, int32_t nstate);
+
 /* ---- law-specific update_auxiliary_state! / update_auxiliary_state_gradient! ----------- */
 /* Laws whose auxiliary state needs more than a nodal refresh override these two methods in
  * the reference (BalanceLaws/interface.jl:276-305; called at DGModel.jl:110-116,161-172 and

@@ -23,10 +23,11 @@ OPT_TENDENCY_PAIRS = 7  # retired: accepted, no effect (and CMDG_Q TENDENCY_PAIR
 OPT_ASYNC_RUN = 8
 OPT_TENDENCY_FOUR_WAVES = 9  # retired: accepted, no effect
 OPT_GRADARG_HANDOFF = 10  # the fused LSRK update forms the next stage's gradient arguments (default on)
+OPT_FUSED_LAPLACIAN = 11  # a hand-off evaluation forms gradients and Laplacians in one launch (default on)
 CMDG_Q = dict(GRADFLUX_LIVE=1, LAW_NEEDS_GRADFLUX=2, NDERIVED=3, NUPDATED_AUX=4, FUSED_UPDATE_AUX=5,
               DIRECT_SEND=6, DIRECT_RECV=7, TENDENCY_ELEMS_PER_GROUP=8, HALO_PIPELINE=9, HOST_POST_NS=10, HOST_POST_COUNT=11, GRAPH_STEPS=12, TENDENCY_PAIRS=13,
               GRADARG_HANDOFF=14, GRADARG_REFRESHES=15,
-              STATE_READ=16, AUX_READ=20)
+              STATE_READ=16, AUX_READ=20, FUSED_LAPLACIAN=24)
 
 
 class CmdgStackIntegralDesc(C.Structure):

@@ -6,6 +6,7 @@
 #include <new>
 #include <tuple>
 
+#include "lapfused_tables.h"
 #include "rccl.h"
 #include "stepping.h"
 
@@ -206,6 +207,67 @@ static __global__ void k_face_digest(const double *__restrict__ vgeo, int nvgeo,
     if (flags) atomicOr(bad, flags);
 }
 
+// The doubles of the fused Laplacian pass's table (lapT of k_lapfused) once the host has found tP
+// (lapfused_tables.h): the neighbour's horizontal metric rows at the plus node, its normal and lift
+// weight at its own face task of the shared node.
+static __global__ void k_lapfused_fill(const double *__restrict__ vgeo, int nvgeo, const int32_t *__restrict__ faceP,
+                                       const double *__restrict__ faceG, const double *__restrict__ faceW,
+                                       const int32_t *__restrict__ lapI, int Np, int NFT, int NL, int64_t nreal,
+                                       double *__restrict__ lapT)
+{
+    const int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (I >= nreal * NL) return;
+    const int64_t e = I / NL;
+    const int t = (int)(I % NL);
+    const int64_t idP = faceP[NFT * e + t], N = idP / Np;
+    const int vidP = (int)(idP - N * Np), tP = lapI[(2 * e + 0) * NL + t];
+    const double *vg = vgeo + (int64_t)Np * nvgeo * N + vidP;
+    const int rows[6] = {XI1X1, XI1X2, XI1X3, XI2X1, XI2X2, XI2X3};
+    double *dst = lapT + 10 * e * NL + t;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) dst[(int64_t)c * NL] = vg[(int64_t)rows[c] * Np];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dst[(int64_t)(6 + c) * NL] = faceG[((int64_t)4 * N + c) * NFT + tP];
+    dst[(int64_t)9 * NL] = faceW[NFT * N + tP];
+}
+
+// CMDG_OPT_FUSED_LAPLACIAN: is this a handle whose hand-off evaluations can take k_lapfused?  What
+// can be known at create is decided here, once: the law and order hand gradient arguments on, one
+// rank without ghosts, horizontal diffusion, a Laplacian pass that overwrites all of
+// Qhypervisc_grad (what the gradient pass would have left there is then seen by nobody), and a grid
+// that lapfused_build accepts.  Everything else keeps the two kernels (lapfused_ok stays false).
+int EngineBase::init_lapfused()
+{
+    if (!garg_capable() || ngl <= 0 || nhyp != 3 * ngl || diffusion_direction != DIR_HORIZONTAL || nghost != 0 ||
+        communicate() || fv || esdg || nreal < 1)
+        return CMDG_OK;
+    const int NFT = 4 * NQ * NQV + 2 * NQ * NQ, NL = 4 * NQ * NQV;
+    std::vector<int32_t> h_faceP((size_t)(nreal * NFT));
+    std::vector<int64_t> h_bndy((size_t)(6 * nreal));
+    HIPCHK(hipMemcpy(h_faceP.data(), d_faceP, sizeof(int32_t) * h_faceP.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h_bndy.data(), g.elemtobndy, sizeof(int64_t) * h_bndy.size(), hipMemcpyDeviceToHost));
+    LapFusedTables tab;
+    lapfused_build(NQ, NQV, nreal, h_faceP.data(), h_bndy.data(), tab);
+    if (!tab.eligible) return CMDG_OK;
+    // lapI[e][c][t]
+    std::vector<int32_t> h_lapI((size_t)(2 * NL * nreal));
+    for (int64_t e = 0; e < nreal; ++e)
+        for (int t = 0; t < NL; ++t) {
+            h_lapI[(size_t)((2 * e + 0) * NL + t)] = tab.tP[(size_t)(NL * e + t)];
+            h_lapI[(size_t)((2 * e + 1) * NL + t)] = tab.tE[(size_t)(NL * e + t)];
+        }
+    HIPCHK(d_lapI.alloc(h_lapI.size()));
+    HIPCHK(d_lapT.alloc((size_t)(10 * NL * nreal)));
+    HIPCHK(hipMemcpy(d_lapI, h_lapI.data(), sizeof(int32_t) * h_lapI.size(), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_lapfused_fill, dim3((unsigned)((nreal * NL + 255) / 256)), dim3(256), 0, s_comp, g.vgeo,
+                       g.nvgeo, d_faceP.get(), d_faceG.get(), d_faceW.get(), d_lapI.get(), Np, NFT, NL, nreal,
+                       d_lapT.get());
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s_comp) != hipSuccess)
+        return fail(CMDG_ERR_HIP, "cmdg_create: the tables of the fused Laplacian pass failed");
+    lapfused_ok = true;
+    return CMDG_OK;
+}
+
 int EngineBase::init(const cmdg_desc *d)
 {
     Np = NQ * NQ * NQV;
@@ -320,6 +382,7 @@ int EngineBase::init(const cmdg_desc *d)
         g.faceW = d_faceW;
         g.facePr = d_facePr;
     }
+    if (int r = init_lapfused()) return r;
     aux = d->state_auxiliary;
     const size_t nd = (size_t)Np * nelem;
     // hipMemset of device memory returns before the fill has run, and on the null stream it is not
@@ -971,6 +1034,7 @@ int cmdg_set_option(cmdg_handle h, int32_t option, int32_t value)
     case CMDG_OPT_TENDENCY_PAIRS:
     case CMDG_OPT_TENDENCY_FOUR_WAVES: return CMDG_OK;  // retired: no effect
     case CMDG_OPT_GRADARG_HANDOFF: e->gradarg_handoff = value != 0; return CMDG_OK;
+    case CMDG_OPT_FUSED_LAPLACIAN: e->fused_laplacian = value != 0; return CMDG_OK;
     case CMDG_OPT_HALO_PIPELINE:
         if (int r = e->synchronize()) return set_err(h, r);
         e->drop_graph();
@@ -998,6 +1062,7 @@ int cmdg_query(cmdg_handle h, int32_t what, int64_t *out)
     case CMDG_Q_TENDENCY_PAIRS: *out = -1; return CMDG_OK;  // retired option: always off
     case CMDG_Q_GRADARG_HANDOFF: *out = e->handoff_used; return CMDG_OK;
     case CMDG_Q_GRADARG_REFRESHES: *out = e->handoff_refreshes; return CMDG_OK;
+    case CMDG_Q_FUSED_LAPLACIAN: *out = e->fused_launches; return CMDG_OK;
     case CMDG_Q_HOST_POST_NS: *out = e->host_post_ns; return CMDG_OK;
     case CMDG_Q_HOST_POST_COUNT: *out = e->host_post_n; return CMDG_OK;
     case CMDG_Q_HALO_PIPELINE: *out = e->pipelined() && !e->has_hooks; return CMDG_OK;

@@ -94,10 +94,14 @@ struct EngineT : EngineBase {
     // The Laplacian and gradient-of-Laplacian passes of an evaluation that reads the records (c.garg_in)
     // hand the Laplacians on as ring-ordered records (cmdg_common.h ring_slot); the second gathers
     // them through facePr.
-    static Kernel pick_divgrad(bool ring)
+    // fused (RhsCtx::lap_fused): the launch does the work of the gradient pass as well, which is then
+    // not launched (k_lapfused).
+    static Kernel pick_divgrad(bool ring, bool fused)
     {
-        if constexpr (HO)
+        if constexpr (HO) {
+            if (ring && fused) return k_lapfused<P, NQ_, NQV_>;
             if (ring) return k_divgrad<P, NQ_, NQV_, true>;
+        }
         return k_divgrad<P, NQ_, NQV_>;
     }
     static Kernel pick_gradlap(bool ring)
@@ -108,6 +112,7 @@ struct EngineT : EngineBase {
     }
     void launch_gradients(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
     {
+        if (c.lap_fused) return;  // (formed inside the Laplacian launch)
         in_pass(GRADIENTS, n, exterior, st, [&] {
             const PassArgs<P> args = make_args(c, elems, n, diffusion_direction, exterior,
                                                gf_live() ? slot[SLOT_GF].sendbuf : nullptr,
@@ -119,8 +124,13 @@ struct EngineT : EngineBase {
     void launch_divgrad(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
     {
         in_pass(DIVGRAD, n, exterior, st, [&] {
-            const PassArgs<P> args = make_args(c, elems, n, diffusion_direction, exterior, slot[SLOT_HD].sendbuf, nullptr);
-            hipLaunchKernelGGL(pick_divgrad(c.garg_in), dim3((unsigned)n), dim3(KDims<NQ_, NQV_>::NT), 0, st, args);
+            PassArgs<P> args = make_args(c, elems, n, diffusion_direction, exterior, slot[SLOT_HD].sendbuf, nullptr);
+            const bool fused = HO && c.garg_in && c.lap_fused;
+            if (fused) {  // (the tables of k_lapfused travel in two arguments the pass does not read)
+                args.g.facePr = d_lapI;
+                args.derived = d_lapT;
+            }
+            hipLaunchKernelGGL(pick_divgrad(c.garg_in, fused), dim3((unsigned)n), dim3(KDims<NQ_, NQV_>::NT), 0, st, args);
         });
     }
     void launch_gradlap(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override

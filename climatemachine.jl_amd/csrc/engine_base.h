@@ -65,6 +65,9 @@ struct RhsCtx {
     // Qhypervisc_div (the run's last evaluation: the array ends a run as the ordinary kernels leave it).
     bool garg_in = false;
     bool hypdiv_out = true;
+    // CMDG_OPT_FUSED_LAPLACIAN: the gradient and Laplacian passes of this evaluation are one launch
+    // (kernels.h k_lapfused); only where garg_in holds on an eligible handle
+    bool lap_fused = false;
     GargOut garg_out = GargOut::none;
     double rkb_dt = 0, rka_next = 0;
     // the law's update_auxiliary_state!(realelems) composition has run already (group_rhs runs the
@@ -246,6 +249,15 @@ struct EngineBase {
                !step_graph && nghost == 0 && !communicate();
     }
     int ensure_garg();
+    // ---- CMDG_OPT_FUSED_LAPLACIAN (kernels.h k_lapfused, lapfused_tables.h) ------------------
+    DevBuf<int32_t> d_lapI;  // lapI / lapT of k_lapfused: allocated at create on an eligible grid only
+    DevBuf<double> d_lapT;
+    bool fused_laplacian = true;   // the option
+    bool lapfused_ok = false;      // the tables exist
+    int64_t fused_launches = 0;    // fused launches of the last cmdg_lsrk_run (cmdg_query)
+    int init_lapfused();           // decides eligibility of the grid, once, at create
+    // the hand-off evaluations of a run take the fused pass (the grid is eligible: lapfused_ok)
+    bool lapfused_eligible() const { return fused_laplacian && lapfused_ok; }
     DevBuf<double> d_partial;           // reduction scratch
     int transport = TRANSPORT_NONE;
     int rank = 0, nranks = 1;

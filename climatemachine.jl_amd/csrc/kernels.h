@@ -42,6 +42,17 @@
 #ifndef CMDG_LAP_MINW
 #define CMDG_LAP_MINW 1
 #endif
+// k_lapfused: its face lanes hold two lines of the neighbour's records in flight (200 VGPRs
+// unconstrained at N = 4, two work-groups per CU); four waves per SIMD keep five resident
+#ifndef CMDG_LAPFUSED_MINW
+#define CMDG_LAPFUSED_MINW 4
+#endif
+// ... and its gathers are issued in stages: the index the next stage's addresses are formed from
+// passes through an empty asm statement together with a result of the stage before, so that the
+// compiler cannot issue those loads before that result exists
+#ifndef CMDG_LAPFUSED_STAGE
+#define CMDG_LAPFUSED_STAGE(idx, dep) asm volatile("" : "+v"(idx) : "v"(dep))
+#endif
 
 namespace cmdg {
 
@@ -811,6 +822,72 @@ __host__ __device__ constexpr unsigned gradient_argument_mask()
     return m;
 }
 
+// ---- the per-node and per-face-node expressions of the hyperdiffusion passes: one text for
+// k_gradients, k_divgrad and k_lapfused, which must agree bit for bit ----------------------------
+// Horizontal volume gradient of one field at node (i, j, .): line1(n) = G(n, j, k), line2(n) =
+// G(i, n, k); added to gh[0..2], xi1 terms first.
+template <int NQ, class Line>
+__device__ __forceinline__ double line_derivative(const double *sD, int i, Line line)
+{
+    double G = 0.0;
+#pragma unroll
+    for (int n = 0; n < NQ; ++n) G += sD[i + NQ * n] * line(n);
+    return G;
+}
+__device__ __forceinline__ void metric_gradient(double x11, double x12, double x13, double x21, double x22,
+                                                double x23, double G1, double G2, double *gh)
+{
+    gh[0] += x11 * G1;
+    gh[1] += x12 * G1;
+    gh[2] += x13 * G1;
+    gh[0] += x21 * G2;
+    gh[1] += x22 * G2;
+    gh[2] += x23 * G2;
+}
+template <int NQ, class Line1, class Line2>
+__device__ __forceinline__ void grad_volume_h(const double *sD, int i, int j, Line1 line1, Line2 line2, double x11,
+                                              double x12, double x13, double x21, double x22, double x23,
+                                              double *gh)
+{
+    const double G1 = line_derivative<NQ>(sD, i, line1), G2 = line_derivative<NQ>(sD, j, line2);
+    metric_gradient(x11, x12, x13, x21, x22, x23, G1, G2, gh);
+}
+// CentralNumericalFluxGradient (NumericalFluxes.jl:67-83), one component of one field
+__device__ __forceinline__ double central_gradient_flux(double nd, double GP, double GM)
+{
+    return nd * (GP + GM) / 2;
+}
+// ... and what a face node adds to the gradient of its minus node
+__device__ __forceinline__ double gradient_lift(double w, double tg, double nGM)
+{
+    return w * (tg - nGM);
+}
+// M * (xi_d . grad G) of one field
+__device__ __forceinline__ double contravariant(double M, double xa, double xb, double xc, double G1, double G2,
+                                                double G3)
+{
+    return M * (xa * G1 + xb * G2 + xc * G3);
+}
+// horizontal volume divergence of one field at node (i, j, k): c1 / c2 = the xi1 / xi2 products [ijk]
+template <int NQ>
+__device__ __forceinline__ double div_volume_h(double MI, const double *sD, const double *c1, const double *c2, int i,
+                                               int j, int k)
+{
+    double dh = 0.0;
+#pragma unroll
+    for (int n = 0; n < NQ; ++n) {
+        dh -= MI * sD[n + NQ * i] * c1[n + NQ * (j + NQ * k)];
+        dh -= MI * sD[n + NQ * j] * c2[i + NQ * (n + NQ * k)];
+    }
+    return dh;
+}
+// CentralNumericalFluxDivergence (NumericalFluxes.jl:720-730) of one field: gP / gM its three components
+__device__ __forceinline__ double central_divergence_flux(const double *gP, const double *gM, double nh0, double nh1,
+                                                          double nh2)
+{
+    return (gP[0] + gM[0]) * nh0 + (gP[1] + gM[1]) * nh1 + (gP[2] + gM[2]) * nh2;
+}
+
 // GARG_IN (GradArgHandoff): the arguments of the volume nodes and of the plus side of interior
 // faces are read from the records the previous stage's fused update left; boundary faces keep
 // boundary_state on the element's own Q / aux; no auxiliary refresh (the update did it).
@@ -877,18 +954,10 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
 #pragma unroll
             for (int s = 0; s < NGRAD; ++s) {
                 if (!(GMASK >> s & 1)) continue;
-                double G1 = 0.0, G2 = 0.0;
-#pragma unroll
-                for (int n = 0; n < NQ; ++n) {
-                    G1 += sD[i + NQ * n] * sG[s * Np + n + NQ * (j + NQ * k)];
-                    G2 += sD[j + NQ * n] * sG[s * Np + i + NQ * (n + NQ * k)];
-                }
-                gh[3 * s + 0] += x11 * G1;
-                gh[3 * s + 1] += x12 * G1;
-                gh[3 * s + 2] += x13 * G1;
-                gh[3 * s + 0] += x21 * G2;
-                gh[3 * s + 1] += x22 * G2;
-                gh[3 * s + 2] += x23 * G2;
+                grad_volume_h<NQ>(
+                    sD, i, j, [&](int n) { return sG[s * Np + n + NQ * (j + NQ * k)]; },
+                    [&](int n) { return sG[s * Np + i + NQ * (n + NQ * k)]; }, x11, x12, x13, x21, x22, x23,
+                    &gh[3 * s]);
             }
         }
         if (vt) {
@@ -967,7 +1036,7 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
 #pragma unroll
                 for (int s = 0; s < NGRAD; ++s)
 #pragma unroll
-                    for (int d = 0; d < 3; ++d) tg[d + 3 * s] = fp.n[d] * (GP[s] + GM[s]) / 2;
+                    for (int d = 0; d < 3; ++d) tg[d + 3 * s] = central_gradient_flux(fp.n[d], GP[s], GM[s]);
             } else {  // numerical_boundary_flux_gradient!  NumericalFluxes.jl:85-123
                 // e+ = e-, vid+ = vid- on boundary faces (:686-692): the plus side starts as
                 // a copy of the minus side, already loaded
@@ -1005,7 +1074,7 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
 #pragma unroll
                 for (int d = 0; d < 3; ++d) {
                     const int q = d + 3 * P::hv_indexmap(s);
-                    corr[NGF + 3 * s + d] = fp.w * (tg[q] - nGM[q]);
+                    corr[NGF + 3 * s + d] = gradient_lift(fp.w, tg[q], nGM[q]);
                 }
             if constexpr (NGF > 0) {
                 Vec<NGF> visc;
@@ -1090,10 +1159,10 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT)) k_divgrad(const PassArgs
         for (int s = 0; s < NGL; ++s) {
             const double G1 = G[3 * s + 0], G2 = G[3 * s + 1], G3 = G[3 * s + 2];
             if (hz) {
-                sC[(0 * NG + s) * Np + tid] = M * (x11 * G1 + x12 * G2 + x13 * G3);
-                sC[(1 * NG + s) * Np + tid] = M * (x21 * G1 + x22 * G2 + x23 * G3);
+                sC[(0 * NG + s) * Np + tid] = contravariant(M, x11, x12, x13, G1, G2, G3);
+                sC[(1 * NG + s) * Np + tid] = contravariant(M, x21, x22, x23, G1, G2, G3);
             }
-            if (vt) sC[(2 * NG + s) * Np + tid] = M * (x31 * G1 + x32 * G2 + x33 * G3);
+            if (vt) sC[(2 * NG + s) * Np + tid] = contravariant(M, x31, x32, x33, G1, G2, G3);
             const int sidx = surf_index<NQ, NQV>(tid);
             if (sidx >= 0) {
                 sM[(3 * s + 0) * NSURF + sidx] = G1;
@@ -1108,13 +1177,7 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT)) k_divgrad(const PassArgs
 #pragma unroll
         for (int s = 0; s < NGL; ++s) {
             double dh = 0.0, dv = 0.0;
-            if (hz) {
-#pragma unroll
-                for (int n = 0; n < NQ; ++n) {
-                    dh -= MI * sD[n + NQ * i] * sC[(0 * NG + s) * Np + n + NQ * (j + NQ * k)];
-                    dh -= MI * sD[n + NQ * j] * sC[(1 * NG + s) * Np + i + NQ * (n + NQ * k)];
-                }
-            }
+            if (hz) dh = div_volume_h<NQ>(MI, sD, sC + (0 * NG + s) * Np, sC + (1 * NG + s) * Np, i, j, k);
             if (vt) {
 #pragma unroll
                 for (int kk = 0; kk < NQV; ++kk)
@@ -1149,9 +1212,7 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT)) k_divgrad(const PassArgs
             const double nh0 = fp.n[0] / 2, nh1 = fp.n[1] / 2, nh2 = fp.n[2] / 2;
 #pragma unroll
             for (int s = 0; s < NGL; ++s) {
-                const double ldiv = (gP[3 * s] + gM[3 * s]) * nh0 +
-                                    (gP[3 * s + 1] + gM[3 * s + 1]) * nh1 +
-                                    (gP[3 * s + 2] + gM[3 * s + 2]) * nh2;
+                const double ldiv = central_divergence_flux(&gP[3 * s], &gM[3 * s], nh0, nh1, nh2);
                 corr[s] = fp.w * ldiv;
             }
             vidM = fp.vidM;
@@ -1179,6 +1240,231 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT)) k_divgrad(const PassArgs
     // (the NGL columns this pass writes are all the next one reads of Qhypervisc_div)
     if constexpr (NGL > 0)
         send_nodes<NGL, NGL>(a.h, 0, e, tid, (int)blockDim.x, [&](int s, int n) { return sA[s * Np + n]; });
+}
+
+// ---------------------------------------------------------------------------------
+// Gradient and Laplacian pass of a hand-off evaluation in one launch: what k_gradients<..., false,
+// GARG_IN> followed by k_divgrad<..., RING> leave in PassArgs::lapr (and Qhypervisc_div), bit for
+// bit, without grad G going to memory and back.  For a horizontal diffusion_direction on a grid
+// whose lateral faces are all interior (lapfused_tables.h): k_divgrad needs the neighbour's grad G
+// only at the shared lateral face nodes, and the neighbour N's value at such a node y is
+//   N's volume gradient at y   two NQ-point contractions over N's own records, along N's xi1 and
+//                              xi2 lines through y, with N's metric rows at y (lapT);
+//   + the lift of N's face that is shared with this element: N's normal and weight there (lapT),
+//     plus side = this element's own record, held in LDS;
+//   + where y is on a vertical edge of N, the lift of N's other lateral face at y (lapI's tE; N's
+//     own faceG / faceW / faceP), whose plus side is one record of N's neighbour --
+// added in N's own order: volume, then the face of the pair xi1 (N's faces 0 / 1), then xi2.  Every
+// term is the text k_gradients evaluates for N (line_derivative, metric_gradient,
+// central_gradient_flux, gradient_lift), so the sum is the value N would have stored.
+// The create-time tables, per lateral face task t = 0 .. NL-1 (NL = 4 Nfph), about the neighbour N
+// on the plus side, whose node y = vidP the task faces:
+//   lapI[e][c][t]  int32: c = 0 tP, N's face task of the same mesh node; c = 1 tE, N's other
+//                  lateral face task at y, or -1
+//   lapT[e][c][t]  c = 0..5 N's horizontal metric rows at y (xi1x1, xi1x2, xi1x3, xi2x1, xi2x2,
+//                  xi2x3), c = 6..9 N's n1, n2, n3 and lift weight at tP
+// 88 B per lateral face node: a digest of grid geometry like faceG, not of caller state.  This
+// launch is handed lapI as GridDev::facePr and lapT as PassArgs::derived, neither of which a
+// Laplacian pass reads (as k_gradlap<..., RING> is handed facePr as faceP): the argument block of
+// every other pass kernel, and with it their code, stays what it was.
+// Lanes: the volume nodes are threads 0 .. Np-1, the 4 Nfph lateral face tasks the LAST threads of
+// the group, so that the gathers of the face lanes and the contractions of the volume lanes fall
+// into different waves where the group has more than one.
+template <class P, int NQ, int NQV = NQ>
+__global__ void __launch_bounds__((KDims<NQ, NQV>::NT), CMDG_LAPFUSED_MINW) k_lapfused(const PassArgs<P> a)
+{
+    using KD = KDims<NQ, NQV>;
+    constexpr int Np = KD::Np, NGL = P::NGL, NHG = 3 * NGL, NHYP = P::NHYP, NG = NGL > 0 ? NGL : 1,
+                  NFT = KD::NFT, NL = 4 * KD::Nfph, NT = KD::NT;
+    static_assert(NT >= NL && NGL > 0, "one lane per lateral face task");
+    __shared__ double sD[NQ * NQ];
+    __shared__ double sG[NG * Np];      // gradient arguments [s][ijk]
+    __shared__ double sA[3 * NG * Np];  // grad G [3 s + d][ijk]
+    __shared__ double sC[2 * NG * Np];  // M * (xi_d . grad) [d][s][ijk], d = 0, 1
+    __shared__ double sL[NG * Np];      // Laplacians [s][ijk]
+    const int tid = threadIdx.x;
+    const int64_t e = a.elems[xcd_remap(blockIdx.x, gridDim.x)] - 1;
+    const int ft = tid - (NT - NL);  // lateral face task of this lane (< 0: none)
+    if (tid < NQ * NQ) sD[tid] = a.g.D[tid];
+    if (tid < Np) {
+        const double *rec = a.garg + garg_at<NGL, Np>(tid, e);
+        Vec<NGL> r;
+#pragma unroll
+        for (int s = 0; s < NGL; ++s) r[s] = rec[s];
+#pragma unroll
+        for (int s = 0; s < NGL; ++s) sG[s * Np + tid] = r[s];
+    }
+    // the face lane's own geometry, and of the neighbour its xi1 line of records through y: in flight
+    // across the barrier.  (The rest of what the lane reads follows in stages below, each issued
+    // when the one before is consumed: all of it at once is 200 VGPRs and two work-groups per CU.)
+    FacePt fp;
+    int tP = 0, tE = -1, iP = 0, jP = 0, kP = 0;
+    int32_t idE = 0;
+    const double *gN = a.garg;  // the neighbour's records
+    if (ft >= 0) {
+        int f, n;
+        KD::face_task(ft, f, n);
+        face_setup<NQ, NQV, true>(a.g, e, ft, f, n, fp);
+        tP = a.g.facePr[((int64_t)2 * e + 0) * NL + ft];
+        tE = a.g.facePr[((int64_t)2 * e + 1) * NL + ft];
+        gN = a.garg + garg_at<NGL, Np>(0, fp.eP);
+        iP = fp.vidP % NQ, jP = (fp.vidP / NQ) % NQ, kP = fp.vidP / (NQ * NQ);
+        if (tE >= 0) idE = a.g.faceP[(int64_t)NFT * fp.eP + tE];
+    }
+    double M = 0, MI = 0, x11 = 0, x12 = 0, x13 = 0, x21 = 0, x22 = 0, x23 = 0;
+    if (tid < Np) {
+        const double *vg = a.g.vgeo + (int64_t)Np * a.g.nvgeo * e + tid;
+        M = vg[VM * Np];
+        MI = vg[VMI * Np];
+        x11 = vg[XI1X1 * Np], x12 = vg[XI1X2 * Np], x13 = vg[XI1X3 * Np];
+        x21 = vg[XI2X1 * Np], x22 = vg[XI2X2 * Np], x23 = vg[XI2X3 * Np];
+    }
+    __syncthreads();
+    // ---- own volume gradient (k_gradients, horizontal)
+    if (tid < Np) {
+        const int i = tid % NQ, j = (tid / NQ) % NQ, k = tid / (NQ * NQ);
+        Vec<NHG> gh;
+        gh.negzero();
+#pragma unroll
+        for (int s = 0; s < NGL; ++s)
+            grad_volume_h<NQ>(
+                sD, i, j, [&](int n) { return sG[s * Np + n + NQ * (j + NQ * k)]; },
+                [&](int n) { return sG[s * Np + i + NQ * (n + NQ * k)]; }, x11, x12, x13, x21, x22, x23, &gh[3 * s]);
+#pragma unroll
+        for (int q = 0; q < NHG; ++q) sA[q * Np + tid] = gh[q];
+    }
+    // ---- face lanes: the lift of the own gradient, and the neighbour's gradient at the plus node
+    Vec<NHG> corr, gP;
+    int fpair = -1;
+    if (ft >= 0) {
+        fpair = ft / (2 * KD::Nfph);
+        const double *lapT = a.derived + (int64_t)10 * NL * e + ft;
+        // the neighbour's volume gradient at y, in its own frame: xi1 line, then xi2 line
+        Vec<NGL> GY, G1, G2;  // (GY: the neighbour's argument at y)
+        double r1[NQ][NG];
+#pragma unroll
+        for (int s = 0; s < NGL; ++s) GY[s] = gN[NGL * fp.vidP + s];
+#pragma unroll
+        for (int n = 0; n < NQ; ++n)
+#pragma unroll
+            for (int s = 0; s < NGL; ++s) r1[n][s] = gN[NGL * (n + NQ * (jP + NQ * kP)) + s];
+#pragma unroll
+        for (int s = 0; s < NGL; ++s) G1[s] = line_derivative<NQ>(sD, iP, [&](int n) { return r1[n][s]; });
+#pragma unroll
+        for (int s = 0; s < NGL; ++s) CMDG_LAPFUSED_STAGE(kP, G1[s]);
+        double r2[NQ][NG];
+#pragma unroll
+        for (int n = 0; n < NQ; ++n)
+#pragma unroll
+            for (int s = 0; s < NGL; ++s) r2[n][s] = gN[NGL * (iP + NQ * (n + NQ * kP)) + s];
+        double T[6];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) T[c] = lapT[c * NL];
+#pragma unroll
+        for (int s = 0; s < NGL; ++s) G2[s] = line_derivative<NQ>(sD, jP, [&](int n) { return r2[n][s]; });
+        gP.negzero();
+#pragma unroll
+        for (int s = 0; s < NGL; ++s) metric_gradient(T[0], T[1], T[2], T[3], T[4], T[5], G1[s], G2[s], &gP[3 * s]);
+#pragma unroll
+        for (int q = 0; q < NHG; ++q) CMDG_LAPFUSED_STAGE(idE, gP[q]);
+        // the neighbour's lateral faces at y: the one shared with this element, and its other one
+        double nS[3], wS, nE[3] = {0, 0, 0}, wE = 0;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) nS[d] = lapT[(6 + d) * NL];
+        wS = lapT[9 * NL];
+        Vec<NGL> GE;
+        int pairE = 2;
+        if (tE >= 0) {
+            const double *sg = a.g.faceG + (int64_t)4 * NFT * fp.eP + tE;
+            nE[0] = sg[0], nE[1] = sg[NFT], nE[2] = sg[2 * NFT];
+            wE = a.g.faceW[(int64_t)NFT * fp.eP + tE];
+            const double *rec = a.garg + (int64_t)NGL * idE;
+#pragma unroll
+            for (int s = 0; s < NGL; ++s) GE[s] = rec[s];
+            int fE, nn;
+            KD::face_task(tE, fE, nn);
+            pairE = fE / 2;
+        }
+        int fS, nn;
+        KD::face_task(tP, fS, nn);
+        const bool edge_first = pairE < fS / 2;
+        Vec<NGL> GM;  // this element's argument at the face node
+#pragma unroll
+        for (int s = 0; s < NGL; ++s) GM[s] = sG[s * Np + fp.vidM];
+        // the neighbour's lifts at y: minus side its own argument, plus side ours / its neighbour's
+#pragma unroll
+        for (int s = 0; s < NGL; ++s)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                const double lS = gradient_lift(wS, central_gradient_flux(nS[d], GM[s], GY[s]), nS[d] * GY[s]);
+                if (tE >= 0) {
+                    const double lE = gradient_lift(wE, central_gradient_flux(nE[d], GE[s], GY[s]), nE[d] * GY[s]);
+                    gP[3 * s + d] += edge_first ? lE : lS;
+                    gP[3 * s + d] += edge_first ? lS : lE;
+                } else {
+                    gP[3 * s + d] += lS;
+                }
+            }
+        // own lift (k_gradients' interface phase, interior face)
+#pragma unroll
+        for (int s = 0; s < NGL; ++s)
+#pragma unroll
+            for (int d = 0; d < 3; ++d)
+                corr[3 * s + d] =
+                    gradient_lift(fp.w, central_gradient_flux(fp.n[d], GY[s], GM[s]), fp.n[d] * GM[s]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        if (fpair == p) {
+#pragma unroll
+            for (int q = 0; q < NHG; ++q) sA[q * Np + fp.vidM] += corr[q];
+        }
+        __syncthreads();
+    }
+    // ---- Laplacian (k_divgrad, horizontal): the own gradient is complete in sA
+    if (tid < Np) {
+#pragma unroll
+        for (int s = 0; s < NGL; ++s) {
+            const double G1 = sA[(3 * s + 0) * Np + tid], G2 = sA[(3 * s + 1) * Np + tid],
+                         G3 = sA[(3 * s + 2) * Np + tid];
+            sC[(0 * NG + s) * Np + tid] = contravariant(M, x11, x12, x13, G1, G2, G3);
+            sC[(1 * NG + s) * Np + tid] = contravariant(M, x21, x22, x23, G1, G2, G3);
+        }
+    }
+    __syncthreads();
+    if (tid < Np) {
+        const int i = tid % NQ, j = (tid / NQ) % NQ, k = tid / (NQ * NQ);
+#pragma unroll
+        for (int s = 0; s < NGL; ++s)
+            sL[s * Np + tid] = div_volume_h<NQ>(MI, sD, sC + (0 * NG + s) * Np, sC + (1 * NG + s) * Np, i, j, k);
+    }
+    Vec<NGL> corrL;
+    if (ft >= 0) {
+        Vec<NHG> gM;
+#pragma unroll
+        for (int q = 0; q < NHG; ++q) gM[q] = sA[q * Np + fp.vidM];
+        const double nh0 = fp.n[0] / 2, nh1 = fp.n[1] / 2, nh2 = fp.n[2] / 2;
+#pragma unroll
+        for (int s = 0; s < NGL; ++s) {
+            const double ldiv = central_divergence_flux(&gP[3 * s], &gM[3 * s], nh0, nh1, nh2);
+            corrL[s] = fp.w * ldiv;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        if (fpair == p) {
+#pragma unroll
+            for (int s = 0; s < NGL; ++s) sL[s * Np + fp.vidM] += corrL[s];
+        }
+        __syncthreads();
+    }
+    store_ring_major<NG, NQ, NQV>(a.lapr, e, tid, (int)blockDim.x, sL);
+    if (tid < Np && a.hypdiv_out) {
+#pragma unroll
+        for (int s = 0; s < NGL; ++s) a.hypdiv[tid + (int64_t)Np * (s + (int64_t)NHYP * e)] = sL[s * Np + tid];
+    }
 }
 
 // ---------------------------------------------------------------------------------

@@ -103,6 +103,8 @@ int group_lsrk_step(std::vector<EngineBase *> &g, double **Q, double **dQ, doubl
             x.garg_out = h.out;
             x.hypdiv_out = !h.garg_in || h.last_eval;
             if (h.out == GargOut::records_refresh) g[i]->handoff_refreshes += 1;
+            x.lap_fused = h.garg_in && g[i]->lapfused_eligible();
+            if (x.lap_fused) g[i]->fused_launches += 1;
         }
         if (int r = group_rhs(g, c, s > 0 || continued)) return r;
     }
@@ -225,6 +227,7 @@ int EngineBase::run_steps(double *Q, double *dQ, double t, double dt, int64_t ns
     int64_t i = 0;
     handoff_used = false;
     handoff_refreshes = 0;
+    fused_launches = 0;
     if (nsteps >= 2 && nstages <= 16 && graph_eligible()) {
         if (int r = lsrk_step(Q, dQ, t, dt, nstages, rka, rkb, rkc, false)) return r;  // eager: packs Q
         t += dt;

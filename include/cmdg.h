@@ -336,12 +336,20 @@ int cmdg_synchronize(cmdg_handle h);
  *   run's last does the refresh when no pass of the law reads the refreshed columns (the dry
  *   atmosphere's theta_v / air_T): the others would be overwritten unseen.  Q, dQ and every column
  *   of state_auxiliary end a run bit-identical.  cmdg_query(CMDG_Q_GRADARG_HANDOFF) says whether
- *   the last run used it. */
+ *   the last run used it.
+ * CMDG_OPT_FUSED_LAPLACIAN (default 1): an evaluation of such a run that reads the records forms the
+ *   gradients and their Laplacians in one launch, so that Qhypervisc_grad's intermediate never
+ *   goes to memory.  Taken only where the diffusion direction is horizontal and every lateral face
+ *   of every real element is interior with a unique opposite face node (decided once at create:
+ *   the sphere, laterally periodic bricks more than one element wide); everything else keeps the
+ *   two launches.  Bit-identical results.  cmdg_query(CMDG_Q_FUSED_LAPLACIAN) counts the
+ *   evaluations of the last run that took it. */
 enum {
     CMDG_OPT_KEEP_GRADFLUX = 1, CMDG_OPT_STACK_HEIGHT = 2, CMDG_OPT_REFERENCE_HALO = 3,
     CMDG_OPT_HALO_PIPELINE = 4, CMDG_OPT_STEP_GRAPH = 5, CMDG_OPT_STREAM_PRIORITY = 6,
     CMDG_OPT_TENDENCY_PAIRS = 7 /* retired */, CMDG_OPT_ASYNC_RUN = 8,
-    CMDG_OPT_TENDENCY_FOUR_WAVES = 9 /* retired */, CMDG_OPT_GRADARG_HANDOFF = 10
+    CMDG_OPT_TENDENCY_FOUR_WAVES = 9 /* retired */, CMDG_OPT_GRADARG_HANDOFF = 10,
+    CMDG_OPT_FUSED_LAPLACIAN = 11
 };
 int cmdg_set_option(cmdg_handle h, int32_t option, int32_t value);
 
@@ -369,7 +377,9 @@ enum {
     CMDG_Q_GRADARG_REFRESHES = 15, /* ... and how many of its hand-off updates carried the nodal auxiliary
                                       refresh: 1 for a law whose refreshed columns no pass reads (only the
                                       last one is ever seen), else all of them; 0 without the hand-off */
-    CMDG_Q_STATE_READ = 16, CMDG_Q_AUX_READ = 20
+    CMDG_Q_STATE_READ = 16, CMDG_Q_AUX_READ = 20,
+    CMDG_Q_FUSED_LAPLACIAN = 24 /* evaluations of the last cmdg_lsrk_run that took CMDG_OPT_FUSED_LAPLACIAN:
+                                   all but the first (5 K - 1 for K LSRK54 steps) on an eligible handle, else 0 */
 };
 int cmdg_query(cmdg_handle h, int32_t what, int64_t *out);
 

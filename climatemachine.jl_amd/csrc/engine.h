@@ -179,15 +179,16 @@ struct EngineT : EngineBase {
     }
     bool has_update_aux() const override { return P::HAS_UPDATE_AUX && P::update_aux_active(prm); }
     bool law_needs_gradflux() const override { return P::needs_gradflux(prm); }
-    bool gf_node_major() const override { return cmdg::gf_node_major<P>::value; }
+    bool gf_node_major() const override { return cmdg::gf_node_major<P>; }
     bool fused_update_aux() const override { return P::HAS_UPDATE_AUX && P::FUSE_UPDATE_AUX; }
     bool garg_capable() const override { return HO && !P::needs_gradflux(prm); }
     bool refresh_elidable() const override { return ELIDE; }
     int law_nder() const override { return P::HAS_SOURCE ? P::NDER : 0; }
     int law_nupd() const override { return P::HAS_UPDATE_AUX ? P::NUPD : 0; }
     int tendency_epb() const override { return TendencyShape<P, NQ_, NQV_>::EPB; }
-    int law_state_read(int pass) const override { return law_reads<P>::state(pass); }
-    int law_aux_read(int pass) const override { return law_reads<P>::aux(pass); }
+    // (a law that does not count them reads every column, law_defaults.h)
+    int law_state_read(int pass) const override { return P::state_read(pass) < 0 ? P::NS : P::state_read(pass); }
+    int law_aux_read(int pass) const override { return P::aux_read(pass) < 0 ? P::NAUX : P::aux_read(pass); }
     int init_derived() override
     {
         if constexpr (P::NDER > 0) {

@@ -27,26 +27,15 @@ enum { FV_RECON_CONSTANT = 0, FV_RECON_LINEAR = 1 };
 enum { FV_LIMITER_VANLEER = 0, FV_LIMITER_NONE = 1 };
 
 // ---- law hooks with the reference's defaults (src/BalanceLaws/prog_prim_conversion.jl) ----------
-// A law that converts says so with static members prognostic_to_primitive / primitive_to_prognostic
-// (prm, out, in, aux) and construct_face_auxiliary_state (prm, aux_face, aux_cell, dz); the defaults
-// are the identity and the copy.
-template <class P, class = void>
-struct has_prim_conversion : std::false_type {
-};
-template <class P>
-struct has_prim_conversion<P, std::void_t<decltype(&P::prognostic_to_primitive)>> : std::true_type {
-};
-template <class P, class = void>
-struct has_face_aux_state : std::false_type {
-};
-template <class P>
-struct has_face_aux_state<P, std::void_t<decltype(&P::construct_face_auxiliary_state)>> : std::true_type {
-};
+// A law that converts says so (HAS_PRIM_CONVERSION, HAS_FACE_AUX_STATE, law_defaults.h) and defines
+// prognostic_to_primitive / primitive_to_prognostic (prm, out, in, aux) or
+// construct_face_auxiliary_state (prm, aux_face, aux_cell, dz); the defaults are the identity and
+// the copy.
 template <class P>
 __device__ __forceinline__ void law_prognostic_to_primitive(const typename P::Params &prm, double *prim,
                                                             const double *prog, const double *aux)
 {
-    if constexpr (has_prim_conversion<P>::value) {
+    if constexpr (P::HAS_PRIM_CONVERSION) {
         P::prognostic_to_primitive(prm, prim, prog, aux);
     } else {
 #pragma unroll
@@ -57,7 +46,7 @@ template <class P>
 __device__ __forceinline__ void law_primitive_to_prognostic(const typename P::Params &prm, double *prog,
                                                             const double *prim, const double *aux)
 {
-    if constexpr (has_prim_conversion<P>::value) {
+    if constexpr (P::HAS_PRIM_CONVERSION) {
         P::primitive_to_prognostic(prm, prog, prim, aux);
     } else {
 #pragma unroll
@@ -68,7 +57,7 @@ template <class P>
 __device__ __forceinline__ void law_face_auxiliary_state(const typename P::Params &prm, double *aux_face,
                                                          const double *aux_cell, double dz)
 {
-    if constexpr (has_face_aux_state<P>::value) {
+    if constexpr (P::HAS_FACE_AUX_STATE) {
         P::construct_face_auxiliary_state(prm, aux_face, aux_cell, dz);
     } else {
 #pragma unroll

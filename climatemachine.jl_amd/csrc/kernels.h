@@ -14,9 +14,8 @@
 // src/Numerics/DGMethods/DGModel_kernels.jl; the accumulation order of the reference
 // is kept term by term (see DESIGN.md "summation order").
 #pragma once
-#include <type_traits>
-
 #include "cmdg_common.h"
+#include "law_defaults.h"
 
 // minimum waves per SIMD requested from the register allocator (tuning knobs)
 #ifndef CMDG_TEND_MINW
@@ -151,32 +150,15 @@ __device__ __forceinline__ void face_setup(const GridDev &g, int64_t e, int t, i
     face_geometry<NQ, NQV, LIFTW>(g, e, t, f, n, idP, bctag, fp);
 }
 
-// A law may offer flux_first_order and wavespeed of one state in one call (both need the same
-// thermodynamic state; the moist law's costs a saturation adjustment): detected by the member
-// HAS_FLUX_WAVESPEED, absent from the other laws, whose code is unchanged.
-template <class P, class = void>
-struct has_flux_wavespeed : std::false_type {
-};
-template <class P>
-struct has_flux_wavespeed<P, std::void_t<decltype(P::HAS_FLUX_WAVESPEED)>> : std::true_type {
-};
+// The optional members of a law functor P, their defaults and what each stands for: law_defaults.h.
 
-// Laws whose state_gradient_flux the library keeps node-major, (NGF, Np, nelem), like
-// Qhypervisc_grad (cmdg_common.h): `static constexpr bool GF_NODE_MAJOR = true` in the functor.
-// The dry atmosphere takes it (10 columns gathered on the plus side of every face node; the moist
-// law was measured and keeps the reference layout, physics_moist.h); laws whose hooks work on the
-// array in the reference layout do not.
-template <class P, class = void>
-struct gf_node_major : std::false_type {
-};
+// is the law's state_gradient_flux kept node-major (P::GF_NODE_MAJOR, and there is one)
 template <class P>
-struct gf_node_major<P, std::void_t<decltype(P::GF_NODE_MAJOR)>>
-    : std::integral_constant<bool, P::GF_NODE_MAJOR && (P::NGF > 0)> {
-};
+inline constexpr bool gf_node_major = P::GF_NODE_MAJOR && P::NGF > 0;
 template <class P, int Np>
 __device__ __forceinline__ int64_t gf_at(int n, int s, int64_t e)
 {
-    return col_at<gf_node_major<P>::value, P::NGF, Np>(n, s, e);
+    return col_at<gf_node_major<P>, P::NGF, Np>(n, s, e);
 }
 template <class P, int Np>
 __device__ __forceinline__ void load_gf(Vec<P::NGF> &dst, const double *__restrict__ arr, int n, int64_t e)
@@ -196,47 +178,16 @@ __device__ __forceinline__ void load_plus_gf(Vec<P::NGF> &dst, const double *__r
     }
 }
 
-// A law may also keep a few derived values per node (P::NCACHE doubles, P::node_cache) that its
-// first-order flux and wave speed are computed from: k_tendency then evaluates them once per
-// volume node and hands the staged copy to the minus side of the faces.
-template <class P, class = void>
-struct node_cache_size : std::integral_constant<int, 0> {
-};
-template <class P>
-struct node_cache_size<P, std::void_t<decltype(P::NCACHE)>> : std::integral_constant<int, P::NCACHE> {
-};
-
-// byte accounting: columns of Q / of the auxiliary state the volume code of a pass reads
-// (P::state_read, P::aux_read; every column for a law that does not say)
-template <class P, class = void>
-struct law_reads {
-    static constexpr int state(int) { return P::NS; }
-    static constexpr int aux(int) { return P::NAUX; }
-};
-template <class P>
-struct law_reads<P, std::void_t<decltype(P::aux_read(0))>> {
-    static constexpr int state(int pass) { return P::state_read(pass); }
-    static constexpr int aux(int pass) { return P::aux_read(pass); }
-};
-
-// laws that carry numerical_flux_first_order! methods of their own (P::LAW_NF)
-template <class P, class = void>
-struct has_law_nf : std::false_type {
-};
-template <class P>
-struct has_law_nf<P, std::void_t<decltype(P::LAW_NF)>> : std::integral_constant<bool, P::LAW_NF> {
-};
-
 // numerical_flux_first_order!  NumericalFluxes.jl:223-285 (Rusanov) / :300-340 (central)
 template <class P>
 __device__ __forceinline__ void nf_first_order(const typename P::Params &prm, int nf,
                                                Vec<P::NS> &fluxn, const double *n,
                                                const double *QM, const double *auxM,
                                                const double *QP, const double *auxP, double t,
-                                               int facedir, const double *cacheM = nullptr)
+                                               int facedir)
 {
     constexpr int NS = P::NS;
-    if constexpr (has_law_nf<P>::value) {
+    if constexpr (P::LAW_NF) {
         if (nf >= NF_ROE) {
             P::numerical_flux_law(prm, nf, fluxn, n, QM, auxM, QP, auxP, t, facedir);
             return;
@@ -246,16 +197,9 @@ __device__ __forceinline__ void nf_first_order(const typename P::Params &prm, in
     Vec<NS> wM, wP;
     FM.negzero();
     FP.negzero();
-    if constexpr (has_flux_wavespeed<P>::value) {
+    if constexpr (P::HAS_FLUX_WAVESPEED) {
         if (nf == NF_RUSANOV) {
-            if constexpr (node_cache_size<P>::value > 0) {
-                if (cacheM)
-                    P::flux_wavespeed_cached(prm, FM, wM, n, QM, auxM, cacheM);
-                else
-                    P::flux_wavespeed(prm, FM, wM, n, QM, auxM, t, facedir);
-            } else {
-                P::flux_wavespeed(prm, FM, wM, n, QM, auxM, t, facedir);
-            }
+            P::flux_wavespeed(prm, FM, wM, n, QM, auxM, t, facedir);
             P::flux_wavespeed(prm, FP, wP, n, QP, auxP, t, facedir);
         } else {
             P::flux_first_order(prm, FM, QM, auxM, t, facedir);
@@ -271,7 +215,7 @@ __device__ __forceinline__ void nf_first_order(const typename P::Params &prm, in
         fluxn[s] += (FM[3 * s] + FP[3 * s]) * nh0 + (FM[3 * s + 1] + FP[3 * s + 1]) * nh1 +
                     (FM[3 * s + 2] + FP[3 * s + 2]) * nh2;
     if (nf == NF_RUSANOV) {
-        if constexpr (!has_flux_wavespeed<P>::value) {
+        if constexpr (!P::HAS_FLUX_WAVESPEED) {
             P::wavespeed(prm, wM, n, QM, auxM, t, facedir);
             P::wavespeed(prm, wP, n, QP, auxP, t, facedir);
         }
@@ -311,34 +255,21 @@ struct SurfDims {
         NQ * NQ * NQV - (NQ - 2) * (NQ - 2) * (NQV > 2 ? NQV - 2 : 0);
 };
 
-// compute_gradient_flux! of a node whose gradient ARGUMENT is at hand (the volume node's own, the
-// minus side of a face): a law whose gradient flux needs a quantity that is also an entry of its
-// argument (the dry atmosphere's theta_v under SmagorinskyLilly, a pow) takes it from there.
-template <class P, class = void>
-struct has_gradient_flux_g : std::false_type {
-};
-template <class P>
-struct has_gradient_flux_g<P, std::void_t<decltype(&P::gradient_flux_g)>> : std::true_type {
-};
+// compute_gradient_flux! of a node whose gradient ARGUMENT G is at hand (P::HAS_GRADIENT_FLUX_G)
 template <class P>
 __device__ __forceinline__ void law_gradient_flux(const typename P::Params &prm, double *gf,
                                                   const double *g, const double *Q, const double *aux,
                                                   double t, const double *G)
 {
-    if constexpr (has_gradient_flux_g<P>::value)
+    if constexpr (P::HAS_GRADIENT_FLUX_G)
         P::gradient_flux_g(prm, gf, g, Q, aux, t, G);
     else
         P::gradient_flux(prm, gf, g, Q, aux, t);
 }
 
-// A law may ask for its own register budget in the gradient pass (waves per SIMD the allocator
-// is to aim for): light laws gain residency, heavy ones keep the default.
-template <class P, class = void>
-struct grad_min_waves : std::integral_constant<int, CMDG_GRAD_MINW> {
-};
+// the register budget of the gradient pass: the law's own (P::GRAD_MIN_WAVES) or the library's
 template <class P>
-struct grad_min_waves<P, std::void_t<decltype(P::GRAD_MIN_WAVES)>> : std::integral_constant<int, P::GRAD_MIN_WAVES> {
-};
+inline constexpr int grad_min_waves = P::GRAD_MIN_WAVES > 0 ? P::GRAD_MIN_WAVES : CMDG_GRAD_MINW;
 
 // ---------------------------------------------------------------------------------
 // Launch shape of the tendency pass.  N <= 4: one element per work-group, 192 threads.  Larger
@@ -346,16 +277,14 @@ struct grad_min_waves<P, std::void_t<decltype(P::GRAD_MIN_WAVES)>> : std::integr
 // carry twice the work and a second six-wave work-group does not become resident above 128
 // VGPRs (profiles/r02_lds_occupancy.jsonl).  Two elements per work-group (686 threads, eleven
 // waves, 3-3-3-2) even that out; the minus side of the faces is then read from memory instead
-// of being staged, so that both elements' flux buffers fit the LDS of a CU.  A law with a node
-// cache takes one element per work-group at every order.  The other shapes measured -- the pass
-// in two launches (volume, then interface + update), paired work-groups that keep a shared xi1
-// face on chip, four-wave work-groups for large elements -- lost and were removed (DESIGN.md
-// Appendix A).
+// of being staged, so that both elements' flux buffers fit the LDS of a CU.  The other shapes
+// measured -- the pass in two launches (volume, then interface + update), paired work-groups that
+// keep a shared xi1 face on chip, four-wave work-groups for large elements -- lost and were removed
+// (DESIGN.md Appendix A).
 template <class P, int NQ, int NQV>
 struct TendencyShape {
     using KD = KDims<NQ, NQV>;
-    static constexpr int EPB =
-        node_cache_size<P>::value != 0 ? 1 : (KD::Np > 125 ? CMDG_TEND_EPB_LARGE : CMDG_TEND_EPB_SMALL);
+    static constexpr int EPB = KD::Np > 125 ? CMDG_TEND_EPB_LARGE : CMDG_TEND_EPB_SMALL;
     static constexpr bool STAGE_M = EPB == 1;  // minus side of the faces staged in LDS
     static constexpr int NTE = EPB == 1 ? KD::NT : (KD::Np > KD::NFT ? KD::Np : KD::NFT);  // threads per element
     static constexpr int NT = EPB == 1 ? KD::NT : ((EPB * NTE + 63) / 64) * 64;
@@ -365,8 +294,8 @@ struct TendencyShape {
 // ---------------------------------------------------------------------------------
 // Hand-off of the gradient arguments inside cmdg_lsrk_run.  The input of stage s+1 is the Q+ the
 // fused update of stage s holds in LDS, and P::gradient_argument is a pure function of the node's
-// (Q, aux) whose time argument is unused.  A law that says `static constexpr bool GRADARG_HANDOFF =
-// true` gets two more instantiations: k_tendency<..., GARG_OUT> evaluates the argument of Q+ once
+// (Q, aux) whose time argument is unused.  A law that says so (P::GRADARG_HANDOFF, law_defaults.h)
+// gets two more instantiations: k_tendency<..., GARG_OUT> evaluates the argument of Q+ once
 // per node, stores the entries the USE_GF = false gradient pass consumes (those of
 // gradient_argument_mask<P, false>(), entry s = G[hv_indexmap(s)]) as one record per node in a
 // library-owned array, node-major like Qhypervisc_grad -- (NGL, Np, nelem) -- and does the nodal
@@ -382,29 +311,15 @@ struct TendencyShape {
 // faster in any pass (profiles/ab_face_contiguous.txt).
 // A run's hand-off launches follow one another with no hook, filter, exchange or caller in between,
 // so the columns the refresh writes are seen by somebody only after the last of them (it leaves the
-// auxiliary state of the final evaluation's input, as every run promises).  A law whose refreshed
-// columns are read by none of its pointwise functions in any pass says `GRADARG_REFRESH_UNREAD =
-// true`; its other hand-off launches then run k_tendency<..., GARG_OUT, false>, which neither
-// calls update_aux nor stores the columns.  Every other law refreshes in every update.
-template <class P, class = void>
-struct law_gradarg_handoff : std::false_type {
-};
-template <class P>
-struct law_gradarg_handoff<P, std::void_t<decltype(P::GRADARG_HANDOFF)>>
-    : std::integral_constant<bool, P::GRADARG_HANDOFF && (P::NGL > 0) && P::HAS_UPDATE_AUX && P::FUSE_UPDATE_AUX> {
-};
-template <class P, class = void>
-struct law_refresh_unread : std::false_type {
-};
-template <class P>
-struct law_refresh_unread<P, std::void_t<decltype(P::GRADARG_REFRESH_UNREAD)>>
-    : std::integral_constant<bool, P::GRADARG_REFRESH_UNREAD && law_gradarg_handoff<P>::value> {
-};
+// auxiliary state of the final evaluation's input, as every run promises).  The other hand-off
+// launches of a law that says P::GRADARG_REFRESH_UNREAD run k_tendency<..., GARG_OUT, false>, which
+// neither calls update_aux nor stores the columns.
 template <class P, int NQ, int NQV>
 struct GradArgHandoff {
-    static constexpr bool value = law_gradarg_handoff<P>::value && TendencyShape<P, NQ, NQV>::EPB == 1;
+    static constexpr bool value = P::GRADARG_HANDOFF && P::NGL > 0 && P::HAS_UPDATE_AUX && P::FUSE_UPDATE_AUX &&
+                                  TendencyShape<P, NQ, NQV>::EPB == 1;
     // may the refresh be left out of the hand-off launches nobody can observe
-    static constexpr bool elide_refresh = value && law_refresh_unread<P>::value;
+    static constexpr bool elide_refresh = value && P::GRADARG_REFRESH_UNREAD;
 };
 template <int NGL, int Np>
 __device__ __forceinline__ int64_t garg_at(int n, int64_t e)
@@ -444,8 +359,7 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
     constexpr int Np = KD::Np, NS = P::NS, NAUX = P::NAUX, NGF = P::NGF,
                   NHYP = P::NHYP, NHG = 3 * P::NGL, NFA = P::NFAUX,
                   NSURF = SurfDims<NQ, NQV>::NSURF, NGFS = USE_GF ? NGF : 0,
-                  NCA = node_cache_size<P>::value,
-                  NMF = (STAGE_M ? NFA + NGFS + NHYP : 0) + NCA, OCA = NMF - NCA;
+                  NMF = STAGE_M ? NFA + NGFS + NHYP : 0;
     // LDS: sD derivative matrices; sF_ contravariant flux [d][s][ijk], later the accumulator; sM_ minus
     // side, surface nodes [field][sidx]; sQ_ the prognostic state of every node (minus side of the
     // faces, and the "Q" of the fused update at the end: re-reading it from memory 20 us after the
@@ -530,18 +444,7 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
         }
         Vec<3 * NS> F, F2;
         F.negzero();
-        if constexpr (NCA > 0) {
-            Vec<NCA> lc;
-            P::node_cache(a.prm, lc, lQ, laux);
-            P::flux_first_order_cached(a.prm, F, lQ, laux, lc);
-            if (sidx >= 0) {
-#pragma unroll
-                for (int s = 0; s < NCA; ++s)
-                    sM[(OCA + s) * NSURF + sidx] = lc[s];
-            }
-        } else {
-            P::flux_first_order(a.prm, F, lQ, laux, a_t, a.model_dir);
-        }
+        P::flux_first_order(a.prm, F, lQ, laux, a_t, a.model_dir);
         F2.negzero();
         P::flux_second_order(a.prm, F2, lQ, lgf, lhyp, laux, a_t);
 #pragma unroll
@@ -662,9 +565,6 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
             for (int s = 0; s < NAUX; ++s) auxM[s] = 0;
 #pragma unroll
             for (int s = 0; s < NS; ++s) QM[s] = sQ[s * Np + fp.vidM];
-            Vec<NCA> cM;  // the law's per-node cache of the minus side (see node_cache_size)
-#pragma unroll
-            for (int s = 0; s < NCA; ++s) cM[s] = sM[(OCA + s) * NSURF + sidx];
 #pragma unroll
             for (int s = 0; s < NFA; ++s)
                 auxM[P::face_aux(s)] =
@@ -699,8 +599,7 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
             for (int s = 0; s < NAUX; ++s) auxPd[s] = auxPn[s];
             flux.negzero();
             if (fp.bctag == 0) {
-                nf_first_order<P>(a.prm, a.nf_first, flux, fp.n, QM, auxM, QPn, auxPn, a_t,
-                                  facedir, NCA > 0 ? (const double *)cM : nullptr);
+                nf_first_order<P>(a.prm, a.nf_first, flux, fp.n, QM, auxM, QPn, auxPn, a_t, facedir);
                 // CentralNumericalFluxSecondOrder  NumericalFluxes.jl:670-715
                 Vec<3 * NS> FM, FP;
                 FM.negzero();
@@ -733,8 +632,7 @@ __device__ __forceinline__ void tendency_body(const PassArgs<P> &a)
                 // numerical_boundary_flux_first_order!  NumericalFluxes.jl:163-205
                 P::boundary_state(a.prm, BS_FIRST, fp.bctag, QPn, auxPn, fp.n, QM, auxM, a_t, Q1,
                                   aux1);
-                nf_first_order<P>(a.prm, a.nf_first, flux, fp.n, QM, auxM, QPn, auxPn, a_t,
-                                  facedir, NCA > 0 ? (const double *)cM : nullptr);
+                nf_first_order<P>(a.prm, a.nf_first, flux, fp.n, QM, auxM, QPn, auxPn, a_t, facedir);
                 // normal_boundary_flux_second_order!  NumericalFluxes.jl:872-918
                 Vec<3 * NS> FP;
                 FP.negzero();
@@ -895,7 +793,7 @@ template <class P, int NQ, int NQV = NQ, bool USE_GF = true, bool GARG_IN = fals
 // (six-wave work-groups of the large elements share a CU only at <= 128 VGPRs, see TendencyShape;
 // a launch bound of 1024 threads is the hard form of that request)
 __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LARGE : KDims<NQ, NQV>::NT),
-                                   (NQ == 5 && NQV == 5 ? grad_min_waves<P>::value : 1)) k_gradients(const PassArgs<P> a)
+                                   (NQ == 5 && NQV == 5 ? grad_min_waves<P> : 1)) k_gradients(const PassArgs<P> a)
 {
     using KD = KDims<NQ, NQV>;
     const double a_t = a.tptr ? *a.tptr : a.t;  // (uniform: one scalar load)
@@ -1096,13 +994,13 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::Np > 125 ? CMDG_GRAD_BOUND_LA
         __syncthreads();
     }
     if (tid < Np) {
-        if constexpr (!gf_node_major<P>::value) {
+        if constexpr (!gf_node_major<P>) {
 #pragma unroll
             for (int s = 0; s < NGF; ++s)
                 a.gf[tid + (int64_t)Np * (s + (int64_t)P::NGF * e)] = sA[s * Np + tid];
         }
     }
-    if constexpr (gf_node_major<P>::value && NGF > 0)
+    if constexpr (gf_node_major<P> && NGF > 0)
         store_node_major<P::NGF, Np, NGF>(a.gf, e, tid, (int)blockDim.x, sA);
     if constexpr (NHG > 0)
         store_node_major<NHG, Np, NHG>(a.hypgrad, e, tid, (int)blockDim.x, sA + NGF * Np);

@@ -18,6 +18,7 @@
 // Grad-type locals are 3 x nvar column-major: g[d + 3*s] (vars_wrappers.jl:52).
 #pragma once
 #include "cmdg_common.h"
+#include "law_defaults.h"
 
 namespace cmdg {
 
@@ -28,7 +29,7 @@ struct AdvDiffParams {
 };
 
 template <bool ADV, bool DIFF, bool HYPER>
-struct AdvDiff {
+struct AdvDiff : LawDefaults {
     using Params = AdvDiffParams;
     static constexpr int NS = 1;
     static constexpr int NAUX = 3 + (ADV ? 3 : 0) + (DIFF ? 9 : 0) + (HYPER ? 9 : 0);
@@ -40,17 +41,11 @@ struct AdvDiff {
     // only problems with variable coefficients refresh the auxiliary state (problem 7:
     // ReversingDeformationalFlow, advection_sphere.jl:56-103); see update_aux_active
     static constexpr bool HAS_UPDATE_AUX = ADV;
-    static constexpr bool FUSE_UPDATE_AUX = false;
-    static constexpr int NUPD = 0;
-    __host__ __device__ static constexpr int upd_aux(int) { return 0; }
-    static constexpr bool HAS_SOURCE = false;
-    static constexpr int NDER = 0;
     __host__ __device__ static bool needs_gradflux(const Params &) { return DIFF; }
     // auxiliary fields the interior-face fluxes read on either side: the velocity (first-order
     // flux and wave speed); boundary faces load the whole minus-side auxiliary state themselves
     static constexpr int NFAUX = ADV ? 3 : 0;
     __host__ __device__ static constexpr int face_aux(int i) { return OU + i; }
-    __host__ __device__ static constexpr int hv_indexmap(int) { return 0; }
 
     static constexpr int BC_INHOM(int o) { return 1 << o; }
     static constexpr int BC_HOM(int o) { return 1 << (o + 4); }
@@ -190,11 +185,6 @@ struct AdvDiff {
         if constexpr (HYPER)
             for (int d = 0; d < 3; ++d) F[d] += hyp[d];
     }
-    __device__ static void source(const Params &, double *, const double *, const double *,
-                                  const double *, const double *, double, int)
-    {
-    }
-    __device__ static void init_derived(const Params &, double *, const double *) {}
     __device__ static void gradient_argument(const Params &, double *G, const double *Q,
                                              const double *, double)
     {
@@ -340,18 +330,6 @@ struct AdvDiff {
             aux[OU + 1] = +ul * cos(lam) - up * sin(lam) * sin(phi);
             aux[OU + 2] = +up * cos(phi);
         }
-    }
-    // the test law defines no local_courant function
-    static constexpr bool HAS_COURANT = false;
-    static constexpr bool HAS_PENALTY = false;  // update_penalty! is the default no-op
-    __device__ static void update_penalty(const Params &, double *, const double *, const double *,
-                                          const double *)
-    {
-    }
-    __device__ static double courant(const Params &, int, const double *, const double *,
-                                     const double *, double, double, double, int)
-    {
-        return 0.0;
     }
 };
 

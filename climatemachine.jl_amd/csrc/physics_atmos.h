@@ -21,6 +21,7 @@
 // MMSSource{3}, boundary kind 2 = InitStateBC with the manufactured solution (same test).
 #pragma once
 #include "cmdg_common.h"
+#include "law_defaults.h"
 
 namespace cmdg {
 
@@ -41,7 +42,7 @@ struct AtmosParams {
 static constexpr int ATMOS_NHOSTCONST = 7;
 
 template <bool ORIENT, bool REF, bool HYPER, bool SMAG = false, bool LAWNF = false>
-struct DryAtmos {
+struct DryAtmos : LawDefaults {
     // RoeNumericalFlux / HLLCNumericalFlux live in a variant of their own so that the
     // kernels of every other configuration keep their register budget
     static constexpr bool LAW_NF = LAWNF;
@@ -59,7 +60,7 @@ struct DryAtmos {
     static constexpr int NGRAD = 4 + (SMAG ? 1 : 0) + (HYPER ? 4 : 0);
     // GradientFlux: grad h_tot, S, [N^2]
     static constexpr int NGF = 9 + (SMAG ? 1 : 0);
-    static constexpr bool GF_NODE_MAJOR = true;  // kernels.h gf_node_major
+    static constexpr bool GF_NODE_MAJOR = true;  // (law_defaults.h)
     static constexpr int NGL = HYPER ? 4 : 0;
     static constexpr int NHYP = HYPER ? 12 : 0;
     static constexpr bool HAS_UPDATE_AUX = true;
@@ -176,10 +177,6 @@ struct DryAtmos {
     static constexpr bool MMS_VARIANT = !ORIENT && !REF && !HYPER && !SMAG && !LAWNF;
     static constexpr bool HAS_COURANT = true;
     static constexpr bool HAS_PENALTY = false;  // update_penalty! is the default no-op
-    __device__ static void update_penalty(const Params &, double *, const double *, const double *,
-                                          const double *)
-    {
-    }
     __device__ static double courant(const Params &m, int kind, const double *Q, const double *aux,
                                      const double *gf, double dx, double dt, double, int direction)
     {
@@ -543,6 +540,7 @@ struct DryAtmos {
     }
     // the same with the node's gradient argument at hand: G[4] is theta_v of this (Q, aux), the
     // very expression above (gradient_argument), so the pow is not evaluated again
+    static constexpr bool HAS_GRADIENT_FLUX_G = true;
     __device__ static void gradient_flux_g(const Params &m, double *gf, const double *g,
                                            const double *, const double *aux, double,
                                            const double *G)
@@ -757,16 +755,6 @@ struct DryAtmos {
 #pragma unroll
             for (int q = 0; q < 15; ++q) F[q] += FPl[q];
         }
-    }
-    __device__ static void boundary_state_divergence(const Params &, int, double *, double *,
-                                                     const double *, const double *,
-                                                     const double *, double)
-    {
-    }
-    __device__ static void boundary_state_higher_order(const Params &, int, double *, double *,
-                                                       double *, const double *, const double *,
-                                                       const double *, const double *, double)
-    {
     }
 };
 

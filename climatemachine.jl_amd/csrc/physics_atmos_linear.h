@@ -23,6 +23,7 @@
 // in p_lin and in the energy flux ((ref.rho e + ref.p) / ref.rho - e_pot) rho u, no source.
 #pragma once
 #include "cmdg_common.h"
+#include "law_defaults.h"
 
 namespace cmdg {
 
@@ -32,24 +33,20 @@ struct AtmosLinearParams {
 };
 
 template <int NAUX_FULL, bool MOIST = false, bool ORIENT = true>
-struct AtmosLinearAG {
+struct AtmosLinearAG : LawDefaults {
     static_assert(ORIENT || !MOIST, "the moist acoustic law is not laid out");
     using Params = AtmosLinearParams;
     // auxiliary layout of DryAtmos with orientation and reference state (physics_atmos.h), which
     // MoistAtmos keeps in its first 15 columns (physics_moist.h)
     static constexpr int OPHI = 3, OREF = ORIENT ? 7 : 3;
-    static constexpr int NS = MOIST ? 6 : 5, NAUX = NAUX_FULL, NGRAD = 0, NGF = 0, NGL = 0, NHYP = 0;
-    static constexpr bool HAS_UPDATE_AUX = false, FUSE_UPDATE_AUX = false, HAS_SOURCE = ORIENT;
-    static constexpr bool HAS_COURANT = false, HAS_PENALTY = false;
-    static constexpr int NUPD = 0, NDER = 0;
+    static constexpr int NS = MOIST ? 6 : 5, NAUX = NAUX_FULL, NGRAD = 0, NGF = 0;
+    static constexpr bool HAS_SOURCE = ORIENT;
     // faces read Phi and the reference rho, p, T, rho e
     static constexpr int NFAUX = ORIENT ? 5 : 4;
     __host__ __device__ static constexpr int face_aux(int i)
     {
         return ORIENT ? (i == 0 ? OPHI : OREF + (i - 1)) : OREF + i;
     }
-    __host__ __device__ static constexpr int upd_aux(int) { return 0; }
-    __host__ __device__ static constexpr int hv_indexmap(int) { return 0; }
     __host__ __device__ static bool needs_gradflux(const Params &) { return false; }
     static void make_params(Params &p, const int32_t *, const double *dp)
     {
@@ -93,10 +90,6 @@ struct AtmosLinearAG {
 #pragma unroll
         for (int d = 0; d < 3; ++d) F[d + 12] = h_ref * Q[1 + d];  // LinearEnergyFlux
     }
-    __device__ static void flux_second_order(const Params &, double *, const double *,
-                                             const double *, const double *, const double *, double)
-    {
-    }
     // Gravity (linear_tendencies.jl: -rho grad Phi in VerticalDirection / EveryDirection only)
     __device__ static void source(const Params &, double *S, const double *Q, const double *,
                                   const double *aux, const double *, double, int direction)
@@ -108,19 +101,6 @@ struct AtmosLinearAG {
         for (int d = 0; d < 3; ++d)
             S[1 + d] = !ORIENT || direction == DIR_HORIZONTAL ? 0.0 : -Q[0] * aux[OPHI + 1 + d];
     }
-    __device__ static void init_derived(const Params &, double *, const double *) {}
-    __device__ static void gradient_argument(const Params &, double *, const double *,
-                                             const double *, double)
-    {
-    }
-    __device__ static void gradient_flux(const Params &, double *, const double *, const double *,
-                                         const double *, double)
-    {
-    }
-    __device__ static void post_gradient_laplacian(const Params &, double *, const double *,
-                                                   const double *, const double *, double)
-    {
-    }
     // wavespeed(::AtmosLinearModel) = soundspeed_air(ref.T) (linear.jl:200-212)
     __device__ static void wavespeed(const Params &m, double *ws, const double *, const double *,
                                      const double *aux, double, int)
@@ -128,10 +108,6 @@ struct AtmosLinearAG {
         const double c = soundspeed(m, aux[OREF + 2]);
 #pragma unroll
         for (int s = 0; s < NS; ++s) ws[s] = c;
-    }
-    __device__ static void update_penalty(const Params &, double *, const double *, const double *,
-                                          const double *)
-    {
     }
     // atmos_boundary_state! of AtmosBC(): Impenetrable(FreeSlip) reflects the normal momentum,
     // Insulating leaves the energy, rho q_tot passes through; the plus-side auxiliary state is the
@@ -144,31 +120,6 @@ struct AtmosLinearAG {
         const double f = 2 * dn;
 #pragma unroll
         for (int d = 0; d < 3; ++d) QP[1 + d] -= f * n[d];
-    }
-    __device__ static void boundary_flux_second_order(const Params &, int, double *, double *,
-                                                      double *, double *, double *, const double *,
-                                                      const double *, const double *,
-                                                      const double *, const double *, double,
-                                                      const double *, const double *,
-                                                      const double *)
-    {
-    }
-    __device__ static void boundary_state_divergence(const Params &, int, double *, double *,
-                                                     const double *, const double *,
-                                                     const double *, double)
-    {
-    }
-    __device__ static void boundary_state_higher_order(const Params &, int, double *, double *,
-                                                       double *, const double *, const double *,
-                                                       const double *, const double *, double)
-    {
-    }
-    __device__ static void update_aux(const Params &, const double *, double *, double) {}
-    __host__ __device__ static bool update_aux_active(const Params &) { return false; }
-    __device__ static double courant(const Params &, int, const double *, const double *,
-                                     const double *, double, double, double, int)
-    {
-        return 0.0;
     }
 };
 

@@ -64,20 +64,14 @@ struct EsdgNode {
     double rho, u[3], rhoe, p, b, usq, e;
 };
 
-struct EsdgDryAtmos {
+struct EsdgDryAtmos : LawDefaults {
     using Params = EsdgDryAtmosParams;
     // NAUX: the columns a kernel may read (Phi, grad Phi); the array has four more with a reference
     // state, so its column count travels in the kernel arguments (EsdgArgs::naux)
-    static constexpr int NS = 5, NAUX = 4, NGRAD = 0, NGF = 0, NGL = 0, NHYP = 0;
+    static constexpr int NS = 5, NAUX = 4, NGRAD = 0, NGF = 0, NFAUX = 1;
     static constexpr int NENT = 6;  // entropy variables: rho, rho u[3], rho e, Phi
-    static constexpr bool HAS_UPDATE_AUX = false, FUSE_UPDATE_AUX = false, HAS_SOURCE = true;
-    static constexpr bool HAS_COURANT = false, HAS_PENALTY = false;
-    static constexpr int NUPD = 0, NDER = 0, NFAUX = 1;
-    __host__ __device__ static constexpr int upd_aux(int) { return 0; }
-    __host__ __device__ static constexpr int hv_indexmap(int) { return 0; }
-    __host__ __device__ static constexpr int face_aux(int) { return 0; }
+    static constexpr bool HAS_SOURCE = true;
     __host__ __device__ static bool needs_gradflux(const Params &) { return false; }
-    __host__ __device__ static bool update_aux_active(const Params &) { return false; }
     static void make_params(Params &p, const int32_t *ip, const double *dp)
     {
         p.nsrc = ip[2] < 0 ? 0 : (ip[2] > 2 ? 2 : ip[2]);
@@ -150,7 +144,6 @@ struct EsdgDryAtmos {
 #pragma unroll
         for (int s = 0; s < NS; ++s) ws[s] = w;
     }
-    __device__ static void update_penalty(const Params &, double *, const double *, const double *, const double *) {}
     // source!  :542-561 (Coriolis), :801-810 (Gravity), in the order of m.sources
     __device__ static void source(const Params &m, double *S, const double *Q, const double *, const double *aux,
                                   const double *, double, int)
@@ -371,43 +364,6 @@ struct EsdgDryAtmos {
             }
             flux[i] -= acc / 2;
         }
-    }
-
-    // ---- what the DG passes of the engine base ask of a law and this one does not have ---------
-    __device__ static void flux_second_order(const Params &, double *, const double *, const double *, const double *,
-                                             const double *, double)
-    {
-    }
-    __device__ static void init_derived(const Params &, double *, const double *) {}
-    __device__ static void gradient_argument(const Params &, double *, const double *, const double *, double) {}
-    __device__ static void gradient_flux(const Params &, double *, const double *, const double *, const double *,
-                                         double)
-    {
-    }
-    __device__ static void post_gradient_laplacian(const Params &, double *, const double *, const double *,
-                                                   const double *, double)
-    {
-    }
-    __device__ static void boundary_flux_second_order(const Params &, int, double *, double *, double *, double *,
-                                                      double *, const double *, const double *, const double *,
-                                                      const double *, const double *, double, const double *,
-                                                      const double *, const double *)
-    {
-    }
-    __device__ static void boundary_state_divergence(const Params &, int, double *, double *, const double *,
-                                                     const double *, const double *, double)
-    {
-    }
-    __device__ static void boundary_state_higher_order(const Params &, int, double *, double *, double *,
-                                                       const double *, const double *, const double *,
-                                                       const double *, double)
-    {
-    }
-    __device__ static void update_aux(const Params &, const double *, double *, double) {}
-    __device__ static double courant(const Params &, int, const double *, const double *, const double *, double,
-                                     double, double, int)
-    {
-        return 0.0;
     }
 };
 

@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "cmdg_common.h"
+#include "law_defaults.h"
 
 namespace cmdg {
 
@@ -34,14 +35,14 @@ struct MoistParams {
 };
 
 template <int CLOSURE, bool LAWNF = false>
-struct MoistAtmos {
+struct MoistAtmos : LawDefaults {
     using Params = MoistParams;
     // RoeNumericalFluxMoist lives in a variant of its own (a 6 x 6 characteristic solve per
     // face node) so that the kernels of every other configuration keep their register budget
     static constexpr bool LAW_NF = LAWNF;
     static constexpr int OPHI = 3, OREF = 7, OTURB = 14, OMOIST = 15;
     static constexpr int NGT = CLOSURE == 2 ? 10 : 7;  // turbulence block of the gradient flux
-    static constexpr int NS = 6, NAUX = 19, NGRAD = 6, NGF = 3 + NGT + 3, NGL = 0, NHYP = 0;
+    static constexpr int NS = 6, NAUX = 19, NGRAD = 6, NGF = 3 + NGT + 3;
     // (state_gradient_flux stays in the reference layout: node-major, as the dry law keeps it, takes 88 B/node
     // off the N = 6 tendency pass and not one microsecond -- profiles/r04_ab_node_major.txt)
     // the nodal refresh (one saturation adjustment per node) runs as its own pass before the
@@ -50,10 +51,9 @@ struct MoistAtmos {
     // reference reads them too (gradient argument / flux) or where the values are the same by
     // construction (source)
     static constexpr bool HAS_UPDATE_AUX = true, FUSE_UPDATE_AUX = false, HAS_SOURCE = true;
-    static constexpr bool HAS_COURANT = true, HAS_PENALTY = false;
+    static constexpr bool HAS_COURANT = true;
     static constexpr int NUPD = 4;
     __host__ __device__ static constexpr int upd_aux(int i) { return OMOIST + i; }
-    static constexpr int NDER = 0;
     // auxiliary fields the interface kernels read on both sides: Phi, grad Phi, ref p, ref rho,
     // Delta and the equilibrium state of the nodal refresh (temperature, q_liq, q_ice)
     static constexpr int NFAUX = 10;
@@ -64,12 +64,10 @@ struct MoistAtmos {
                                : (i == 5 ? OREF + 1
                                          : (i == 6 ? OTURB : (i == 7 ? OMOIST : OMOIST + i - 6))));
     }
-    __host__ __device__ static constexpr int hv_indexmap(int) { return 0; }
     // Byte accounting (cmdg_query, bench.py): columns the volume code of a pass reads.  Gradients
     // (pass 0): the refreshed equilibrium state (temperature, theta_v, q_liq, q_ice) and grad Phi
     // (N^2); tendency (pass 3): the ten columns of face_aux (Phi, grad Phi, ref rho, ref p, Delta,
     // temperature, q_liq, q_ice) -- coord, the rest of ref_state and theta_v are never loaded.
-    __host__ __device__ static constexpr int state_read(int) { return NS; }
     __host__ __device__ static constexpr int aux_read(int pass) { return pass == 0 ? 7 : (pass == 3 ? 10 : 0); }
     __host__ __device__ static bool needs_gradflux(const Params &) { return true; }
     __host__ __device__ static bool update_aux_active(const Params &) { return true; }
@@ -248,10 +246,6 @@ struct MoistAtmos {
         return ts.R_m / m.R_d * (ts.T / exner);
     }
 
-    __device__ static void update_penalty(const Params &, double *, const double *, const double *,
-                                          const double *)
-    {
-    }
     // local Courant numbers of src/Atmos/Model/courant.jl:12-83 (kind 0 advective, 1
     // nondiffusive with the moist sound speed, 2 diffusive with the closure's viscosity)
     __device__ static double courant(const Params &m, int kind, const double *Q, const double *aux,
@@ -431,7 +425,6 @@ struct MoistAtmos {
 #pragma unroll
         for (int d = 0; d < 3; ++d) F[d + 15] = dq[d] * rho;
     }
-    __device__ static void init_derived(const Params &, double *, const double *) {}
     // sources in the order of the model's tuple: Gravity, BomexTendencies, BomexSponge,
     // BomexGeostrophic (bomex_model.jl:396-420)
     __device__ static void source(const Params &m, double *S, const double *Q, const double *gf,
@@ -552,10 +545,6 @@ struct MoistAtmos {
                       g[2 + 3 * 4] * aux[OPHI + 3]) / th;
 #pragma unroll
         for (int d = 0; d < 3; ++d) gf[3 + NGT + d] = g[d + 15];
-    }
-    __device__ static void post_gradient_laplacian(const Params &, double *, const double *,
-                                                   const double *, const double *, double)
-    {
     }
     __device__ static void wavespeed(const Params &m, double *ws, const double *n, const double *Q,
                                      const double *aux, double, int)
@@ -807,16 +796,6 @@ struct MoistAtmos {
         for (int s = 0; s < 6; ++s)
 #pragma unroll
             for (int d = 0; d < 3; ++d) F[d + 3 * s] += X[s] * n[d];
-    }
-    __device__ static void boundary_state_divergence(const Params &, int, double *, double *,
-                                                     const double *, const double *,
-                                                     const double *, double)
-    {
-    }
-    __device__ static void boundary_state_higher_order(const Params &, int, double *, double *,
-                                                       double *, const double *, const double *,
-                                                       const double *, const double *, double)
-    {
     }
 };
 

@@ -17,6 +17,7 @@
 // f_o beta, [11..15] = tau_o rho_o L_y lambda_r theta_E.
 #pragma once
 #include "cmdg_common.h"
+#include "law_defaults.h"
 
 namespace cmdg {
 
@@ -26,17 +27,13 @@ struct OceanParams {
     double grav, ch, cz, aT, nuh, nuz, kh, kz, kc, fo, beta, tau_o, rho_o, Ly, lam_r, thE;
 };
 
-struct HydroBoussinesq {
+struct HydroBoussinesq : LawDefaults {
     using Params = OceanParams;
     enum { U = 0, V = 1, ETA = 2, TH = 3 };
     enum { AY = 0, AW = 1, APKIN = 2, AWZ0 = 3, AUD = 4 };
     enum { GDIVH = 0, GNU = 1, GKAPPA = 7 };
-    static constexpr int NS = 4, NAUX = 8, NGRAD = 5, NGF = 10, NGL = 0, NHYP = 0;
-    static constexpr bool HAS_UPDATE_AUX = false, FUSE_UPDATE_AUX = false, HAS_SOURCE = true;
-    static constexpr bool HAS_COURANT = true, HAS_PENALTY = true;
-    static constexpr int NUPD = 0, NDER = 0;
-    __host__ __device__ static constexpr int upd_aux(int) { return 0; }
-    __host__ __device__ static constexpr int hv_indexmap(int) { return 0; }
+    static constexpr int NS = 4, NAUX = 8, NGRAD = 5, NGF = 10;
+    static constexpr bool HAS_SOURCE = true, HAS_COURANT = true, HAS_PENALTY = true;
     __host__ __device__ static bool needs_gradflux(const Params &) { return true; }
     // the face fluxes read w and pkin (and y never): aux columns 1, 2
     static constexpr int NFAUX = 2;
@@ -124,7 +121,6 @@ struct HydroBoussinesq {
         S[ETA] += 0;
         S[TH] += 0;
     }
-    __device__ static void init_derived(const Params &, double *, const double *) {}
     __device__ static void gradient_argument(const Params &m, double *G, const double *Q,
                                              const double *aux, double)
     {
@@ -152,10 +148,6 @@ struct HydroBoussinesq {
         const double kap[3] = {m.kh, m.kh, g[2 + 3 * 4] < 0 ? m.kc : m.kz};
 #pragma unroll
         for (int d = 0; d < 3; ++d) D[GKAPPA + d] = -kap[d] * g[d + 3 * 4];
-    }
-    __device__ static void post_gradient_laplacian(const Params &, double *, const double *,
-                                                   const double *, const double *, double)
-    {
     }
     __device__ static void wavespeed(const Params &m, double *ws, const double *n, const double *,
                                      const double *, double, int)
@@ -238,18 +230,6 @@ struct HydroBoussinesq {
         }
         flux_second_order(m, F, QP, gfP, hypP, auxP, t);
     }
-    __device__ static void boundary_state_divergence(const Params &, int, double *, double *,
-                                                     const double *, const double *,
-                                                     const double *, double)
-    {
-    }
-    __device__ static void boundary_state_higher_order(const Params &, int, double *, double *,
-                                                       double *, const double *, const double *,
-                                                       const double *, const double *, double)
-    {
-    }
-    __device__ static void update_aux(const Params &, const double *, double *, double) {}
-    __host__ __device__ static bool update_aux_active(const Params &) { return false; }
     // local Courant numbers of src/Ocean/HydrostaticBoussinesq/Courant.jl:13-111:
     // kind 0 advective (|w|, |u| or |(u, v, w)| by direction), 1 nondiffusive (gravity waves,
     // c_h), 2 diffusive (kappa; the factor 1000 on kappa_z stands for convective adjustment),

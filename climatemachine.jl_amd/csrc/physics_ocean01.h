@@ -17,6 +17,7 @@
 // kappa_c f_o beta, [11..16] = tau_o rho_o L_y lambda_r theta_E H.
 #pragma once
 #include "cmdg_common.h"
+#include "law_defaults.h"
 
 namespace cmdg {
 
@@ -56,44 +57,14 @@ static inline void se01_make_params(OceanSE01Params &p, const int32_t *ip, const
     p.H = dp[16];
 }
 
-// the pieces every law of this file leaves at their defaults
-struct SE01Defaults {
-    static constexpr int NGL = 0, NHYP = 0, NUPD = 0, NDER = 0;
-    static constexpr bool HAS_UPDATE_AUX = false, FUSE_UPDATE_AUX = false, HAS_COURANT = false;
-    __host__ __device__ static constexpr int upd_aux(int) { return 0; }
-    __host__ __device__ static constexpr int hv_indexmap(int) { return 0; }
-    __host__ __device__ static bool update_aux_active(const OceanSE01Params &) { return false; }
-    __device__ static void init_derived(const OceanSE01Params &, double *, const double *) {}
-    __device__ static void post_gradient_laplacian(const OceanSE01Params &, double *, const double *,
-                                                   const double *, const double *, double)
-    {
-    }
-    __device__ static void boundary_state_divergence(const OceanSE01Params &, int, double *, double *,
-                                                     const double *, const double *, const double *,
-                                                     double)
-    {
-    }
-    __device__ static void boundary_state_higher_order(const OceanSE01Params &, int, double *,
-                                                       double *, double *, const double *,
-                                                       const double *, const double *,
-                                                       const double *, double)
-    {
-    }
-    __device__ static void update_aux(const OceanSE01Params &, const double *, double *, double) {}
-    __device__ static double courant(const OceanSE01Params &, int, const double *, const double *,
-                                     const double *, double, double, double, int)
-    {
-        return 0.0;
-    }
-    // abs(SVector(c_h, c_h, c_z)' * n)
-    __device__ static double gravity_wavespeed(const OceanSE01Params &m, const double *n)
-    {
-        return fabs(m.ch * n[0] + m.ch * n[1] + m.cz * n[2]);
-    }
-};
+// abs(SVector(c_h, c_h, c_z)' * n)
+__device__ static inline double se01_gravity_wavespeed(const OceanSE01Params &m, const double *n)
+{
+    return fabs(m.ch * n[0] + m.ch * n[1] + m.cz * n[2]);
+}
 
 // ---------------------------------------------------------------------------------------
-struct OceanSE01 : SE01Defaults {
+struct OceanSE01 : LawDefaults {
     using Params = OceanSE01Params;
     enum { U = 0, V = 1, ETA = 2, TH = 3 };
     enum { AW = 0, APKIN = 1, AWZ0 = 2, AUD = 3, ADGU = 5, AY = 7 };  // OceanModel.jl:186-195
@@ -166,7 +137,7 @@ struct OceanSE01 : SE01Defaults {
     __device__ static void wavespeed(const Params &m, double *ws, const double *n, const double *,
                                      const double *, double, int)
     {
-        const double w = gravity_wavespeed(m, n);
+        const double w = se01_gravity_wavespeed(m, n);
 #pragma unroll
         for (int s = 0; s < NS; ++s) ws[s] = w;
     }
@@ -238,13 +209,11 @@ struct OceanSE01 : SE01Defaults {
 
 // ---------------------------------------------------------------------------------------
 // Continuity3dModel: the tendency of the theta slot of one evaluation is -grad_h . u
-struct Continuity3dSE01 : SE01Defaults {
+struct Continuity3dSE01 : LawDefaults {
     using Params = OceanSE01Params;
     enum { U = 0, V = 1, ETA = 2, TH = 3 };
-    static constexpr int NS = 4, NAUX = 0, NGRAD = 0, NGF = 0, NFAUX = 0;
-    static constexpr bool HAS_SOURCE = false, HAS_PENALTY = false;
+    static constexpr int NS = 4, NAUX = 0, NGRAD = 0, NGF = 0;
     __host__ __device__ static bool needs_gradflux(const Params &) { return false; }
-    __host__ __device__ static constexpr int face_aux(int) { return 0; }
     static void make_params(Params &p, const int32_t *ip, const double *dp) { se01_make_params(p, ip, dp); }
     __device__ static void flux_first_order(const Params &, double *F, const double *Q,
                                             const double *, double, int)
@@ -253,31 +222,11 @@ struct Continuity3dSE01 : SE01Defaults {
 #pragma unroll
         for (int d = 0; d < 3; ++d) F[d + 3 * TH] += v[d];
     }
-    __device__ static void flux_second_order(const Params &, double *, const double *, const double *,
-                                             const double *, const double *, double)
-    {
-    }
-    __device__ static void source(const Params &, double *, const double *, const double *,
-                                  const double *, const double *, double, int)
-    {
-    }
-    __device__ static void gradient_argument(const Params &, double *, const double *, const double *,
-                                             double)
-    {
-    }
-    __device__ static void gradient_flux(const Params &, double *, const double *, const double *,
-                                         const double *, double)
-    {
-    }
     __device__ static void wavespeed(const Params &, double *ws, const double *, const double *,
                                      const double *, double, int)
     {  // -zero: the jump of theta must not enter (Continuity3dModel.jl:48-50)
 #pragma unroll
         for (int s = 0; s < NS; ++s) ws[s] = -0.0;
-    }
-    __device__ static void update_penalty(const Params &, double *, const double *, const double *,
-                                          const double *)
-    {
     }
     // boundary_conditions(cm) = (bc[1], bc[1], bc[1]): the coastline condition on every tag
     __device__ static void boundary_state(const Params &m, int kind, int, double *QP, double *,
@@ -295,26 +244,17 @@ struct Continuity3dSE01 : SE01Defaults {
             QP[V] = QM[V] - 2 * dn * n[1];
         }
     }
-    __device__ static void boundary_flux_second_order(const Params &, int, double *, double *,
-                                                      double *, double *, double *, const double *,
-                                                      const double *, const double *,
-                                                      const double *, const double *, double,
-                                                      const double *, const double *,
-                                                      const double *)
-    {
-    }
 };
 
 // ---------------------------------------------------------------------------------------
-struct BarotropicSE01 : SE01Defaults {
+struct BarotropicSE01 : LawDefaults {
     using Params = OceanSE01Params;
     enum { U1 = 0, U2 = 1, ETA = 2 };
     // G_U[2], U_c[2], eta_c, U_s[2], eta_s, Delta_u[2], eta_diag, Delta_eta, y  (BarotropicModel.jl:32-44)
     enum { AGU = 0, AUC = 2, AETAC = 4, AUS = 5, AETAS = 7, ADU = 8, AETAD = 10, ADETA = 11, AY = 12 };
-    static constexpr int NS = 3, NAUX = 13, NGRAD = 2, NGF = 6, NFAUX = 0;
+    static constexpr int NS = 3, NAUX = 13, NGRAD = 2, NGF = 6;
     static constexpr bool HAS_SOURCE = true, HAS_PENALTY = true;
     __host__ __device__ static bool needs_gradflux(const Params &) { return true; }
-    __host__ __device__ static constexpr int face_aux(int) { return 0; }
     static void make_params(Params &p, const int32_t *ip, const double *dp) { se01_make_params(p, ip, dp); }
     __device__ static void flux_first_order(const Params &m, double *F, const double *Q,
                                             const double *, double, int)
@@ -362,7 +302,7 @@ struct BarotropicSE01 : SE01Defaults {
     __device__ static void wavespeed(const Params &m, double *ws, const double *n, const double *,
                                      const double *, double, int)
     {
-        ws[0] = ws[1] = ws[2] = gravity_wavespeed(m, n);
+        ws[0] = ws[1] = ws[2] = se01_gravity_wavespeed(m, n);
     }
     __device__ static void update_penalty(const Params &, double *pen, const double *,
                                           const double *, const double *)

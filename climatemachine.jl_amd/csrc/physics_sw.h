@@ -11,6 +11,7 @@
 // [3] coupling; dparam[0..5] = grav H c nu_or_lambda f_o beta.
 #pragma once
 #include "cmdg_common.h"
+#include "law_defaults.h"
 
 namespace cmdg {
 
@@ -19,19 +20,13 @@ struct SWParams {
     double grav, H, c, nu, fo, beta;
 };
 
-struct ShallowWater {
+struct ShallowWater : LawDefaults {
     using Params = SWParams;
     enum { ETA = 0, U1 = 1, U2 = 2 };
     enum { AY = 0, AG = 1, ADU = 3 };
-    static constexpr int NS = 3, NAUX = 5, NGRAD = 2, NGF = 6, NGL = 0, NHYP = 0;
-    static constexpr bool HAS_UPDATE_AUX = false, FUSE_UPDATE_AUX = false, HAS_SOURCE = true;
-    static constexpr bool HAS_COURANT = false, HAS_PENALTY = false;
-    static constexpr int NUPD = 0, NDER = 0, NFAUX = 0;
-    __host__ __device__ static constexpr int upd_aux(int) { return 0; }
-    __host__ __device__ static constexpr int hv_indexmap(int) { return 0; }
-    __host__ __device__ static constexpr int face_aux(int) { return 0; }
+    static constexpr int NS = 3, NAUX = 5, NGRAD = 2, NGF = 6;
+    static constexpr bool HAS_SOURCE = true;
     __host__ __device__ static bool needs_gradflux(const Params &m) { return !m.drag; }
-    __host__ __device__ static bool update_aux_active(const Params &) { return false; }
     static void make_params(Params &p, const int32_t *ip, const double *dp)
     {
         p.adv = ip[0];
@@ -90,7 +85,6 @@ struct ShallowWater {
             S[U2] -= m.nu * Q[U2];
         }
     }
-    __device__ static void init_derived(const Params &, double *, const double *) {}
     __device__ static void gradient_argument(const Params &m, double *G, const double *Q,
                                              const double *, double)
     {
@@ -108,47 +102,10 @@ struct ShallowWater {
 #pragma unroll
             for (int d = 0; d < 3; ++d) D[d + 3 * c] = -nu[d] * g[d + 3 * c];
     }
-    __device__ static void post_gradient_laplacian(const Params &, double *, const double *,
-                                                   const double *, const double *, double)
-    {
-    }
     __device__ static void wavespeed(const Params &m, double *ws, const double *, const double *,
                                      const double *, double, int)
     {
         ws[0] = ws[1] = ws[2] = m.c;
-    }
-    __device__ static void update_penalty(const Params &, double *, const double *, const double *,
-                                          const double *)
-    {
-    }
-    __device__ static void boundary_state(const Params &, int, int, double *, double *,
-                                          const double *, const double *, const double *, double,
-                                          const double *, const double *)
-    {
-    }
-    __device__ static void boundary_flux_second_order(const Params &, int, double *, double *,
-                                                      double *, double *, double *, const double *,
-                                                      const double *, const double *,
-                                                      const double *, const double *, double,
-                                                      const double *, const double *,
-                                                      const double *)
-    {
-    }
-    __device__ static void boundary_state_divergence(const Params &, int, double *, double *,
-                                                     const double *, const double *,
-                                                     const double *, double)
-    {
-    }
-    __device__ static void boundary_state_higher_order(const Params &, int, double *, double *,
-                                                       double *, const double *, const double *,
-                                                       const double *, const double *, double)
-    {
-    }
-    __device__ static void update_aux(const Params &, const double *, double *, double) {}
-    __device__ static double courant(const Params &, int, const double *, const double *,
-                                     const double *, double, double, double, int)
-    {
-        return 0.0;
     }
 };
 

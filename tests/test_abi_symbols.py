@@ -109,6 +109,26 @@ def test_engine_plugin_builds_and_loads():
     assert r.returncode == 0, r.stderr
 
 
+def test_minimal_law_plugin_builds_on_the_defaults():
+    """tests/host/minimal_law.h defines the mandatory members of csrc/law_defaults.h and nothing
+    else.  Built as a plug-in at N = 2, every pass kernel an EngineT instantiates compiles for gfx950
+    on the base's defaults; the shared object exports cmdg_plugin_make_engine and cmdg_load_plugin
+    takes it (in a child process, as above)."""
+    import subprocess
+    import sys
+    from cmdg_loader import cm
+    so = cm.plugins.build("minimal_law", "minimal_law.h", "MinimalLaw", 9901, 2,
+                          include_dirs=[os.path.join(ROOT, "tests", "host")])
+    names = subprocess.check_output(["nm", "-D", so]).decode()
+    assert " T cmdg_plugin_make_engine" in names
+    assert " T cmdg_plugin_abi" in names
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "from cmdg_loader import cm\n"
+            "assert cm._lib.lib().cmdg_load_plugin(sys.argv[1].encode()) == 0\n" % ROOT)
+    r = subprocess.run([sys.executable, "-c", code, so], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+
+
 def test_plugin_built_against_other_headers_is_refused(tmp_path):
     """A plug-in shares the C++ layout of the engine base class with the library (cmdg_plugin_abi);
     one whose stamp differs -- or that has none -- is refused at load with the reason."""

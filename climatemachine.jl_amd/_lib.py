@@ -141,6 +141,7 @@ class CmdgFvDesc(C.Structure):
 
 
 FV_CONSTANT, FV_LINEAR = 0, 1
+FV_HYDROSTATIC = 0x100      # CMDG_FV_HYDROSTATIC: OR-ed into CmdgFvDesc.reconstruction
 
 
 class CmdgEsdgDesc(C.Structure):

@@ -32,7 +32,9 @@ from .mesh import grids as G
 __all__ = ["PlanetParameters", "DryAtmosModel", "IsentropicVortexSetup", "HeldSuarezSetup",
            "DecayingTemperatureProfile", "DryAdiabaticProfile", "RisingBubbleSetup",
            "CourantTestSetup", "MMSSetup", "IsothermalProfile", "AtmosAcousticGravityLinearModel",
-           "IsentropicVortexReferenceState", "AtmosAcousticLinearModel"]
+           "IsentropicVortexReferenceState", "AtmosAcousticLinearModel", "HBFVReconstruction",
+           "prognostic_to_primitive", "primitive_to_prognostic", "construct_face_auxiliary_state",
+           "fvm_balance", "vert_fvm_auxiliary_field_gradient"]
 
 
 class PlanetParameters:
@@ -142,10 +144,14 @@ class RisingBubbleSetup:
 
 
 class IsentropicVortexSetup:
-    """``IsentropicVortexSetup`` (isentropicvortex_setup.jl:3-60)."""
+    """``IsentropicVortexSetup`` (isentropicvortex_setup.jl:3-60).  ``plane``: the two coordinate
+    directions the vortex turns and travels in, ``(0, 1)`` as in the reference's three-dimensional
+    runs; ``(0, 2)`` puts the plane of a ``dims = 2`` run (horizontal, vertical) into the y-invariant
+    slice of a three-dimensional grid."""
 
-    def __init__(self, ps):
+    def __init__(self, ps, plane=(0, 1)):
         self.ps = ps
+        self.plane = tuple(plane)
         self.p_inf, self.T_inf = 1e5, 300.0
         self.rho_inf = self.p_inf / (ps.R_d * self.T_inf)
         self.translation_speed, self.translation_angle = 150.0, np.pi / 4
@@ -155,14 +161,17 @@ class IsentropicVortexSetup:
     def __call__(self, law, aux, coord, t):
         ps = self.ps
         a = self.translation_angle
-        uinf = np.array([self.translation_speed * np.cos(a), self.translation_speed * np.sin(a), 0.0])
+        i, j = self.plane
+        uinf = np.zeros(3)
+        uinf[i], uinf[j] = self.translation_speed * np.cos(a), self.translation_speed * np.sin(a)
         L, R = self.domain_halflength, self.vortex_radius
         x = [coord[d] - uinf[d] * t for d in range(3)]
         x = [xd - np.floor((xd + L) / (2 * L)) * 2 * L for xd in x]
-        r = np.sqrt(x[0] ** 2 + x[1] ** 2)
-        du_x = -self.vortex_speed * x[1] / R * np.exp(-(r / R) ** 2 / 2)
-        du_y = self.vortex_speed * x[0] / R * np.exp(-(r / R) ** 2 / 2)
-        u = [uinf[0] + du_x, uinf[1] + du_y, uinf[2] + 0 * du_x]
+        r = np.sqrt(x[i] ** 2 + x[j] ** 2)
+        du = [0 * x[i], 0 * x[i], 0 * x[i]]
+        du[i] = -self.vortex_speed * x[j] / R * np.exp(-(r / R) ** 2 / 2)
+        du[j] = self.vortex_speed * x[i] / R * np.exp(-(r / R) ** 2 / 2)
+        u = [uinf[d] + du[d] for d in range(3)]
         T = self.T_inf * (1 - ps.kappa_d * self.vortex_speed ** 2 / 2 * self.rho_inf / self.p_inf
                           * np.exp(-(r / R) ** 2))
         p = self.p_inf * (T / self.T_inf) ** (1.0 / ps.kappa_d)
@@ -369,7 +378,14 @@ class DryAtmosModel:
             aux[:, self.off_phi, :] = phi
             # auxiliary_field_gradient!: element-local strong gradient
             # (dgsem_auxiliary_field_gradient!, DGModel_kernels.jl:3097-3232)
-            aux[:, self.off_phi + 1:self.off_phi + 4, :] = G.auxiliary_field_gradient(grid, phi)
+            if _vertical_fvm(grid):
+                # polynomialorder = (N_h, 0): the horizontal DG part, then the vertical finite-volume
+                # difference incrementing (SpaceDiscretization.jl:413-481)
+                gphi = G.auxiliary_field_gradient(grid, phi, 1)
+                gphi += vert_fvm_auxiliary_field_gradient(grid, phi)
+                aux[:, self.off_phi + 1:self.off_phi + 4, :] = gphi
+            else:
+                aux[:, self.off_phi + 1:self.off_phi + 4, :] = G.auxiliary_field_gradient(grid, phi)
         if isinstance(self.ref_state, IsentropicVortexReferenceState):
             self.ref_state.fill(ps, aux, self.off_ref)
         elif self.ref_state is not None:
@@ -380,6 +396,10 @@ class DryAtmosModel:
             z = aux[:, self.off_phi, :] / ps.grav
             Tv, p = self.ref_state(z)
             rho = p / (Tv * ps.R_d)
+            if _vertical_fvm(grid):
+                # atmos_init_aux! step 2 of a finite-volume vertical (ref_state.jl:160-166):
+                # p_i - p_{i+1} = g (rho_{i+1} dz_{i+1} + rho_i dz_i) / 2 up every stack
+                rho, p = fvm_balance(grid, rho, p, ps)
             T = p / (ps.R_d * rho)
             o = self.off_ref
             aux[:, o + 0, :] = rho
@@ -439,6 +459,136 @@ class DryAtmosModel:
             Q[:, 1 + d, :] = rhou[d]
         Q[:, 4, :] = rhoe
         return Q
+
+
+# ---- DGFVModel on the dry law: a finite-volume vertical, polynomialorder = (N_h, 0) ---------------
+def _vertical_fvm(grid):
+    return grid.dim == 3 and grid.N[2] == 0
+
+
+def _stack_view(grid, a):
+    """(nelem, ..., Np) as (nstack, nvertelem, ..., Np): elements are numbered up their stacks."""
+    nv = int(grid.topology.stacksize)
+    assert a.shape[0] % nv == 0
+    return a.reshape((a.shape[0] // nv, nv) + a.shape[1:])
+
+
+def vert_fvm_auxiliary_field_gradient(grid, a):
+    """``vert_fvm_auxiliary_field_gradient!`` (DGFVModel_kernels.jl:946-1063) of a field ``a``
+    (nelem, Np): the difference of the cells above and below over ``dz_top / 2 + dz + dz_bottom / 2``,
+    one-sided through linear extrapolation at a boundary face, rotated back to Cartesian with the
+    vertical metric terms.  Returns (nelem, 3, Np), to be added to the horizontal DG part."""
+    vg = grid.vgeo
+    nv = int(grid.topology.stacksize)
+    periodic = bool(grid.topology.periodicstack)
+    s, dzh = _stack_view(grid, a), _stack_view(grid, vg[:, G._JcV, :])
+    top, bot = np.roll(s, -1, axis=1), np.roll(s, 1, axis=1)
+    dzh_top, dzh_bot = np.roll(dzh, -1, axis=1), np.roll(dzh, 1, axis=1)
+    if not periodic:
+        assert nv >= 2
+        bot[:, 0] = 2 * s[:, 0] - top[:, 0]
+        dzh_bot[:, 0] = dzh_top[:, 0]
+        top[:, -1] = 2 * s[:, -1] - bot[:, -1]
+        dzh_top[:, -1] = dzh_bot[:, -1]
+    dz = dzh_top + 2 * dzh + dzh_bot
+    grad_v = ((top - bot) / dz).reshape(a.shape)
+    out = np.zeros((a.shape[0], 3, a.shape[1]))
+    for d, c in enumerate((G._xi3x1, G._xi3x2, G._xi3x3)):
+        out[:, d, :] = vg[:, c, :] * vg[:, G._JcV, :] * grad_v
+    return out
+
+
+def fvm_balance(grid, rho, p, ps):
+    """``fvm_balance!(fvm_balance_init!, ...)`` (DGFVModel_kernels.jl:1079-1149, ref_state.jl:265-285):
+    walking each stack from its bottom cell, ``rho_i = rho_{i-1} (R_d T_{i-1} - g dz_{i-1} / 2) /
+    (R_d T_i + g dz_i / 2)`` and ``p_i = R_d rho_i T_i`` with the virtual temperatures ``T = p /
+    (R_d rho)`` of the state it is handed.  Returns the balanced ``(rho, p)``, (nelem, Np)."""
+    nv = int(grid.topology.stacksize)
+    r, q = _stack_view(grid, rho.copy()), _stack_view(grid, p.copy())
+    dz = 2 * _stack_view(grid, grid.vgeo[:, G._JcV, :])
+    R_d, grav = ps.R_d, ps.grav
+    for i in range(1, nv):
+        T_virt = q[:, i - 1] / (R_d * r[:, i - 1])
+        top_T_virt = q[:, i] / (R_d * r[:, i])
+        r[:, i] = r[:, i - 1] * (R_d * T_virt - grav * dz[:, i - 1] / 2) / (R_d * top_T_virt + grav * dz[:, i] / 2)
+        q[:, i] = R_d * r[:, i] * top_T_virt
+    return r.reshape(rho.shape), q.reshape(p.shape)
+
+
+def prognostic_to_primitive(law, Q, aux):
+    """``prognostic_to_primitive!`` of the ``DryModel`` (prog_prim_conversion.jl:67-78): ``Q``
+    (..., 5, Np) to the primitives ``rho, u (3), p`` with the full pressure of the dry phase."""
+    ps = law.ps
+    rho = Q[..., 0, :]
+    e_pot = aux[..., law.off_phi, :] if law.orientation != ORIENT_NONE else 0.0
+    rhoe_kin = (Q[..., 1, :] ** 2 + Q[..., 2, :] ** 2 + Q[..., 3, :] ** 2) / rho / 2
+    e_int = (Q[..., 4, :] - rhoe_kin - rho * e_pot) / rho
+    T = ps.T_0 + e_int / ps.cv_d
+    prim = np.empty_like(Q)
+    prim[..., 0, :] = rho
+    for d in range(3):
+        prim[..., 1 + d, :] = Q[..., 1 + d, :] / rho
+    prim[..., 4, :] = ps.R_d * rho * T
+    return prim
+
+
+def primitive_to_prognostic(law, prim, aux):
+    """``primitive_to_prognostic!`` (prog_prim_conversion.jl:114-131): ``PhaseDry_rho_p``, ``T = p /
+    (rho R_d)``, ``rho e = rho (cv_d (T - T_0) + |u|^2 / 2 + Phi)`` with ``Phi`` of ``aux``."""
+    ps = law.ps
+    rho, p = prim[..., 0, :], prim[..., 4, :]
+    T = p / (ps.R_d * rho)
+    e_kin = (prim[..., 1, :] ** 2 + prim[..., 2, :] ** 2 + prim[..., 3, :] ** 2) / 2
+    e_pot = aux[..., law.off_phi, :] if law.orientation != ORIENT_NONE else 0.0
+    Q = np.empty_like(prim)
+    Q[..., 0, :] = rho
+    for d in range(3):
+        Q[..., 1 + d, :] = rho * prim[..., 1 + d, :]
+    Q[..., 4, :] = rho * (ps.cv_d * (T - ps.T_0) + e_kin + e_pot)
+    return Q
+
+
+def construct_face_auxiliary_state(law, aux_cell, dz):
+    """``construct_face_auxiliary_state!`` (prog_prim_conversion.jl:187-202): the copy, with ``Phi +
+    g dz / 2`` under an orientation; ``dz`` is signed (negative towards the bottom face)."""
+    aux_face = aux_cell.copy()
+    if law.orientation != ORIENT_NONE:
+        aux_face[..., law.off_phi, :] = aux_cell[..., law.off_phi, :] + law.ps.grav * dz / 2
+    return aux_face
+
+
+class HBFVReconstruction:
+    """``HBFVReconstruction(atmos, reconstruction)`` (src/Atmos/Model/reconstructions.jl:15-73): the
+    hydrostatic reference pressures of the stencil, built outward from the centre cell with ``rho g
+    dz / 2`` of the cell weights, are taken off ``p`` before ``reconstruction`` (an ``FVConstant`` or
+    ``FVLinear``) and ``p_ref +- rho g dz / 2`` of the centre cell is put back on the two face values.
+    ``DGFVModel`` hands it to the library as ``reconstruction | FV_HYDROSTATIC``.  Called with primitive
+    cell states ``(2 w + 1, 5, ...)`` and weights ``(2 w + 1, ...)`` it evaluates on the host like the inner object."""
+
+    def __init__(self, model, reconstruction):
+        self.model, self.reconstruction = model, reconstruction
+        self.reconstruction_id = int(reconstruction.reconstruction_id) | 0x100
+        self.width, self.limiter = reconstruction.width, reconstruction.limiter
+
+    def __call__(self, cell_states, cell_weights):
+        c = np.array(cell_states, dtype=np.float64)
+        w = np.asarray(cell_weights, dtype=np.float64)
+        D = c.shape[0]
+        W = (D - 1) // 2
+        grav = self.model.ps.grav
+        half = c[:, 0] * grav * w / 2
+        p_ref = c[W, 4].copy()
+        c[W, 4] -= p_ref
+        p_minus, p_plus = p_ref.copy(), p_ref.copy()
+        for i in range(1, W + 1):
+            p_minus = p_minus + (half[W - i + 1] + half[W - i])
+            c[W - i, 4] -= p_minus
+            p_plus = p_plus - (half[W + i - 1] + half[W + i])
+            c[W + i, 4] -= p_plus
+        bot, top = self.reconstruction(c, w)
+        bot[4] += p_ref + half[W]
+        top[4] += p_ref - half[W]
+        return bot, top
 
 
 class AtmosAcousticGravityLinearModel:

@@ -295,6 +295,7 @@ struct EngineBase {
     bool esdg = false;
     bool fused_lsrk() const { return tendency_filter == nullptr && !fv && !esdg; }
     int init_fv();
+    virtual int fv_prepare() { return CMDG_OK; }  // (engine_fv.h: HB flag against the law, LDS limit of a tall stack)
     // the orders the column operators and the filters are compiled for (one order in every direction)
     bool column_orders() const { return NQ >= 2 && NQ <= 8 && NQV == NQ; }
     // does an evaluation of this handle exchange ghosts (DGModel.jl:104-108: not the vertical

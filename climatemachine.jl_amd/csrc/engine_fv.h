@@ -38,8 +38,9 @@ struct EngineFV : EngineT<P, NQ_, 1> {
         a.add_source = this->direction == DIR_VERTICAL;
         a.model_dir = this->direction;
         a.nf_first = this->nf_first;
-        a.recon = fvd.reconstruction;
+        a.recon = fvd.reconstruction & ~CMDG_FV_HYDROSTATIC;
         a.limiter = fvd.limiter;
+        a.hydrostatic = (fvd.reconstruction & CMDG_FV_HYDROSTATIC) != 0;
         return a;
     }
     template <bool PERIODIC>
@@ -51,6 +52,30 @@ struct EngineFV : EngineT<P, NQ_, 1> {
         case 2: return k_fv_tendency<P, NQ_, 2, PERIODIC>;
         default: return k_fv_tendency<P, NQ_, 3, PERIODIC>;
         }
+    }
+    FvKernel fv_tendency_kernel() const
+    {
+        return fvd.periodicstack ? pick_fv_tendency<true>(fvd.width) : pick_fv_tendency<false>(fvd.width);
+    }
+    // What create asks of the instantiation.  HBFVReconstruction needs a functor that names a
+    // pressure primitive (law_defaults.h PRIM_P).  A stack whose staging passes the 64 KiB a launch
+    // may ask for by default: the dynamic-LDS limit of the one tendency kernel this handle launches
+    // is raised to what the stack needs (up to the 160 KiB a work-group may own on gfx950), on this
+    // handle's device, when the handle is created.
+    int fv_prepare() override
+    {
+        if ((fvd.reconstruction & CMDG_FV_HYDROSTATIC) && P::PRIM_P < 0)
+            return this->fail(CMDG_ERR_INVALID, "cmdg_create_dgfv: CMDG_FV_HYDROSTATIC (HBFVReconstruction) needs a "
+                                                "law that names a pressure primitive (the dry atmosphere law)");
+        const size_t need = fv_lds_bytes(P::NS, NQ_ * NQ_, fvd.nvertelem);
+        if (need <= FV_LDS_DEFAULT) return CMDG_OK;
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(fv_tendency_kernel()),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)need) != hipSuccess) {
+            (void)hipGetLastError();
+            return this->fail(CMDG_ERR_UNSUPPORTED, "cmdg_create_dgfv: the device refuses the LDS a stack of this "
+                                                    "height is staged in");
+        }
+        return CMDG_OK;
     }
     void launch_gradients(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
     {
@@ -90,7 +115,7 @@ struct EngineFV : EngineT<P, NQ_, 1> {
             this->prof_begin(CMDG_K_FV_TENDENCY, st);
             const FvArgs<P> a = fv_args(c, elems, n);
             const int nv = fvd.nvertelem;
-            const FvKernel k = fvd.periodicstack ? pick_fv_tendency<true>(fvd.width) : pick_fv_tendency<false>(fvd.width);
+            const FvKernel k = fv_tendency_kernel();
             hipLaunchKernelGGL(k, dim3((unsigned)(n / nv)), dim3(fv_threads(NQ_ * NQ_, nv)),
                                fv_lds_bytes(P::NS, NQ_ * NQ_, nv), st, a);
             this->prof_end(st);

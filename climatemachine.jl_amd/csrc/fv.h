@@ -17,7 +17,8 @@
 //            reference's summation order per cell -- and its write rules (:597-613, :634-643,
 //            :720-734).
 // LDS: Nq^2 * (NS * nvertelem + NS * (nvertelem + 1) + nvertelem) doubles (fv_lds_bytes: primitives,
-// fluxes of nvertelem + 1 faces, weights).
+// fluxes of nvertelem + 1 faces, weights).  Up to FV_LDS_DEFAULT a launch asks for it as it is; up to
+// FV_LDS_MAX the handle raises the kernel's dynamic-LDS limit when it is created (engine_fv.h).
 #pragma once
 #include "kernels.h"
 
@@ -80,6 +81,7 @@ struct FvArgs {
     int add_source;  // dg.direction isa VerticalDirection
     int model_dir, nf_first;
     int recon, limiter;
+    int hydrostatic;  // HBFVReconstruction around the reconstruction (laws with P::PRIM_P >= 0)
 };
 
 // slope of the limited linear reconstruction (FVReconstructions.jl:168-192)
@@ -106,28 +108,68 @@ __device__ __forceinline__ int fv_half_width(int k, int nv)
 // Face primitives of cell k from the 2 hw + 1 cells around it (neighbours taken modulo the stack
 // height, as the reference loads them).  FVConstant and a one-cell range copy the cell; FVLinear on
 // a wider range works on its middle three cells (FVReconstructions.jl:103-143).
+// hb (laws that name a pressure primitive, P::PRIM_P >= 0; hb_g their g): HBFVReconstruction around it
+// (src/Atmos/Model/reconstructions.jl:15-73) -- the hydrostatic reference pressures of the stencil,
+// built outward from the centre cell with rho g dz / 2 of the cell weights, leave p before the
+// reconstruction, and p_ref +- rho g dz / 2 of the centre cell joins the two face values after it.
+// Cells further out than the middle three never reach the inner reconstruction, so their
+// reference pressures are not formed.
 template <class P, int W, bool PERIODIC>
 __device__ __forceinline__ void fv_reconstruct(const double *sP, const double *sW, int Nh, int nv, int n, int k,
-                                               int recon, int limiter, double *bot, double *top)
+                                               int recon, int limiter, bool hb, double hb_g, double *bot,
+                                               double *top)
 {
     constexpr int NS = P::NS;
+    constexpr bool CAN_HB = P::PRIM_P >= 0;
+    constexpr int PP = CAN_HB ? P::PRIM_P : 0, PR = CAN_HB ? P::PRIM_RHO : 0;
     const int hw = fv_half_width<W, PERIODIC>(k, nv);
+    double p_ref = 0, h2 = 0;  // centre cell: reference pressure, rho g dz / 2
+    if constexpr (CAN_HB) {
+        if (hb) {
+            p_ref = sP[(k * NS + PP) * Nh + n];
+            h2 = sP[(k * NS + PR) * Nh + n] * hb_g * sW[k * Nh + n] / 2;
+        }
+    }
     if (W == 0 || recon == FV_RECON_CONSTANT || hw == 0) {
 #pragma unroll
         for (int s = 0; s < NS; ++s) bot[s] = top[s] = sP[(k * NS + s) * Nh + n];
+        if constexpr (CAN_HB) {
+            if (hb) {
+                const double c2 = bot[PP] - p_ref;
+                bot[PP] = c2 + (p_ref + h2);
+                top[PP] = c2 + (p_ref - h2);
+            }
+        }
         return;
     }
     const int km = k == 0 ? nv - 1 : k - 1, kp = k == nv - 1 ? 0 : k + 1;
     const double w1 = sW[km * Nh + n], w2 = sW[k * Nh + n], w3 = sW[kp * Nh + n];
     const double wi_top = 1 / (w3 + w2), wi_bot = 1 / (w2 + w1);
+    double pm_ref = 0, pp_ref = 0;  // reference pressures of the cells below and above
+    if constexpr (CAN_HB) {
+        if (hb) {
+            const double h1 = sP[(km * NS + PR) * Nh + n] * hb_g * w1 / 2;
+            const double h3 = sP[(kp * NS + PR) * Nh + n] * hb_g * w3 / 2;
+            pm_ref = p_ref + (h2 + h1);
+            pp_ref = p_ref - (h2 + h3);
+        }
+    }
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        const double c1 = sP[(km * NS + s) * Nh + n], c2 = sP[(k * NS + s) * Nh + n],
-                     c3 = sP[(kp * NS + s) * Nh + n];
+        double c1 = sP[(km * NS + s) * Nh + n], c2 = sP[(k * NS + s) * Nh + n], c3 = sP[(kp * NS + s) * Nh + n];
+        if constexpr (CAN_HB) {
+            if (hb && s == PP) c1 -= pm_ref, c2 -= p_ref, c3 -= pp_ref;
+        }
         const double d_top = wi_top * (c3 - c2), d_bot = wi_bot * (c2 - c1);
         const double d = fv_limited_slope(limiter, d_top, d_bot);
         top[s] = c2 + d * w2;
         bot[s] = c2 - d * w2;
+    }
+    if constexpr (CAN_HB) {
+        if (hb) {
+            bot[PP] += p_ref + h2;
+            top[PP] += p_ref - h2;
+        }
     }
 }
 
@@ -136,6 +178,8 @@ __host__ __device__ inline int fv_threads(int Nh, int nvert)
     const int want = Nh * (nvert + 1);
     return want >= 256 ? 256 : ((want + 63) / 64) * 64;
 }
+// what a launch may ask for without more ado, and what a work-group may own on gfx950
+constexpr size_t FV_LDS_DEFAULT = 64 * 1024, FV_LDS_MAX = 160 * 1024;
 inline size_t fv_lds_bytes(int ns, int Nh, int nvert)
 {
     return sizeof(double) * (size_t)Nh * ((size_t)ns * nvert + (size_t)ns * (nvert + 1) + nvert);
@@ -155,6 +199,8 @@ __global__ void __launch_bounds__(256) k_fv_tendency(const FvArgs<P> a)
     const int nt = (int)blockDim.x, tid = (int)threadIdx.x;
     const int64_t vstride = (int64_t)Nh * a.g.nvgeo;
     constexpr int NFP = Nh;  // stride of the face tables (Nfp_max of an (N_h, 0) grid)
+    const bool hb = P::PRIM_P >= 0 && a.hydrostatic;
+    const double hb_g = P::prim_gravity(a.prm);
     // ---- phase 1
     for (int w = tid; w < nv * Nh; w += nt) {
         const int k = w / Nh, n = w - k * Nh;
@@ -191,7 +237,7 @@ __global__ void __launch_bounds__(256) k_fv_tendency(const FvArgs<P> a)
         load_state<NS, Nh>(QcM, a.Q, n, eM);
         load_state<NAUX, Nh>(auxcM, a.aux, n, eM);
         if (NGF > 0 && P::needs_gradflux(a.prm)) load_gf<P, Nh>(gfM, a.gf, n, eM);
-        fv_reconstruct<P, W, PERIODIC>(sP, sW, Nh, nv, n, km, a.recon, a.limiter, bot, top);
+        fv_reconstruct<P, W, PERIODIC>(sP, sW, Nh, nv, n, km, a.recon, a.limiter, hb, hb_g, bot, top);
         const double wM = sW[km * Nh + n];
         law_face_auxiliary_state<P>(a.prm, auxM, auxcM, top_bc ? wM : -wM);
         law_primitive_to_prognostic<P>(a.prm, QM, top_bc ? top : bot, auxM);
@@ -224,7 +270,7 @@ __global__ void __launch_bounds__(256) k_fv_tendency(const FvArgs<P> a)
             load_state<NS, Nh>(QcP, a.Q, n, eP);
             load_state<NAUX, Nh>(auxcP, a.aux, n, eP);
             if (NGF > 0 && P::needs_gradflux(a.prm)) load_gf<P, Nh>(gfP, a.gf, n, eP);
-            fv_reconstruct<P, W, PERIODIC>(sP, sW, Nh, nv, n, kp, a.recon, a.limiter, botP, topP);
+            fv_reconstruct<P, W, PERIODIC>(sP, sW, Nh, nv, n, kp, a.recon, a.limiter, hb, hb_g, botP, topP);
             law_face_auxiliary_state<P>(a.prm, auxPn, auxcP, sW[kp * Nh + n]);
             law_primitive_to_prognostic<P>(a.prm, QPn, topP, auxPn);
             nf_first_order<P>(a.prm, a.nf_first, flux, nrm, QM, auxM, QPn, auxPn, a.t, DIR_VERTICAL);

@@ -32,7 +32,8 @@
 // Members a kernel names only under a flag have no default (the `if constexpr` on the flag discards
 // the call): numerical_flux_law (LAW_NF), flux_wavespeed (HAS_FLUX_WAVESPEED), gradient_flux_g
 // (HAS_GRADIENT_FLUX_G), prognostic_to_primitive / primitive_to_prognostic (HAS_PRIM_CONVERSION),
-// construct_face_auxiliary_state (HAS_FACE_AUX_STATE).  The entropy-stable passes (esdg.h) ask for
+// construct_face_auxiliary_state (HAS_FACE_AUX_STATE; PRIM_RHO / PRIM_P / prim_gravity go with the
+// conversion).  The entropy-stable passes (esdg.h) ask for
 // more -- NENT, state_to_entropy_variables, state_to_entropy, volume_flux, surface_* -- of the one
 // law they serve (physics_esdg_dryatmos.h).
 #pragma once
@@ -177,6 +178,15 @@ struct LawDefaults {
     static constexpr bool HAS_PRIM_CONVERSION = false;
     // construct_face_auxiliary_state(prm, aux_face, aux_cell, dz); default: the copy
     static constexpr bool HAS_FACE_AUX_STATE = false;
+    // HBFVReconstruction (src/Atmos/Model/reconstructions.jl): a law whose primitives name a density
+    // and a pressure says which entries they are and defines prim_gravity(prm); PRIM_P < 0: the law
+    // has no pressure primitive and cmdg_create_dgfv refuses the wrapper on it
+    static constexpr int PRIM_RHO = -1, PRIM_P = -1;
+    template <class... A>
+    __host__ __device__ static double prim_gravity(A &&...)
+    {
+        return 0.0;
+    }
 };
 
 }  // namespace cmdg

@@ -172,6 +172,44 @@ struct DryAtmos : LawDefaults {
         return sqrt(m.gamma_R * T);  // gamma = cp_d / cv_d; sqrt(gamma * R_d * T)
     }
 
+    // ---- vertical finite volume: src/Atmos/Model/prog_prim_conversion.jl:67-78, 114-131, 187-202
+    // (DryModel).  Primitives rho, u (3), p; read by fv.h only.
+    static constexpr bool HAS_PRIM_CONVERSION = true, HAS_FACE_AUX_STATE = true;
+    static constexpr int PRIM_RHO = 0, PRIM_P = 4;
+    __host__ __device__ static double prim_gravity(const Params &m) { return m.grav; }
+    __device__ static void prognostic_to_primitive(const Params &m, double *prim, const double *Q,
+                                                   const double *aux)
+    {
+        const double rho = Q[0];
+        const double T = air_T(m, internal_energy(m, Q, aux));
+        prim[0] = rho;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) prim[1 + d] = Q[1 + d] / rho;
+        prim[4] = air_p(m, T, rho);
+    }
+    // PhaseDry_rho_p: T = p / (R_d rho); total_energy = e_int + e_kin + e_pot
+    __device__ static void primitive_to_prognostic(const Params &m, double *Q, const double *prim,
+                                                   const double *aux)
+    {
+        const double rho = prim[0];
+        const double T = prim[4] / (m.R_d * rho);
+        const double e_int = m.cv_d * (T - m.T_0);
+        const double e_kin = (prim[1] * prim[1] + prim[2] * prim[2] + prim[3] * prim[3]) / 2;
+        const double e_pot = ORIENT ? aux[OPHI] : 0.0;
+        Q[0] = rho;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) Q[1 + d] = rho * prim[1 + d];
+        Q[4] = rho * (e_int + e_kin + e_pot);
+    }
+    // dz is signed: negative towards the bottom face of the cell
+    __device__ static void construct_face_auxiliary_state(const Params &m, double *aux_face,
+                                                          const double *aux_cell, double dz)
+    {
+#pragma unroll
+        for (int s = 0; s < NAUX; ++s) aux_face[s] = aux_cell[s];
+        if constexpr (ORIENT) aux_face[OPHI] = aux_cell[OPHI] + m.grav * dz / 2;
+    }
+
     // ---- local Courant numbers: src/Atmos/Model/courant.jl:12-83 ------------------------
     // the manufactured-solution pieces (source, InitStateBC) exist in the plain variant only
     static constexpr bool MMS_VARIANT = !ORIENT && !REF && !HYPER && !SMAG && !LAWNF;

@@ -399,7 +399,9 @@ class DGFVModel(DGModel):
     direction)`` (src/Numerics/DGMethods/DGFVModel.jl:22-69): spectral-element DG in the
     horizontal, cell-centred finite volumes in the vertical, on a stacked grid built with
     ``polynomialorder = (N_h, 0)``.  ``fv_reconstruction`` is an ``fvreconstructions.FVConstant()``
-    or ``FVLinear(width, limiter)``.  Same methods as ``DGModel`` (``cmdg_create_dgfv`` handle)."""
+    or ``FVLinear(width, limiter)``, or for the dry atmosphere law an ``atmos.HBFVReconstruction(model,
+    reconstruction)`` around either (its ``reconstruction_id`` carries ``_lib.FV_HYDROSTATIC``).  Same
+    methods as ``DGModel`` (``cmdg_create_dgfv`` handle)."""
 
     def __init__(self, balance_law, grid, fv_reconstruction, numerical_flux_first_order=RusanovNumericalFlux,
                  direction=EveryDirection, device="cuda:0", state_auxiliary=None):

@@ -166,8 +166,11 @@ int cmdg_destroy(cmdg_handle h);
  * (src/Numerics/DGMethods/FVReconstructions.jl:60-192). */
 enum { CMDG_FV_CONSTANT = 0, CMDG_FV_LINEAR = 1 };
 enum { CMDG_FV_VANLEER = 0, CMDG_FV_NOLIMITER = 1 };
+/* HBFVReconstruction(atmos, reconstruction) (src/Atmos/Model/reconstructions.jl:15-73): OR-ed into
+ * cmdg_fv_desc.reconstruction, wraps either reconstruction; the law must name a pressure primitive. */
+enum { CMDG_FV_HYDROSTATIC = 0x100 };
 typedef struct cmdg_fv_desc {
-    int32_t reconstruction; /* CMDG_FV_CONSTANT | CMDG_FV_LINEAR */
+    int32_t reconstruction; /* CMDG_FV_CONSTANT | CMDG_FV_LINEAR, optionally | CMDG_FV_HYDROSTATIC */
     int32_t width;          /* width(reconstruction): 0 for the constant, 1..3 for the linear one */
     int32_t limiter;        /* CMDG_FV_VANLEER | CMDG_FV_NOLIMITER */
     int32_t nvertelem;      /* grid.topology.stacksize */
@@ -181,9 +184,16 @@ typedef struct cmdg_fv_desc {
  * (dgfvm::DGFVModel)(tendency, Q, _, t, alpha, beta), DGFVModel.jl:85-320.
  * Refused with CMDG_ERR_INVALID and a message in cmdg_last_error(NULL): N[2] != 0 (and N[2] == 0
  * through cmdg_create), an unstacked grid, nvertelem < 2, width outside 0..3 or 0 with a linear
- * reconstruction, element lists that are not whole stacks.  CMDG_ERR_UNSUPPORTED: a law or order
- * not compiled in (AdvectionDiffusion, advection or advection + diffusion, N_h = 1 and 4), a law
- * with hyperdiffusive states (DGFVModel.jl:91), a stack too tall for the LDS staging.  On such a
+ * reconstruction, element lists that are not whole stacks, CMDG_FV_HYDROSTATIC on a law without a
+ * pressure primitive (AdvectionDiffusion).  CMDG_ERR_UNSUPPORTED: a law or order not compiled in, a
+ * law with hyperdiffusive states (DGFVModel.jl:91), a stack too tall for the LDS staging.  Compiled
+ * in: AdvectionDiffusion, advection or advection + diffusion, N_h = 1 and 4; the dry atmosphere law
+ * at N_h = 4 with constant viscosity and no hyperdiffusion, either without orientation and
+ * reference state or with both, with the Rusanov, central, Roe, HLLC or LMARS first-order flux.
+ * A stack is staged in 8 Nq^2 (ns nvertelem + ns (nvertelem + 1) + nvertelem) bytes of LDS: up to
+ * 64 KiB launches as it is, up to the 160 KiB a work-group may own on gfx950 the handle raises the
+ * kernel's dynamic-LDS limit when it is created (74 cells at N_h = 4 with 5 states), beyond that
+ * the handle is refused.  On such a
  * handle element filters, cmdg_courant, cmdg_min_node_distance and cmdg_columnlu_create are refused
  * with CMDG_ERR_UNSUPPORTED. */
 int cmdg_create_dgfv(const cmdg_desc *desc, const cmdg_fv_desc *fv, cmdg_handle *out);

@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "band_solve.h"
 #include "stepping.h"
 
 namespace cmdg {
@@ -86,63 +87,6 @@ __global__ void k_band_lu(double *A, int64_t ncol, int64_t n, int p, int q)
     }
 }
 
-// band_forward_kernel! then band_back_kernel! on one matrix column per lane.  W = p + 1 = q + 1 =
-// NQV * NS: the row loaded ahead (behind) is the same (node, state) of the next (previous)
-// element.  The window shifts by one register per row, so its indices are static; it stays in
-// registers for every compiled (NQV, NS) (scratch 0).
-template <int NQV, int NS>
-__global__ void __launch_bounds__(64) k_band_solve(double *X, const double *B, const double *A, int64_t ncol,
-                                                   int nvert, int nqh2)
-{
-    constexpr int W = NQV * NS, p = W - 1, q = W - 1, P = p + q + 1;
-    const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (c >= ncol) return;
-    const int Np = nqh2 * NQV;
-    const int64_t h = c / nqh2;
-    const int ij = (int)(c % nqh2);
-    const int64_t n = (int64_t)W * nvert;
-    // node (k, s) of vertical element v of this column in the (Np, nstate, nelem) layout
-    auto idx = [&](int v, int r) -> int64_t {
-        const int k = r / NS, s = r % NS;
-        return ((h * nvert + v) * NS + s) * (int64_t)Np + ij + (int64_t)nqh2 * k;
-    };
-    auto L = [&](int64_t col, int d) -> double { return A[(col * P + d) * ncol + c]; };
-    double lb[W];
-#pragma unroll
-    for (int r = 0; r < W; ++r) lb[r] = B[idx(0, r)];
-    for (int v = 0; v < nvert; ++v) {
-        // one row per iteration: unrolling the rows of an element hoisted every row's p band
-        // loads at once and spilled the window to scratch
-#pragma unroll 1
-        for (int r = 0; r < W; ++r) {
-            const int64_t jj = (int64_t)v * W + r;
-#pragma unroll
-            for (int ii = 1; ii <= p; ++ii) lb[ii] -= L(jj, ii + q) * lb[0];
-            X[idx(v, r)] = lb[0];
-#pragma unroll
-            for (int ii = 0; ii < p; ++ii) lb[ii] = lb[ii + 1];
-            lb[p] = 0.0;
-            if (jj + p + 1 < n) lb[p] = B[idx(v + 1, r)];
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < W; ++r) lb[r] = X[idx(nvert - 1, r)];
-    for (int v = nvert - 1; v >= 0; --v) {
-#pragma unroll 1
-        for (int r = W - 1; r >= 0; --r) {
-            const int64_t jj = (int64_t)v * W + r;
-            lb[q] /= L(jj, q);
-#pragma unroll
-            for (int ii = 0; ii < q; ++ii) lb[ii] -= L(jj, ii) * lb[q];
-            X[idx(v, r)] = lb[q];
-#pragma unroll
-            for (int ii = q - 1; ii >= 0; --ii) lb[ii + 1] = lb[ii];
-            lb[0] = 0.0;
-            if (jj - q > 0) lb[0] = X[idx(v - 1, r)];
-        }
-    }
-}
-
 }  // namespace
 }  // namespace cmdg
 
@@ -164,9 +108,9 @@ struct cmdg_columnlu : cmdg::BackwardEuler {
 namespace {
 
 // the (vertical order, state count) pairs k_band_solve is compiled for
-bool compiled(int nqv, int ns) { return ns == 5 ? (nqv == 5 || nqv == 6) : ns == 6 && (nqv == 5 || nqv == 7); }
+bool compiled(int nqv, int ns) { return ns == 5 ? (nqv >= 4 && nqv <= 6) : ns == 6 && (nqv == 5 || nqv == 7); }
 const char *const compiled_pairs =
-    "vertical order / state count not compiled in (have N = 4, 5 with five states, N = 4, 6 with six)";
+    "vertical order / state count not compiled in (have N = 3, 4, 5 with five states, N = 4, 6 with six)";
 
 int lu_fail(cmdg_columnlu *lu, int code, const std::string &msg)
 {
@@ -224,7 +168,9 @@ int solve(cmdg_columnlu *lu, double *X, const double *B)
     if (lu->state != 2) return lu_fail(lu, CMDG_ERR_INVALID, "the band is not factored");
     hipStream_t st = lu->lin->eng->s_comp;
     const dim3 g(blocks(lu->ncol, 64)), b(64);
-    if (lu->ns == 5 && lu->nqv == 5)
+    if (lu->ns == 5 && lu->nqv == 4)  // (the order of the ESDG linear law alone: engine_esdg_linear.hip)
+        band_solve_nqv4_ns5(g, b, st, X, B, lu->band, lu->ncol, lu->nvert, lu->nqh2);
+    else if (lu->ns == 5 && lu->nqv == 5)
         hipLaunchKernelGGL((k_band_solve<5, 5>), g, b, 0, st, X, B, lu->band, lu->ncol, lu->nvert, lu->nqh2);
     else if (lu->ns == 5 && lu->nqv == 6)
         hipLaunchKernelGGL((k_band_solve<6, 5>), g, b, 0, st, X, B, lu->band, lu->ncol, lu->nvert, lu->nqh2);

@@ -36,6 +36,7 @@ const Law LAWS[] = {
     {CMDG_PHYSICS_MOIST_LINEAR_AG, make_engine_moist_linear, counts_moist_linear},
     {CMDG_PHYSICS_ESDG_DRY_ATMOS, nullptr, counts_esdg_dryatmos},
     {CMDG_PHYSICS_ATMOS_LINEAR_ACOUSTIC, make_engine_atmos_acoustic, counts_atmos_acoustic},
+    {CMDG_PHYSICS_ESDG_DRY_ATMOS_LINEAR_AG, make_engine_esdg_dryatmos_linear, counts_esdg_dryatmos_linear},
 };
 const Law *find_law(int32_t physics_id)
 {

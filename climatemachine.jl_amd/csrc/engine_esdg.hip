@@ -57,6 +57,27 @@ struct EngineESDG : EngineT<P, NQ_, NQ_> {
         hipLaunchKernelGGL(pick(), dim3((unsigned)n), dim3(KDims<NQ_, NQ_>::NT), 0, st, a);
         this->prof_end(st);
     }
+    // advective_courant / nondiffusive_courant of the law (DryAtmos.jl:758-793); the minimum node
+    // distance (mode 0) is the grid's
+    template <class PA>
+    void launch_courant_t(int kind, const double *Q, double dt, double t, int dir, double *out_elem)
+    {
+        constexpr int NT = KDims<NQ_, NQ_>::Np <= 128 ? 128 : 256;
+        hipLaunchKernelGGL((k_courant<PA, NQ_, NQ_, 1>), dim3((unsigned)this->nreal), dim3(NT), 0, this->s_comp,
+                           this->prm, this->g.vgeo, this->g.nvgeo, Q, this->aux, this->gf, kind, dt, t, dir, out_elem);
+    }
+    int launch_courant(int mode, int kind, const double *Q, double dt, double t, int dir, double *out_elem) override
+    {
+        if (mode == 0) return Base::launch_courant(mode, kind, Q, dt, t, dir, out_elem);
+        if (kind != CMDG_ADVECTIVE_COURANT && kind != CMDG_NONDIFFUSIVE_COURANT)
+            return this->fail(CMDG_ERR_UNSUPPORTED, "courant: the DryAtmosModel of the entropy-stable discretisation "
+                                                    "defines the advective and the nondiffusive Courant number only");
+        if (this->naux == EsdgDryAtmosRef::NAUX)
+            launch_courant_t<EsdgDryAtmosRef>(kind, Q, dt, t, dir, out_elem);
+        else
+            launch_courant_t<P>(kind, Q, dt, t, dir, out_elem);
+        return CMDG_OK;
+    }
     int launch_entropy(const double *Q, double *beta, double *eta) override
     {
         constexpr int Np = KDims<NQ_, NQ_>::Np;

@@ -175,6 +175,29 @@ struct EsdgDryAtmos : LawDefaults {
         auxP[0] = auxM[0];
     }
 
+    // ---- local Courant numbers  :747-793 (kind 0 advective, 1 nondiffusive; the law has no diffusive
+    // one): k_hat = grad Phi / grav, norm_u by direction
+    static constexpr bool HAS_COURANT = true;
+    __device__ static double courant(const Params &m, int kind, const double *Q, const double *aux, const double *,
+                                     double dx, double dt, double, int direction)
+    {
+        const double k[3] = {aux[1] / m.grav, aux[2] / m.grav, aux[3] / m.grav};
+        const double dotk = Q[1] * k[0] + Q[2] * k[1] + Q[3] * k[2];
+        double normu;
+        if (direction == DIR_VERTICAL) {
+            normu = fabs(dotk) / Q[0];
+        } else {
+            double v[3];
+#pragma unroll
+            for (int d = 0; d < 3; ++d)
+                v[d] = direction == DIR_HORIZONTAL ? (Q[1 + d] - dotk * k[d]) / Q[0] : Q[1 + d] / Q[0];
+            normu = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        }
+        if (kind == 0) return dt * normu / dx;
+        const double ss = soundspeed(m, Q[0], pressure(m, Q[0], Q + 1, Q[4]));
+        return dt * (normu + ss) / dx;
+    }
+
     // ---- entropy  :339-409 -----------------------------------------------------------------
     __device__ static void state_to_entropy_variables(const Params &m, double *ent, const double *Q, const double *)
     {
@@ -365,6 +388,13 @@ struct EsdgDryAtmos : LawDefaults {
             flux[i] -= acc / 2;
         }
     }
+};
+
+// The law on the auxiliary array of a model with a reference state: the column count a pointwise
+// kernel strides by (the Courant kernel loads NAUX columns per node; the flux-differencing passes
+// carry the count in their arguments).
+struct EsdgDryAtmosRef : EsdgDryAtmos {
+    static constexpr int NAUX = 8;
 };
 
 }  // namespace cmdg

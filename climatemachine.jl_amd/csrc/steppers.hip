@@ -107,6 +107,11 @@ int ark_step(cmdg_handle full, BackwardEuler *be, double *Q, double *const *work
                                                         "; they must be the same"));
     if (ef->nreal != el->nreal || ef->Np != el->Np || ef->dev != el->dev)
         return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: the full and the linear model live on different grids"));
+    // an ESDGModel handle as the full operator: eager evaluations through Op::eval like any other, on
+    // one rank (its exchanges have not been driven from inside a step)
+    if (ef->esdg && (ef->nghost > 0 || el->nghost > 0))
+        return gc.finish(ef->fail(CMDG_ERR_UNSUPPORTED, "ark: an ESDGModel as the full operator on a partitioned grid "
+                                                        "is not supported (one rank only)"));
     const int ns = nstages;
     for (int i = 0; i < 2 * ns + 1; ++i)
         if (!work[i]) return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: work array " + std::to_string(i) + " is NULL"));

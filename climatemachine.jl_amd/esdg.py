@@ -15,14 +15,22 @@ import numpy as np
 
 from .atmos import PlanetParameters
 from .mesh.grids import _x1, _x2, _x3
+from .mesh.topologies import equiangular_cubed_sphere_warp
 
 PHYSICS_ESDG_DRY_ATMOS = 12
+PHYSICS_ESDG_DRY_ATMOS_LINEAR_AG = 14
 
 __all__ = ["DryAtmosModel", "FlatOrientation", "SphericalOrientation", "Coriolis", "Gravity",
            "DryReferenceState", "EntropyConservative", "CentralVolumeFlux", "KGVolumeFlux",
            "RusanovNumericalFlux", "EntropyConservativeWithPenalty", "MatrixFlux",
            "state_to_entropy_variables", "entropy_variables_to_state", "state_to_entropy", "pressure",
-           "totalenergy", "soundspeed", "gamma"]
+           "totalenergy", "soundspeed", "gamma", "DryAtmosAcousticGravityLinearModel", "BaroclinicWave",
+           "cubedshellwarp", "sphr_to_cart_vec"]
+
+# ``cubedshellwarp`` of DryAtmos.jl:827-860 is ``cubed_sphere_warp(EquiangularCubedSphere(), ...)``
+# (Topologies.jl:1253-1298) restated: the same ``tan(pi xi / 4)`` map, the same face branches in the
+# same order, ``R = max(|a|, |b|, |c|)`` by default.
+cubedshellwarp = equiangular_cubed_sphere_warp
 
 
 class FlatOrientation:
@@ -199,3 +207,116 @@ class DryAtmosModel:
     def init_state_prognostic(self, grid, aux, t=0.0):
         coord = [grid.vgeo[:, c, :] for c in (_x1, _x2, _x3)]
         return np.ascontiguousarray(self.problem.init_state_prognostic(coord, aux), dtype=np.float64)
+
+
+class DryAtmosAcousticGravityLinearModel:
+    """``DryAtmosAcousticGravityLinearModel(atmos)`` (test/Numerics/ESDGMethods/DryAtmos/linear.jl) of
+    a ``DryAtmosModel`` with a reference state: prognostic ``rho, rho u, rho e``, first-order fluxes
+    ``rho u``, ``pL I`` with ``pL = (gamma - 1) rho e`` and ``((ref.rho e + ref.p) / ref.rho) rho u``,
+    source ``rho u -= rho grad Phi``, ``rho e -= rho u . grad Phi`` (vertical and every direction), Rusanov
+    wavespeed ``soundspeed(ref.rho, ref.p)``, the full model's wall on tags 1 and 2.  It reads the full
+    model's auxiliary state: build it as ``DGModel(linear, grid, RusanovNumericalFlux,
+    direction=VerticalDirection, state_auxiliary=esdg_model.state_auxiliary)``.  Device functor:
+    csrc/physics_esdg_dryatmos_linear.h."""
+    physics_id = PHYSICS_ESDG_DRY_ATMOS_LINEAR_AG
+    ns, ngrad, ngradflux, ngradlap, nhyper = 5, 0, 0, 0, 0
+
+    def __init__(self, atmos):
+        if atmos.ref_state is None:
+            raise ValueError("DryAtmosAcousticGravityLinearModel needs a model with a reference state")
+        self.atmos = atmos
+        self.param_set = atmos.param_set
+        self.naux = atmos.naux
+
+    def descriptor(self):
+        return self.atmos.descriptor()
+
+    def init_state_auxiliary(self, grid):
+        raise ValueError("DryAtmosAcousticGravityLinearModel shares the full model's auxiliary state: "
+                         "pass state_auxiliary=esdg_model.state_auxiliary")
+
+    def init_state_prognostic(self, grid, aux, t=0.0):
+        return np.zeros((grid.nelem, self.ns, grid.Np))
+
+
+def sphr_to_cart_vec(vec, lat, lon):
+    """``sphr_to_cart_vec`` of baroclinic_wave.jl:38-48."""
+    slat, clat = np.sin(lat), np.cos(lat)
+    slon, clon = np.sin(lon), np.cos(lon)
+    return [-slon * vec[0] - slat * clon * vec[1] + clat * clon * vec[2],
+            clon * vec[0] - slat * slon * vec[1] + clat * slon * vec[2],
+            clat * vec[1] + slat * vec[2]]
+
+
+class BaroclinicWave:
+    """``BaroclinicWave()`` of test/Numerics/ESDGMethods/DryAtmos/baroclinic_wave.jl:50-178: the
+    deep-atmosphere baroclinic wave (``q_0 = 0``), the reference's expressions in their order, on
+    the host."""
+
+    def __init__(self, param_set=None):
+        self.param_set = param_set or PlanetParameters()
+
+    def base_state(self, coord):
+        """``(lam, phi, z, T_v, p, u_ref)`` at the nodes."""
+        ps = self.param_set
+        _grav, _R_d, _Omega, _a, _p_0 = ps.grav, ps.R_d, ps.Omega, ps.planet_radius, ps.MSLP
+        k, T_E, T_P = 3.0, 310.0, 240.0
+        T_0 = 0.5 * (T_E + T_P)
+        Gamma = 0.005
+        A = 1 / Gamma
+        B = (T_0 - T_P) / T_0 / T_P
+        Cc = 0.5 * (k + 2) * (T_E - T_P) / T_E / T_P
+        b = 2.0
+        H = _R_d * T_0 / _grav
+        x1, x2, x3 = coord
+        nrm = np.sqrt(x1 * x1 + x2 * x2 + x3 * x3)
+        lam = np.arctan2(x2, x1)
+        phi = np.arcsin(x3 / nrm)
+        z = nrm - _a
+        g = 1.0        # deep atmosphere
+        zbH = z / b / H
+        tau_z_1 = np.exp(Gamma * z / T_0)
+        tau_z_2 = 1 - 2 * (zbH * zbH)
+        tau_z_3 = np.exp(-(zbH * zbH))
+        tau_1 = 1 / T_0 * tau_z_1 + B * tau_z_2 * tau_z_3
+        tau_2 = Cc * tau_z_2 * tau_z_3
+        tau_int_1 = A * (tau_z_1 - 1) + B * z * tau_z_3
+        tau_int_2 = Cc * z * tau_z_3
+        cz = np.cos(phi) * (1 + g * z / _a)
+        I_T = cz ** k - k / (k + 2) * cz ** (k + 2)
+        T_v = 1 / (tau_1 - tau_2 * I_T)
+        p = _p_0 * np.exp(-_grav / _R_d * (tau_int_1 - tau_int_2 * I_T))
+        U = _grav * k / _a * tau_int_2 * T_v * (cz ** (k - 1) - cz ** (k + 1))
+        oc = _Omega * (_a + g * z) * np.cos(phi)
+        u_ref = -oc + np.sqrt(oc * oc + (_a + g * z) * np.cos(phi) * U)
+        return lam, phi, z, T_v, p, u_ref
+
+    def perturbation(self, lam, phi, z):
+        """``(u', v', d)``: zero unless ``0 < d < d_0``."""
+        _a = self.param_set.planet_radius
+        z_t, lam_c, phi_c, d_0, V_p = 15e3, np.pi / 9, 2 * np.pi / 9, _a / 6, 1.0
+        zz = z / z_t
+        F_z = np.where(z > z_t, 0.0, 1 - 3 * (zz * zz) + 2 * (zz * zz * zz))
+        d = _a * np.arccos(np.sin(phi) * np.sin(phi_c) + np.cos(phi) * np.cos(phi_c) * np.cos(lam - lam_c))
+        c1 = np.cos(np.pi * d / 2 / d_0)
+        c3 = c1 * c1 * c1
+        s1 = np.sin(np.pi * d / 2 / d_0)
+        inside = (0 < d) & (d < d_0) & (d != _a * np.pi)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            up = (-16 * V_p / 3 / np.sqrt(3.0) * F_z * c3 * s1
+                  * (-np.sin(phi_c) * np.cos(phi) + np.cos(phi_c) * np.sin(phi) * np.cos(lam - lam_c))
+                  / np.sin(d / _a))
+            vp = 16 * V_p / 3 / np.sqrt(3.0) * F_z * c3 * s1 * np.cos(phi_c) * np.sin(lam - lam_c) / np.sin(d / _a)
+        return np.where(inside, up, 0.0), np.where(inside, vp, 0.0), d
+
+    def init_state_prognostic(self, coord, aux):
+        ps = self.param_set
+        lam, phi, z, T_v, p, u_ref = self.base_state(coord)
+        up, vp, _ = self.perturbation(lam, phi, z)
+        zero = np.zeros_like(z)
+        u_cart = sphr_to_cart_vec([u_ref + up, zero + vp, zero + zero], phi, lam)
+        T = T_v
+        rho = p / (ps.R_d * T)
+        e_kin = 0.5 * (u_cart[0] * u_cart[0] + u_cart[1] * u_cart[1] + u_cart[2] * u_cart[2])
+        e_int = ps.cv_d * T
+        return np.stack([rho] + [rho * u for u in u_cart] + [rho * (e_int + e_kin)], axis=1)

@@ -84,7 +84,12 @@ enum {
     /* AtmosAcousticLinearModel (linear.jl:214-245) of a dry AtmosModel with NoOrientation() and a
      * reference state: no gravity source, e_pot = 0; on the full model's parameter block and
      * 12-column auxiliary array; N = 4; Rusanov or central first-order flux */
-    CMDG_PHYSICS_ATMOS_LINEAR_ACOUSTIC = 13
+    CMDG_PHYSICS_ATMOS_LINEAR_ACOUSTIC = 13,
+    /* DryAtmosAcousticGravityLinearModel (test/Numerics/ESDGMethods/DryAtmos/linear.jl) of the
+     * CMDG_PHYSICS_ESDG_DRY_ATMOS model with a reference state: an ordinary DGModel law (cmdg_create)
+     * on that model's parameter block and 8-column auxiliary array; N = 3, 4; Rusanov or central
+     * first-order flux */
+    CMDG_PHYSICS_ESDG_DRY_ATMOS_LINEAR_AG = 14
 };
 
 /* Construction record: the fields of `DGModel(balance_law, grid, nf1, nf2, nfgrad;
@@ -523,7 +528,9 @@ enum {
  * maximum over this rank's real nodes of the law's local Courant number, with dx the
  * minimum neighbour distance of the node in `direction`; -inf when the rank owns no element.
  * The caller applies MPI.Allreduce(max) (:364).  calculate_dt (DGMethods.jl:79-83) is
- * Courant_number / cmdg_courant(NONDIFFUSIVE, dt = 1).  Blocks until the value is on the host. */
+ * Courant_number / cmdg_courant(NONDIFFUSIVE, dt = 1).  Blocks until the value is on the host.
+ * An ESDGModel handle serves the advective and the nondiffusive kind of its DryAtmosModel
+ * (test/Numerics/ESDGMethods/DryAtmos/DryAtmos.jl:747-793) and refuses the others. */
 int cmdg_courant(cmdg_handle h, int32_t kind, const double *Q, double dt, double simtime,
                  int32_t direction, double *out_host);
 /* min_node_distance(grid, direction) (Grids.jl:455-486): rank-local minimum, +inf for an empty
@@ -918,9 +925,9 @@ int cmdg_profile_reset(cmdg_handle h);
 
 /* ---- ManyColumnLU and the IMEX step (columnwise_lu_solver.jl, AdditiveRungeKuttaMethod.jl) ----
  * A column solver owns the banded matrix I - alpha L of every column of a VerticalDirection DG
- * model `linear` on a stacked grid (CMDG_PHYSICS_ATMOS_LINEAR_AG with nstate = 5 or
- * CMDG_PHYSICS_MOIST_LINEAR_AG with nstate = 6; eband = 1, bandwidths p = q = Nq_v nstate - 1;
- * compiled for (N, nstate) = (4, 5), (5, 5), (4, 6), (6, 6)).  A column is one horizontal node of one stack of `nvertelem` elements;
+ * model `linear` on a stacked grid (CMDG_PHYSICS_ATMOS_LINEAR_AG or
+ * CMDG_PHYSICS_ESDG_DRY_ATMOS_LINEAR_AG with nstate = 5, CMDG_PHYSICS_MOIST_LINEAR_AG with nstate = 6; eband = 1, bandwidths p = q = Nq_v nstate - 1;
+ * compiled for (N, nstate) = (3, 5), (4, 5), (5, 5), (4, 6), (6, 6)).  A column is one horizontal node of one stack of `nvertelem` elements;
  * the real elements must be whole stacks, bottom first.  Every stack must end in boundary faces:
  * a vertically periodic stack (no boundary face at the bottom of its first or the top of its last
  * element) is refused with CMDG_ERR_UNSUPPORTED, since the band cannot hold the coupling of its
@@ -954,8 +961,9 @@ int cmdg_columnlu_destroy(cmdg_columnlu_handle lu);
  * Qhat, Qtt).  split_explicit_implicit != 0: the explicit operator is full minus linear,
  * evaluated as `full` followed by `linear` with alpha = -1 and increment.  The solver is refactored
  * when dt a_ii differs from its alpha.  `full` and `linear` must have the same state count
- * (CMDG_ERR_INVALID otherwise).  A failure's message is on both handles.  Returns after the step
- * has finished. */
+ * (CMDG_ERR_INVALID otherwise).  `full` may be an ESDGModel handle (cmdg_create_esdg) with
+ * CMDG_PHYSICS_ESDG_DRY_ATMOS_LINEAR_AG as `linear`, on one rank (CMDG_ERR_UNSUPPORTED with ghost
+ * elements).  A failure's message is on both handles.  Returns after the step has finished. */
 int cmdg_ark_step(cmdg_handle full, cmdg_columnlu_handle lu, double *Q, double *const *work, double t,
                   double dt, int32_t nstages, const double *rka_explicit, const double *rka_implicit,
                   const double *rkb, const double *rkc, int32_t split_explicit_implicit);

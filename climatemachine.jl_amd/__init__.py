@@ -8,7 +8,7 @@ are imported lazily so that the host-side pieces work without a GPU."""
 from . import atmos, balancelaws, esdg, mesh, moist, ocean, ocean01  # noqa: F401
 
 __all__ = ["mesh", "balancelaws", "atmos", "esdg", "moist", "ocean", "ocean01", "dgmodel", "odesolvers", "systemsolvers", "plugins",
-           "reductions", "fvreconstructions", "weightedsum", "norm", "dot", "euclidean_distance", "mapreduce", "ConsCallback"]
+           "reductions", "fvreconstructions", "diagnostics", "weightedsum", "norm", "dot", "euclidean_distance", "mapreduce", "ConsCallback"]
 
 # MPIStateArrays reductions (reductions.py), exported by name; loaded on first use like dgmodel
 _REDUCTIONS = ("weightedsum", "norm", "dot", "euclidean_distance", "mapreduce", "group_weightedsum",
@@ -17,7 +17,8 @@ _REDUCTIONS = ("weightedsum", "norm", "dot", "euclidean_distance", "mapreduce", 
 
 def __getattr__(name):
     import importlib
-    if name in ("dgmodel", "odesolvers", "_lib", "plugins", "reductions", "systemsolvers", "fvreconstructions"):
+    if name in ("dgmodel", "odesolvers", "_lib", "plugins", "reductions", "systemsolvers", "fvreconstructions",
+                "diagnostics"):
         return importlib.import_module("." + name, __name__)
     if name in _REDUCTIONS:
         return getattr(importlib.import_module(".reductions", __name__), name)

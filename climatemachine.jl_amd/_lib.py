@@ -155,6 +155,12 @@ class CmdgEsdgDesc(C.Structure):
 FV_VANLEER, FV_NOLIMITER = 0, 1
 
 
+class CmdgLesResult(C.Structure):
+    """``cmdg_les_result`` of include/cmdg.h."""
+    _fields_ = [("simple_sums", C.c_void_p), ("simple_avgs", C.c_void_p), ("ho_sums", C.c_void_p),
+                ("ho_avgs", C.c_void_p), ("cloud_levels", C.c_void_p), ("cloud_scalars", C.c_void_p)]
+
+
 # every symbol include/cmdg.h declares: (name, restype, argtypes)
 _vp, _i32, _i64, _d = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = [
@@ -252,6 +258,12 @@ SYMBOLS = [
     ("cmdg_dss_apply", C.c_int, [_vp, _vp, _vp, _i32]),
     ("cmdg_dss", C.c_int, [_vp, _vp, _vp, _i32]),
     ("cmdg_group_dss", C.c_int, [_vp, _i32, _vp, _vp, _i32]),
+    ("cmdg_les_query", C.c_int, [_vp, _i32, _vp]),
+    ("cmdg_les_nodal", C.c_int, [_vp, _vp, _d, _vp]),
+    ("cmdg_les_init", C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+    ("cmdg_les_collect", C.c_int, [_vp, _vp, _d, C.POINTER(CmdgLesResult)]),
+    ("cmdg_group_les_init", C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    ("cmdg_group_les_collect", C.c_int, [_vp, _i32, _vp, _d, C.POINTER(CmdgLesResult)]),
 ]
 
 _LIB = None

@@ -7,6 +7,7 @@
 
 #include "engine_base.h"
 #include "laws.h"
+#include "diagnostics.h"
 #include "reductions.h"
 
 using namespace cmdg;
@@ -342,6 +343,7 @@ int cmdg_destroy(cmdg_handle h)
                 peer->transport = TRANSPORT_NONE;
             }
         reduce_release(h->eng);
+        les_release(h->eng);
         delete h->eng;
     }
     delete h;

@@ -177,6 +177,25 @@ struct EngineT : EngineBase {
                                g.vgeo, g.nvgeo, Q, aux, gf, kind, dt, t, dir, out_elem);
         return CMDG_OK;
     }
+    int launch_les_nodal(const double *Q, double t, double *D, int *ndiag, int *moist) override
+    {
+        if constexpr (P::HAS_LES_DIAGNOSTICS) {
+            if (!P::les_diagnostics_active(prm))
+                return fail(CMDG_ERR_UNSUPPORTED, "AtmosLESDefault diagnostics: this configuration of the law is "
+                                                  "not an LES one (flat orientation)");
+            *ndiag = P::NDIAG;
+            *moist = P::LES_MOIST;
+            if (!D) return CMDG_OK;
+            const int64_t n = nreal * KDims<NQ_, NQV_>::Np;
+            if (n <= 0) return CMDG_OK;
+            hipLaunchKernelGGL((k_les_nodal<P, NQ_, NQV_>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s_comp,
+                               prm, Q, aux, gf, (int)(gf_live() && gf != nullptr), t, nreal, D);
+            return CMDG_OK;
+        } else {
+            return fail(CMDG_ERR_UNSUPPORTED, "AtmosLESDefault diagnostics: this balance law defines no LES "
+                                              "diagnostics (the dry and the moist atmosphere laws do)");
+        }
+    }
     bool has_update_aux() const override { return P::HAS_UPDATE_AUX && P::update_aux_active(prm); }
     bool law_needs_gradflux() const override { return P::needs_gradflux(prm); }
     bool gf_node_major() const override { return cmdg::gf_node_major<P>; }

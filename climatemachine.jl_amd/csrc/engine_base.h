@@ -336,6 +336,11 @@ struct EngineBase {
         return fail(CMDG_ERR_UNSUPPORTED, "cmdg_esdg_entropy: not an ESDGModel handle (cmdg_create_esdg)");
     }
 
+    // cmdg_les_nodal: the law's nodal AtmosLESDefault diagnostics of the real elements into D
+    // (ndiag, Np, nreal), from (Q, aux, gradient flux) as the last evaluation left them; *ndiag and
+    // *moist describe the law (D may be NULL to ask for them alone)
+    virtual int launch_les_nodal(const double *Q, double t, double *D, int *ndiag, int *moist) = 0;
+
     // ---- ghost exchange without pack / unpack launches (HaloDev, cmdg_common.h) -------------
     // tables built at create from vmapsend / vmaprecv / the digested face table; *_ok = they
     // could be built (every node of vmapsend in an exterior element, every ghost node received
@@ -606,11 +611,12 @@ inline int object_call_done(cmdg_handle h, int r, const std::string &err)
 }
 
 // what a plug-in and the library must agree on (cmdg_load_plugin): the layout of the engine base
-// class and of the descriptor, folded into one number
+// class and of the descriptor, folded into one number (plus the revision of its virtual interface,
+// which no size shows: 1 = launch_les_nodal)
 inline unsigned long engine_abi_stamp()
 {
     return (unsigned long)sizeof(EngineBase) * 1000003ul + (unsigned long)sizeof(cmdg_desc) * 10007ul +
-           (unsigned long)sizeof(RhsCtx) * 101ul + (unsigned long)sizeof(cmdg_rhs_hooks);
+           (unsigned long)sizeof(RhsCtx) * 101ul + (unsigned long)sizeof(cmdg_rhs_hooks) + 1ul * 100000007ul;
 }
 
 }  // namespace cmdg

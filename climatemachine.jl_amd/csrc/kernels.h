@@ -1622,4 +1622,38 @@ __global__ __launch_bounds__((KDims<NQ, NQV>::Np <= 128 ? 128 : 256)) void k_cou
     if (tid == 0) out[e] = sred[0];
 }
 
+// ---- AtmosLESDefault diagnostics, nodal pass (src/Diagnostics/atmos_les_default.jl:629-636) ----
+// compute_thermo! and the two sub-grid terms at every node of the real elements: one thread per
+// node, D[n, s, e] in the layout of the auxiliary state; the level reductions that read D are
+// law-independent (diagnostics.hip).  has_gf = 0: the handle forms no gradient flux (its diffusivity
+// is zero) and the law is handed zeros.
+template <class P, int NQ, int NQV>
+__global__ __launch_bounds__(256) void k_les_nodal(typename P::Params prm, const double *__restrict__ Q,
+                                                   const double *__restrict__ aux, const double *__restrict__ gf,
+                                                   int has_gf, double t, int64_t nreal, double *__restrict__ D)
+{
+    constexpr int Np = KDims<NQ, NQV>::Np, ND = P::NDIAG;
+    const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t e = I / Np;
+    const int n = (int)(I - e * Np);
+    if (e >= nreal) return;
+    Vec<P::NS> lQ;
+    Vec<P::NAUX> lA;
+    Vec<P::NGF> lG;
+    Vec<ND> d;
+    load_state<P::NS, Np>(lQ, Q, n, e);
+    load_state<P::NAUX, Np>(lA, aux, n, e);
+    if constexpr (P::NGF > 0) {
+        if (has_gf) {
+            load_gf<P, Np>(lG, gf, n, e);
+        } else {
+#pragma unroll
+            for (int s = 0; s < P::NGF; ++s) lG[s] = 0.0;
+        }
+    }
+    P::les_diagnostics(prm, d, lQ, lA, lG, t);
+#pragma unroll
+    for (int s = 0; s < ND; ++s) D[n + (int64_t)Np * (s + (int64_t)ND * e)] = d[s];
+}
+
 }  // namespace cmdg

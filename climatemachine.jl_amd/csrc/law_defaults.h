@@ -141,6 +141,23 @@ struct LawDefaults {
         return 0.0;
     }
 
+    // ---- AtmosLESDefault diagnostics (diagnostics.h; src/Diagnostics/thermo.jl:33-68) ------------
+    // les_diagnostics(prm, D, Q, aux, gf, t) fills the NDIAG nodal columns of compute_thermo! and the
+    // two sub-grid terms; LES_MOIST: the law carries the EquilMoist columns and sums;
+    // les_diagnostics_active(prm): this parameter block is an LES configuration.  cmdg_les_* refuse a
+    // law without HAS_LES_DIAGNOSTICS.
+    static constexpr bool HAS_LES_DIAGNOSTICS = false, LES_MOIST = false;
+    static constexpr int NDIAG = 0;
+    template <class... A>
+    __host__ __device__ static bool les_diagnostics_active(A &&...)
+    {
+        return true;
+    }
+    template <class... A>
+    __device__ static void les_diagnostics(A &&...)
+    {
+    }
+
     // ---- first-order numerical flux --------------------------------------------------------------
     // A law may offer flux_first_order and wavespeed of one state in one call, flux_wavespeed(prm, F,
     // ws, n, Q, aux, t, direction): both need the same thermodynamic state, and the moist law's costs

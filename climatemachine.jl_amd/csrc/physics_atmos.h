@@ -210,6 +210,36 @@ struct DryAtmos : LawDefaults {
         if constexpr (ORIENT) aux_face[OPHI] = aux_cell[OPHI] + m.grav * dz / 2;
     }
 
+    // ---- AtmosLESDefault diagnostics: compute_thermo! of a DryModel (src/Diagnostics/thermo.jl:33-49)
+    // and the sub-grid enthalpy flux of atmos_les_default_simple_sums! (atmos_les_default.jl:168-170).
+    // Columns temp, pres, theta_dry, e_int, h_tot, h_int, d_h_tot[3].  The LES configurations: an
+    // orientation that is flat, no hyperdiffusion; MoistAtmos::les_diagnostics reduces to this at
+    // q_tot = 0.
+    static constexpr bool HAS_LES_DIAGNOSTICS = ORIENT && !HYPER && !LAWNF;
+    static constexpr int NDIAG = 7;
+    __host__ __device__ static bool les_diagnostics_active(const Params &m) { return m.orient == 1; }
+    __device__ static void les_diagnostics(const Params &m, double *D, const double *Q, const double *aux,
+                                           const double *gf, double)
+    {
+        const double rho = Q[0];
+        const double e_tot = Q[4] / rho;
+        const double e_int = internal_energy(m, Q, aux);
+        const double T = air_T(m, e_int);
+        const double p = air_p(m, T, rho);
+        const double exner = pow(p / m.MSLP, m.kappa);
+        const double RT = m.R_d * T;
+        D[0] = T;
+        D[1] = p;
+        D[2] = T / exner;
+        D[3] = e_int;
+        D[4] = e_tot + RT;
+        D[5] = e_int + RT;
+        double nu[3], tau[9];
+        turbulence_tensors(m, Q, gf, aux, nu, tau);
+        const double Dt = nu[2] * m.invPr;
+        D[6] = (-Dt) * gf[2];
+    }
+
     // ---- local Courant numbers: src/Atmos/Model/courant.jl:12-83 ------------------------
     // the manufactured-solution pieces (source, InitStateBC) exist in the plain variant only
     static constexpr bool MMS_VARIANT = !ORIENT && !REF && !HYPER && !SMAG && !LAWNF;

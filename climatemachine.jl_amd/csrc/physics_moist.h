@@ -246,6 +246,47 @@ struct MoistAtmos : LawDefaults {
         return ts.R_m / m.R_d * (ts.T / exner);
     }
 
+    // ---- AtmosLESDefault diagnostics: compute_thermo! (src/Diagnostics/thermo.jl:33-68) and the
+    // sub-grid terms of atmos_les_default_simple_sums! (atmos_les_default.jl:168-170, 218-219).
+    // Columns temp, pres, theta_dry, e_int, h_tot, h_int, d_h_tot[3] | q_liq, q_ice, q_vap, theta_vir,
+    // theta_liq_ice, has_condensate, d_q_tot[3].  The thermodynamic state is the one the nodal refresh
+    // of the last evaluation left (no second saturation adjustment); the potential temperatures
+    // restate Thermodynamics.jl's published formulas (parity of saturated values unpinned).  With
+    // q_tot = 0 the first seven are DryAtmos::les_diagnostics operation for operation.
+    static constexpr bool HAS_LES_DIAGNOSTICS = true, LES_MOIST = true;
+    static constexpr int NDIAG = 14;
+    __device__ static void les_diagnostics(const Params &m, double *D, const double *Q, const double *aux,
+                                           const double *gf, double)
+    {
+        Thermo ts;
+        thermo_state_refreshed(m, Q, aux, ts);
+        const double rho = Q[0];
+        const double e_tot = Q[4] / rho;
+        const double e_int = internal_energy(Q, aux);
+        const double p = air_pressure(ts, rho);
+        const double exner = pow(p / m.MSLP, ts.R_m / ts.cp_m);
+        const double th_dry = ts.T / exner;
+        const double RT = ts.R_m * ts.T;
+        D[0] = ts.T;
+        D[1] = p;
+        D[2] = th_dry;
+        D[3] = e_int;
+        D[4] = e_tot + RT;
+        D[5] = e_int + RT;
+        double nu[3], tau[9];
+        turbulence_tensors(m, Q, gf, aux, nu, tau);
+        const double Dt = nu[2] * m.invPr;
+        D[6] = (-Dt) * gf[2];
+        D[7] = ts.q_liq;
+        D[8] = ts.q_ice;
+        const double qv = ts.q_tot - ts.q_liq - ts.q_ice;
+        D[9] = qv > 0.0 ? qv : 0.0;
+        D[10] = ts.R_m / m.R_d * th_dry;
+        D[11] = th_dry * (1 - (m.LH_v0 * ts.q_liq + m.LH_s0 * ts.q_ice) / (ts.cp_m * ts.T));
+        D[12] = ts.q_liq + ts.q_ice > 0.0 ? 1.0 : 0.0;
+        D[13] = (-Dt) * gf[3 + NGT + 2];
+    }
+
     // local Courant numbers of src/Atmos/Model/courant.jl:12-83 (kind 0 advective, 1
     // nondiffusive with the moist sound speed, 2 diffusive with the closure's viscosity)
     __device__ static double courant(const Params &m, int kind, const double *Q, const double *aux,

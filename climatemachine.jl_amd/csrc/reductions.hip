@@ -32,43 +32,6 @@ constexpr int NT = 256;      // threads per block, both stages
 constexpr int NW = NT / 64;  // waves per block
 constexpr int NB_MAX = 2048; // stage-1 blocks: 8 per CU on the 256 CUs of an MI355X
 
-struct DD {
-    double hi, lo;
-};
-
-// ---- error-free transformations ---------------------------------------------------------
-__host__ __device__ inline DD two_sum(double a, double b)
-{
-    const double s = a + b, bb = s - a;
-    return {s, (a - (s - bb)) + (b - bb)};
-}
-__host__ __device__ inline DD fast_two_sum(double a, double b)  // |a| >= |b|
-{
-    const double s = a + b;
-    return {s, b - (s - a)};
-}
-__device__ inline DD two_prod(double a, double b)
-{
-    const double p = a * b;
-    return {p, fma(a, b, -p)};
-}
-// accurate double-double addition (both components' errors carried)
-__device__ inline DD dd_add(DD a, DD b)
-{
-    DD s = two_sum(a.hi, b.hi);
-    const DD t = two_sum(a.lo, b.lo);
-    s.lo += t.hi;
-    s = fast_two_sum(s.hi, s.lo);
-    s.lo += t.lo;
-    return fast_two_sum(s.hi, s.lo);
-}
-// (hi + lo) * b; exact when lo == 0 (TwoProd)
-__device__ inline DD dd_mul_d(DD a, double b)
-{
-    DD p = two_prod(a.hi, b);
-    p.lo = fma(a.lo, b, p.lo);
-    return fast_two_sum(p.hi, p.lo);
-}
 // maximum / minimum that propagate a NaN in either argument (Julia's max / min)
 __host__ __device__ inline double nmax(double a, double b) { return (a > b || a != a) ? a : b; }
 __host__ __device__ inline double nmin(double a, double b) { return (a < b || a != a) ? a : b; }

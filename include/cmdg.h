@@ -1059,6 +1059,56 @@ int cmdg_mrigark_step_gmres(cmdg_handle slow, cmdg_handle slow_minus, cmdg_handl
                             cmdg_gmres_handle gmres, const cmdg_mrigark_desc *d, double *Q,
                             double *const *work, double t, double dt);
 
+/* ---- AtmosLESDefault diagnostics (src/Diagnostics/atmos_les_default.jl) ------------------------
+ * Density-weighted horizontal means, variances and vertical eddy fluxes per level of a stacked
+ * grid, plus the cloud statistics of the moist law, formed on the device.  Levels: L = Nqk *
+ * nvertelem, evk = Nqk (ev - 1) + k, element e = ev + (eh - 1) nvertelem (helpers.jl:6-28).  Served
+ * for the dry atmosphere law in its LES configurations (flat orientation, no hyperdiffusion) and
+ * the moist law; any other law, a grid that is not stacked and a vertical order of 0 are refused
+ * (CMDG_ERR_UNSUPPORTED / CMDG_ERR_INVALID with a message).
+ *
+ * Every level sum is accumulated in double-double from terms that are the correctly rounded double
+ * expressions the reference writes, partials are combined in a fixed order (work-group, then rank),
+ * and the returned sum is the double nearest to the double-double: two calls on the same input
+ * return the same bits.  The calls read aux.moisture and the gradient flux as the last evaluation
+ * of the handle left them: evaluate the handle at (Q, t) first where they must belong to Q. */
+/* out[4] = ndiag (nodal columns), nsimple (13 / 20), nho (11 / 21), nlevels */
+int cmdg_les_query(cmdg_handle h, int32_t nvertelem, int32_t *out);
+/* the nodal pass alone: D is a DEVICE array (ndiag, Np, nelem), its real elements are written.
+ * Columns: temp, pres, theta_dry, e_int, h_tot, h_int, d_h_tot[3]; the moist law adds q_liq, q_ice,
+ * q_vap, theta_vir, theta_liq_ice, has_condensate (0.0 / 1.0), d_q_tot[3].  Returns when D is ready. */
+int cmdg_les_nodal(cmdg_handle h, const double *Q, double t, double *D);
+/* atmos_collect_onetime (atmos_common.jl:12-38): HOST zvals[L] (x3 of the last node this rank
+ * visits on the level) and MH_z[L] (the level's sum of MH over all ranks).  Required once before
+ * cmdg_les_collect; a handle with an RCCL communicator combines across ranks (collective).
+ * omega: HOST, the Nqk quadrature weights of the vertical direction (grid.omega[end]) for the
+ * water paths, Mvert = omega_k JcV[1, k, ev, eh = 1] (:781-790); NULL: lwp and iwp come out 0. */
+int cmdg_les_init(cmdg_handle h, int32_t nvertelem, const double *omega, double *zvals, double *MH_z);
+/* HOST arrays of one collection, row-major; a NULL member is not written */
+typedef struct cmdg_les_result {
+    double *simple_sums;   /* (L, nsimple) the sums of atmos_les_default_simple_sums! */
+    double *simple_avgs;   /* (L, nsimple) ... / MH_z, and all but avg_rho / avg_rho */
+    double *ho_sums;       /* (L, nho) the sums of atmos_les_default_ho_sums! about simple_avgs */
+    double *ho_avgs;       /* (L, nho) ... / MH_z / avg_rho */
+    /* moist law only (untouched otherwise).  cloud_levels (L, 6): nodes with condensate, nodes,
+     * sum MH q_liq rho rho, sum MH q_ice rho rho, and those two / MH_z / avg_rho.  cloud_scalars
+     * [8]: cld_top, cld_base (NaN without condensate), cld_cover, lwp, iwp, node columns with
+     * condensate, node columns, 0. */
+    double *cloud_levels;
+    double *cloud_scalars;
+} cmdg_les_result;
+/* atmos_les_default_collect (:567-871) at (Q, t).  Without a communicator everything up to the final
+ * copy-out is enqueued on the compute stream; with an RCCL communicator the ranks' double-double
+ * partials are gathered and combined in rank order on every rank (collective).  Returns when the
+ * results are on the host. */
+int cmdg_les_collect(cmdg_handle h, const double *Q, double t, const cmdg_les_result *out);
+/* ... for handles connected with cmdg_comm_connect_local (handle i = rank i): zvals are rank 0's;
+ * Q: HOST array of n device arrays */
+int cmdg_group_les_init(cmdg_handle *handles, int32_t n, int32_t nvertelem, const double *omega, double *zvals,
+                        double *MH_z);
+int cmdg_group_les_collect(cmdg_handle *handles, int32_t n, const double *const *Q, double t,
+                           const cmdg_les_result *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -264,6 +264,10 @@ SYMBOLS = [
     ("cmdg_les_collect", C.c_int, [_vp, _vp, _d, C.POINTER(CmdgLesResult)]),
     ("cmdg_group_les_init", C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
     ("cmdg_group_les_collect", C.c_int, [_vp, _i32, _vp, _d, C.POINTER(CmdgLesResult)]),
+    ("cmdg_vector_gradients", C.c_int, [_vp, _vp, _vp]),
+    ("cmdg_vorticity", C.c_int, [_vp, _vp, _vp]),
+    ("cmdg_gcm_nodal", C.c_int, [_vp, _vp, _d, _vp, _vp]),
+    ("cmdg_interp_gcm_finish", C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
 ]
 
 _LIB = None

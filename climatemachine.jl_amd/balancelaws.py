@@ -32,6 +32,7 @@ PHYSICS_MOIST_ATMOS = 6
 PHYSICS_ATMOS_LINEAR_AG = 10
 PHYSICS_MOIST_LINEAR_AG = 11
 PHYSICS_ATMOS_LINEAR_ACOUSTIC = 13
+PHYSICS_VORTICITY = 15
 
 __all__ = [
     "EveryDirection", "HorizontalDirection", "VerticalDirection",
@@ -79,6 +80,23 @@ class PressureGradientModel:
 
     def init_state_auxiliary(self, grid):
         return self._p
+
+    def init_state_prognostic(self, grid, aux, t):
+        return np.zeros((grid.nelem, 3, grid.Np))
+
+
+class VorticityModel:
+    """``VorticityModel`` (src/Diagnostics/vorticity_balancelaw.jl): state ``Ω_bl`` (3), auxiliary
+    ``u`` (3, zero until the caller fills it); with the central first-order flux and ``beta = 0`` the
+    tendency is ``curl u`` in weak form.  Every boundary is the ``nothing`` condition."""
+    physics_id = PHYSICS_VORTICITY
+    ns, naux, ngrad, ngradflux, ngradlap, nhyper = 3, 3, 0, 0, 0, 0
+
+    def descriptor(self):
+        return np.zeros(16, dtype=np.int32), np.zeros(32)
+
+    def init_state_auxiliary(self, grid):
+        return np.zeros((grid.nelem, 3, grid.Np))
 
     def init_state_prognostic(self, grid, aux, t):
         return np.zeros((grid.nelem, 3, grid.Np))

@@ -38,6 +38,7 @@ const Law LAWS[] = {
     {CMDG_PHYSICS_ESDG_DRY_ATMOS, nullptr, counts_esdg_dryatmos},
     {CMDG_PHYSICS_ATMOS_LINEAR_ACOUSTIC, make_engine_atmos_acoustic, counts_atmos_acoustic},
     {CMDG_PHYSICS_ESDG_DRY_ATMOS_LINEAR_AG, make_engine_esdg_dryatmos_linear, counts_esdg_dryatmos_linear},
+    {CMDG_PHYSICS_VORTICITY, make_engine_vorticity, counts_vorticity},
 };
 const Law *find_law(int32_t physics_id)
 {

@@ -12,6 +12,10 @@
 // :815-846, so that the higher-order pass finds the finished averages of its level on the device.
 // No floating-point atomics; the slice length depends on the grid only: the same input gives the
 // same bits.
+//
+// AtmosGCMDefault diagnostics (src/Diagnostics/atmos_gcm_default.jl, diagnostic_fields.jl): the entries
+// cmdg_vector_gradients, cmdg_vorticity and cmdg_gcm_nodal at the end of this file; their kernels need
+// the order (and the nodal pass the law) and live in kernels.h, the finishing pass in interpolation.hip.
 #include <math.h>
 #include <string.h>
 
@@ -22,6 +26,7 @@
 
 #include "diagnostics.h"
 #include "engine_base.h"
+#include "kernels.h"
 #include "rccl.h"
 #include "reductions.h"
 
@@ -268,6 +273,22 @@ __global__ __launch_bounds__(64) void k_les_levels(const double *__restrict__ vg
     const int64_t elast = ev + (nhorz - 1) * nvert;
     zvals[evk] = vgeo[Nij * k + Nij - 1 + (int64_t)Np * (V_X3 + (int64_t)nvgeo * elast)];
     jcv[evk] = vgeo[Nij * k + (int64_t)Np * (V_JCV + (int64_t)nvgeo * ev)];
+}
+
+// vorticity_kernel! (diagnostic_fields.jl:382-396): vgrad (nreal, 9, Np) -> vort (nreal, 3, Np); n = nreal Np
+__global__ __launch_bounds__(256) void k_vorticity(const double *__restrict__ vgrad, double *__restrict__ vort,
+                                                   int Np, int64_t n)
+{
+    for (int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x; I < n; I += (int64_t)gridDim.x * 256) {
+        const int64_t e = I / Np;
+        const int node = (int)(I - e * Np);
+        double g[9], om[3];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) g[c] = vgrad[node + (int64_t)Np * (c + 9 * e)];
+        vorticity_node(g, om);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) vort[node + (int64_t)Np * (c + 3 * e)] = om[c];
+    }
 }
 
 // ---- per-engine state ---------------------------------------------------------------------------
@@ -576,6 +597,26 @@ int refuse_group_member(EngineBase *e, const char *who)
     return CMDG_OK;
 }
 
+// what the three GCM entries refuse before they ask the engine
+int gcm_refusals(EngineBase *e, const char *who)
+{
+    if (e->fv || e->NQV < 2)
+        return e->fail(CMDG_ERR_UNSUPPORTED, std::string(who) + ": a DGFVModel handle (vertical polynomial order "
+                                                                "0) has no vertical derivative matrix");
+    if (e->esdg) return e->fail(CMDG_ERR_UNSUPPORTED, std::string(who) + ": not served for an ESDGModel handle");
+    return CMDG_OK;
+}
+
+// the launch status, then the wait: the entries return when their output is ready
+int gcm_done(cmdg_handle h, const char *who)
+{
+    EngineBase *e = h->eng;
+    if (int r = e->launch_status(who)) return set_err(h, r);
+    if (hipStreamSynchronize(e->s_comp) != hipSuccess)
+        return set_err(h, e->fail(CMDG_ERR_HIP, std::string(who) + ": the kernel failed"));
+    return CMDG_OK;
+}
+
 }  // namespace
 
 void les_release(EngineBase *e)
@@ -692,6 +733,43 @@ int cmdg_group_les_collect(cmdg_handle *handles, int32_t n, const double *const 
     if (int r = pass_group(handles, n, PASS_SIMPLE, Q, t)) return gc.finish(r);
     if (int r = pass_group(handles, n, PASS_HO, Q, t)) return gc.finish(r);
     return gc.finish(copy_out(handles[0]->eng, state(handles[0]->eng), out));
+}
+
+// ---- AtmosGCMDefault diagnostics: VectorGradients, Vorticity, the nodal pass -----------------------
+// (the kernels need the order, and the nodal pass the law: kernels.h, launched by EngineT)
+int cmdg_vector_gradients(cmdg_handle h, const double *Q, double *vgrad)
+{
+    if (!h) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    EngineBase *e = h->eng;
+    if (!Q || !vgrad) return set_err(h, e->fail(CMDG_ERR_INVALID, "cmdg_vector_gradients: Q or vgrad is NULL"));
+    if (int r = gcm_refusals(e, "cmdg_vector_gradients")) return set_err(h, r);
+    if (int r = e->launch_vector_gradients(Q, vgrad)) return set_err(h, r);
+    return gcm_done(h, "cmdg_vector_gradients");
+}
+
+int cmdg_vorticity(cmdg_handle h, const double *vgrad, double *vort)
+{
+    if (!h) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    EngineBase *e = h->eng;
+    if (!vgrad || !vort) return set_err(h, e->fail(CMDG_ERR_INVALID, "cmdg_vorticity: vgrad or vort is NULL"));
+    if (int r = gcm_refusals(e, "cmdg_vorticity")) return set_err(h, r);
+    const int64_t n = e->nreal * e->Np;
+    if (n > 0)
+        hipLaunchKernelGGL(k_vorticity, dim3(nblocks(n)), dim3(256), 0, e->s_comp, vgrad, vort, e->Np, n);
+    return gcm_done(h, "cmdg_vorticity");
+}
+
+int cmdg_gcm_nodal(cmdg_handle h, const double *Q, double t, double *G, double *u)
+{
+    if (!h) return CMDG_ERR_INVALID;
+    DevGuard guard_(h->eng);
+    EngineBase *e = h->eng;
+    if (!Q || !G || !u) return set_err(h, e->fail(CMDG_ERR_INVALID, "cmdg_gcm_nodal: Q, G or u is NULL"));
+    if (int r = gcm_refusals(e, "cmdg_gcm_nodal")) return set_err(h, r);
+    if (int r = e->launch_gcm_nodal(Q, t, G, u)) return set_err(h, r);
+    return gcm_done(h, "cmdg_gcm_nodal");
 }
 
 }  // extern "C"

@@ -196,6 +196,34 @@ struct EngineT : EngineBase {
                                               "diagnostics (the dry and the moist atmosphere laws do)");
         }
     }
+    int launch_vector_gradients(const double *Q, double *vgrad) override
+    {
+        if constexpr (P::STATE_RHO_RHOU && NQV_ >= 2) {
+            if (nreal > 0)
+                hipLaunchKernelGGL((k_vector_gradients<NQ_, NQV_>), dim3((unsigned)nreal), dim3(KDims<NQ_, NQV_>::Np),
+                                   0, s_comp, Q, P::NS, g.vgeo, g.nvgeo, g.D, g.Dv, vgrad);
+            return CMDG_OK;
+        } else {
+            return fail(CMDG_ERR_UNSUPPORTED, "VectorGradients: the state of this balance law does not begin rho, "
+                                              "rho u[3] (the dry and the moist atmosphere laws' do)");
+        }
+    }
+    int launch_gcm_nodal(const double *Q, double, double *G, double *u) override
+    {
+        if constexpr (P::HAS_GCM_DIAGNOSTICS && NQV_ >= 2) {
+            if (nreal > 0)
+                hipLaunchKernelGGL((k_gcm_nodal<P, NQ_, NQV_>), dim3((unsigned)nreal), dim3(KDims<NQ_, NQV_>::Np), 0,
+                                   s_comp, prm, Q, aux, g.vgeo, g.nvgeo, g.D, g.Dv, G, u);
+            return CMDG_OK;
+        } else if constexpr (P::LES_MOIST) {
+            return fail(CMDG_ERR_UNSUPPORTED, "AtmosGCMDefault diagnostics: the moist columns are not built (the "
+                                              "moist law here is the flat LES configuration, and the group "
+                                              "requires a cubed sphere)");
+        } else {
+            return fail(CMDG_ERR_UNSUPPORTED, "AtmosGCMDefault diagnostics: this balance law defines no GCM "
+                                              "diagnostics (the dry atmosphere law with an orientation does)");
+        }
+    }
     bool has_update_aux() const override { return P::HAS_UPDATE_AUX && P::update_aux_active(prm); }
     bool law_needs_gradflux() const override { return P::needs_gradflux(prm); }
     bool gf_node_major() const override { return cmdg::gf_node_major<P>; }

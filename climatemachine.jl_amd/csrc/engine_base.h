@@ -340,6 +340,11 @@ struct EngineBase {
     // (ndiag, Np, nreal), from (Q, aux, gradient flux) as the last evaluation left them; *ndiag and
     // *moist describe the law (D may be NULL to ask for them alone)
     virtual int launch_les_nodal(const double *Q, double t, double *D, int *ndiag, int *moist) = 0;
+    // cmdg_vector_gradients: d u_c / d x_m of u = rho u / rho on the real elements, vgrad (nreal, 9, Np)
+    virtual int launch_vector_gradients(const double *Q, double *vgrad) = 0;
+    // cmdg_gcm_nodal: the nodal pass of the AtmosGCMDefault group (kernels.h k_gcm_nodal) on the real
+    // elements: G (nelem, 14, Np) and the velocity u (nelem, 3, Np)
+    virtual int launch_gcm_nodal(const double *Q, double t, double *G, double *u) = 0;
 
     // ---- ghost exchange without pack / unpack launches (HaloDev, cmdg_common.h) -------------
     // tables built at create from vmapsend / vmaprecv / the digested face table; *_ok = they
@@ -612,11 +617,11 @@ inline int object_call_done(cmdg_handle h, int r, const std::string &err)
 
 // what a plug-in and the library must agree on (cmdg_load_plugin): the layout of the engine base
 // class and of the descriptor, folded into one number (plus the revision of its virtual interface,
-// which no size shows: 1 = launch_les_nodal)
+// which no size shows: 1 = launch_les_nodal, 2 = launch_vector_gradients and launch_gcm_nodal)
 inline unsigned long engine_abi_stamp()
 {
     return (unsigned long)sizeof(EngineBase) * 1000003ul + (unsigned long)sizeof(cmdg_desc) * 10007ul +
-           (unsigned long)sizeof(RhsCtx) * 101ul + (unsigned long)sizeof(cmdg_rhs_hooks) + 1ul * 100000007ul;
+           (unsigned long)sizeof(RhsCtx) * 101ul + (unsigned long)sizeof(cmdg_rhs_hooks) + 2ul * 100000007ul;
 }
 
 }  // namespace cmdg

@@ -20,4 +20,7 @@ int interp_project(const InterpObj *o, double *v, int nstate, const int32_t *uvw
                    std::string &err);
 int interp_scatter(const InterpObj *const *o, int n, const double *const *v, int nstate, double *fiv,
                    hipStream_t st, bool wait, std::string &err);
+// the finishing pass of the AtmosGCMDefault group: projection, quotients and scatter of the 13 variables
+int interp_gcm_finish(const InterpObj *const *o, int n, const double *const *vG, const double *const *vB,
+                      double *fiv, hipStream_t st, bool wait, std::string &err);
 }  // namespace cmdg

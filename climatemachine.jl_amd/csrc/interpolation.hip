@@ -107,22 +107,66 @@ __global__ __launch_bounds__(NT) void k_interpolate(const Work *__restrict__ wor
     }
 }
 
+// project_cubed_sphere! at one point (:1332-1414): the unit vectors of the point's latitude and longitude
+struct LatLong {
+    double cl, sl, co, so;
+    __device__ LatLong(double lat_deg, double long_deg)
+    {
+        const double deg2rad = M_PI / 180.0;
+        const double la = lat_deg * deg2rad, lo = long_deg * deg2rad;
+        cl = cos(la), sl = sin(la), co = cos(lo), so = sin(lo);
+    }
+    // Cartesian (x, y, z) -> components along longitude, latitude, radius
+    __device__ __forceinline__ void project(double x, double y, double z, double &vlon, double &vlat,
+                                            double &vrad) const
+    {
+        vrad = x * cl * co + y * cl * so + z * sl;
+        vlat = -x * sl * co - y * sl * so + z * cl;
+        vlon = -x * so + y * co;
+    }
+};
+
 __global__ void k_project(double *__restrict__ v, const int32_t *__restrict__ ilong, const int32_t *__restrict__ ilat,
                           const double *__restrict__ long_grd, const double *__restrict__ lat_grd, int64_t npoints,
                           int cu, int cv, int cw)
 {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= npoints) return;
-    const double deg2rad = M_PI / 180.0;
-    const double la = lat_grd[ilat[p] - 1] * deg2rad, lo = long_grd[ilong[p] - 1] * deg2rad;
-    const double cl = cos(la), sl = sin(la), co = cos(lo), so = sin(lo);
-    const double x = v[p + cu * npoints], y = v[p + cv * npoints], z = v[p + cw * npoints];
-    const double vrad = x * cl * co + y * cl * so + z * sl;
-    const double vlat = -x * sl * co - y * sl * so + z * cl;
-    const double vlon = -x * so + y * co;
+    const LatLong ll(lat_grd[ilat[p] - 1], long_grd[ilong[p] - 1]);
+    double vlon, vlat, vrad;
+    ll.project(v[p + cu * npoints], v[p + cv * npoints], v[p + cw * npoints], vlon, vlat, vrad);
     v[p + cu * npoints] = vlon;
     v[p + cv * npoints] = vlat;
     v[p + cw * npoints] = vrad;
+}
+
+// The finishing pass of the AtmosGCMDefault group (atmos_gcm_default.jl:375-379, :150-165): vG (14,
+// npoints) the interpolated nodal array (kernels.h GCM_NCOL), vB (3, npoints) the interpolated
+// VorticityModel tendency.  Projects rho u, Omega and Omega_bl, forms u, v, w = rho u_i / rho_i and et =
+// rho e_i / rho_i and stores u, v, w, rho, temp, pres, thd, et, ei, ht, hi, vort, vort2 as k_scatter stores.
+constexpr int GCM_NIN = 14, GCM_NOUT = 13;
+__global__ void k_gcm_finish(double *__restrict__ fiv, const double *__restrict__ vG, const double *__restrict__ vB,
+                             const int32_t *__restrict__ i1, const int32_t *__restrict__ i2,
+                             const int32_t *__restrict__ i3, const double *__restrict__ long_grd,
+                             const double *__restrict__ lat_grd, int64_t npoints, int64_t n1, int64_t n2, int64_t n3)
+{
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npoints) return;
+    const LatLong ll(lat_grd[i2[p] - 1], long_grd[i1[p] - 1]);
+    double g[GCM_NIN];
+#pragma unroll
+    for (int s = 0; s < GCM_NIN; ++s) g[s] = vG[p + npoints * s];
+    double mlon, mlat, mrad, olon, olat, orad, blon, blat, brad;
+    ll.project(g[1], g[2], g[3], mlon, mlat, mrad);
+    ll.project(g[11], g[12], g[13], olon, olat, orad);
+    ll.project(vB[p], vB[p + npoints], vB[p + 2 * npoints], blon, blat, brad);
+    const double rho = g[0];
+    const double out[GCM_NOUT] = {mlon / rho, mlat / rho, mrad / rho, rho,  g[5], g[6], g[7],
+                                  g[4] / rho, g[8],       g[9],       g[10], orad, brad};
+    const int64_t at = (i1[p] - 1) + n1 * ((i2[p] - 1) + n2 * (int64_t)(i3[p] - 1));
+    const int64_t ntot = n1 * n2 * n3;
+#pragma unroll
+    for (int s = 0; s < GCM_NOUT; ++s) fiv[at + ntot * s] = out[s];
 }
 
 __global__ void k_scatter(double *__restrict__ fiv, const double *__restrict__ v, const int32_t *__restrict__ i1,
@@ -351,6 +395,32 @@ int interp_scatter(const InterpObj *const *o, int n, const double *const *v, int
     return finish(st, wait, "cmdg_interp_scatter", err);
 }
 
+int interp_gcm_finish(const InterpObj *const *o, int n, const double *const *vG, const double *const *vB, double *fiv,
+                      hipStream_t st, bool wait, std::string &err)
+{
+    for (int r = 0; r < n; ++r) {
+        if (!o[r]->lat) {
+            err = "cmdg_interp_gcm_finish: object " + std::to_string(r) + " has no latitude-longitude grid (a brick)";
+            return CMDG_ERR_INVALID;
+        }
+        if (o[r]->n1 != o[0]->n1 || o[r]->n2 != o[0]->n2 || o[r]->n3 != o[0]->n3 || o[r]->dev != o[0]->dev) {
+            err = "cmdg_interp_gcm_finish: object " + std::to_string(r) + " has another output grid or device";
+            return CMDG_ERR_INVALID;
+        }
+        if (o[r]->npoints > 0 && (!vG[r] || !vB[r])) {
+            err = "cmdg_interp_gcm_finish: no arrays for object " + std::to_string(r);
+            return CMDG_ERR_INVALID;
+        }
+    }
+    for (int r = 0; r < n; ++r) {
+        if (o[r]->npoints == 0) continue;
+        hipLaunchKernelGGL(k_gcm_finish, dim3((unsigned)((o[r]->npoints + 255) / 256)), dim3(256), 0, st, fiv, vG[r],
+                           vB[r], o[r]->idx[0], o[r]->idx[1], o[r]->idx[2], o[r]->lon, o[r]->lat, o[r]->npoints,
+                           o[r]->n1, o[r]->n2, o[r]->n3);
+    }
+    return finish(st, wait, "cmdg_interp_gcm_finish", err);
+}
+
 }  // namespace cmdg
 
 // ---- the C entries ------------------------------------------------------------------------------
@@ -425,6 +495,22 @@ int cmdg_interp_scatter(cmdg_handle h, const cmdg_interp *its, int32_t n, const 
         return object_call_done(h, CMDG_ERR_INVALID, "cmdg_interp_scatter: the objects live on another device than the handle");
     ObjectDevice dev_(interp_device(o[0]));
     return object_call_done(h, interp_scatter(o, n, v, nstate, fiv, h ? h->eng->s_comp : nullptr, !h, err), err);
+}
+
+int cmdg_interp_gcm_finish(cmdg_handle h, const cmdg_interp *its, int32_t n, const double *const *vG,
+                           const double *const *vB, double *fiv)
+{
+    if (!its || !vG || !vB || !fiv || n < 1) return CMDG_ERR_INVALID;
+    for (int i = 0; i < n; ++i)
+        if (!its[i]) return CMDG_ERR_INVALID;
+    const InterpObj *const *o = reinterpret_cast<const InterpObj *const *>(its);
+    std::optional<DevGuard> guard_;
+    if (h) guard_.emplace(h->eng);
+    std::string err;
+    if (h && h->eng->dev != interp_device(o[0]))
+        return object_call_done(h, CMDG_ERR_INVALID, "cmdg_interp_gcm_finish: the objects live on another device than the handle");
+    ObjectDevice dev_(interp_device(o[0]));
+    return object_call_done(h, interp_gcm_finish(o, n, vG, vB, fiv, h ? h->eng->s_comp : nullptr, !h, err), err);
 }
 
 }  // extern "C"

@@ -158,6 +158,17 @@ struct LawDefaults {
     {
     }
 
+    // ---- AtmosGCMDefault diagnostics (src/Diagnostics/atmos_gcm_default.jl, diagnostic_fields.jl) ---
+    // STATE_RHO_RHOU: the prognostic state begins rho, rho u[3], so that VectorGradients / Vorticity can
+    // form u = rho u / rho (cmdg_vector_gradients refuses any other law).  HAS_GCM_DIAGNOSTICS:
+    // gcm_thermo(prm, d, Q, aux) fills temp, pres, theta_dry, e_int, h_tot, h_int of compute_thermo!
+    // (thermo.jl:33-44); cmdg_gcm_nodal refuses a law without it.
+    static constexpr bool STATE_RHO_RHOU = false, HAS_GCM_DIAGNOSTICS = false;
+    template <class... A>
+    __device__ static void gcm_thermo(A &&...)
+    {
+    }
+
     // ---- first-order numerical flux --------------------------------------------------------------
     // A law may offer flux_first_order and wavespeed of one state in one call, flux_wavespeed(prm, F,
     // ws, n, Q, aux, t, direction): both need the same thermodynamic state, and the moist law's costs

@@ -22,6 +22,7 @@ EngineBase *make_engine_moist_linear(const cmdg_desc *d, std::string &err);
 EngineBase *make_engine_atmos_acoustic(const cmdg_desc *d, std::string &err);
 EngineBase *make_engine_esdg(const cmdg_desc *d, const cmdg_esdg_desc *ed, std::string &err);
 EngineBase *make_engine_esdg_dryatmos_linear(const cmdg_desc *d, std::string &err);
+EngineBase *make_engine_vorticity(const cmdg_desc *d, std::string &err);
 
 // out: num_state_conservative, auxiliary, gradient, gradient_flux, gradient_laplacian, hyperdiffusive
 int counts_advdiff(const int32_t *iparam, int32_t out[6]);
@@ -38,6 +39,7 @@ int counts_moist_linear(const int32_t *iparam, int32_t out[6]);
 int counts_atmos_acoustic(const int32_t *iparam, int32_t out[6]);
 int counts_esdg_dryatmos(const int32_t *iparam, int32_t out[6]);
 int counts_esdg_dryatmos_linear(const int32_t *iparam, int32_t out[6]);
+int counts_vorticity(const int32_t *iparam, int32_t out[6]);
 int host_constants_atmos(const int32_t *iparam, const double *dparam, double out[7]);
 
 }  // namespace cmdg

@@ -221,6 +221,16 @@ struct DryAtmos : LawDefaults {
     __device__ static void les_diagnostics(const Params &m, double *D, const double *Q, const double *aux,
                                            const double *gf, double)
     {
+        thermo_columns(m, D, Q, aux);
+        double nu[3], tau[9];
+        turbulence_tensors(m, Q, gf, aux, nu, tau);
+        const double Dt = nu[2] * m.invPr;
+        D[6] = (-Dt) * gf[2];
+    }
+    // compute_thermo! of a DryModel: temp, pres, theta_dry, e_int, h_tot, h_int (thermo.jl:33-44); the
+    // one place the six expressions are written, for the LES and the GCM groups
+    __device__ static void thermo_columns(const Params &m, double *D, const double *Q, const double *aux)
+    {
         const double rho = Q[0];
         const double e_tot = Q[4] / rho;
         const double e_int = internal_energy(m, Q, aux);
@@ -234,10 +244,15 @@ struct DryAtmos : LawDefaults {
         D[3] = e_int;
         D[4] = e_tot + RT;
         D[5] = e_int + RT;
-        double nu[3], tau[9];
-        turbulence_tensors(m, Q, gf, aux, nu, tau);
-        const double Dt = nu[2] * m.invPr;
-        D[6] = (-Dt) * gf[2];
+    }
+
+    // ---- AtmosGCMDefault diagnostics (src/Diagnostics/atmos_gcm_default.jl): the same six columns,
+    // for every configuration with an orientation (a reference state or hyperdiffusion do not enter)
+    static constexpr bool STATE_RHO_RHOU = true;
+    static constexpr bool HAS_GCM_DIAGNOSTICS = ORIENT;
+    __device__ static void gcm_thermo(const Params &m, double *D, const double *Q, const double *aux)
+    {
+        thermo_columns(m, D, Q, aux);
     }
 
     // ---- local Courant numbers: src/Atmos/Model/courant.jl:12-83 ------------------------

@@ -52,6 +52,7 @@ struct MoistAtmos : LawDefaults {
     // construction (source)
     static constexpr bool HAS_UPDATE_AUX = true, FUSE_UPDATE_AUX = false, HAS_SOURCE = true;
     static constexpr bool HAS_COURANT = true;
+    static constexpr bool STATE_RHO_RHOU = true;  // (VectorGradients; the GCM group's moist columns are not built)
     static constexpr int NUPD = 4;
     __host__ __device__ static constexpr int upd_aux(int i) { return OMOIST + i; }
     // auxiliary fields the interface kernels read on both sides: Phi, grad Phi, ref p, ref rho,

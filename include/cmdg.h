@@ -89,7 +89,12 @@ enum {
      * CMDG_PHYSICS_ESDG_DRY_ATMOS model with a reference state: an ordinary DGModel law (cmdg_create)
      * on that model's parameter block and 8-column auxiliary array; N = 3, 4; Rusanov or central
      * first-order flux */
-    CMDG_PHYSICS_ESDG_DRY_ATMOS_LINEAR_AG = 14
+    CMDG_PHYSICS_ESDG_DRY_ATMOS_LINEAR_AG = 14,
+    /* VorticityModel (src/Diagnostics/vorticity_balancelaw.jl): state Omega_bl (3), auxiliary u (3)
+     * filled by the caller, first-order flux the antisymmetric matrix of u, every boundary tag the
+     * `nothing` condition; with CMDG_CENTRAL_FIRST_ORDER and beta = 0 the tendency is curl u in weak
+     * form.  N = 2..6, one order in every direction */
+    CMDG_PHYSICS_VORTICITY = 15
 };
 
 /* Construction record: the fields of `DGModel(balance_law, grid, nf1, nf2, nfgrad;
@@ -661,6 +666,15 @@ int cmdg_interp_project(cmdg_handle h, cmdg_interp it, double *v, int32_t nstate
  * arrays of n objects / device arrays.  Gathering across processes is the caller's. */
 int cmdg_interp_scatter(cmdg_handle h, const cmdg_interp *its, int32_t n, const double *const *v,
                         int32_t nstate, double *fiv);
+/* the finishing pass of the AtmosGCMDefault group (atmos_gcm_default.jl:375-379, :150-165) for the n
+ * ranks of one process.  vG[r] (14, npoints_r) is the interpolated nodal array G of cmdg_gcm_nodal,
+ * vB[r] (3, npoints_r) the interpolated VorticityModel tendency; neither is changed.  The triples rho u,
+ * Omega and Omega_bl are projected with the expressions of cmdg_interp_project, u, v, w = rho u_i /
+ * rho_i and et = rho e_i / rho_i are formed, and the 13 variables u, v, w, rho, temp, pres, thd, et,
+ * ei, ht, hi, vort, vort2 are stored through the index triples: fiv is (n1, n2, n3, 13) column-major.
+ * The objects must carry a latitude-longitude grid. */
+int cmdg_interp_gcm_finish(cmdg_handle h, const cmdg_interp *its, int32_t n, const double *const *vG,
+                           const double *const *vB, double *fiv);
 
 /* ---- direct stiffness summation (src/Numerics/Mesh/DSS.jl) --------------------------------------
  * dss!(Q, grid) makes a DG field single-valued at the nodes elements share: every copy of a shared
@@ -1108,6 +1122,23 @@ int cmdg_group_les_init(cmdg_handle *handles, int32_t n, int32_t nvertelem, cons
                         double *MH_z);
 int cmdg_group_les_collect(cmdg_handle *handles, int32_t n, const double *const *Q, double t,
                            const cmdg_les_result *out);
+
+/* ---- AtmosGCMDefault diagnostics (src/Diagnostics/atmos_gcm_default.jl, diagnostic_fields.jl) ---
+ * Served for cmdg_create handles of laws whose state begins rho, rho u[3] (the dry and the moist
+ * atmosphere); any other law, a DGFVModel handle (vertical order 0) and an ESDGModel handle are
+ * refused with CMDG_ERR_UNSUPPORTED and the reason.  Arrays are DEVICE arrays in the layout of a
+ * state; the calls return when their output is ready.
+ * VectorGradients(dg, Q): vgrad (Np, 9, nreal), columns d1 u1, d2 u1, d3 u1, d1 u2, ... of u = rho u /
+ * rho, with the reference's arithmetic (every sum left to right over rounded products). */
+int cmdg_vector_gradients(cmdg_handle h, const double *Q, double *vgrad);
+/* Vorticity(dg, vgrad): vort (Np, 3, nreal) = (d2 u3 - d3 u2, d3 u1 - d1 u3, d1 u2 - d2 u1) */
+int cmdg_vorticity(cmdg_handle h, const double *vgrad, double *vort);
+/* the nodal pass of the group in one launch: G (Np, 14, nelem) = rho, rho u[3], rho e | temp, pres,
+ * theta_dry, e_int, h_tot, h_int of compute_thermo! (thermo.jl:33-44) | Omega[3], and u (Np, 3, nelem),
+ * the auxiliary array of the group's CMDG_PHYSICS_VORTICITY handle; real elements are written.  Bit for
+ * bit the columns of the separate calls.  The dry atmosphere law with an orientation; the moist law
+ * is refused (its columns are not built). */
+int cmdg_gcm_nodal(cmdg_handle h, const double *Q, double t, double *G, double *u);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,11 @@ Phi(3)] [, ref rho, p, T, rho*e, rho*q_tot, rho*q_liq, rho*q_ice] [, Delta] , th
 air_T``; gradient ``u(3), h_tot [, u_h(3), h_tot]``; gradient flux ``grad h_tot(3),
 S(6)``; gradient-laplacian ``u_h(3), h_tot``; hyperdiffusive ``nu grad^3 u_h (9), nu
 grad^3 h_tot (3)``.
+
+With ``tracers=NTracers(delta_chi)`` (``src/Atmos/Model/tracers.jl``, ``tendencies_tracers.jl``,
+``bc_tracer.jl``) the ``NT`` tracers follow every other component: prognostic ``rho*chi[NT]``,
+auxiliary ``delta_chi[NT]`` after ``theta_v, air_T``, gradient ``chi[NT]`` last, gradient flux
+``grad chi`` (3 x NT, three consecutive columns per tracer) last.
 """
 import numpy as np
 
@@ -29,7 +34,7 @@ from .balancelaws import (PHYSICS_ATMOS_LINEAR_ACOUSTIC, PHYSICS_ATMOS_LINEAR_AG
                           PHYSICS_MOIST_ATMOS, PHYSICS_MOIST_LINEAR_AG)
 from .mesh import grids as G
 
-__all__ = ["PlanetParameters", "DryAtmosModel", "IsentropicVortexSetup", "HeldSuarezSetup",
+__all__ = ["PlanetParameters", "DryAtmosModel", "NTracers", "IsentropicVortexSetup", "HeldSuarezSetup",
            "DecayingTemperatureProfile", "DryAdiabaticProfile", "RisingBubbleSetup",
            "CourantTestSetup", "MMSSetup", "IsothermalProfile", "AtmosAcousticGravityLinearModel",
            "IsentropicVortexReferenceState", "AtmosAcousticLinearModel", "HBFVReconstruction",
@@ -237,7 +242,13 @@ class CourantTestSetup:
 
 
 class HeldSuarezSetup:
-    """``init_heldsuarez!`` (experiments/AtmosGCM/heldsuarez.jl:47-104)."""
+    """``init_heldsuarez!`` (experiments/AtmosGCM/heldsuarez.jl:47-104).  On a model with tracers it
+    adds the experiment's dummy initialisation ``rho chi[k] = k`` (:99-100, ``k`` counted from one);
+    ``HeldSuarezSetup.tracers(n)`` is the model to go with it, ``delta_chi[k] = k`` (:184-186)."""
+
+    @staticmethod
+    def tracers(number_of_tracers):
+        return NTracers([float(k) for k in range(1, int(number_of_tracers) + 1)]) if number_of_tracers else None
 
     def __init__(self, ps):
         self.ps = ps
@@ -274,6 +285,8 @@ class HeldSuarezSetup:
         e_kin = 0.5 * (u[0] * u[0] + u[1] * u[1] + u[2] * u[2])
         rho = aux[:, law.off_ref + 0, :]
         rhoe = aux[:, law.off_ref + 3, :] + rho * e_kin
+        if getattr(law, "ntracers", 0):
+            return rho, [rho * u[0], rho * u[1], rho * u[2]], rhoe, [k + 0.0 * rho for k in range(1, law.ntracers + 1)]
         return rho, [rho * u[0], rho * u[1], rho * u[2]], rhoe
 
 
@@ -282,6 +295,24 @@ SRC_GRAVITY, SRC_CORIOLIS, SRC_HELD_SUAREZ, SRC_MMS = 1, 2, 4, 8
 # AtmosBC() default (Impenetrable(FreeSlip), Insulating); InitStateBC (bc_initstate.jl) with the
 # manufactured solution of MMSSetup
 BC_NONE, BC_ATMOS_DEFAULT, BC_INIT_STATE_MMS = 0, 1, 2
+
+
+MAX_TRACERS = 8
+
+
+class NTracers:
+    """``NTracers{N, FT}(delta_chi)`` (src/Atmos/Model/tracers.jl:111-125): ``N = len(delta_chi)``
+    passive tracers ``rho chi[k]``, advected with ``u`` and diffused with ``delta_chi[k] D_t``, the
+    turbulence closure's diffusivity scaled per tracer; ``ImpermeableTracer`` on every boundary."""
+
+    def __init__(self, delta_chi):
+        self.delta_chi = tuple(float(x) for x in np.atleast_1d(np.asarray(delta_chi, dtype=np.float64)))
+        if not 1 <= len(self.delta_chi) <= MAX_TRACERS:
+            raise ValueError("NTracers: 1 to %d tracers (got %d); no tracers is tracers=None"
+                             % (MAX_TRACERS, len(self.delta_chi)))
+
+    def __len__(self):
+        return len(self.delta_chi)
 
 
 class DryAtmosModel:
@@ -294,7 +325,13 @@ class DryAtmosModel:
                  subtract_off=True, viscosity=0.0, dynamic_viscosity=False,
                  hyperdiffusion_timescale=None, sources=0, boundary_conditions=(),
                  param_set=None, smagorinsky=None, discrete_hydrostatic_balance=False,
-                 with_divergence=False, zero_enthalpy=False):
+                 with_divergence=False, zero_enthalpy=False, tracers=None):
+        if tracers is not None and not isinstance(tracers, NTracers):
+            tracers = NTracers(tracers)
+        self.tracers = tracers
+        self.ntracers = nt = 0 if tracers is None else len(tracers)
+        if nt and (int(sources) & SRC_MMS or BC_INIT_STATE_MMS in tuple(boundary_conditions)):
+            raise ValueError("DryAtmosModel: MMSSource / InitStateBC are not defined for a model with tracers")
         # ConstantViscosity(..., WithDivergence()) (TurbulenceClosures.jl:290-370) and the
         # total_specific_enthalpy == 0 override of mms_bc_atmos.jl:50-51
         self.with_divergence, self.zero_enthalpy = bool(with_divergence), bool(zero_enthalpy)
@@ -331,9 +368,11 @@ class DryAtmosModel:
         o += 1 if has_hyp else 0
         self.off_moist = o
         o += 2
-        self.ns, self.naux = 5, o
-        self.ngrad = 4 + (1 if has_smag else 0) + (4 if has_hyp else 0)
-        self.ngradflux = 9 + (1 if has_smag else 0)
+        self.off_tracers = o                   # tracers.delta_chi[NT]
+        o += nt
+        self.ns, self.naux = 5 + nt, o
+        self.ngrad = 4 + (1 if has_smag else 0) + (4 if has_hyp else 0) + nt
+        self.ngradflux = 9 + (1 if has_smag else 0) + 3 * nt
         self.ngradlap = 4 if has_hyp else 0
         self.nhyper = 12 if has_hyp else 0
 
@@ -357,10 +396,14 @@ class DryAtmosModel:
         dp[2:13] = [ps.R_d, ps.cp_d, ps.cv_d, ps.T_0, ps.grav, ps.Omega, ps.MSLP, ps.day,
                     ps.planet_radius, ps.inv_Pr_turb, ps.kappa_d]
         dp[13] = self.C_smag if self.C_smag is not None else 0.0
+        if self.ntracers:       # NT in bits 8..15 of iparam[15], delta_chi[k] in dparam[16 + k]
+            ip[15] |= self.ntracers << 8
+            dp[16:16 + self.ntracers] = self.tracers.delta_chi
         return ip, dp
 
     def state_names(self):
-        return ["ρ", "ρu[1]", "ρu[2]", "ρu[3]", "energy.ρe"]
+        return (["ρ", "ρu[1]", "ρu[2]", "ρu[3]", "energy.ρe"]
+                + ["tracers.ρχ[%d]" % (k + 1) for k in range(self.ntracers)])
 
     # -- init_state_auxiliary! (AtmosModel.jl:880-940) -------------------------------------
     def init_state_auxiliary(self, grid):
@@ -431,6 +474,8 @@ class DryAtmosModel:
             c1 = np.sqrt((J[..., :, 0] ** 2).sum(axis=-1))
             c2 = np.sqrt((J[..., :, 1] ** 2).sum(axis=-1))
             aux[:, self.off_delta, :] = (c1 * 2 / N[0] + c2 * 2 / N[1]) / 2
+        for k in range(self.ntracers):       # atmos_init_aux!(::NTracers) (tracers.jl:133-140)
+            aux[:, self.off_tracers + k, :] = self.tracers.delta_chi[k]
         return aux
 
     def rebalance_reference_state(self, grid, aux, gradp):
@@ -453,11 +498,21 @@ class DryAtmosModel:
     def init_state_prognostic(self, grid, aux, t):
         Q = np.zeros((grid.nelem, self.ns, grid.Np))
         coord = [aux[:, d, :] for d in range(3)]
-        rho, rhou, rhoe = self.init_state(self, aux, coord, t)
+        out = self.init_state(self, aux, coord, t)
+        if len(out) != (4 if self.ntracers else 3):
+            raise ValueError("DryAtmosModel: init_state of a model with %d tracers returns (rho, rhou, rhoe%s)"
+                             % (self.ntracers, ", [rho chi[k]]" if self.ntracers else ""))
+        rho, rhou, rhoe = out[:3]
         Q[:, 0, :] = rho
         for d in range(3):
             Q[:, 1 + d, :] = rhou[d]
         Q[:, 4, :] = rhoe
+        if self.ntracers:
+            if len(out[3]) != self.ntracers:
+                raise ValueError("DryAtmosModel: init_state returned %d tracer fields for %d tracers"
+                                 % (len(out[3]), self.ntracers))
+            for k in range(self.ntracers):
+                Q[:, 5 + k, :] = out[3][k]
         return Q
 
 
@@ -602,6 +657,10 @@ class AtmosAcousticGravityLinearModel:
     state_auxiliary=dg.state_auxiliary)``.  Device functor: csrc/physics_atmos_linear.h.
 
     Of a ``moist.MoistAtmosModel`` (``EquilMoist``, linear.jl:57-72) it carries the sixth state
+    Of a model with tracers it carries none (AtmosModel.jl:399-406, linear.jl:104-112): five states,
+    the leading ones of the full model, on the full model's wider auxiliary array; ``AdditiveRungeKutta``
+    with the column solver steps such a pair, the tracers explicitly.
+
     ``rho q_tot`` (no flux, no source), ``p_lin`` gains ``- rho q_tot e_int_v0``, the auxiliary state
     is the moist model's 19 columns and the physics id is ``PHYSICS_MOIST_LINEAR_AG``."""
     physics_id = PHYSICS_ATMOS_LINEAR_AG
@@ -632,7 +691,7 @@ class AtmosAcousticGravityLinearModel:
         return self.atmos.descriptor()
 
     def state_names(self):
-        return self.atmos.state_names()
+        return self.atmos.state_names()[:self.ns]
 
     def init_state_auxiliary(self, grid):
         raise ValueError("AtmosAcousticGravityLinearModel shares the full model's auxiliary state: "
@@ -653,6 +712,8 @@ class AtmosAcousticLinearModel(AtmosAcousticGravityLinearModel):
     physics_id = PHYSICS_ATMOS_LINEAR_ACOUSTIC
 
     def __init__(self, atmos):
+        if getattr(atmos, "ntracers", 0):
+            raise ValueError("AtmosAcousticLinearModel: a model with tracers is not served")
         if atmos.physics_id != PHYSICS_DRY_ATMOS:
             raise ValueError("AtmosAcousticLinearModel: only the dry model is implemented (the moist "
                              "acoustic law is not)")

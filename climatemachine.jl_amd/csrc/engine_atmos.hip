@@ -9,10 +9,12 @@ namespace cmdg {
 int counts_atmos(const int32_t *ip, int32_t out[6])
 {
     const bool orient = ip[0] != 0, ref = ip[1] != 0, hyp = ip[4] != 0, smag = ip[14] == 1;
-    out[0] = 5;
-    out[1] = 3 + (orient ? 4 : 0) + (ref ? 7 : 0) + (smag ? 1 : 0) + (hyp ? 1 : 0) + 2;
-    out[2] = 4 + (smag ? 1 : 0) + (hyp ? 4 : 0);
-    out[3] = 9 + (smag ? 1 : 0);
+    const int nt = atmos_ntracers(ip);  // NTracers: rho chi, chi, grad chi (3 each), delta_chi
+    if (nt > ATMOS_MAX_TRACERS) return CMDG_ERR_UNSUPPORTED;
+    out[0] = 5 + nt;
+    out[1] = 3 + (orient ? 4 : 0) + (ref ? 7 : 0) + (smag ? 1 : 0) + (hyp ? 1 : 0) + 2 + nt;
+    out[2] = 4 + (smag ? 1 : 0) + (hyp ? 4 : 0) + nt;
+    out[3] = 9 + (smag ? 1 : 0) + 3 * nt;
     out[4] = hyp ? 4 : 0;
     out[5] = hyp ? 12 : 0;
     return CMDG_OK;
@@ -78,8 +80,38 @@ static EngineBase *pick(const cmdg_desc *d, std::string &err)
     return nullptr;
 }
 
+// a descriptor with tracers never reaches the five-state engines of pick: the units of their own
+// (engine_atmos_tracers<NT>.hip) serve it or nobody here does
+static EngineBase *pick_tracers(const cmdg_desc *d, int nt, std::string &err)
+{
+    bool mms = (d->iparam[5] & 8) != 0;
+    for (int i = 0; i < d->iparam[6] && i < 7; ++i) mms = mms || d->iparam[7 + i] == 2;
+    if (nt > ATMOS_MAX_TRACERS) {
+        err = "DryAtmos: at most 8 tracers";
+        return nullptr;
+    }
+    if (mms) {
+        err = "DryAtmos: MMSSource / InitStateBC are not defined for a model with tracers";
+        return nullptr;
+    }
+    if (d->nf_first >= NF_ROE) {
+        err = "DryAtmos: the Roe / HLLC / LMARS numerical fluxes have no tracer methods (tracers need Rusanov or "
+              "the central flux)";
+        return nullptr;
+    }
+    if (d->iparam[14] != 0 && d->iparam[14] != 1) {
+        err = "DryAtmos: unknown turbulence closure";
+        return nullptr;
+    }
+    if (nt == 1) return make_engine_atmos_tracers1(d, err);
+    if (nt == 2) return make_engine_atmos_tracers2(d, err);
+    err = "DryAtmos: 1 or 2 tracers are compiled in (more: plugins.build_dry_atmos(ntracers=...))";
+    return nullptr;
+}
+
 EngineBase *make_engine_atmos(const cmdg_desc *d, std::string &err)
 {
+    if (const int nt = atmos_ntracers(d->iparam)) return pick_tracers(d, nt, err);
     if (d->iparam[4] != 0 && d->iparam[0] == 0) {
         err = "DryAtmos: hyperdiffusion needs an orientation";
         return nullptr;

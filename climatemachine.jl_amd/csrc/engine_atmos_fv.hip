@@ -15,6 +15,11 @@ EngineBase *make_engine_atmos_fv(const cmdg_desc *d, const cmdg_fv_desc *fv, std
     const bool orient = d->iparam[0] != 0, ref = d->iparam[1] != 0, hyp = d->iparam[4] != 0;
     bool mms = (d->iparam[5] & 8) != 0;
     for (int i = 0; i < d->iparam[6] && i < 7; ++i) mms = mms || d->iparam[7 + i] == 2;
+    if (atmos_ntracers(d->iparam) != 0) {
+        err = std::string("DGFVModel DryAtmos: a model with tracers is not compiled in (the primitive conversion "
+                          "carries rho, u, p); ") + have;
+        return nullptr;
+    }
     if (hyp) {
         err = std::string("DGFVModel: a law with hyperdiffusive states is not supported (DGFVModel.jl:91); ") + have;
         return nullptr;

@@ -1,7 +1,8 @@
 // Engine instantiations for AtmosAcousticGravityLinearModel (physics_atmos_linear.h).  The law
 // shares the full model's auxiliary array.  Of the dry law the count comes from the full model's
 // parameter block: orientation and reference state are required, hyperdiffusion or
-// SmagorinskyLilly add one column each.  Of the moist LES law (CMDG_PHYSICS_MOIST_LINEAR_AG) it is
+// SmagorinskyLilly add one column each, a tracer of the full model one more (the linear model itself
+// carries none: five states, AtmosModel.jl:399-406).  Of the moist LES law (CMDG_PHYSICS_MOIST_LINEAR_AG) it is
 // always MoistAtmos's 19, at the orders the moist law is compiled for.
 #include "engine.h"
 #include "laws.h"
@@ -29,10 +30,15 @@ static EngineBase *pick(const cmdg_desc *d, std::string &err)
 {
     switch (naux_of_full(d->iparam)) {
     case 16: return make_engine<AtmosLinearAG<16>, NQ>(d);  // no hyperdiffusion, no Smagorinsky
-    case 17: return make_engine<AtmosLinearAG<17>, NQ>(d);  // DryBiharmonic (Held-Suarez)
+    case 17: return make_engine<AtmosLinearAG<17>, NQ>(d);  // DryBiharmonic (Held-Suarez), or one tracer
+    // the count is a stride only: the law reads Phi, grad Phi and the reference state, which precede
+    // every optional column.  One or two tracers (delta_chi columns) on top of the above:
+    case 18: return make_engine<AtmosLinearAG<18>, NQ>(d);
+    case 19: return make_engine<AtmosLinearAG<19>, NQ>(d);
     default:
         err = "AtmosAcousticGravityLinearModel: the full model's auxiliary layout is not compiled in "
-              "(have orientation + reference state, with or without hyperdiffusion)";
+              "(have orientation + reference state, with or without hyperdiffusion or SmagorinskyLilly, and "
+              "up to two tracers on top: 16 to 19 columns)";
         return nullptr;
     }
 }

@@ -11,6 +11,8 @@ namespace cmdg {
 EngineBase *make_engine_advdiff(const cmdg_desc *d, std::string &err);
 EngineBase *make_engine_advdiff_fv(const cmdg_desc *d, const cmdg_fv_desc *fv, std::string &err);
 EngineBase *make_engine_atmos(const cmdg_desc *d, std::string &err);
+EngineBase *make_engine_atmos_tracers1(const cmdg_desc *d, std::string &err);  // (NTracers: one unit per count)
+EngineBase *make_engine_atmos_tracers2(const cmdg_desc *d, std::string &err);
 EngineBase *make_engine_atmos_fv(const cmdg_desc *d, const cmdg_fv_desc *fv, std::string &err);
 EngineBase *make_engine_ocean(const cmdg_desc *d, std::string &err);
 EngineBase *make_engine_pgrad(const cmdg_desc *d, std::string &err);

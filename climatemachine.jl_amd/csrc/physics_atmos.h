@@ -19,6 +19,11 @@
 // iparam[15] bit 0 WithDivergence stress, bit 1 total_specific_enthalpy == 0 (the override of
 // test/Numerics/DGMethods/compressible_Navier_Stokes/mms_bc_atmos.jl:50-51).  Source bit 8 =
 // MMSSource{3}, boundary kind 2 = InitStateBC with the manufactured solution (same test).
+// NTracers (src/Atmos/Model/tracers.jl, tendencies_tracers.jl, bc_tracer.jl): iparam[15] bits 8..15
+// the number of tracers NT (at most ATMOS_MAX_TRACERS), dparam[16 + k] the diffusivity ratio
+// delta_chi[k].  The tracers follow every other component: prognostic rho chi[NT] after rho e,
+// gradient chi[NT] last, gradient flux grad chi (3 x NT, tracer k owns entries 3 k .. 3 k + 2) last,
+// auxiliary delta_chi[NT] after moisture.theta_v / air_T.
 #pragma once
 #include "cmdg_common.h"
 #include "law_defaults.h"
@@ -40,27 +45,53 @@ struct AtmosParams {
     double R_ratio;         // R_m / R_d of a dry phase: R_d / R_d (virtual_pottemp)
 };
 static constexpr int ATMOS_NHOSTCONST = 7;
+static constexpr int ATMOS_MAX_TRACERS = 8;
+__host__ __device__ inline int atmos_ntracers(const int32_t *ip) { return (ip[15] >> 8) & 0xff; }
+// the parameter block of a law with tracers: the tracer-free block, then delta_chi.  (A type of its
+// own, so that the tracer-free kernels keep their arguments.)
+template <int NT>
+struct AtmosTracerParams : AtmosParams {
+    double dchi[NT];
+};
+template <int NT>
+struct AtmosParamsOf {
+    using type = AtmosTracerParams<NT>;
+};
+template <>
+struct AtmosParamsOf<0> {
+    using type = AtmosParams;
+};
 
-template <bool ORIENT, bool REF, bool HYPER, bool SMAG = false, bool LAWNF = false>
+template <bool ORIENT, bool REF, bool HYPER, bool SMAG = false, bool LAWNF = false, int NT = 0>
 struct DryAtmos : LawDefaults {
     // RoeNumericalFlux / HLLCNumericalFlux live in a variant of their own so that the
     // kernels of every other configuration keep their register budget
     static constexpr bool LAW_NF = LAWNF;
     static_assert(!(SMAG && HYPER), "gradient-variable order of this combination is not laid out");
     static_assert(!SMAG || ORIENT, "SmagorinskyLilly needs an orientation (buoyancy correction)");
-    using Params = AtmosParams;
-    static constexpr int NS = 5;
+    static_assert(NT >= 0 && NT <= ATMOS_MAX_TRACERS, "iparam[15] bits 8..15 hold at most ATMOS_MAX_TRACERS tracers");
+    static_assert(!(LAWNF && NT > 0), "Roe / HLLC / LMARS have no tracer methods in the reference");
+    using Params = typename AtmosParamsOf<NT>::type;
+    static constexpr int NS = 5 + NT;
     static constexpr int OPHI = 3;
     static constexpr int OREF = OPHI + (ORIENT ? 4 : 0);
     static constexpr int OTURB = OREF + (REF ? 7 : 0);   // turbulence.Delta (SmagorinskyLilly)
     static constexpr int ODELTA = OTURB + (SMAG ? 1 : 0);  // hyperdiffusion.Delta
     static constexpr int OMOIST = ODELTA + (HYPER ? 1 : 0);
-    static constexpr int NAUX = OMOIST + 2;
-    // Gradient: u, h_tot, [turbulence.theta_v], [hyperdiffusion u_h, h_tot]
-    static constexpr int NGRAD = 4 + (SMAG ? 1 : 0) + (HYPER ? 4 : 0);
-    // GradientFlux: grad h_tot, S, [N^2]
-    static constexpr int NGF = 9 + (SMAG ? 1 : 0);
+    static constexpr int OTRAC = OMOIST + 2;  // tracers.delta_chi[NT]: layout parity, read from Params
+    static constexpr int NAUX = OTRAC + NT;
+    // Gradient: u, h_tot, [turbulence.theta_v], [hyperdiffusion u_h, h_tot], [tracers.chi]
+    static constexpr int OGCHI = 4 + (SMAG ? 1 : 0) + (HYPER ? 4 : 0);
+    static constexpr int NGRAD = OGCHI + NT;
+    // GradientFlux: grad h_tot, S, [N^2], [grad chi (3, NT)]
+    static constexpr int OGFCHI = 9 + (SMAG ? 1 : 0);
+    static constexpr int NGF = OGFCHI + 3 * NT;
     static constexpr bool GF_NODE_MAJOR = true;  // (law_defaults.h)
+    // The gradient pass holds 3 NGRAD gradient components per node.  With tracers the widest
+    // combinations no longer fit the 128 VGPRs of the library's four waves per SIMD: DryBiharmonic
+    // takes 132 (NT = 1) and 142 (NT = 2), SmagorinskyLilly with two tracers spilled 12 bytes at 128.
+    // They ask for three waves (168 VGPRs); every other combination keeps the library's budget.
+    static constexpr int GRAD_MIN_WAVES = NT > 0 && (HYPER || (SMAG && NT >= 2)) ? 3 : 0;
     static constexpr int NGL = HYPER ? 4 : 0;
     static constexpr int NHYP = HYPER ? 12 : 0;
     static constexpr bool HAS_UPDATE_AUX = true;
@@ -91,6 +122,8 @@ struct DryAtmos : LawDefaults {
     // refresh), grad Phi for the horizontal projection of u (DryBiharmonic) or N^2
     // (SmagorinskyLilly).  Gradient of Laplacian: hyperdiffusion.Delta alone (nu_4), no state.
     // Tendency: Phi, grad Phi (gravity, Held-Suarez drag), ref_state rho and p, turbulence.Delta.
+    // A tracer adds its state column to the gradient and tendency passes and no auxiliary column:
+    // delta_chi comes from Params.
     __host__ __device__ static constexpr int state_read(int pass) { return pass == 1 || pass == 2 ? 0 : NS; }
     __host__ __device__ static constexpr int aux_read(int pass)
     {
@@ -135,6 +168,9 @@ struct DryAtmos : LawDefaults {
         p.C_smag = dp[13];
         p.withdiv = ip[15] & 1;
         p.zero_h = (ip[15] >> 1) & 1;
+        if constexpr (NT > 0) {
+            for (int k = 0; k < NT; ++k) p.dchi[k] = dp[16 + k];
+        }
         derive_params(p);
     }
     static void derive_params(Params &p)
@@ -215,7 +251,7 @@ struct DryAtmos : LawDefaults {
     // Columns temp, pres, theta_dry, e_int, h_tot, h_int, d_h_tot[3].  The LES configurations: an
     // orientation that is flat, no hyperdiffusion; MoistAtmos::les_diagnostics reduces to this at
     // q_tot = 0.
-    static constexpr bool HAS_LES_DIAGNOSTICS = ORIENT && !HYPER && !LAWNF;
+    static constexpr bool HAS_LES_DIAGNOSTICS = ORIENT && !HYPER && !LAWNF && NT == 0;
     static constexpr int NDIAG = 7;
     __host__ __device__ static bool les_diagnostics_active(const Params &m) { return m.orient == 1; }
     __device__ static void les_diagnostics(const Params &m, double *D, const double *Q, const double *aux,
@@ -249,7 +285,7 @@ struct DryAtmos : LawDefaults {
     // ---- AtmosGCMDefault diagnostics (src/Diagnostics/atmos_gcm_default.jl): the same six columns,
     // for every configuration with an orientation (a reference state or hyperdiffusion do not enter)
     static constexpr bool STATE_RHO_RHOU = true;
-    static constexpr bool HAS_GCM_DIAGNOSTICS = ORIENT;
+    static constexpr bool HAS_GCM_DIAGNOSTICS = ORIENT && NT == 0;
     __device__ static void gcm_thermo(const Params &m, double *D, const double *Q, const double *aux)
     {
         thermo_columns(m, D, Q, aux);
@@ -257,7 +293,7 @@ struct DryAtmos : LawDefaults {
 
     // ---- local Courant numbers: src/Atmos/Model/courant.jl:12-83 ------------------------
     // the manufactured-solution pieces (source, InitStateBC) exist in the plain variant only
-    static constexpr bool MMS_VARIANT = !ORIENT && !REF && !HYPER && !SMAG && !LAWNF;
+    static constexpr bool MMS_VARIANT = !ORIENT && !REF && !HYPER && !SMAG && !LAWNF && NT == 0;
     static constexpr bool HAS_COURANT = true;
     static constexpr bool HAS_PENALTY = false;  // update_penalty! is the default no-op
     __device__ static double courant(const Params &m, int kind, const double *Q, const double *aux,
@@ -324,6 +360,11 @@ struct DryAtmos : LawDefaults {
                 F[d + 3 * (1 + c)] = Q[1 + d] * u[c] + (0.0 + (d == c ? pp : 0.0));
 #pragma unroll
         for (int d = 0; d < 3; ++d) F[d + 12] = u[d] * Q[4] + u[d] * p;
+        // Tracers, Advect (tendencies_tracers.jl:7-11): rho chi[k] u with u = rho u / rho
+#pragma unroll
+        for (int k = 0; k < NT; ++k)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) F[d + 3 * (5 + k)] = Q[5 + k] * u[d];
     }
     __device__ static double sym(const double *c, int i, int j)
     {  // SHermitianCompact{3}: (1,1),(2,1),(3,1),(2,2),(3,2),(3,3)
@@ -406,6 +447,17 @@ struct DryAtmos : LawDefaults {
             }
             F[d + 12] = x;
         }
+        // Tracers, Diffusion (tendencies_tracers.jl:17-22): d_chi = ((-D_t) delta_chi') .* grad chi,
+        // then d_chi rho, with the D_t of the energy flux above
+        if constexpr (NT > 0) {
+#pragma unroll
+            for (int k = 0; k < NT; ++k)
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    const double Dt = nu[d] * m.invPr;
+                    F[d + 3 * (5 + k)] = (((-Dt) * m.dchi[k]) * gf[OGFCHI + d + 3 * k]) * rho;
+                }
+        }
     }
     // Held-Suarez forcing coefficients (heldsuarez.jl:116-155)
     __device__ static void init_derived(const Params &, double *der, const double *aux)
@@ -482,6 +534,8 @@ struct DryAtmos : LawDefaults {
         S[2] = Sm[1];
         S[3] = Sm[2];
         S[4] = Se;
+#pragma unroll
+        for (int k = 0; k < NT; ++k) S[5 + k] = 0;  // no tracer source
         if constexpr (MMS_VARIANT) {
             if (m.src & 8) {  // MMSSource{3} (mms_bc_atmos.jl:65-86)
                 double Sx[5];
@@ -590,6 +644,9 @@ struct DryAtmos : LawDefaults {
         // the nodal refresh of this same (Q, aux) -- evaluated here so that the fused refresh
         // of neighbouring elements is never read (see FUSE_UPDATE_AUX)
         if constexpr (SMAG) G[4] = theta_v(m, T, Q[0]);
+        // transform.tracers.chi = rho chi * rhoinv (tracers.jl:141-150)
+#pragma unroll
+        for (int k = 0; k < NT; ++k) G[OGCHI + k] = Q[5 + k] * rhoinv;
         if constexpr (HYPER && ORIENT) {
             double u[3], k[3];
 #pragma unroll
@@ -645,6 +702,11 @@ struct DryAtmos : LawDefaults {
         gf[6] = g[1 + 3 * 1];
         gf[7] = (g[2 + 3 * 1] + g[1 + 3 * 2]) / 2;
         gf[8] = g[2 + 3 * 2];
+        // diffusive.tracers.grad chi = grad transform.tracers.chi (tracers.jl:151-160)
+#pragma unroll
+        for (int k = 0; k < NT; ++k)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) gf[OGFCHI + d + 3 * k] = g[d + 3 * (OGCHI + k)];
     }
     __device__ static void post_gradient_laplacian(const Params &m, double *hyp, const double *gl,
                                                    const double *, const double *aux, double)
@@ -665,6 +727,9 @@ struct DryAtmos : LawDefaults {
         const double ss = soundspeed(m, air_T(m, internal_energy(m, Q, aux)));
 #pragma unroll
         for (int s = 0; s < 5; ++s) ws[s] = uN + ss;
+        // wavespeed_tracers! (tracers.jl:162-178): |n . u| alone
+#pragma unroll
+        for (int k = 0; k < NT; ++k) ws[5 + k] = uN;
     }
     // RoeNumericalFlux (AtmosModel.jl:1003-1130, DryModel only), HLLCNumericalFlux
     // (:1154-1276) and LMARSNumericalFlux (:1515-1600); adds the normal flux to fluxn
@@ -789,8 +854,8 @@ struct DryAtmos : LawDefaults {
     __device__ static void update_aux(const Params &m, const double *Q, double *aux, double)
     {
         static_assert(!GRADARG_REFRESH_UNREAD ||
-                          (upd_aux(0) == NAUX - NUPD && aux_read(0) <= NAUX - NUPD &&
-                           aux_read(2) <= NAUX - NUPD && aux_read(3) <= NAUX - NUPD),
+                          (upd_aux(0) == OTRAC - NUPD && aux_read(0) <= OTRAC - NUPD &&
+                           aux_read(2) <= OTRAC - NUPD && aux_read(3) <= OTRAC - NUPD),
                       "a pass that reads moisture.theta_v / air_T needs the refresh in every update");
         const double T = air_T(m, internal_energy(m, Q, aux));
         aux[OMOIST] = theta_v(m, T, Q[0]);
@@ -808,6 +873,7 @@ struct DryAtmos : LawDefaults {
                 return;
             }
         }
+        // ImpermeableTracer (bc_tracer.jl): rho chi on the plus side stays the copy of the minus side
         if (m.bc[bctag - 1] == 1) {  // Impenetrable(FreeSlip) + Insulating
             const double dn = QM[1] * n[0] + QM[2] * n[1] + QM[3] * n[2];
             const double f = kind == BS_FIRST ? 2 * dn : dn;

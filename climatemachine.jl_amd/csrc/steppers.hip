@@ -75,6 +75,45 @@ __global__ void k_add(double *a, const double *b, int64_t len)
     if (i < len) a[i] += b[i];
 }
 
+// A linear model that ends before the full model's trailing states (AtmosLinearModel carries no
+// tracers, AtmosModel.jl:399-406): its arrays are narrow, (Np, nsl, nelem), and the step moves the
+// leading nsl columns of the wide (Np, nsf, nelem) arrays in and out.  One thread per narrow entry.
+struct Lead {
+    int64_t len;  // nreal * nsl * Np
+    int nsl, nsf, Np;
+    __device__ int64_t wide(int64_t i) const
+    {
+        const int64_t col = i / Np, e = col / nsl;
+        return i + e * (int64_t)(nsf - nsl) * Np;
+    }
+};
+// narrow = the leading columns of wide
+__global__ void __launch_bounds__(256) k_lead_get(const Lead l, double *__restrict__ narrow, const double *__restrict__ wide)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i < l.len) narrow[i] = wide[l.wide(i)];
+}
+// the leading columns of wide = narrow (the linear tendency leaves the trailing columns alone,
+// DGModel.jl:98-102)
+__global__ void __launch_bounds__(256) k_lead_put(const Lead l, double *__restrict__ wide, const double *__restrict__ narrow)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i < l.len) wide[l.wide(i)] = narrow[i];
+}
+// Qs += Qtt, where Qtt is Qhat with its leading columns replaced by the solve's result: the column
+// solver does Q .= Qrhs and substitutes over the linear model's states only
+// (columnwise_lu_solver.jl:119,132).  One thread per wide entry.
+__global__ void __launch_bounds__(256) k_add_solved(double *__restrict__ Qs, const double *__restrict__ Qhat,
+                                                    const double *__restrict__ Qtt_narrow, int nsl, int nsf, int Np,
+                                                    int64_t len)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    const int64_t col = i / Np, e = col / nsf;
+    const int s = (int)(col - e * nsf);
+    Qs[i] += s < nsl ? Qtt_narrow[i - e * (int64_t)(nsf - nsl) * Np] : Qhat[i];
+}
+
 // solution_update! (LowStorageVariant, :670-690)
 __global__ void __launch_bounds__(256) k_ark_solution(const ArkArgs a, int nstages)
 {
@@ -101,10 +140,14 @@ int ark_step(cmdg_handle full, BackwardEuler *be, double *Q, double *const *work
     if (!gc.ok()) return CMDG_ERR_INVALID;
     EngineBase *ef = full->eng, *el = lin->eng;
     if (nstages < 2 || nstages > 4) return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: 2 to 4 stages"));
-    if (ef->ns != el->ns)
-        return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: the full model has " + std::to_string(ef->ns) +
-                                                        " states, the linear model " + std::to_string(el->ns) +
-                                                        "; they must be the same"));
+    // narrow: the linear model's states are the leading ones of a wider full model (tracers)
+    const bool narrow = el->ns < ef->ns;
+    if (ef->ns < el->ns || (narrow && (be->iterative || ef->esdg)))
+        return gc.finish(ef->fail(CMDG_ERR_INVALID,
+                                  "ark: the full model has " + std::to_string(ef->ns) + " states, the linear model " +
+                                      std::to_string(el->ns) + "; served are equal counts, and with the column solver a "
+                                      "linear model that ends before the full model's trailing states (tracers): not "
+                                      "with GMRES, not with an ESDGModel"));
     if (ef->nreal != el->nreal || ef->Np != el->Np || ef->dev != el->dev)
         return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: the full and the linear model live on different grids"));
     // an ESDGModel handle as the full operator: eager evaluations through Op::eval like any other, on
@@ -113,10 +156,11 @@ int ark_step(cmdg_handle full, BackwardEuler *be, double *Q, double *const *work
         return gc.finish(ef->fail(CMDG_ERR_UNSUPPORTED, "ark: an ESDGModel as the full operator on a partitioned grid "
                                                         "is not supported (one rank only)"));
     const int ns = nstages;
-    for (int i = 0; i < 2 * ns + 1; ++i)
+    for (int i = 0; i < 2 * ns + 1 + (narrow ? 4 : 0); ++i)
         if (!work[i]) return gc.finish(ef->fail(CMDG_ERR_INVALID, "ark: work array " + std::to_string(i) + " is NULL"));
     auto A = [&](const double *m, int i, int j) { return m[i * ns + j]; };  // row-major (stage, stage)
-    // work: Qstages[1..ns-1], Rstages[0..ns-1], Qhat, Qtt
+    // work: Qstages[1..ns-1], Rstages[0..ns-1], Qhat, Qtt; narrow: then four arrays shaped like the
+    // linear model's state -- the leading columns of a stage and of its tendency, Qhat and Qtt of the solve
     ArkArgs a{};
     a.Qs[0] = Q;
     for (int i = 1; i < ns; ++i) a.Qs[i] = work[i - 1];
@@ -126,13 +170,42 @@ int ark_step(cmdg_handle full, BackwardEuler *be, double *Q, double *const *work
     a.len = real_len(ef);
     for (int is = 0; is < ns; ++is) a.bdt[is] = rkb[is] * dt;
     const dim3 g(grid_one_per_thread(a.len)), b(256);
-    hipStream_t sf = ef->s_comp, sl = el->s_comp;
+    double *nQ = nullptr, *nT = nullptr, *nQhat = nullptr, *nQtt = nullptr;
+    Lead lead{};
+    if (narrow) {
+        nQ = work[2 * ns + 1], nT = work[2 * ns + 2], nQhat = work[2 * ns + 3], nQtt = work[2 * ns + 4];
+        lead.len = real_len(el);
+        lead.nsl = el->ns, lead.nsf = ef->ns, lead.Np = ef->Np;
+    }
+    const dim3 gl(grid_one_per_thread(narrow ? lead.len : 1));
     Chain ch(ef, "ark");
     if (int r = ch.create()) return gc.finish(r);
     // the explicit tendency: the full operator, or "full minus linear" as two evaluations (not the
     // reference's fused RemBL kernel)
-    const Op expl{full, split_explicit_implicit ? lin : nullptr}, impl{lin};
-    if (int r = expl.eval(ch, R[0], Qs[0], t + rkc[0] * dt, 0.0)) return gc.finish(r);
+    const Op expl{full, split_explicit_implicit && !narrow ? lin : nullptr}, impl{lin};
+    hipStream_t sf = ef->s_comp, sl = el->s_comp;
+    // narrow: R[lead] += sign L(Q[lead]) on the linear handle's stream.  The leading columns of R
+    // go through a narrow array, so that the linear operator increments them with (alpha, beta) =
+    // (sign, 1) exactly as it increments the whole array of a pair of equal counts: the same bits.
+    auto add_linear = [&](double *Rw, double *Qw, double tt, double sign) -> int {
+        if (int r = ch.to(sl)) return r;
+        hipLaunchKernelGGL(k_lead_get, gl, b, 0, sl, lead, nQ, Qw);
+        hipLaunchKernelGGL(k_lead_get, gl, b, 0, sl, lead, nT, Rw);
+        RhsCtx c;
+        c.tendency = nT;
+        c.Qin = nQ;
+        c.t = tt;
+        c.alpha = sign;
+        c.beta = 1.0;
+        if (int r = el->rhs_async(c)) return r;
+        hipLaunchKernelGGL(k_lead_put, gl, b, 0, sl, lead, Rw, nT);
+        return CMDG_OK;
+    };
+    auto explicit_eval = [&](double *Rw, double *Qw, double tt) -> int {
+        if (int r = expl.eval(ch, Rw, Qw, tt, 0.0)) return r;
+        return narrow && split_explicit_implicit ? add_linear(Rw, Qw, tt, -1.0) : CMDG_OK;
+    };
+    if (int r = explicit_eval(R[0], Qs[0], t + rkc[0] * dt)) return gc.finish(r);
     for (int is = 1; is < ns; ++is) {
         for (int js = 0; js < is; ++js) {
             a.rkcoeff[js] = split_explicit_implicit
@@ -147,14 +220,22 @@ int ark_step(cmdg_handle full, BackwardEuler *be, double *Q, double *const *work
         const double alpha = dt * A(rka_implicit, is, is);
         if (alpha != be->alpha())
             if (int r = be->ready(alpha)) return gc.finish(r);
-        if (int r = be->solve(Qtt, Qhat, t + rkc[is] * dt)) return gc.finish(r);
-        hipLaunchKernelGGL(k_add, g, b, 0, sl, Qs[is], Qtt, a.len);
-        if (int r = expl.eval(ch, R[is], Qs[is], t + rkc[is] * dt, 0.0)) return gc.finish(r);
+        if (narrow) {
+            hipLaunchKernelGGL(k_lead_get, gl, b, 0, sl, lead, nQhat, Qhat);
+            if (int r = be->solve(nQtt, nQhat, t + rkc[is] * dt)) return gc.finish(r);
+            hipLaunchKernelGGL(k_add_solved, g, b, 0, sl, Qs[is], Qhat, nQtt, lead.nsl, lead.nsf, lead.Np, a.len);
+        } else {
+            if (int r = be->solve(Qtt, Qhat, t + rkc[is] * dt)) return gc.finish(r);
+            hipLaunchKernelGGL(k_add, g, b, 0, sl, Qs[is], Qtt, a.len);
+        }
+        if (int r = explicit_eval(R[is], Qs[is], t + rkc[is] * dt)) return gc.finish(r);
     }
     if (split_explicit_implicit)
         // rhs_implicit!(Rstages[is], Qstages[is], p, stagetime, increment = true)
         for (int is = 0; is < ns; ++is)
-            if (int r = impl.eval(ch, R[is], Qs[is], t + rkc[is] * dt, 1.0)) return gc.finish(r);
+            if (int r = narrow ? add_linear(R[is], Qs[is], t + rkc[is] * dt, 1.0)
+                               : impl.eval(ch, R[is], Qs[is], t + rkc[is] * dt, 1.0))
+                return gc.finish(r);
     if (int r = ch.to(sf)) return gc.finish(r);
     hipLaunchKernelGGL(k_ark_solution, g, b, 0, sf, a, ns);
     if (int r = ef->launch_status("ark kernels")) return gc.finish(r);

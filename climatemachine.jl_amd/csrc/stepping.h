@@ -100,7 +100,8 @@ inline int check_same_grid(const char *stepper, EngineBase *ref, EngineBase *e, 
         return e->fail(CMDG_ERR_INVALID, the + "lives on another grid than the slow operator");
     if (e->ns != ref->ns)
         return e->fail(CMDG_ERR_INVALID, the + "has " + std::to_string(e->ns) + " states, the slow operator " +
-                                             std::to_string(ref->ns) + "; they must be the same");
+                                             std::to_string(ref->ns) + "; they must be the same (a linear model without the full model's "
+                                             "tracers is served by the additive Runge-Kutta step with the column solver only)");
     return CMDG_OK;
 }
 

@@ -533,7 +533,8 @@ def remainder_DGModel(dg, subtract):
     if lin.grid is not dg.grid:
         raise _lib.CmdgError("remainder_DGModel: the subtracted model lives on another grid")
     if lin.balance_law.ns != dg.balance_law.ns:
-        raise _lib.CmdgError("remainder_DGModel: the subtracted model has %d states, the main model %d"
+        raise _lib.CmdgError("remainder_DGModel: the subtracted model has %d states, the main model %d (pairs of "
+                             "one state count are served: a linear model without the main model's tracers is not)"
                              % (lin.balance_law.ns, dg.balance_law.ns))
     if lin.state_auxiliary.data_ptr() != dg.state_auxiliary.data_ptr():
         raise _lib.CmdgError("remainder_DGModel: the subtracted model must share the main model's "

@@ -52,12 +52,21 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _refuse_tracers(who, dg):
+    # the reference's default groups have no tracer variables; the device columns are laid out for
+    # the tracer-free state
+    if getattr(dg.balance_law, "ntracers", 0):
+        raise ValueError("%s: a model with tracers is not served (the diagnostics are compiled for the "
+                         "tracer-free dry law)" % who)
+
+
 class AtmosLESDefault:
     """``setup_atmos_default_diagnostics(::AtmosLESConfigType, ...)`` for one ``DGModel`` (or one rank
     of a ``connect_local`` group, through ``group_init`` / ``group_collect``)."""
 
     def __init__(self, dg):
         g = dg.grid
+        _refuse_tracers("AtmosLESDefault", dg)
         self.dg, self.L_ = dg, dg.L
         # (the library refuses, with the reason: a law without the diagnostics, a grid that is not
         # stacked, a vertical order of 0)
@@ -310,6 +319,7 @@ class AtmosGCMDefault:
         from .mesh.interpolation import InterpolationCubedSphere
         if not isinstance(interpol, InterpolationCubedSphere):
             raise ValueError(GCM_REQUIRES_SPHERE)
+        _refuse_tracers("AtmosGCMDefault", dg)
         if interpol.Nel != dg.grid.nreal or tuple(interpol.Nq) != tuple(int(q) for q in dg.grid.Nq):
             raise ValueError("AtmosGCMDefault: the interpolation was built for another grid")
         self.dg, self.interpol, self.L_ = dg, interpol, dg.L

@@ -222,7 +222,10 @@ class MoistAtmosModel:
     def __init__(self, init_state, ref_state, closure=CLOSURE_SMAGORINSKY, coefficient=None,
                  kinematic=True, subtract_off=True, sources=SRC_GRAVITY,
                  boundary_conditions=(BC_ATMOS_DEFAULT, BC_ATMOS_DEFAULT), param_set=None,
-                 maxiter=8, tolerance=1e-1, no_orientation=False):
+                 maxiter=8, tolerance=1e-1, no_orientation=False, tracers=None):
+        if tracers is not None:
+            raise ValueError("MoistAtmosModel: tracers are carried by the dry law only (DryAtmosModel(tracers=...)); "
+                             "the moist functor has no tracer columns")
         self.ps = param_set or MoistParameters()
         # NoOrientation + NoReferenceState (the moist isentropic vortex): the potential, its
         # gradient, the reference state and Delta keep their slots of the auxiliary state and

@@ -271,6 +271,16 @@ class AdditiveRungeKutta:
         self.split_explicit_implicit = bool(split_explicit_implicit)
         self.dt, self.t, self.steps = float(dt), t0, 0
         self.work = [dg.create_state(Q.shape[1]) for _ in range(2 * ns + 1)]
+        nsl = linear_dg.balance_law.ns
+        if nsl < Q.shape[1]:
+            # a linear model without the full model's trailing tracers: four work states of its own
+            # shape (the leading columns of a stage and of its tendency, Qhat and Qtt of the solve).
+            # (Any other mismatch is the library's to refuse.)
+            if not isinstance(backward_euler_solver.solver, ManyColumnLU):
+                raise ValueError("AdditiveRungeKutta: the full model has %d states, the linear model %d; served are "
+                                 "equal counts, and with ManyColumnLU a linear model that ends before the full "
+                                 "model's tracers (GMRES pairs with differing counts are not)" % (Q.shape[1], nsl))
+            self.work += [linear_dg.create_state() for _ in range(4)]
         self._ptrs = (C.c_void_p * len(self.work))(*[w.data_ptr() for w in self.work])
         self.isadjustable = backward_euler_solver.isadjustable
         self._diag = diag[1]

@@ -974,8 +974,13 @@ int cmdg_columnlu_destroy(cmdg_columnlu_handle lu);
  * (0, c, ..., c).  work: 2 nstages + 1 device state arrays shaped like Q (Qstages[2..], Rstages,
  * Qhat, Qtt).  split_explicit_implicit != 0: the explicit operator is full minus linear,
  * evaluated as `full` followed by `linear` with alpha = -1 and increment.  The solver is refactored
- * when dt a_ii differs from its alpha.  `full` and `linear` must have the same state count
- * (CMDG_ERR_INVALID otherwise).  `full` may be an ESDGModel handle (cmdg_create_esdg) with
+ * when dt a_ii differs from its alpha.  `full` and `linear` have the same state count, or `linear`
+ * ends before trailing states of `full` that the linear model does not carry (the tracers of
+ * CMDG_PHYSICS_DRY_ATMOS, iparam[15] bits 8..15; AtmosModel.jl:399-406): work then holds four more
+ * arrays shaped like the linear handle's state, the leading columns are moved in and out of them,
+ * the trailing states are stepped explicitly and the column solver's band is that of the model
+ * without them.  Any other pair of counts is CMDG_ERR_INVALID, as is such a pair with GMRES or with
+ * an ESDGModel.  `full` may be an ESDGModel handle (cmdg_create_esdg) with
  * CMDG_PHYSICS_ESDG_DRY_ATMOS_LINEAR_AG as `linear`, on one rank (CMDG_ERR_UNSUPPORTED with ghost
  * elements).  A failure's message is on both handles.  Returns after the step has finished. */
 int cmdg_ark_step(cmdg_handle full, cmdg_columnlu_handle lu, double *Q, double *const *work, double t,

@@ -208,27 +208,35 @@ static __global__ void k_face_digest(const double *__restrict__ vgeo, int nvgeo,
 }
 
 // The doubles of the fused Laplacian pass's table (lapT of k_lapfused) once the host has found tP
-// (lapfused_tables.h): the neighbour's horizontal metric rows at the plus node, its normal and lift
-// weight at its own face task of the shared node.
+// and tE (lapfused_tables.h): the neighbour's horizontal metric rows at the plus node, its normal and
+// lift weight at its own face task of the shared node; and, behind these rows, the edge block: its
+// normal and lift weight at tE, for the two tasks of a row that have one.
 static __global__ void k_lapfused_fill(const double *__restrict__ vgeo, int nvgeo, const int32_t *__restrict__ faceP,
                                        const double *__restrict__ faceG, const double *__restrict__ faceW,
-                                       const int32_t *__restrict__ lapI, int Np, int NFT, int NL, int64_t nreal,
-                                       double *__restrict__ lapT)
+                                       const int32_t *__restrict__ lapI, const int32_t *__restrict__ tE_of, int NQ,
+                                       int NQV, int64_t nreal, double *__restrict__ lapT)
 {
+    const int Np = NQ * NQ * NQV, Nfph = NQ * NQV, NL = 4 * Nfph, NFT = NL + 2 * NQ * NQ, NE = 8 * NQV;
     const int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (I >= nreal * NL) return;
     const int64_t e = I / NL;
     const int t = (int)(I % NL);
     const int64_t idP = faceP[NFT * e + t], N = idP / Np;
-    const int vidP = (int)(idP - N * Np), tP = lapI[(2 * e + 0) * NL + t];
+    const int vidP = (int)(idP - N * Np), tP = lapI[(2 * e + 0) * NL + t], tE = tE_of[I];
     const double *vg = vgeo + (int64_t)Np * nvgeo * N + vidP;
     const int rows[6] = {XI1X1, XI1X2, XI1X3, XI2X1, XI2X2, XI2X3};
-    double *dst = lapT + 10 * e * NL + t;
+    double *dst = lapT + (int64_t)(10 * NL + 4 * NE) * e + t;
 #pragma unroll
     for (int c = 0; c < 6; ++c) dst[(int64_t)c * NL] = vg[(int64_t)rows[c] * Np];
 #pragma unroll
     for (int c = 0; c < 3; ++c) dst[(int64_t)(6 + c) * NL] = faceG[((int64_t)4 * N + c) * NFT + tP];
     dst[(int64_t)9 * NL] = faceW[NFT * N + tP];
+    if (tE < 0) return;
+    const bool last = lapfused_index_in_face(NQ, tP / Nfph, vidP) == NQ - 1;
+    double *edge = lapT + (int64_t)(10 * NL + 4 * NE) * e + 10 * NL + lapfused_edge_slot(NQV, t / Nfph, (t % Nfph) / NQ, last);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) edge[c * NE] = faceG[((int64_t)4 * N + c) * NFT + tE];
+    edge[3 * NE] = faceW[NFT * N + tE];
 }
 
 // CMDG_OPT_FUSED_LAPLACIAN: is this a handle whose hand-off evaluations can take k_lapfused?  What
@@ -249,18 +257,21 @@ int EngineBase::init_lapfused()
     LapFusedTables tab;
     lapfused_build(NQ, NQV, nreal, h_faceP.data(), h_bndy.data(), tab);
     if (!tab.eligible) return CMDG_OK;
-    // lapI[e][c][t]
+    // lapI[e][c][t]: tP and idE; tE goes to the kernel that fills lapT and no further
     std::vector<int32_t> h_lapI((size_t)(2 * NL * nreal));
     for (int64_t e = 0; e < nreal; ++e)
         for (int t = 0; t < NL; ++t) {
             h_lapI[(size_t)((2 * e + 0) * NL + t)] = tab.tP[(size_t)(NL * e + t)];
-            h_lapI[(size_t)((2 * e + 1) * NL + t)] = tab.tE[(size_t)(NL * e + t)];
+            h_lapI[(size_t)((2 * e + 1) * NL + t)] = tab.idE[(size_t)(NL * e + t)];
         }
+    DevBuf<int32_t> d_tE;
     HIPCHK(d_lapI.alloc(h_lapI.size()));
-    HIPCHK(d_lapT.alloc((size_t)(10 * NL * nreal)));
+    HIPCHK(d_tE.alloc(tab.tE.size()));
+    HIPCHK(d_lapT.alloc((size_t)((10 * NL + 4 * 8 * NQV) * nreal)));
     HIPCHK(hipMemcpy(d_lapI, h_lapI.data(), sizeof(int32_t) * h_lapI.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_tE, tab.tE.data(), sizeof(int32_t) * tab.tE.size(), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_lapfused_fill, dim3((unsigned)((nreal * NL + 255) / 256)), dim3(256), 0, s_comp, g.vgeo,
-                       g.nvgeo, d_faceP.get(), d_faceG.get(), d_faceW.get(), d_lapI.get(), Np, NFT, NL, nreal,
+                       g.nvgeo, d_faceP.get(), d_faceG.get(), d_faceW.get(), d_lapI.get(), d_tE.get(), NQ, NQV, nreal,
                        d_lapT.get());
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s_comp) != hipSuccess)
         return fail(CMDG_ERR_HIP, "cmdg_create: the tables of the fused Laplacian pass failed");

@@ -41,16 +41,9 @@
 #ifndef CMDG_LAP_MINW
 #define CMDG_LAP_MINW 1
 #endif
-// k_lapfused: its face lanes hold two lines of the neighbour's records in flight (200 VGPRs
-// unconstrained at N = 4, two work-groups per CU); four waves per SIMD keep five resident
+// k_lapfused: 4 waves per SIMD keep five work-groups of N = 4 resident (<= 128 VGPRs)
 #ifndef CMDG_LAPFUSED_MINW
 #define CMDG_LAPFUSED_MINW 4
-#endif
-// ... and its gathers are issued in stages: the index the next stage's addresses are formed from
-// passes through an empty asm statement together with a result of the stage before, so that the
-// compiler cannot issue those loads before that result exists
-#ifndef CMDG_LAPFUSED_STAGE
-#define CMDG_LAPFUSED_STAGE(idx, dep) asm volatile("" : "+v"(idx) : "v"(dep))
 #endif
 
 namespace cmdg {
@@ -1150,21 +1143,32 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT)) k_divgrad(const PassArgs
 //                              xi2 lines through y, with N's metric rows at y (lapT);
 //   + the lift of N's face that is shared with this element: N's normal and weight there (lapT),
 //     plus side = this element's own record, held in LDS;
-//   + where y is on a vertical edge of N, the lift of N's other lateral face at y (lapI's tE; N's
-//     own faceG / faceW / faceP), whose plus side is one record of N's neighbour --
+//   + where y is on a vertical edge of N, the lift of N's other lateral face at y (its normal
+//     and weight: the edge block), whose plus side is one record of N's neighbour (lapI's idE) --
 // added in N's own order: volume, then the face of the pair xi1 (N's faces 0 / 1), then xi2.  Every
 // term is the text k_gradients evaluates for N (line_derivative, metric_gradient,
 // central_gradient_flux, gradient_lift), so the sum is the value N would have stored.
+// Of N's two lines through y one is normal to the shared face and one lies in it.  The records of the
+// in-face line are the plus nodes of the row of sibling tasks (same face, same level: create checks
+// this of every row, lapfused_tables.h), so a face lane gathers the normal line alone -- NQ records,
+// y among them -- and the lanes of a row hand each other their y through LDS (sX), each slot under
+// the index of its y along N's face; line_derivative then sums the same values in the same order.
 // The create-time tables, per lateral face task t = 0 .. NL-1 (NL = 4 Nfph), about the neighbour N
 // on the plus side, whose node y = vidP the task faces:
-//   lapI[e][c][t]  int32: c = 0 tP, N's face task of the same mesh node; c = 1 tE, N's other
-//                  lateral face task at y, or -1
+//   lapI[e][c][t]  int32: c = 0 tP, N's face task of the same mesh node; c = 1 idE, the global node
+//                  faced by N's other lateral face task at y (tE), or -1
 //   lapT[e][c][t]  c = 0..5 N's horizontal metric rows at y (xi1x1, xi1x2, xi1x3, xi2x1, xi2x2,
 //                  xi2x3), c = 6..9 N's n1, n2, n3 and lift weight at tP
-// 88 B per lateral face node: a digest of grid geometry like faceG, not of caller state.  This
+//   edge[e][c][r]  behind lapT[e]: N's n1, n2, n3 and lift weight at tE, r = 2 (row of t) + (y is the
+//                  last node of N's row, not the first): the 2 of the NQ tasks of a row that have a tE
+// 88 B per lateral face node and 32 B per edge slot (8 NQV of them): a digest of grid geometry like faceG, not of caller state.  This
 // launch is handed lapI as GridDev::facePr and lapT as PassArgs::derived, neither of which a
 // Laplacian pass reads (as k_gradlap<..., RING> is handed facePr as faceP): the argument block of
 // every other pass kernel, and with it their code, stays what it was.
+// A face lane reads in three dependent trips: elems; its own tables (faceP, faceG, faceW, lapI);
+// N's records.  What only the neighbour's gradient gP needs (lapT, edge, the record at idE) is
+// asked for behind the barrier that ends the own-gradient phase and gP formed while the volume
+// lanes contract the Laplacian: gP is first used by the Laplacian's own face phase.
 // Lanes: the volume nodes are threads 0 .. Np-1, the 4 Nfph lateral face tasks the LAST threads of
 // the group, so that the gathers of the face lanes and the contractions of the volume lanes fall
 // into different waves where the group has more than one.
@@ -1173,49 +1177,73 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT), CMDG_LAPFUSED_MINW) k_la
 {
     using KD = KDims<NQ, NQV>;
     constexpr int Np = KD::Np, NGL = P::NGL, NHG = 3 * NGL, NHYP = P::NHYP, NG = NGL > 0 ? NGL : 1,
-                  NFT = KD::NFT, NL = 4 * KD::Nfph, NT = KD::NT;
+                  NL = 4 * KD::Nfph, NT = KD::NT, NE = 8 * NQV, LT = 10 * NL + 4 * NE;
     static_assert(NT >= NL && NGL > 0, "one lane per lateral face task");
     __shared__ double sD[NQ * NQ];
     __shared__ double sG[NG * Np];      // gradient arguments [s][ijk]
     __shared__ double sA[3 * NG * Np];  // grad G [3 s + d][ijk]
     __shared__ double sC[2 * NG * Np];  // M * (xi_d . grad) [d][s][ijk], d = 0, 1
     __shared__ double sL[NG * Np];      // Laplacians [s][ijk]
+    __shared__ double sX[NG * NL];      // the exchange: N's argument at y [s][row of the task][index of y in N's row]
+    static_assert(sizeof(double) * (NQ * NQ + 7 * NG * Np + NG * NL) <= 32768,
+                  "LDS of k_lapfused: five work-groups per CU");
     const int tid = threadIdx.x;
     const int64_t e = a.elems[xcd_remap(blockIdx.x, gridDim.x)] - 1;
     const int ft = tid - (NT - NL);  // lateral face task of this lane (< 0: none)
     if (tid < NQ * NQ) sD[tid] = a.g.D[tid];
+    // Everything a lane can ask for knowing the element alone, in one trip: the volume lanes their
+    // record and metric terms, the face lanes their own tables.
+    Vec<NGL> r;
+    double M = 0, MI = 0, x11 = 0, x12 = 0, x13 = 0, x21 = 0, x22 = 0, x23 = 0;
+#pragma unroll
+    for (int s = 0; s < NGL; ++s) r[s] = 0;
     if (tid < Np) {
         const double *rec = a.garg + garg_at<NGL, Np>(tid, e);
-        Vec<NGL> r;
 #pragma unroll
         for (int s = 0; s < NGL; ++s) r[s] = rec[s];
-#pragma unroll
-        for (int s = 0; s < NGL; ++s) sG[s * Np + tid] = r[s];
-    }
-    // the face lane's own geometry, and of the neighbour its xi1 line of records through y: in flight
-    // across the barrier.  (The rest of what the lane reads follows in stages below, each issued
-    // when the one before is consumed: all of it at once is 200 VGPRs and two work-groups per CU.)
-    FacePt fp;
-    int tP = 0, tE = -1, iP = 0, jP = 0, kP = 0;
-    int32_t idE = 0;
-    const double *gN = a.garg;  // the neighbour's records
-    if (ft >= 0) {
-        int f, n;
-        KD::face_task(ft, f, n);
-        face_setup<NQ, NQV, true>(a.g, e, ft, f, n, fp);
-        tP = a.g.facePr[((int64_t)2 * e + 0) * NL + ft];
-        tE = a.g.facePr[((int64_t)2 * e + 1) * NL + ft];
-        gN = a.garg + garg_at<NGL, Np>(0, fp.eP);
-        iP = fp.vidP % NQ, jP = (fp.vidP / NQ) % NQ, kP = fp.vidP / (NQ * NQ);
-        if (tE >= 0) idE = a.g.faceP[(int64_t)NFT * fp.eP + tE];
-    }
-    double M = 0, MI = 0, x11 = 0, x12 = 0, x13 = 0, x21 = 0, x22 = 0, x23 = 0;
-    if (tid < Np) {
         const double *vg = a.g.vgeo + (int64_t)Np * a.g.nvgeo * e + tid;
         M = vg[VM * Np];
         MI = vg[VMI * Np];
         x11 = vg[XI1X1 * Np], x12 = vg[XI1X2 * Np], x13 = vg[XI1X3 * Np];
         x21 = vg[XI2X1 * Np], x22 = vg[XI2X2 * Np], x23 = vg[XI2X3 * Np];
+    }
+    FacePt fp = {};
+    int32_t idE = -1;
+    int tP = 0;
+    if (ft >= 0) {
+        int f, n;
+        KD::face_task(ft, f, n);
+        face_setup<NQ, NQV, true>(a.g, e, ft, f, n, fp);
+        tP = a.g.facePr[((int64_t)2 * e + 0) * NL + ft];
+        idE = a.g.facePr[((int64_t)2 * e + 1) * NL + ft];
+    }
+    // (A use of all of it on every path: these values are loaded and used under the same conditions
+    // in separate blocks, and what the compiler knows of a load's completion is lost where paths
+    // join.  Without this, every later use waits for all the loads the lane has issued since -- the
+    // volume lanes of the middle wave for the gathers of its face lanes.)
+    asm volatile("" ::"v"(M), "v"(MI), "v"(x11), "v"(x12), "v"(x13), "v"(x21), "v"(x22), "v"(x23), "v"(r[0]),
+                 "v"(r[NGL - 1]), "v"(fp.vidP), "v"(fp.w), "v"(fp.n[0]), "v"(fp.n[1]), "v"(fp.n[2]), "v"(tP), "v"(idE));
+    if (tid < Np) {
+#pragma unroll
+        for (int s = 0; s < NGL; ++s) sG[s * Np + tid] = r[s];
+    }
+    // of the neighbour its normal line of records through y: in flight across the barrier
+    int idx = 0, xrow = 0;  // index of y along N's face; first exchange slot of the lane's row
+    bool x1 = true, far = false;  // N's normal line at y is its xi1 line; y is the last node of it
+    double rn[NQ][NG] = {};
+    if (ft >= 0) {
+        int fS, nn;
+        KD::face_task(tP, fS, nn);
+        x1 = fS < 2, far = fS & 1;
+        const int iP = fp.vidP % NQ, jP = (fp.vidP / NQ) % NQ, kP = fp.vidP / (NQ * NQ);
+        idx = x1 ? jP : iP;
+        xrow = ft - ft % NQ;
+        const double *line = a.garg + garg_at<NGL, Np>(x1 ? NQ * (jP + NQ * kP) : iP + NQ * NQ * kP, fp.eP);
+        const int step = x1 ? NGL : NGL * NQ;
+#pragma unroll
+        for (int m = 0; m < NQ; ++m)
+#pragma unroll
+            for (int s = 0; s < NGL; ++s) rn[m][s] = line[m * step + s];
     }
     __syncthreads();
     // ---- own volume gradient (k_gradients, horizontal)
@@ -1231,78 +1259,23 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT), CMDG_LAPFUSED_MINW) k_la
 #pragma unroll
         for (int q = 0; q < NHG; ++q) sA[q * Np + tid] = gh[q];
     }
-    // ---- face lanes: the lift of the own gradient, and the neighbour's gradient at the plus node
-    Vec<NHG> corr, gP;
+    // ---- face lanes: the lift of the own gradient; N's argument at y into the exchange; N's
+    // derivative along its normal line at y
+    Vec<NHG> corr;
+    Vec<NGL> Gn;
     int fpair = -1;
     if (ft >= 0) {
         fpair = ft / (2 * KD::Nfph);
-        const double *lapT = a.derived + (int64_t)10 * NL * e + ft;
-        // the neighbour's volume gradient at y, in its own frame: xi1 line, then xi2 line
-        Vec<NGL> GY, G1, G2;  // (GY: the neighbour's argument at y)
-        double r1[NQ][NG];
+        Vec<NGL> GY, GM;  // N's argument at y (an end of the normal line), this element's at the face node
 #pragma unroll
-        for (int s = 0; s < NGL; ++s) GY[s] = gN[NGL * fp.vidP + s];
+        for (int s = 0; s < NGL; ++s) GY[s] = far ? rn[NQ - 1][s] : rn[0][s];
 #pragma unroll
-        for (int n = 0; n < NQ; ++n)
-#pragma unroll
-            for (int s = 0; s < NGL; ++s) r1[n][s] = gN[NGL * (n + NQ * (jP + NQ * kP)) + s];
-#pragma unroll
-        for (int s = 0; s < NGL; ++s) G1[s] = line_derivative<NQ>(sD, iP, [&](int n) { return r1[n][s]; });
-#pragma unroll
-        for (int s = 0; s < NGL; ++s) CMDG_LAPFUSED_STAGE(kP, G1[s]);
-        double r2[NQ][NG];
-#pragma unroll
-        for (int n = 0; n < NQ; ++n)
-#pragma unroll
-            for (int s = 0; s < NGL; ++s) r2[n][s] = gN[NGL * (iP + NQ * (n + NQ * kP)) + s];
-        double T[6];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) T[c] = lapT[c * NL];
-#pragma unroll
-        for (int s = 0; s < NGL; ++s) G2[s] = line_derivative<NQ>(sD, jP, [&](int n) { return r2[n][s]; });
-        gP.negzero();
-#pragma unroll
-        for (int s = 0; s < NGL; ++s) metric_gradient(T[0], T[1], T[2], T[3], T[4], T[5], G1[s], G2[s], &gP[3 * s]);
-#pragma unroll
-        for (int q = 0; q < NHG; ++q) CMDG_LAPFUSED_STAGE(idE, gP[q]);
-        // the neighbour's lateral faces at y: the one shared with this element, and its other one
-        double nS[3], wS, nE[3] = {0, 0, 0}, wE = 0;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) nS[d] = lapT[(6 + d) * NL];
-        wS = lapT[9 * NL];
-        Vec<NGL> GE;
-        int pairE = 2;
-        if (tE >= 0) {
-            const double *sg = a.g.faceG + (int64_t)4 * NFT * fp.eP + tE;
-            nE[0] = sg[0], nE[1] = sg[NFT], nE[2] = sg[2 * NFT];
-            wE = a.g.faceW[(int64_t)NFT * fp.eP + tE];
-            const double *rec = a.garg + (int64_t)NGL * idE;
-#pragma unroll
-            for (int s = 0; s < NGL; ++s) GE[s] = rec[s];
-            int fE, nn;
-            KD::face_task(tE, fE, nn);
-            pairE = fE / 2;
-        }
-        int fS, nn;
-        KD::face_task(tP, fS, nn);
-        const bool edge_first = pairE < fS / 2;
-        Vec<NGL> GM;  // this element's argument at the face node
+        for (int s = 0; s < NGL; ++s) sX[s * NL + xrow + idx] = GY[s];
 #pragma unroll
         for (int s = 0; s < NGL; ++s) GM[s] = sG[s * Np + fp.vidM];
-        // the neighbour's lifts at y: minus side its own argument, plus side ours / its neighbour's
 #pragma unroll
         for (int s = 0; s < NGL; ++s)
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const double lS = gradient_lift(wS, central_gradient_flux(nS[d], GM[s], GY[s]), nS[d] * GY[s]);
-                if (tE >= 0) {
-                    const double lE = gradient_lift(wE, central_gradient_flux(nE[d], GE[s], GY[s]), nE[d] * GY[s]);
-                    gP[3 * s + d] += edge_first ? lE : lS;
-                    gP[3 * s + d] += edge_first ? lS : lE;
-                } else {
-                    gP[3 * s + d] += lS;
-                }
-            }
+            Gn[s] = line_derivative<NQ>(sD, far ? NQ - 1 : 0, [&](int m) { return rn[m][s]; });
         // own lift (k_gradients' interface phase, interior face)
 #pragma unroll
         for (int s = 0; s < NGL; ++s)
@@ -1312,6 +1285,9 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT), CMDG_LAPFUSED_MINW) k_la
                     gradient_lift(fp.w, central_gradient_flux(fp.n[d], GY[s], GM[s]), fp.n[d] * GM[s]);
     }
     __syncthreads();
+    // (as above, of the gathered line: the registers it arrived in are used again by the volume lanes)
+#pragma unroll
+    for (int m = 0; m < NQ; ++m) asm volatile("" ::"v"(rn[m][0]), "v"(rn[m][NGL - 1]));
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         if (fpair == p) {
@@ -1319,6 +1295,23 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT), CMDG_LAPFUSED_MINW) k_la
             for (int q = 0; q < NHG; ++q) sA[q * Np + fp.vidM] += corr[q];
         }
         __syncthreads();
+    }
+    // what the neighbour's gradient needs besides the two lines: in flight while the
+    // volume lanes form the contravariant products
+    double T[10], nE[3] = {0, 0, 0}, wE = 0;
+    Vec<NGL> GE;
+    if (ft >= 0) {
+        const double *lapT = a.derived + (int64_t)LT * e;
+#pragma unroll
+        for (int c = 0; c < 10; ++c) T[c] = lapT[c * NL + ft];
+        if (idE >= 0) {
+            const double *edge = lapT + 10 * NL + 2 * (ft / NQ) + (idx == NQ - 1 ? 1 : 0);
+            nE[0] = edge[0], nE[1] = edge[NE], nE[2] = edge[2 * NE];
+            wE = edge[3 * NE];
+            const double *rec = a.garg + (int64_t)NGL * idE;
+#pragma unroll
+            for (int s = 0; s < NGL; ++s) GE[s] = rec[s];
+        }
     }
     // ---- Laplacian (k_divgrad, horizontal): the own gradient is complete in sA
     if (tid < Np) {
@@ -1339,6 +1332,36 @@ __global__ void __launch_bounds__((KDims<NQ, NQV>::NT), CMDG_LAPFUSED_MINW) k_la
     }
     Vec<NGL> corrL;
     if (ft >= 0) {
+        // the neighbour's gradient at y, as it forms it: volume (xi1 line, then xi2 line), then the
+        // lifts of its lateral faces at y in its own order, the face of the pair xi1 first -- the one
+        // shared with this element, and at a vertical edge of N its other one
+        Vec<NGL> GY, GM, Gf;
+#pragma unroll
+        for (int s = 0; s < NGL; ++s) GY[s] = sX[s * NL + xrow + idx];
+#pragma unroll
+        for (int s = 0; s < NGL; ++s) GM[s] = sG[s * Np + fp.vidM];
+#pragma unroll
+        for (int s = 0; s < NGL; ++s)
+            Gf[s] = line_derivative<NQ>(sD, idx, [&](int m) { return sX[s * NL + xrow + m]; });
+        Vec<NHG> gP;
+        gP.negzero();
+#pragma unroll
+        for (int s = 0; s < NGL; ++s)
+            metric_gradient(T[0], T[1], T[2], T[3], T[4], T[5], x1 ? Gn[s] : Gf[s], x1 ? Gf[s] : Gn[s], &gP[3 * s]);
+        const bool edge_first = !x1;  // (the other face is of the other pair)
+#pragma unroll
+        for (int s = 0; s < NGL; ++s)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                const double lS = gradient_lift(T[9], central_gradient_flux(T[6 + d], GM[s], GY[s]), T[6 + d] * GY[s]);
+                if (idE >= 0) {
+                    const double lE = gradient_lift(wE, central_gradient_flux(nE[d], GE[s], GY[s]), nE[d] * GY[s]);
+                    gP[3 * s + d] += edge_first ? lE : lS;
+                    gP[3 * s + d] += edge_first ? lS : lE;
+                } else {
+                    gP[3 * s + d] += lS;
+                }
+            }
         Vec<NHG> gM;
 #pragma unroll
         for (int q = 0; q < NHG; ++q) gM[q] = sA[q * Np + fp.vidM];

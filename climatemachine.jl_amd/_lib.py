@@ -168,6 +168,8 @@ SYMBOLS = [
     ("cmdg_status_string", C.c_char_p, [C.c_int]),
     ("cmdg_physics_counts", C.c_int, [_i32, _vp, _vp]),
     ("cmdg_atmos_host_constants", C.c_int, [_vp, _vp, _vp]),
+    ("cmdg_probe_quot", C.c_int, [_vp, _vp, _vp, _vp, _i64]),
+    ("cmdg_probe_dry_atmos_pointwise", C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64]),
     ("cmdg_create", C.c_int, [C.POINTER(CmdgDesc), C.POINTER(_vp)]),
     ("cmdg_create_dgfv", C.c_int, [C.POINTER(CmdgDesc), C.POINTER(CmdgFvDesc), C.POINTER(_vp)]),
     ("cmdg_create_esdg", C.c_int, [C.POINTER(CmdgDesc), C.POINTER(CmdgEsdgDesc), C.POINTER(_vp)]),

@@ -73,7 +73,8 @@ static EngineBase *pick(const cmdg_desc *d, std::string &err)
               "(subtract_off = false), without hyperdiffusion";
         return nullptr;
     }
-    if (orient && ref && hyp) return make_engine<DryAtmos<true, true, true>, NQ>(d);
+    // Held-Suarez: shared reciprocals (XQ) at N = 4, where every kernel keeps its register class
+    if (orient && ref && hyp) return make_engine<DryAtmos<true, true, true, false, false, 0, NQ == 5>, NQ>(d);
     if (orient && ref && !hyp) return make_engine<DryAtmos<true, true, false>, NQ>(d);
     if (orient && !ref && !hyp) return make_engine<DryAtmos<true, false, false>, NQ>(d);
     err = "DryAtmos: this orientation/ref-state/hyperdiffusion combination is not compiled in";

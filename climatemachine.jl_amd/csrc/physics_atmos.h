@@ -25,7 +25,10 @@
 // gradient chi[NT] last, gradient flux grad chi (3 x NT, tracer k owns entries 3 k .. 3 k + 2) last,
 // auxiliary delta_chi[NT] after moisture.theta_v / air_T.
 #pragma once
+#include <type_traits>
+
 #include "cmdg_common.h"
+#include "exact_quotient.h"
 #include "law_defaults.h"
 
 namespace cmdg {
@@ -43,6 +46,13 @@ struct AtmosParams {
     double kappa;           // R_d / cp_d (the Exner exponent)
     double gamma, gamma_R;  // cp_d / cv_d; gamma * R_d (soundspeed)
     double R_ratio;         // R_m / R_d of a dry phase: R_d / R_d (virtual_pottemp)
+};
+// The block of a law with shared reciprocals (DryAtmos<..., XQ = true>): the uniform divisors of per-lane
+// values, each with its reciprocal (one IEEE division on the host) -- quot(x, m.r_grav) has the bits of
+// x / m.grav in four instructions (exact_quotient.h).  A type of its own, so that every other kernel keeps
+// its arguments.
+struct AtmosXqParams : AtmosParams {
+    QuotPair r_grav, r_cv_d, r_MSLP, r_tau;
 };
 static constexpr int ATMOS_NHOSTCONST = 7;
 static constexpr int ATMOS_MAX_TRACERS = 8;
@@ -62,7 +72,12 @@ struct AtmosParamsOf<0> {
     using type = AtmosParams;
 };
 
-template <bool ORIENT, bool REF, bool HYPER, bool SMAG = false, bool LAWNF = false, int NT = 0>
+// XQ: quotients by a uniform divisor and by a density used more than once share a reciprocal
+// (exact_quotient.h: the bits of `/` in four instructions).  The shorter instruction stream lets the
+// scheduler keep more values in flight, and in many instantiations that costs the tendency pass its
+// register class (profiles/ab_exact_quotient.txt), so the engine turns it on where it was measured to
+// pay and to fit -- the Held-Suarez law at N = 4 -- and every other instantiation keeps the division.
+template <bool ORIENT, bool REF, bool HYPER, bool SMAG = false, bool LAWNF = false, int NT = 0, bool XQ = false>
 struct DryAtmos : LawDefaults {
     // RoeNumericalFlux / HLLCNumericalFlux live in a variant of their own so that the
     // kernels of every other configuration keep their register budget
@@ -71,8 +86,43 @@ struct DryAtmos : LawDefaults {
     static_assert(!SMAG || ORIENT, "SmagorinskyLilly needs an orientation (buoyancy correction)");
     static_assert(NT >= 0 && NT <= ATMOS_MAX_TRACERS, "iparam[15] bits 8..15 hold at most ATMOS_MAX_TRACERS tracers");
     static_assert(!(LAWNF && NT > 0), "Roe / HLLC / LMARS have no tracer methods in the reference");
-    using Params = typename AtmosParamsOf<NT>::type;
+    static_assert(!XQ || NT == 0, "shared reciprocals are laid out for the tracer-free block");
+    using Params = std::conditional_t<XQ, AtmosXqParams, typename AtmosParamsOf<NT>::type>;
     static constexpr int NS = 5 + NT;
+    static constexpr bool SHARED_RECIPROCALS = XQ;
+    // x / m.grav, x / m.cv_d, x / m.MSLP, x / m.tau and x / rho: the division, or with XQ its bits from
+    // the shared reciprocal
+    __host__ __device__ static double by_grav(const Params &m, double a)
+    {
+        if constexpr (XQ) return quot(a, m.r_grav);
+        else return a / m.grav;
+    }
+    __host__ __device__ static double by_cv_d(const Params &m, double a)
+    {
+        if constexpr (XQ) return quot(a, m.r_cv_d);
+        else return a / m.cv_d;
+    }
+    __host__ __device__ static double by_MSLP(const Params &m, double a)
+    {
+        if constexpr (XQ) return quot(a, m.r_MSLP);
+        else return a / m.MSLP;
+    }
+    __host__ __device__ static double by_tau(const Params &m, double a)
+    {
+        if constexpr (XQ) return quot(a, m.r_tau);
+        else return a / m.tau;
+    }
+    // a density that divides more than once in a function: one pair with XQ, else the divisor alone
+    __host__ __device__ static QuotPair rho_pair(double rho)
+    {
+        if constexpr (XQ) return quot_pair(rho);
+        else return QuotPair{rho, 0.0};
+    }
+    __host__ __device__ static double by_rho(double a, const QuotPair &d)
+    {
+        if constexpr (XQ) return quot(a, d);
+        else return a / d.b;
+    }
     static constexpr int OPHI = 3;
     static constexpr int OREF = OPHI + (ORIENT ? 4 : 0);
     static constexpr int OTURB = OREF + (REF ? 7 : 0);   // turbulence.Delta (SmagorinskyLilly)
@@ -183,6 +233,12 @@ struct DryAtmos : LawDefaults {
         p.gamma = cp_d / cv_d;
         p.gamma_R = p.gamma * R_d;
         p.R_ratio = R_d / R_d;
+        if constexpr (XQ) {
+            p.r_grav = quot_pair(p.grav);
+            p.r_cv_d = quot_pair(cv_d);
+            p.r_MSLP = quot_pair(p.MSLP);
+            p.r_tau = quot_pair(p.tau);
+        }
     }
     static void host_constants(const Params &p, double *out)
     {
@@ -191,7 +247,7 @@ struct DryAtmos : LawDefaults {
     }
 
     // ---- dry thermodynamics ----------------------------------------------------------
-    __device__ static double internal_energy(const Params &, const double *Q, const double *aux)
+    __host__ __device__ static double internal_energy(const Params &, const double *Q, const double *aux)
     {
         const double rho = Q[0];
         const double rhoinv = 1 / rho;
@@ -201,9 +257,15 @@ struct DryAtmos : LawDefaults {
         const double rhoe_int = Q[4] - rhoe_kin - rhoe_pot;
         return rhoinv * rhoe_int;
     }
-    __device__ static double air_T(const Params &m, double e_int) { return m.T_0 + e_int / m.cv_d; }
-    __device__ static double air_p(const Params &m, double T, double rho) { return m.R_d * rho * T; }
-    __device__ static double soundspeed(const Params &m, double T)
+    __host__ __device__ static double air_T(const Params &m, double e_int)
+    {
+        return m.T_0 + by_cv_d(m, e_int);
+    }
+    __host__ __device__ static double air_p(const Params &m, double T, double rho)
+    {
+        return m.R_d * rho * T;
+    }
+    __host__ __device__ static double soundspeed(const Params &m, double T)
     {
         return sqrt(m.gamma_R * T);  // gamma = cp_d / cv_d; sqrt(gamma * R_d * T)
     }
@@ -219,8 +281,9 @@ struct DryAtmos : LawDefaults {
         const double rho = Q[0];
         const double T = air_T(m, internal_energy(m, Q, aux));
         prim[0] = rho;
+        const QuotPair rp = rho_pair(rho);
 #pragma unroll
-        for (int d = 0; d < 3; ++d) prim[1 + d] = Q[1 + d] / rho;
+        for (int d = 0; d < 3; ++d) prim[1 + d] = by_rho(Q[1 + d], rp);
         prim[4] = air_p(m, T, rho);
     }
     // PhaseDry_rho_p: T = p / (R_d rho); total_energy = e_int + e_kin + e_pot
@@ -272,7 +335,7 @@ struct DryAtmos : LawDefaults {
         const double e_int = internal_energy(m, Q, aux);
         const double T = air_T(m, e_int);
         const double p = air_p(m, T, rho);
-        const double exner = pow(p / m.MSLP, m.kappa);
+        const double exner = pow(by_MSLP(m, p), m.kappa);
         const double RT = m.R_d * T;
         D[0] = T;
         D[1] = p;
@@ -302,7 +365,7 @@ struct DryAtmos : LawDefaults {
         double k[3] = {0, 0, 0};
         if constexpr (ORIENT) {
 #pragma unroll
-            for (int d = 0; d < 3; ++d) k[d] = aux[OPHI + 1 + d] / m.grav;
+            for (int d = 0; d < 3; ++d) k[d] = by_grav(m, aux[OPHI + 1 + d]);
         }
         if (kind == 2) {  // diffusive_courant
             double nu[3], tau[9];
@@ -324,14 +387,16 @@ struct DryAtmos : LawDefaults {
             return dt * normnu / (dx * dx);
         }
         const double dotk = Q[1] * k[0] + Q[2] * k[1] + Q[3] * k[2];
+        const QuotPair rp = rho_pair(Q[0]);
         double normu;
         if (direction == DIR_VERTICAL) {
-            normu = fabs(dotk) / Q[0];
+            normu = by_rho(fabs(dotk), rp);
         } else {
             double v[3];
 #pragma unroll
             for (int d = 0; d < 3; ++d)
-                v[d] = direction == DIR_HORIZONTAL ? (Q[1 + d] - dotk * k[d]) / Q[0] : Q[1 + d] / Q[0];
+                v[d] = direction == DIR_HORIZONTAL ? by_rho(Q[1 + d] - dotk * k[d], rp)
+                                                   : by_rho(Q[1 + d], rp);
             normu = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
         }
         if (kind == 0) return dt * normu / dx;
@@ -340,15 +405,17 @@ struct DryAtmos : LawDefaults {
     }
 
     // ---- fluxes ----------------------------------------------------------------------
-    __device__ static void flux_first_order(const Params &m, double *F, const double *Q,
+    __host__ __device__ static void flux_first_order(const Params &m, double *F, const double *Q,
                                             const double *aux, double, int)
     {
         const double rho = Q[0];
         const double T = air_T(m, internal_energy(m, Q, aux));
         const double p = air_p(m, T, rho);
+        // three quotients by rho: one pair (its reciprocal is the rhoinv of internal_energy)
+        const QuotPair rp = rho_pair(rho);
         double u[3];
 #pragma unroll
-        for (int d = 0; d < 3; ++d) u[d] = Q[1 + d] / rho;
+        for (int d = 0; d < 3; ++d) u[d] = by_rho(Q[1 + d], rp);
 #pragma unroll
         for (int d = 0; d < 3; ++d) F[d] = Q[1 + d];
         double pp = p;
@@ -393,7 +460,7 @@ struct DryAtmos : LawDefaults {
             const double normS = sqrt(2 * norm2);
             double k[3];
 #pragma unroll
-            for (int d = 0; d < 3; ++d) k[d] = aux[OPHI + 1 + d] / m.grav;
+            for (int d = 0; d < 3; ++d) k[d] = by_grav(m, aux[OPHI + 1 + d]);
             const double epsn = nextafter(fabs(normS), INFINITY) - fabs(normS);  // eps(normS)
             const double Ri = gf[9] / (normS * normS + epsn);
             double c = 1.0 - Ri * m.invPr;
@@ -469,13 +536,13 @@ struct DryAtmos : LawDefaults {
             der[1] = cos(phi);
         }
     }
-    __device__ static void hs_coeffs(const Params &m, const double *Q, const double *der,
+    __host__ __device__ static void hs_coeffs(const Params &m, const double *Q, const double *der,
                                      double T, double &k_v, double &k_T, double &T_equil)
     {
         const double k_a = m.k_a, k_f = m.k_f, k_s = m.k_s;  // 1 / (40 day), 1 / day, 1 / (4 day)
         const double dTy = 60, dthz = 10, T_eq = 315, T_min = 200, sig_b = 7.0 / 10;
         const double p = air_p(m, T, Q[0]);
-        const double sig = p / m.MSLP;
+        const double sig = by_MSLP(m, p);
         const double exner = pow(sig, m.kappa);
         const double dsig = (sig - sig_b) / (1 - sig_b);
         const double hf = dsig > 0 ? dsig : 0;
@@ -486,7 +553,7 @@ struct DryAtmos : LawDefaults {
         k_T = k_a + (k_s - k_a) * hf * ((c * c) * (c * c));
         k_v = k_f * hf;
     }
-    __device__ static void source(const Params &m, double *S, const double *Q, const double *,
+    __host__ __device__ static void source(const Params &m, double *S, const double *Q, const double *,
                                   const double *aux, const double *der, double t, int)
     {
         const double rho = Q[0];
@@ -518,7 +585,7 @@ struct DryAtmos : LawDefaults {
             if (m.src & 4) {  // HeldSuarezForcing
                 double k[3];
 #pragma unroll
-                for (int d = 0; d < 3; ++d) k[d] = aux[OPHI + 1 + d] / m.grav;
+                for (int d = 0; d < 3; ++d) k[d] = by_grav(m, aux[OPHI + 1 + d]);
                 const double kn = k[0] * Q[1] + k[1] * Q[2] + k[2] * Q[3];
 #pragma unroll
                 for (int d = 0; d < 3; ++d) {
@@ -631,7 +698,7 @@ struct DryAtmos : LawDefaults {
         const double udEP = u[0] * (dE[0] + dP[0]) + u[1] * (dE[1] + dP[1]) + u[2] * (dE[2] + dP[2]);
         S[4] = E_t + (E + P) * divu + udEP - work;
     }
-    __device__ static void gradient_argument(const Params &m, double *G, const double *Q,
+    __host__ __device__ static void gradient_argument(const Params &m, double *G, const double *Q,
                                              const double *aux, double)
     {
         const double rhoinv = 1 / Q[0];
@@ -652,7 +719,7 @@ struct DryAtmos : LawDefaults {
 #pragma unroll
             for (int d = 0; d < 3; ++d) u[d] = Q[1 + d] * rhoinv;
 #pragma unroll
-            for (int d = 0; d < 3; ++d) k[d] = aux[OPHI + 1 + d] / m.grav;
+            for (int d = 0; d < 3; ++d) k[d] = by_grav(m, aux[OPHI + 1 + d]);
 #pragma unroll
             for (int i = 0; i < 3; ++i) {  // (SDiagonal(1,1,1) - k k') * u
                 double acc = 0;
@@ -666,9 +733,9 @@ struct DryAtmos : LawDefaults {
             G[7] = G[3];
         }
     }
-    __device__ static double theta_v(const Params &m, double T, double rho)
+    __host__ __device__ static double theta_v(const Params &m, double T, double rho)
     {  // virtual_pottemp of a dry phase (moisture.jl:53-62)
-        const double exner = pow(air_p(m, T, rho) / m.MSLP, m.kappa);
+        const double exner = pow(by_MSLP(m, air_p(m, T, rho)), m.kappa);
         return m.R_ratio * (T / exner);
     }
     __device__ static void gradient_flux(const Params &m, double *gf, const double *g,
@@ -713,12 +780,12 @@ struct DryAtmos : LawDefaults {
     {
         if constexpr (HYPER) {
             const double h = aux[ODELTA] / 2;
-            const double nu4 = (h * h) * (h * h) / 2 / m.tau;
+            const double nu4 = by_tau(m, (h * h) * (h * h) / 2);
 #pragma unroll
             for (int q = 0; q < 12; ++q) hyp[q] = nu4 * gl[q];
         }
     }
-    __device__ static void wavespeed(const Params &m, double *ws, const double *n, const double *Q,
+    __host__ __device__ static void wavespeed(const Params &m, double *ws, const double *n, const double *Q,
                                      const double *aux, double, int)
     {
         const double rhoinv = 1 / Q[0];

@@ -157,6 +157,19 @@ int cmdg_physics_counts(int32_t physics_id, const int32_t *iparam, int32_t out[6
  * R_d / cp_d, cp_d / cv_d, (cp_d / cv_d) R_d, R_d / R_d */
 int cmdg_atmos_host_constants(const int32_t *iparam, const double *dparam, double out[7]);
 
+/* ---- probes, for the tests only (no handle, no grid) ------------------------------ */
+/* q_quot[i]: a[i] over b[i] by the shared-reciprocal quotient the balance laws use (csrc/exact_quotient.h,
+ * the pair made from b[i] on the device); q_div[i] = a[i] / b[i].  DEVICE pointers, n doubles each. */
+int cmdg_probe_quot(const double *a, const double *b, double *q_quot, double *q_div, int64_t n);
+/* CMDG_PHYSICS_DRY_ATMOS with orientation, reference state and DryBiharmonic (the Held-Suarez
+ * instantiation; anything else CMDG_ERR_UNSUPPORTED): its pointwise functions at npts points, row-major
+ * Q (npts, 5), aux (npts, 17), nrm (npts, 3), der (npts, 2: sin and cos of the latitude) ->
+ * out (npts, 33): flux_first_order[15], wavespeed[5], source[5], gradient_argument[8].
+ * where = 1: DEVICE pointers, one thread per point; where = 0: HOST pointers, the same text on the host. */
+int cmdg_probe_dry_atmos_pointwise(const int32_t *iparam, const double *dparam, int32_t where, const double *Q,
+                                   const double *aux, const double *nrm, const double *der, double *out,
+                                   int64_t npts);
+
 /* ---- lifetime ----------------------------------------------------------------- */
 /* replaces DGModel(...) construction, DGModel.jl:22-65.
  * Preconditions on the grid tables, checked on the device at create (CMDG_ERR_INVALID with the

@@ -581,6 +581,91 @@ def periodic_hyperdiffusion_dim2_setup(Ne=4, N=4, direction=0):
     return law, grid, dt, np.sqrt(Ly)
 
 
+# ---- the moist law away from the warm branch ----------------------------------------------------
+def moist_converged_law(closure=1, **kw):
+    """The moist LES law of the cloudy-bubble tests with a converged saturation adjustment
+    (maxiter 40, tolerance 1e-11 K); the state comes from the caller, not from the law."""
+    A, MO = cm.atmos, cm.moist
+    ps = MO.MoistParameters()
+    kw.setdefault("coefficient", {0: 75.0, 1: ps.C_smag, 2: 1.0}[closure])
+    return MO.MoistAtmosModel(None, A.DryAdiabaticProfile(ps, 300.0, 0.0), closure=closure, param_set=ps,
+                              maxiter=40, tolerance=1e-11, **kw)
+
+
+def periodic_brick_grid(L=1500.0, N=4):
+    """The grid of ``isentropic_vortex_moist_setup(1)`` (periodic BrickTopology, 5 x 5 x 1 elements,
+    face connectivity) stretched to ``[0, L]^3``, so that a law with an orientation has a potential
+    of thousands of J/kg across it."""
+    rng = [np.linspace(0.0, L, n + 1) for n in (5, 5, 1)]
+    topl = M.BrickTopology(rng, periodicity=(True,) * 3, connectivity="face")
+    return M.DiscontinuousSpectralElementGrid(topl, N)
+
+
+def tile_moist_phase_cases(grid, aux, cases, seed=0):
+    """One case of tests/golden/moist_phase_cases.npz per node, tiled over the grid: ``rho`` and
+    ``q_tot`` as stored, ``rho e = rho (e_int + Phi + |u|^2 / 2)`` with ``Phi`` from ``aux`` and random
+    winds of a few m/s.  Returns ``(Q, index of the case at every node)``."""
+    n = len(cases["rho"])
+    idx = (np.arange(grid.nelem * grid.Np) % n).reshape(grid.nelem, grid.Np)
+    rng = np.random.default_rng(seed)
+    u = 3.0 * rng.standard_normal((grid.nelem, 3, grid.Np))
+    rho = cases["rho"][idx]
+    Q = np.zeros((grid.nelem, 6, grid.Np))
+    Q[:, 0] = rho
+    Q[:, 1:4] = rho[:, None, :] * u
+    Q[:, 4] = rho * (cases["e_int"][idx] + aux[:, 3] + (u * u).sum(axis=1) / 2)
+    Q[:, 5] = rho * cases["q_tot"][idx]
+    return Q, idx
+
+
+def cold_cloudy_state(law, grid, aux, jet=0.0):
+    """A smooth state that crosses every phase regime of the equilibrium thermodynamics: the
+    equilibrium temperature falls from about 295 K at the bottom of the box to 221 K at its top with
+    a horizontal sine of 3 K, the supersaturation ``s = 0.15 sin(...)`` changes sign across the box
+    (``q_tot = q_vs(T*, rho) (1 + s)``: cloudy where ``s > 0``, with liquid, both phases or ice by
+    temperature; unsaturated where ``s < 0``), the density is smooth and the winds are of a few m/s.
+    ``jet`` (m/s) adds a zonal jet at mid-height, in the mixed-phase layer, strongest where ``s`` is
+    largest: a maximum over the nodes of ``|u| + c`` then sits on a mixed-phase node instead of on
+    the warmest one.  Not a reference configuration."""
+    ps = law.ps
+    unit = []
+    for d in range(3):
+        lo, hi = aux[:, d].min(), aux[:, d].max()
+        unit.append((aux[:, d] - lo) / (hi - lo))
+    xi, eta, zeta = unit
+    T = 295.0 - 74.0 * zeta + 3.0 * np.sin(2 * np.pi * xi) * np.cos(2 * np.pi * eta)
+    s = 0.15 * np.sin(2 * np.pi * (xi + eta) + 3 * np.pi * zeta)
+    rho = 1.1 - 0.5 * zeta + 0.03 * np.cos(2 * np.pi * xi)
+    lam = np.clip((T - ps.T_icenuc) / (ps.T_freeze - ps.T_icenuc), 0.0, 1.0)
+    LH_0 = lam * ps.LH_v0 + (1 - lam) * ps.LH_s0
+    dcp = lam * (ps.cp_v - ps.cp_l) + (1 - lam) * (ps.cp_v - ps.cp_i)
+    p_vs = ps.press_triple * (T / ps.T_triple) ** (dcp / ps.R_v) * np.exp(
+        (LH_0 - dcp * ps.T_0) / ps.R_v * (1 / ps.T_triple - 1 / T))
+    q_vs = p_vs / (rho * ps.R_v * T)
+    q_tot = q_vs * (1 + s)
+    q_c = np.maximum(q_tot - q_vs, 0.0)
+    e_int = ps.internal_energy(T, q_tot, lam * q_c, (1 - lam) * q_c)
+    u = [3.0 * np.sin(2 * np.pi * xi) * np.cos(2 * np.pi * eta) + jet * np.sin(np.pi * zeta) ** 2 * (1 + s),
+         2.0 * np.cos(2 * np.pi * xi),
+         1.5 * np.sin(2 * np.pi * (xi + eta)) * np.sin(np.pi * zeta)]
+    Q = np.zeros((grid.nelem, 6, grid.Np))
+    Q[:, 0] = rho
+    for d in range(3):
+        Q[:, 1 + d] = rho * u[d]
+    Q[:, 4] = rho * (e_int + aux[:, law.off_phi] + (u[0] ** 2 + u[1] ** 2 + u[2] ** 2) / 2)
+    Q[:, 5] = rho * q_tot
+    return Q
+
+
+def phase_census(aux):
+    """Node counts of the refreshed moisture block ``aux[:, 15:19]``: ice only, mixed (liquid and
+    ice both above 1e-6), warm cloudy, unsaturated."""
+    T, ql, qi = aux[:, 15], aux[:, 17], aux[:, 18]
+    return dict(ice=int(((ql == 0) & (qi > 0)).sum()), mixed=int(((ql > 1e-6) & (qi > 1e-6)).sum()),
+                warm=int(((ql > 0) & (qi == 0)).sum()), unsaturated=int(((ql == 0) & (qi == 0)).sum()),
+                T_min=float(T.min()), T_max=float(T.max()))
+
+
 OBSERVED = {}
 
 

@@ -4,7 +4,8 @@
   * test/Numerics/DGMethods/compressible_Navier_Stokes/density_current_model.jl:247 -- EquilMoist
     at q_tot = 0 with the AnisoMinDiss closure: norm(Q_10) / norm(Q_0) = 9.9999970927037096e-01;
   * the saturated branch (Thermodynamics.jl 0.3.2, not in the reference tree) is PARITY UNPINNED:
-    only its self-consistency is checked here.
+    only its self-consistency is checked here (its values in the ice, mixed and warm regimes are held
+    to a 40-digit statement of the physics in tests/test_moist_phases_host.py).
 CPU only (~1.5 min, the density current is the reference's full 10 000-element mesh)."""
 import ctypes as C
 

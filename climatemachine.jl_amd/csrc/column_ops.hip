@@ -468,12 +468,16 @@ int EngineBase::filter_create(const cmdg_filter_desc *d, FilterObj **out)
     return CMDG_OK;
 }
 
+static_assert(FILTER_FAM_SPECTRAL == CMDG_FILTER_SPECTRAL && FILTER_FAM_MASS_PRESERVING == CMDG_FILTER_MASS_PRESERVING &&
+                  FILTER_FAM_TMAR == CMDG_FILTER_TMAR,
+              "filter_lds.h numbers the kernel families as cmdg.h numbers the filter kinds");
+
 template <int NQ_>
 static void launch_filter(const FilterObj *f, const FilterArgs &a, int nfs, int64_t nreal,
                           hipStream_t st)
 {
     const dim3 grid((unsigned)nreal), block(FDims<NQ_>::NT);
-    const size_t lds = sizeof(double) * 2 * nfs * FDims<NQ_>::Np;
+    const size_t lds = sizeof(double) * filter_dynamic_doubles(f->kind, NQ_, nfs);
     auto spectral = [&](auto K) { hipLaunchKernelGGL(K, grid, block, lds, st, a); };
     if (f->kind == CMDG_FILTER_TMAR) {
         hipLaunchKernelGGL((k_apply_tmar_filter<NQ_>), grid, dim3(64), 0, st, a);
@@ -509,10 +513,11 @@ int EngineBase::filter_apply(const FilterObj *f, double *Q, int nstate)
     }
     const bool every = f->direction == DIR_EVERY;
     const bool h = every || f->direction == DIR_HORIZONTAL, v = every || f->direction == DIR_VERTICAL;
-    // FilterIndices states are independent: at most CHUNK of them share the LDS of a launch
-    // (two LDS buffers of nfs * Np doubles, below the 64 KB a work-group may claim by default)
-    const int CHUNK = std::max(1, std::min(16, (56 * 1024) / (16 * Np)));
+    // FilterIndices states are independent: at most CHUNK of them share the LDS of a launch, the most
+    // whose buffers, with the kernel family's static arrays, stay within 64 KiB (filter_lds.h)
+    const int CHUNK = filter_chunk(f->kind, NQ);
     const int ntot = f->target == CMDG_TARGET_INDICES ? f->nindices : ATMOS_NS;
+    if (CHUNK < (f->target == CMDG_TARGET_INDICES ? 1 : ATMOS_NS)) return fail(CMDG_ERR_UNSUPPORTED, no_order);
     for (int c0 = 0; c0 < ntot; c0 += CHUNK) {
         const int nfs = std::min(CHUNK, ntot - c0);
         a.nfs = nfs;

@@ -13,12 +13,12 @@
 // Sums run in the reference's order: accumulator from zero, n ascending, no contraction.
 #pragma once
 #include "cmdg_common.h"
+#include "filter_lds.h"
 
 namespace cmdg {
 
 enum { TGT_INDICES = 0, TGT_ATMOS_PERT = 1, TGT_ATMOS_SPECIFIC = 2 };
 constexpr int FILTER_MAXS = 32;
-constexpr int ATMOS_NS = 5;  // rho, rho u[3], rho e
 
 struct FilterArgs {
     double *Q;
@@ -37,6 +37,7 @@ struct FDims {
     static constexpr int Np = NQ * NQ * NQ;
     static constexpr int NT = ((Np + 63) / 64) * 64;
     static constexpr int pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
+    static_assert(Np == filter_np(NQ) && NT == filter_nt(NQ), "filter_lds.h charges these sizes");
 };
 
 // compute_filter_argument! / compute_filter_result! of the atmos targets
@@ -117,6 +118,8 @@ __global__ __launch_bounds__(FDims<NQ>::NT) void k_apply_filter(FilterArgs a)
     constexpr int Np = FDims<NQ>::Np, NT = FDims<NQ>::NT;
     extern __shared__ double lds[];
     __shared__ double sFh[NQ * NQ], sFv[NQ * NQ];
+    static_assert(sizeof(sFh) + sizeof(sFv) == 8 * filter_static_doubles(FILTER_FAM_SPECTRAL, NQ),
+                  "filter_lds.h charges the static arrays of k_apply_filter");
     const int tid = threadIdx.x;
     const int64_t e = xcd_remap(blockIdx.x, gridDim.x);
     const int nfs = TARGET == TGT_INDICES ? a.nfs : ATMOS_NS;
@@ -250,6 +253,8 @@ __global__ __launch_bounds__(FDims<NQ>::NT) void k_apply_mp_filter(FilterArgs a)
     constexpr int Np = FDims<NQ>::Np, NT = FDims<NQ>::NT;
     extern __shared__ double lds[];
     __shared__ double sF[NQ * NQ], sM[NT], sB[NT], sA[NT];
+    static_assert(sizeof(sF) + sizeof(sM) + sizeof(sB) + sizeof(sA) == 8 * filter_static_doubles(FILTER_FAM_MASS_PRESERVING, NQ),
+                  "filter_lds.h charges the static arrays of k_apply_mp_filter");
     const int tid = threadIdx.x;
     const int64_t e = xcd_remap(blockIdx.x, gridDim.x);
     const int nfs = TARGET == TGT_INDICES ? a.nfs : ATMOS_NS;
@@ -327,6 +332,8 @@ __global__ __launch_bounds__(64) void k_apply_tmar_filter(FilterArgs a)
     constexpr int Np = NQ * NQ * NQ, Nij = NQ * NQ;
     static_assert(Nij <= 64, "TMAR kernel: one wavefront per element");
     __shared__ double sMJQ[64], sMJQc[64];
+    static_assert(sizeof(sMJQ) + sizeof(sMJQc) == 8 * filter_static_doubles(FILTER_FAM_TMAR, NQ),
+                  "filter_lds.h charges the static arrays of k_apply_tmar_filter");
     const int tid = threadIdx.x;
     const int64_t e = xcd_remap(blockIdx.x, gridDim.x);
     double *Qe = a.Q + (int64_t)Np * a.nstate * e;

@@ -672,6 +672,12 @@ int EngineBase::rhs_segment(int seg, const RhsCtx &c)
         }
         return CMDG_OK;
     };
+    // a pass launch between a begin and its end: the bracket is closed whether the launch failed (the
+    // engine class has no kernel for what it was asked) or not, and the launch's failure comes first
+    auto closed = [&](int launched, auto &end) -> int {
+        const int ended = end();
+        return launched != CMDG_OK ? launched : ended;
+    };
     switch (seg) {
     case 0:
         if (has_hooks) {
@@ -682,8 +688,7 @@ int EngineBase::rhs_segment(int seg, const RhsCtx &c)
         if (comm) TRY(halo_begin(SLOT_Q, c.Qin, ns, 0, pipe));
         if (grad) {
             TRY(interior_begin());
-            launch_gradients(c, d_interior, ninterior, false, s_comp);
-            TRY(interior_end());
+            TRY(closed(launch_gradients(c, d_interior, ninterior, false, s_comp), interior_end));
         }
         break;
     case 1:
@@ -702,8 +707,7 @@ int EngineBase::rhs_segment(int seg, const RhsCtx &c)
         if (dsend && gfl) TRY(before_direct_send(SLOT_GF, s_ext));
         if (dsend && hyper) TRY(before_direct_send(SLOT_HG, s_ext));
         TRY(exterior_begin());
-        launch_gradients(c, d_exterior, nexterior, comm, s_ext);
-        TRY(exterior_end());
+        TRY(closed(launch_gradients(c, d_exterior, nexterior, comm, s_ext), exterior_end));
         if (dsend && gfl && !gradient_filter) mark_fresh(SLOT_GF, gf, ngf);
         if (dsend && hyper) mark_fresh(SLOT_HG, hypgrad, 3 * ngl);
         if (gradient_filter && gfl) {  // (:185-193)
@@ -734,8 +738,7 @@ int EngineBase::rhs_segment(int seg, const RhsCtx &c)
         if (has_hooks && gfl) TRY(run_gradient_hooks(c, 0, nreal));
         if (hyper) {
             TRY(interior_begin());
-            launch_divgrad(c, d_interior, ninterior, false, s_comp);
-            TRY(interior_end());
+            TRY(closed(launch_divgrad(c, d_interior, ninterior, false, s_comp), interior_end));
         }
         break;
     case 2:
@@ -743,27 +746,23 @@ int EngineBase::rhs_segment(int seg, const RhsCtx &c)
         if (comm) TRY(halo_end(SLOT_HG, hypgrad, 3 * ngl, unpack, pipe));
         if (dsend) TRY(before_direct_send(SLOT_HD, s_ext));
         TRY(exterior_begin());
-        launch_divgrad(c, d_exterior, nexterior, comm, s_ext);
-        TRY(exterior_end());
+        TRY(closed(launch_divgrad(c, d_exterior, nexterior, comm, s_ext), exterior_end));
         if (dsend) mark_fresh(SLOT_HD, hypdiv, nhd);
         if (comm) TRY(halo_begin(SLOT_HD, hypdiv, nhd, nhyp, pipe));
         TRY(interior_begin());
-        launch_gradlap(c, d_interior, ninterior, false, s_comp);
-        TRY(interior_end());
+        TRY(closed(launch_gradlap(c, d_interior, ninterior, false, s_comp), interior_end));
         break;
     case 3:
         if (hyper) {
             if (comm) TRY(halo_end(SLOT_HD, hypdiv, nhd, unpack, pipe));
             if (dsend) TRY(before_direct_send(SLOT_HG, s_ext));
             TRY(exterior_begin());
-            launch_gradlap(c, d_exterior, nexterior, comm, s_ext);
-            TRY(exterior_end());
+            TRY(closed(launch_gradlap(c, d_exterior, nexterior, comm, s_ext), exterior_end));
             if (dsend) mark_fresh(SLOT_HG, hypgrad, 3 * ngl);
             if (comm) TRY(halo_begin(SLOT_HG, hypgrad, 3 * ngl, 0, pipe));
         }
         TRY(interior_begin());
-        launch_tendency(c, d_interior, ninterior, false, s_comp);
-        TRY(interior_end());
+        TRY(closed(launch_tendency(c, d_interior, ninterior, false, s_comp), interior_end));
         break;
     case 4:  // the exchanges the tendency pass waits for end here, on every rank of a local group,
              // before any rank's exterior launch overwrites a send buffer (case 5)
@@ -784,8 +783,7 @@ int EngineBase::rhs_segment(int seg, const RhsCtx &c)
     case 5:
         if (dsend && c.lsrk) TRY(before_direct_send(SLOT_Q, s_ext));
         TRY(exterior_begin());
-        launch_tendency(c, d_exterior, nexterior, comm, s_ext);
-        TRY(exterior_end());
+        TRY(closed(launch_tendency(c, d_exterior, nexterior, comm, s_ext), exterior_end));
         if (dsend && c.lsrk) mark_fresh(SLOT_Q, c.Qout, ns);
         // whatever follows on the compute stream (a filter, the caller's next call, the next
         // evaluation's first interior launch) finds this evaluation complete

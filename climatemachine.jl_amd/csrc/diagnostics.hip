@@ -26,7 +26,7 @@
 
 #include "diagnostics.h"
 #include "engine_base.h"
-#include "kernels.h"
+#include "kernels_nodal.h"
 #include "rccl.h"
 #include "reductions.h"
 

@@ -2,8 +2,9 @@
 // and enqueues the passes of one right-hand-side evaluation in the order of the
 // reference's `(dg::DGModel)(tendency, Q, _, t, alpha, beta)`
 // (src/Numerics/DGMethods/DGModel.jl:85-427).  The physics/polynomial-order specific
-// kernel launches live in EngineT<P, NQ> (engine.h); nothing here needs the pass kernels, so the
-// steppers, the solvers and the C entries compile against this header alone.
+// kernel launches live in EngineLaw<P, NQ> (engine_law.h) and EngineT<P, NQ> (engine.h); nothing here
+// needs the pass kernels, so the steppers, the solvers and the C entries compile against this header
+// alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -303,11 +304,12 @@ struct EngineBase {
     bool exchanges() const { return communicate() && !(stacked && direction == DIR_VERTICAL); }
 
     // physics / order specific launches; `exterior`: the launch of the exterior element list of a
-    // handle with neighbours (writes the send buffers of what it produces, see HaloDev)
-    virtual void launch_gradients(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) = 0;
-    virtual void launch_divgrad(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) = 0;
-    virtual void launch_gradlap(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) = 0;
-    virtual void launch_tendency(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) = 0;
+    // handle with neighbours (writes the send buffers of what it produces, see HaloDev).  A pass launch
+    // fails, with the message set, when the engine class has no kernel for what it is asked.
+    virtual int launch_gradients(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) = 0;
+    virtual int launch_divgrad(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) = 0;
+    virtual int launch_gradlap(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) = 0;
+    virtual int launch_tendency(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) = 0;
     virtual void launch_update_aux(const RhsCtx &c, int64_t e0, int64_t e1) = 0;
     virtual bool has_update_aux() const = 0;
     virtual bool law_needs_gradflux() const = 0;
@@ -617,11 +619,12 @@ inline int object_call_done(cmdg_handle h, int r, const std::string &err)
 
 // what a plug-in and the library must agree on (cmdg_load_plugin): the layout of the engine base
 // class and of the descriptor, folded into one number (plus the revision of its virtual interface,
-// which no size shows: 1 = launch_les_nodal, 2 = launch_vector_gradients and launch_gcm_nodal)
+// which no size shows: 1 = launch_les_nodal, 2 = launch_vector_gradients and launch_gcm_nodal, 3 = the
+// pass launchers return a status)
 inline unsigned long engine_abi_stamp()
 {
     return (unsigned long)sizeof(EngineBase) * 1000003ul + (unsigned long)sizeof(cmdg_desc) * 10007ul +
-           (unsigned long)sizeof(RhsCtx) * 101ul + (unsigned long)sizeof(cmdg_rhs_hooks) + 2ul * 100000007ul;
+           (unsigned long)sizeof(RhsCtx) * 101ul + (unsigned long)sizeof(cmdg_rhs_hooks) + 3ul * 100000007ul;
 }
 
 }  // namespace cmdg

@@ -4,16 +4,17 @@
 // one exchange of Q with the interior element list launched before the ghosts arrive and the
 // exterior list after -- (esdg::ESDGModel)(tendency, Q, _, t, alpha, beta), ESDGModel.jl:110-316,
 // whose volume launches read no ghost and commute with the end of the exchange.  The tendency of
-// either list is the one launch of esdg.h.
-#include "engine.h"
+// either list is the one launch of esdg.h, so the class sits on the law layer and compiles no DG pass
+// kernel: the three passes an ESDGModel evaluation never reaches fail.
+#include "engine_law.h"
 #include "laws.h"
 #include "esdg.h"
 
 namespace cmdg {
 
 template <class P, int NQ_>
-struct EngineESDG : EngineT<P, NQ_, NQ_> {
-    using Base = EngineT<P, NQ_, NQ_>;
+struct EngineESDG : EngineLaw<P, NQ_, NQ_> {
+    using Base = EngineLaw<P, NQ_, NQ_>;
     using Kernel = void (*)(EsdgArgs<P>);
     cmdg_esdg_desc ed{};
 
@@ -37,9 +38,21 @@ struct EngineESDG : EngineT<P, NQ_, NQ_> {
         default: return pick_surface<ESDG_KG>(ed.surface_flux);
         }
     }
-    void launch_tendency(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
+    int launch_gradients(const RhsCtx &, const int64_t *, int64_t, bool, hipStream_t) override
     {
-        if (n <= 0) return;
+        return this->no_pass("gradient", "ESDGModel");
+    }
+    int launch_divgrad(const RhsCtx &, const int64_t *, int64_t, bool, hipStream_t) override
+    {
+        return this->no_pass("Laplacian", "ESDGModel");
+    }
+    int launch_gradlap(const RhsCtx &, const int64_t *, int64_t, bool, hipStream_t) override
+    {
+        return this->no_pass("gradient-of-Laplacian", "ESDGModel");
+    }
+    int launch_tendency(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
+    {
+        if (n <= 0) return CMDG_OK;
         Range range_(exterior ? "cmdg:esdg_tendency:exterior" : "cmdg:esdg_tendency");
         this->prof_begin(CMDG_K_ESDG_TENDENCY, st);
         EsdgArgs<P> a;
@@ -56,6 +69,7 @@ struct EngineESDG : EngineT<P, NQ_, NQ_> {
         a.beta = c.beta;
         hipLaunchKernelGGL(pick(), dim3((unsigned)n), dim3(KDims<NQ_, NQ_>::NT), 0, st, a);
         this->prof_end(st);
+        return CMDG_OK;
     }
     // advective_courant / nondiffusive_courant of the law (DryAtmos.jl:758-793); the minimum node
     // distance (mode 0) is the grid's
@@ -92,15 +106,12 @@ struct EngineESDG : EngineT<P, NQ_, NQ_> {
 template <class P, int NQ_>
 static EngineBase *make_engine_esdg_t(const cmdg_desc *d, const cmdg_esdg_desc *ed)
 {
+    static_assert(P::NGRAD == 0 && P::NGF == 0 && P::NGL == 0 && P::NHYP == 0, "an ESDGModel has one pass");
     auto *e = new EngineESDG<P, NQ_>();
-    e->NQ = NQ_;
-    e->NQV = NQ_;
-    e->ns = P::NS;
-    e->naux = P::NAUX + (d->iparam[1] != 0 ? 4 : 0);
-    e->ngrad = e->ngf = e->ngl = e->nhyp = 0;
+    e->init_law(d);
+    e->naux += d->iparam[1] != 0 ? 4 : 0;
     e->esdg = true;
     e->ed = *ed;
-    P::make_params(e->prm, d->iparam, d->dparam);
     e->prm.Mcut = ed->Mcut;
     e->prm.low_mach = ed->low_mach != 0;
     e->prm.kep = ed->kinetic_energy_preserving != 0;

@@ -6,6 +6,9 @@
 // 1100-1158,1224-1278): the DG kernels at (NQ, NQV = 1) in the horizontal direction (faces 1-4,
 // volume sources added), then the finite-volume kernel of fv.h on the same element list.  The
 // vertical passes read their own stack only, so they need no halo of their own.
+// The class sits on the law layer and names the DG kernels a DGFVModel handle launches: the gradient
+// pass, and the one tendency variant with neither the fused update nor the receive buffers.  A law
+// with hyperdiffusive states is refused at create, so its two passes are not compiled for it.
 #pragma once
 #include "engine.h"
 #include "fv.h"
@@ -13,8 +16,8 @@
 namespace cmdg {
 
 template <class P, int NQ_>
-struct EngineFV : EngineT<P, NQ_, 1> {
-    using Base = EngineT<P, NQ_, 1>;
+struct EngineFV : EngineLaw<P, NQ_, 1> {
+    using Base = EngineLaw<P, NQ_, 1>;
     cmdg_fv_desc fvd{};
     using FvKernel = void (*)(FvArgs<P>);
 
@@ -77,15 +80,17 @@ struct EngineFV : EngineT<P, NQ_, 1> {
         }
         return CMDG_OK;
     }
-    void launch_gradients(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
+    int launch_gradients(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
     {
-        if (n <= 0) return;
+        if (n <= 0) return CMDG_OK;
+        int r = CMDG_OK;
         if (this->diffusion_direction != DIR_VERTICAL) {
-            this->in_pass(Base::GRADIENTS, n, exterior, st, [&] {
+            r = this->in_pass(Base::GRADIENTS, n, exterior, st, [&] {
                 const PassArgs<P> args = this->make_args(c, elems, n, DIR_HORIZONTAL, exterior, nullptr, nullptr);
-                hipLaunchKernelGGL(Base::pick_gradients(this->gf_live(), false), dim3((unsigned)n),
-                                   dim3(KDims<NQ_, 1>::NT), 0, st, args);
+                return this->launch_picked(gradients_kernel<P, NQ_, 1>(this->gf_live()), (unsigned)n, KDims<NQ_, 1>::NT,
+                                           st, args, "gradient", "gf_live = %d", (int)this->gf_live());
             });
+            if (r != CMDG_OK) return r;
         }
         if (this->diffusion_direction != DIR_HORIZONTAL && P::NGF > 0 && this->gf_live()) {
             this->prof_begin(CMDG_K_FV_GRADIENTS, st);
@@ -99,17 +104,28 @@ struct EngineFV : EngineT<P, NQ_, 1> {
             hipLaunchKernelGGL(k, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, st, a);
             this->prof_end(st);
         }
+        return CMDG_OK;
     }
-    void launch_tendency(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
+    int launch_divgrad(const RhsCtx &, const int64_t *, int64_t, bool, hipStream_t) override
     {
-        if (n <= 0) return;
+        return this->no_pass("Laplacian", "DGFVModel");
+    }
+    int launch_gradlap(const RhsCtx &, const int64_t *, int64_t, bool, hipStream_t) override
+    {
+        return this->no_pass("gradient-of-Laplacian", "DGFVModel");
+    }
+    int launch_tendency(const RhsCtx &c, const int64_t *elems, int64_t n, bool exterior, hipStream_t st) override
+    {
+        if (n <= 0) return CMDG_OK;
         if (this->direction != DIR_VERTICAL) {
-            this->in_pass(Base::TENDENCY, n, exterior, st, [&] {
+            const int r = this->in_pass(Base::TENDENCY, n, exterior, st, [&] {
                 using SH = TendencyShape<P, NQ_, 1>;
                 const PassArgs<P> args = this->make_args(c, elems, n, DIR_HORIZONTAL, exterior, nullptr, nullptr);
-                hipLaunchKernelGGL(Base::pick_tendency(false, P::needs_gradflux(this->prm), false, GargOut::none),
-                                   dim3((unsigned)SH::blocks(n)), dim3(SH::NT), 0, st, args);
+                const bool gf = needs_gradflux<P>(this->prm);
+                return this->launch_picked(tendency_kernel<P, NQ_, 1, false, false>(gf), (unsigned)SH::blocks(n),
+                                           SH::NT, st, args, "tendency", "gradient flux = %d", (int)gf);
             });
+            if (r != CMDG_OK) return r;
         }
         if (this->direction != DIR_HORIZONTAL) {
             this->prof_begin(CMDG_K_FV_TENDENCY, st);
@@ -120,6 +136,7 @@ struct EngineFV : EngineT<P, NQ_, 1> {
                                fv_lds_bytes(P::NS, NQ_ * NQ_, nv), st, a);
             this->prof_end(st);
         }
+        return CMDG_OK;
     }
 };
 
@@ -127,18 +144,10 @@ template <class P, int NQ_>
 EngineBase *make_engine_fv(const cmdg_desc *d, const cmdg_fv_desc *fv)
 {
     auto *e = new EngineFV<P, NQ_>();
-    e->NQ = NQ_;
-    e->NQV = 1;
-    e->ns = P::NS;
-    e->naux = P::NAUX;
-    e->ngrad = P::NGRAD;
-    e->ngf = P::NGF;
-    e->ngl = P::NGL;
-    e->nhyp = P::NHYP;
+    e->init_law(d);
     e->fv = true;
     e->fv_nvert = fv->nvertelem;
     e->fvd = *fv;
-    P::make_params(e->prm, d->iparam, d->dparam);
     return e;
 }
 

@@ -17,7 +17,7 @@
 // so that one copy of the flux code is resident.  Ghost neighbours are read from the ghost elements
 // of Q: an ESDG handle unpacks its exchange as the reference does.
 #pragma once
-#include "kernels.h"
+#include "kernels_common.h"
 #include "physics_esdg_dryatmos.h"
 
 namespace cmdg {

@@ -20,7 +20,7 @@
 // fluxes of nvertelem + 1 faces, weights).  Up to FV_LDS_DEFAULT a launch asks for it as it is; up to
 // FV_LDS_MAX the handle raises the kernel's dynamic-LDS limit when it is created (engine_fv.h).
 #pragma once
-#include "kernels.h"
+#include "kernels_common.h"
 
 namespace cmdg {
 
@@ -236,7 +236,7 @@ __global__ void __launch_bounds__(256) k_fv_tendency(const FvArgs<P> a)
         nrm[0] = sg[SN1], nrm[1] = sg[SN2], nrm[2] = sg[SN3];
         load_state<NS, Nh>(QcM, a.Q, n, eM);
         load_state<NAUX, Nh>(auxcM, a.aux, n, eM);
-        if (NGF > 0 && P::needs_gradflux(a.prm)) load_gf<P, Nh>(gfM, a.gf, n, eM);
+        if (NGF > 0 && needs_gradflux<P>(a.prm)) load_gf<P, Nh>(gfM, a.gf, n, eM);
         fv_reconstruct<P, W, PERIODIC>(sP, sW, Nh, nv, n, km, a.recon, a.limiter, hb, hb_g, bot, top);
         const double wM = sW[km * Nh + n];
         law_face_auxiliary_state<P>(a.prm, auxM, auxcM, top_bc ? wM : -wM);
@@ -269,7 +269,7 @@ __global__ void __launch_bounds__(256) k_fv_tendency(const FvArgs<P> a)
             Vec<NS> botP, topP;
             load_state<NS, Nh>(QcP, a.Q, n, eP);
             load_state<NAUX, Nh>(auxcP, a.aux, n, eP);
-            if (NGF > 0 && P::needs_gradflux(a.prm)) load_gf<P, Nh>(gfP, a.gf, n, eP);
+            if (NGF > 0 && needs_gradflux<P>(a.prm)) load_gf<P, Nh>(gfP, a.gf, n, eP);
             fv_reconstruct<P, W, PERIODIC>(sP, sW, Nh, nv, n, kp, a.recon, a.limiter, hb, hb_g, botP, topP);
             law_face_auxiliary_state<P>(a.prm, auxPn, auxcP, sW[kp * Nh + n]);
             law_primitive_to_prognostic<P>(a.prm, QPn, topP, auxPn);
@@ -308,7 +308,7 @@ __global__ void __launch_bounds__(256) k_fv_tendency(const FvArgs<P> a)
                 load_state<NAUX, Nh>(ax, a.aux, n, e);
 #pragma unroll
                 for (int s = 0; s < NGF; ++s) lgf[s] = 0.0;
-                if (NGF > 0 && P::needs_gradflux(a.prm)) load_gf<P, Nh>(lgf, a.gf, n, e);
+                if (NGF > 0 && needs_gradflux<P>(a.prm)) load_gf<P, Nh>(lgf, a.gf, n, e);
                 load_state<P::NDER, Nh>(lder, a.derived, n, e);
                 P::source(a.prm, S, q, lgf, ax, lder, a.t, a.model_dir);
             }

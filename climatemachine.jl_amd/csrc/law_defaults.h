@@ -12,10 +12,15 @@
 //                        NGF          number_states(GradientFlux)
 //   static void make_params(Params &, const int32_t *iparam, const double *dparam)
 //                                     host: the block out of cmdg_desc::iparam / dparam
-//   __host__ __device__ static bool needs_gradflux(const Params &)
+//   static constexpr GradFlux GRADFLUX = GradFlux::never / GradFlux::always
+//     or  __host__ __device__ static bool needs_gradflux(const Params &)
 //                                     does flux_second_order read the gradient-flux state at all (a
 //                                     zero viscosity only multiplies it by zero): if not, the passes
-//                                     take the instantiations that neither form nor read it
+//                                     take the instantiations that neither form nor read it.  A law
+//                                     whose answer is a constant states it, and the engine instantiates
+//                                     the pass kernels of that answer alone; only a law whose answer
+//                                     depends on its parameters defines the function (GRADFLUX is then
+//                                     the default, GradFlux::ask).  Read through needs_gradflux<P>(prm).
 //   __device__ static void flux_first_order(const Params &, double *F, const double *Q,
 //                                           const double *aux, double t, int direction)
 //                                     flux_first_order!: F[d + 3 s] += ...
@@ -40,7 +45,14 @@
 
 namespace cmdg {
 
+// what a law knows at compile time about its gradient-flux state (GRADFLUX below)
+enum class GradFlux { ask, never, always };
+
 struct LawDefaults {
+    // does flux_second_order read the gradient-flux state: never, always, or ask
+    // needs_gradflux(prm) of the law at run time.  The engine names the pass kernels of the answers
+    // that are left (engine.h pick_tendency, pick_gradients).
+    static constexpr GradFlux GRADFLUX = GradFlux::ask;
     // ---- sizes ---------------------------------------------------------------------------------
     static constexpr int NGL = 0;    // number_states(GradientLaplacian): fields whose Laplacian is formed
     static constexpr int NHYP = 0;   // number_states(Hyperdiffusive)
@@ -216,5 +228,21 @@ struct LawDefaults {
         return 0.0;
     }
 };
+
+// What the law says about its gradient flux, for the engine: a law without gradient-flux states never
+// reads them, whatever else it says.
+template <class P>
+inline constexpr GradFlux gradflux_of = P::NGF > 0 ? P::GRADFLUX : GradFlux::never;
+// ... and the answer for one parameter block: the one place that calls P::needs_gradflux
+template <class P>
+__host__ __device__ inline bool needs_gradflux(const typename P::Params &prm)
+{
+    static_assert(P::NGF > 0 || P::GRADFLUX != GradFlux::always,
+                  "a law with no gradient-flux states (NGF == 0) cannot always read them");
+    if constexpr (gradflux_of<P> == GradFlux::ask)
+        return P::needs_gradflux(prm);
+    else
+        return gradflux_of<P> == GradFlux::always;
+}
 
 }  // namespace cmdg

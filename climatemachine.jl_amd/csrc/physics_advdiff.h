@@ -41,7 +41,7 @@ struct AdvDiff : LawDefaults {
     // only problems with variable coefficients refresh the auxiliary state (problem 7:
     // ReversingDeformationalFlow, advection_sphere.jl:56-103); see update_aux_active
     static constexpr bool HAS_UPDATE_AUX = ADV;
-    __host__ __device__ static bool needs_gradflux(const Params &) { return DIFF; }
+    static constexpr GradFlux GRADFLUX = DIFF ? GradFlux::always : GradFlux::never;
     // auxiliary fields the interior-face fluxes read on either side: the velocity (first-order
     // flux and wave speed); boundary faces load the whole minus-side auxiliary state themselves
     static constexpr int NFAUX = ADV ? 3 : 0;

@@ -184,7 +184,8 @@ struct DryAtmos : LawDefaults {
     }
     __host__ __device__ static constexpr int hv_indexmap(int s) { return 4 + s; }
     // tau = (-2 nu) S and D_t = nu / Pr: with nu == 0 the gradient-flux state only multiplies zeros
-    __host__ __device__ static bool needs_gradflux(const Params &m) { return SMAG || m.visc != 0; }
+    static constexpr GradFlux GRADFLUX = SMAG ? GradFlux::always : GradFlux::ask;
+    __host__ __device__ static bool needs_gradflux(const Params &m) { return m.visc != 0; }  // (asked without SMAG)
     // auxiliary fields the interior-face fluxes read from the minus side: Phi (potential
     // energy in the thermodynamic state), the reference pressure and, for SmagorinskyLilly,
     // grad Phi (vertical unit vector) and the filter width

@@ -47,7 +47,7 @@ struct AtmosLinearAG : LawDefaults {
     {
         return ORIENT ? (i == 0 ? OPHI : OREF + (i - 1)) : OREF + i;
     }
-    __host__ __device__ static bool needs_gradflux(const Params &) { return false; }
+    static constexpr GradFlux GRADFLUX = GradFlux::never;
     static void make_params(Params &p, const int32_t *, const double *dp)
     {
         p.R_d = dp[2];

@@ -71,7 +71,7 @@ struct EsdgDryAtmos : LawDefaults {
     static constexpr int NS = 5, NAUX = 4, NGRAD = 0, NGF = 0, NFAUX = 1;
     static constexpr int NENT = 6;  // entropy variables: rho, rho u[3], rho e, Phi
     static constexpr bool HAS_SOURCE = true;
-    __host__ __device__ static bool needs_gradflux(const Params &) { return false; }
+    static constexpr GradFlux GRADFLUX = GradFlux::never;
     static void make_params(Params &p, const int32_t *ip, const double *dp)
     {
         p.nsrc = ip[2] < 0 ? 0 : (ip[2] > 2 ? 2 : ip[2]);

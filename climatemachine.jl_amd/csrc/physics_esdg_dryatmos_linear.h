@@ -27,7 +27,7 @@ struct EsdgDryAtmosLinearAG : LawDefaults {
     static constexpr bool HAS_SOURCE = true;
     static constexpr int NFAUX = 3;
     __host__ __device__ static constexpr int face_aux(int i) { return OREF + 1 + i; }
-    __host__ __device__ static bool needs_gradflux(const Params &) { return false; }
+    static constexpr GradFlux GRADFLUX = GradFlux::never;
     static void make_params(Params &p, const int32_t *ip, const double *dp) { Full::make_params(p, ip, dp); }
 
     // linearized_pressure  linear.jl:16-24 (total_energy = false)

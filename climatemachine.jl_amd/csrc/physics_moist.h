@@ -70,7 +70,7 @@ struct MoistAtmos : LawDefaults {
     // (N^2); tendency (pass 3): the ten columns of face_aux (Phi, grad Phi, ref rho, ref p, Delta,
     // temperature, q_liq, q_ice) -- coord, the rest of ref_state and theta_v are never loaded.
     __host__ __device__ static constexpr int aux_read(int pass) { return pass == 0 ? 7 : (pass == 3 ? 10 : 0); }
-    __host__ __device__ static bool needs_gradflux(const Params &) { return true; }
+    static constexpr GradFlux GRADFLUX = GradFlux::always;
     __host__ __device__ static bool update_aux_active(const Params &) { return true; }
 
     static void make_params(Params &p, const int32_t *ip, const double *dp)

@@ -34,7 +34,7 @@ struct HydroBoussinesq : LawDefaults {
     enum { GDIVH = 0, GNU = 1, GKAPPA = 7 };
     static constexpr int NS = 4, NAUX = 8, NGRAD = 5, NGF = 10;
     static constexpr bool HAS_SOURCE = true, HAS_COURANT = true, HAS_PENALTY = true;
-    __host__ __device__ static bool needs_gradflux(const Params &) { return true; }
+    static constexpr GradFlux GRADFLUX = GradFlux::always;
     // the face fluxes read w and pkin (and y never): aux columns 1, 2
     static constexpr int NFAUX = 2;
     __host__ __device__ static constexpr int face_aux(int i) { return 1 + i; }

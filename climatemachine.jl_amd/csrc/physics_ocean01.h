@@ -71,7 +71,7 @@ struct OceanSE01 : LawDefaults {
     enum { GNU = 0, GKAPPA = 6 };                                      // :237-242
     static constexpr int NS = 4, NAUX = 8, NGRAD = 5, NGF = 9;
     static constexpr bool HAS_SOURCE = true, HAS_PENALTY = true;
-    __host__ __device__ static bool needs_gradflux(const Params &) { return true; }
+    static constexpr GradFlux GRADFLUX = GradFlux::always;
     static constexpr int NFAUX = 2;  // the face fluxes read w and pkin
     __host__ __device__ static constexpr int face_aux(int i) { return AW + i; }
     static void make_params(Params &p, const int32_t *ip, const double *dp) { se01_make_params(p, ip, dp); }
@@ -213,7 +213,7 @@ struct Continuity3dSE01 : LawDefaults {
     using Params = OceanSE01Params;
     enum { U = 0, V = 1, ETA = 2, TH = 3 };
     static constexpr int NS = 4, NAUX = 0, NGRAD = 0, NGF = 0;
-    __host__ __device__ static bool needs_gradflux(const Params &) { return false; }
+    static constexpr GradFlux GRADFLUX = GradFlux::never;
     static void make_params(Params &p, const int32_t *ip, const double *dp) { se01_make_params(p, ip, dp); }
     __device__ static void flux_first_order(const Params &, double *F, const double *Q,
                                             const double *, double, int)
@@ -254,7 +254,7 @@ struct BarotropicSE01 : LawDefaults {
     enum { AGU = 0, AUC = 2, AETAC = 4, AUS = 5, AETAS = 7, ADU = 8, AETAD = 10, ADETA = 11, AY = 12 };
     static constexpr int NS = 3, NAUX = 13, NGRAD = 2, NGF = 6;
     static constexpr bool HAS_SOURCE = true, HAS_PENALTY = true;
-    __host__ __device__ static bool needs_gradflux(const Params &) { return true; }
+    static constexpr GradFlux GRADFLUX = GradFlux::always;
     static void make_params(Params &p, const int32_t *ip, const double *dp) { se01_make_params(p, ip, dp); }
     __device__ static void flux_first_order(const Params &m, double *F, const double *Q,
                                             const double *, double, int)

@@ -16,7 +16,7 @@ struct PGradParams {
 struct PressureGradient : LawDefaults {
     using Params = PGradParams;
     static constexpr int NS = 3, NAUX = 1, NGRAD = 0, NGF = 0, NFAUX = 1;
-    __host__ __device__ static bool needs_gradflux(const Params &) { return false; }
+    static constexpr GradFlux GRADFLUX = GradFlux::never;
     static void make_params(Params &p, const int32_t *, const double *) { p.unused = 0; }
 
     __device__ static void flux_first_order(const Params &, double *F, const double *,

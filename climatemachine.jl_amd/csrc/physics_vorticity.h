@@ -20,7 +20,7 @@ struct VorticityLaw : LawDefaults {
     using Params = VorticityParams;
     static constexpr int NS = 3, NAUX = 3, NGRAD = 0, NGF = 0, NFAUX = 3;
     __host__ __device__ static constexpr int face_aux(int i) { return i; }
-    __host__ __device__ static bool needs_gradflux(const Params &) { return false; }
+    static constexpr GradFlux GRADFLUX = GradFlux::never;
     static void make_params(Params &p, const int32_t *, const double *) { p.unused = 0; }
 
     // flux.Omega_bl = [0 u3 -u2; -u3 0 u1; u2 -u1 0]: row d, column c -> F[d + 3 c]
